@@ -43,13 +43,18 @@ def parse():
     ap.add_argument("--width", type=int, default=224)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--streams", type=int, default=1, help="HIP streams per GPU; every stream gets --batch frames of a step (round 3: one stream over 2672 "
-                    "frames = two streams of 1336 within 1 %, profiles/r03_stream_skew_ab.txt -- the launches of two parts do not overlap usefully)")
+                    "frames = two streams of 1336 within 1 %%, profiles/r03_stream_skew_ab.txt -- the launches of two parts do not overlap usefully)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-temporal", action="store_true")
     ap.add_argument("--no-ddp-train", action="store_true", help="N > 1: skip the data-parallel training sub-record")
     ap.add_argument("--ddp-timeout", type=float, default=300.0, help="N > 1: seconds after which the data-parallel training sub-record is given up and the headline line is printed without it")
     ap.add_argument("--per-layer", default="", help="write a per-conv-layer timing table (json) to this path")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned (rank 0) "
+                    "as DIR/<name>.npy, float32, at most 64 MB in all (see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def conv_flops_per_frame(model, h, w):
@@ -689,6 +694,30 @@ def ddp_train_bench(dev, dist, world, rank):
 
 
 METRIC = "frames/sec spatial-extract + per-video TCN latency, Cholec80, 1/2/4/8 GPU"
+DUMP_MAX_BYTES = 64 * 10**6    # --dump-outputs: the files of one dump together, .npy headers included
+
+
+def dump_outputs(out, path, seed=1234):
+    """--dump-outputs: the arrays `extract_u8` handed back in the last timed step -- the four logit heads and the pooled feature, one row
+    per frame in frame order -- as <path>/<name>.npy in float32, so that two builds can be compared output for output.  When the step's
+    rows exceed DUMP_MAX_BYTES in all, every array keeps the same fixed, seeded sample of frames (sorted), and their indices go to
+    frame_index.npy (float64, exact)."""
+    (_, i), (_, v), (_, t), (feat, ivt) = out
+    arrays = {"logits_i": i, "logits_v": v, "logits_t": t, "logits_ivt": ivt, "feature": feat}
+    n = feat.shape[0]
+    row_bytes = sum(x[0].numel() * 4 for x in arrays.values())
+    rows = None
+    if n * row_bytes + 1024 * len(arrays) > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 1024 * (len(arrays) + 1)) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        x = x.detach().float()
+        if rows is not None:
+            x = x[torch.from_numpy(rows).to(x.device)]
+        np.save(os.path.join(path, name + ".npy"), x.cpu().numpy())
+    if rows is not None:
+        np.save(os.path.join(path, "frame_index.npy"), rows.astype(np.float64))
 
 
 def main():
@@ -746,6 +775,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert torch.isfinite(out[3][1]).all()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(out, a.dump_outputs)
 
     ms_per_step = dt / a.steps * 1e3
     fps = world * nstep * a.steps / dt

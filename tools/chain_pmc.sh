@@ -1,7 +1,7 @@
 #!/bin/bash
 # where a chain_gemm wave's cycles go: SQ counters of the micro bench (two passes), summed per kernel
 set -e
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out
 rm -rf $O/pmc_chain1 $O/pmc_chain2

@@ -3,7 +3,7 @@
 # spatial extractor (the headline kernel) and for the temporal head (per-video latency), kernel stats of the MS-TCT training step.
 # Every rocprofv3 command has the program directly after `--`.
 set -e
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out
 mkdir -p $O; rm -rf $O/pmc_fetch $O/pmc_write $O/prof_final $O/pmc_mfma $O/prof_tenco_f32 $O/prof_tenco_bf16 $O/pmc_tenco_FETCH_SIZE $O/pmc_tenco_WRITE_SIZE $O/prof_mstct_train $O/prof_q2l_train $O/prof_tenco2000_f32 $O/prof_tenco2000_bf16 $O/prof_swin

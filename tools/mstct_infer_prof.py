@@ -1,5 +1,5 @@
 """One MS-TCT teacher window (T = 256, D = 2048, ivt head) under rocprofv3: warm-up, then 20 eager windows and 20 hipGraph replays.
-cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o mstct -- python3 $GRAFT_REPO_ROOT/tools/mstct_infer_prof.py"""
+cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o mstct -- python3 <repo>/tools/mstct_infer_prof.py"""
 import os, sys, types, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

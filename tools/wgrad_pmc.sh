@@ -1,6 +1,6 @@
 #!/bin/bash
 # LDS / MFMA counters of the weight-gradient kernels on one ResNet-50 layer shape (GPU box): bash tools/wgrad_pmc.sh [shape index ...]
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 ONLY=${1:-12,14}
