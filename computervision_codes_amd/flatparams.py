@@ -1,0 +1,293 @@
+"""The host-side core of the four trainers: every trained tensor in ONE flat fp32 parameter buffer P and ONE flat gradient buffer G (packed
+GEMM layouts, every slot padded to 4 floats), the weight copies derived from the masters by one launch, and the data-parallel exchange of G
+-- per-bucket all-reduces behind the backward or one flat all-reduce after it -- ahead of one `mt4_sgd_step_f32`.
+
+* `FlatParams` lays the slots out in the order they are declared, loads them from the reference state dict and exports P or G back in the
+  reference's key names and shapes;
+* `FlatTrainer` is the trainers' base: the buffers, SGD, the exchange and the hipGraph capture of a step's device part;
+* `GemmTrainer` adds the bf16 operand copies and the LayerNorm helpers of the nn.Linear-built trainers (MS-TCT, Swin + Q2L).
+"""
+from __future__ import annotations
+
+from typing import Dict, List
+
+import torch
+
+from . import ops
+
+F32 = torch.float32
+
+
+def _r4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+class Lin:
+    """a packed GEMM / conv weight [cout][kpad] (kernel kh x taps; cout padded to 4, the padding rows zero) and its bias, with gradient views;
+    `wt` = the transposed, tap-reversed copy of the data gradient, `w16` / `wt16` = bf16 copies of both (bf16-operand mode)"""
+    __slots__ = ("name", "wkey", "bkey", "cout", "cout_real", "cin", "kh", "taps", "dgrad", "off", "src", "ref", "w", "b", "gw", "gb",
+                 "wt", "w16", "wt16")
+
+
+class Vec:
+    """a plain vector (LayerNorm / BatchNorm affine, tables) viewed as `shape`; `ref` = its shape in the reference state dict"""
+    __slots__ = ("key", "shape", "off", "ref", "p", "g")
+
+
+class FlatParams:
+    """the flat buffers P / G.  Declare the slots (`lin`, `vec`, `reserve`; `bucket` names the gradient bucket the following slots fall into),
+    then `build` allocates, loads and registers the derived copies"""
+
+    def __init__(self, device, op16: bool = False):
+        self.dev, self.op16 = device, op16
+        self.tab = ops.RefreshTable(device)          # every derived matrix (transposed fp32, bf16 copies) from one launch per refresh
+        self.L: Dict[str, Lin] = {}
+        self.V: Dict[str, Vec] = {}
+        self.ranges: Dict[str, list] = {}            # flat range [a, b) of every gradient bucket
+        self._slots: list = []
+        self._n = 0
+        self._bucket = None
+
+    def _take(self, n: int) -> int:
+        off = self._n
+        self._n += _r4(n)
+        if self._bucket is not None:
+            self.ranges[self._bucket][1] = self._n
+        return off
+
+    def bucket(self, name: str):
+        """the slots declared from here on belong to the gradient bucket `name` (continued if it is the current one)"""
+        self._bucket = name
+        self.ranges.setdefault(name, [self._n, self._n])
+
+    def lin(self, name, cout, cin, taps=1, kh=1, wkey=None, bkey=None, bias=True, dgrad=True, src=None) -> Lin:
+        """reference keys default to name + '.weight' / '.bias'; src = (weight, bias) loaded instead of the state dict's tensors (a slot that
+        is not one reference tensor); dgrad False: no transposed copy (nothing needs the layer's data gradient)"""
+        l = Lin()
+        l.name, l.cout_real, l.cout, l.cin, l.kh, l.taps, l.dgrad, l.src = name, cout, _r4(cout), cin, kh, taps, dgrad, src
+        l.wkey = wkey or name + ".weight"
+        l.bkey = (bkey or name + ".bias") if bias else None
+        l.off = self._take(l.cout * ops.packed_k(cin, kh, taps, F32))
+        if bias:
+            self._take(l.cout)
+        self.L[name] = l
+        self._slots.append(l)
+        return l
+
+    def vec(self, key, shape) -> Vec:
+        v = Vec()
+        v.key, v.shape = key, tuple(shape)
+        v.off = self._take(int(torch.tensor(v.shape).prod()))
+        self.V[key] = v
+        self._slots.append(v)
+        return v
+
+    def reserve(self, n: int):
+        """n unused floats (a slot the layout keeps)"""
+        self._take(n)
+
+    def build(self, sd: Dict[str, torch.Tensor], derive: bool = True):
+        """allocate P / G, cut every slot's views, load it; derive: register the transposed / bf16 copies of every GEMM weight"""
+        self.P = torch.zeros(self._n, dtype=F32, device=self.dev)
+        self.G = torch.zeros(self._n, dtype=F32, device=self.dev)
+        for s in self._slots:
+            if isinstance(s, Vec):
+                n = int(torch.tensor(s.shape).prod())
+                s.p, s.g = self.P[s.off:s.off + n].view(*s.shape), self.G[s.off:s.off + n].view(*s.shape)
+                src = sd[s.key]
+                s.ref = tuple(src.shape)
+                s.p.copy_(src.float().reshape(s.shape).to(self.dev))
+                continue
+            l, kp = s, ops.packed_k(s.cin, s.kh, s.taps, F32)
+            a, n = l.off, l.cout * kp
+            l.w, l.gw = self.P[a:a + n].view(l.cout, kp), self.G[a:a + n].view(l.cout, kp)
+            l.b, l.gb = (self.P[a + n:a + n + l.cout], self.G[a + n:a + n + l.cout]) if l.bkey else (None, None)
+            w, b = l.src if l.src is not None else (sd[l.wkey], sd[l.bkey] if l.bkey else None)
+            l.src, l.ref = None, tuple(w.shape)
+            w = w.float().reshape(l.cout_real, l.cin, l.kh, l.taps)
+            if l.cout != l.cout_real:
+                w = torch.cat([w, torch.zeros((l.cout - l.cout_real,) + tuple(w.shape[1:]))], 0)
+            l.w.copy_(ops.pack_conv_weight(w.to(self.dev), None, F32))
+            if b is not None:
+                l.b[:l.cout_real].copy_(b.float().to(self.dev))
+            if derive:
+                self._derive(l, l.dgrad)
+        return self
+
+    def _derive(self, l: Lin, need_dgrad: bool):
+        """the matrices the kernels read besides the master weight: the transposed (tap-reversed) copy of the data gradient (fp32) and, in the
+        bf16-operand mode, bf16 copies of both for the single-tap GEMMs whose channel counts allow it"""
+        l.wt = self.tab.add(l.w, l.cout, l.cin, F32, True, [l.taps - 1 - i for i in range(l.taps)]) if need_dgrad else None
+        l.w16 = l.wt16 = None
+        if self.op16 and l.taps == 1 and l.cin % 8 == 0 and l.cout % 8 == 0 and l.cout >= 64:
+            l.w16 = self.tab.add(l.w, l.cout, l.cin, torch.bfloat16, False, [0])
+            if need_dgrad:
+                l.wt16 = self.tab.add(l.w, l.cout, l.cin, torch.bfloat16, True, [0])
+
+    def rows(self, name: str, lo: int, hi: int) -> Lin:
+        """a row slice of a packed weight (nn.MultiheadAttention's in_proj split into q / k / v) with its own derived copies"""
+        src = self.L[name]
+        l = Lin()
+        l.name, l.cout, l.cin, l.taps = f"{name}[{lo}:{hi}]", hi - lo, src.cin, 1
+        l.w, l.gw, l.b, l.gb = src.w[lo:hi], src.gw[lo:hi], src.b[lo:hi], src.gb[lo:hi]
+        self._derive(l, True)
+        return l
+
+    def keys(self) -> set:
+        """the reference keys the slots hold"""
+        return {k for s in self._slots for k in ((s.key,) if isinstance(s, Vec) else (s.wkey, s.bkey)) if k}
+
+    def export(self, which: str) -> Dict[str, torch.Tensor]:
+        """P ('p') or G ('g') in the reference's key names and shapes, on the CPU"""
+        out = {}
+        for s in self._slots:
+            if isinstance(s, Vec):
+                out[s.key] = (s.p if which == "p" else s.g).reshape(s.ref).clone().cpu()
+                continue
+            w, b = (s.w, s.b) if which == "p" else (s.gw, s.gb)
+            tapw = _r4(s.cin)
+            w = w[:s.cout_real, :s.kh * s.taps * tapw].reshape(s.cout_real, s.kh, s.taps, tapw)[..., :s.cin].permute(0, 3, 1, 2)
+            out[s.wkey] = w.reshape(s.ref).contiguous().cpu()
+            if s.bkey:
+                out[s.bkey] = b[:s.cout_real].clone().cpu()
+        return out
+
+
+def allreduce_sum_flat(flat_grad: torch.Tensor, group=None) -> float:
+    """The ONE exchange of a data-parallel step: sum the flat gradient buffer over ranks in place (RCCL on the GPU,
+    gloo in the CPU tests) and return the factor that turns the sum into the mean (1/world).  No-op for one rank."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return 1.0
+    dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=group)
+    return 1.0 / dist.get_world_size(group)
+
+
+class FlatTrainer:
+    """the trainers' base: `fp` (a built `FlatParams`), SGD (`lr`, `wd`) and the data-parallel exchange of G over `pg`.
+    exchange False: rank-local steps (bench: the step without its exchange).  overlap: the backward calls `_reduce_bucket` where a gradient
+    bucket is complete and the bucket's all-reduce runs behind the backward of the earlier layers; otherwise `apply_update`
+    all-reduces the whole of G once."""
+
+    def __init__(self, lr: float, weight_decay: float, device, process_group, overlap: bool = False):
+        self.lr, self.wd = lr, weight_decay
+        self.dev, self.pg = torch.device(device), process_group
+        self.exchange = True
+        self.overlap = overlap
+        self.bucket_order: List[str] = []           # gradient buckets in the order their all-reduce was issued this step
+        self._pending: list = []
+        self._capturing = False
+        self._cut = None
+        self._graphs: Dict[tuple, object] = {}
+
+    @property
+    def P(self) -> torch.Tensor:
+        return self.fp.P
+
+    @property
+    def G(self) -> torch.Tensor:
+        return self.fp.G
+
+    def _refresh(self):
+        """derived copies after a parameter change"""
+        self.fp.tab.run()
+
+    def _ddp_world(self) -> int:
+        import torch.distributed as dist
+        return dist.get_world_size(self.pg) if (dist.is_available() and dist.is_initialized()) else 1
+
+    def _reduce_bucket(self, name: str):
+        """the bucket's gradients are complete: enqueue its all-reduce behind the kernels that wrote it (`apply_update` waits for all of them).
+        Under a segmented capture the graph is cut here instead and the all-reduce is issued at replay."""
+        if self._capturing:
+            if self._cut is not None:
+                self._cut(name)
+            return
+        if self.overlap and self.exchange and self._ddp_world() > 1:
+            self._issue_bucket(name)
+
+    def _issue_bucket(self, name: str):
+        import torch.distributed as dist
+        a, b = self.fp.ranges[name]
+        self.bucket_order.append(name)
+        if b > a:
+            self._pending.append(dist.all_reduce(self.G[a:b], op=dist.ReduceOp.SUM, group=self.pg, async_op=True))
+
+    def _graph_step(self, key, fn, inputs: List[torch.Tensor]):
+        """`fn(*inputs)` (a step's device part) replayed from the hipGraph captured for `key` on first use.  Data-parallel steps with bucket
+        overlap are captured in segments cut at `_reduce_bucket`, a bucket's all-reduce issued between two replays (`graph.SegmentedGraph`);
+        otherwise one graph, one flat all-reduce behind it."""
+        seg = bool(self.overlap and self.exchange and self._ddp_world() > 1)
+        g = self._graphs.get((key, seg))
+        if g is None:
+            g = self._graphs[(key, seg)] = self._capture(fn, inputs, seg)
+        return g(*inputs, on_cut=self._issue_bucket) if seg else g(*inputs)
+
+    def _capture(self, fn, inputs: List[torch.Tensor], seg: bool):
+        from .graph import GraphedForward, SegmentedGraph
+        self._capturing = True
+        try:
+            if not seg:
+                return GraphedForward(fn, inputs)
+
+            def fn_cut(cut, *a):
+                self._cut = cut
+                try:
+                    return fn(*a)
+                finally:
+                    self._cut = None
+            return SegmentedGraph(fn_cut, inputs)
+        finally:
+            self._capturing = False
+
+    def apply_update(self):
+        """DDP exchange (mean over ranks) + SGD + refresh of the derived copies"""
+        if self._pending:                                   # buckets were reduced during the backward
+            for h in self._pending:
+                h.wait()
+            self._pending = []
+            scale = 1.0 / self._ddp_world()
+        else:
+            scale = allreduce_sum_flat(self.G, self.pg) if self.exchange else 1.0
+        ops.sgd_step(self.P, self.G, self.lr, self.wd, scale)
+        self._refresh()
+
+
+class GemmTrainer(FlatTrainer):
+    """trainers built from nn.Linear GEMMs on rows whose bf16-operand mode reads bf16 copies of the operands (`Lin.w16`), and LayerNorms"""
+
+    def _begin_step(self):
+        """every parameter gradient of a step ADDS into G; the operand copies of the previous step are dropped"""
+        self.G.zero_()
+        self._c16: Dict[tuple, tuple] = {}
+        self._dy16 = None
+
+    def _cast(self, x2d, grad=False):
+        """bf16 copy of a GEMM operand.  Forward activations: made once per step and kept with their source (the copy also serves the weight
+        gradient; holding the source keeps the allocator from handing its address to another tensor).  Gradients are short-lived: only the
+        latest one is remembered (a layer's data and weight gradient ask for the same tensor back to back)."""
+        key = (x2d.data_ptr(), tuple(x2d.shape))
+        if grad:
+            if self._dy16 is not None and self._dy16[0] == key:
+                return self._dy16[2]
+            y = ops.cast_bf16(x2d)
+            self._dy16 = (key, x2d, y)
+            return y
+        hit = self._c16.get(key)
+        if hit is None:
+            hit = self._c16[key] = (x2d, ops.cast_bf16(x2d))
+        return hit[1]
+
+    def _fwd(self, x, l: Lin, residual=None, act=None, out_row_map=None):
+        if l.w16 is not None:
+            x = x if x.is_contiguous() else x.contiguous()
+            return ops.linear(self._cast(x), l.w16, l.b, residual=residual, act=act, out_row_map=out_row_map, out_dtype=F32)
+        return ops.linear(x, l.w, l.b, residual=residual, act=act, out_row_map=out_row_map)
+
+    def _ln(self, x, key):
+        V = self.fp.V
+        return ops.layernorm(x, V[key + ".weight"].p, V[key + ".bias"].p)
+
+    def _ln_bwd(self, dy, x, key, dx=None, accumulate=False):
+        V = self.fp.V
+        return ops.layernorm_bwd(dy, x, V[key + ".weight"].p, V[key + ".weight"].g, V[key + ".bias"].g, dx=dx, accumulate_dx=accumulate)

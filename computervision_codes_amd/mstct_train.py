@@ -24,8 +24,8 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import ops
+from .flatparams import FlatParams, GemmTrainer, Lin, _r4
 from .shapes import mstct_shapes
-from .tenco_train import allreduce_sum_flat
 
 F32 = torch.float32
 NCLS = {"i": 6, "v": 10, "t": 15, "ivt": 100}
@@ -37,24 +37,12 @@ POS_W = {"i": [0.93487068, 0.94234964, 0.93487068, 1.18448115, 1.02368339, 0.979
          "ivt": None}
 
 
-class _Lin:
-    """nn.Linear / Conv1d parameter pair with its gradient views and the transposed copy for the data gradient"""
-    __slots__ = ("name", "cout", "cout_real", "cin", "taps", "w", "b", "gw", "gb", "wt", "kpad", "conv_shape", "w16", "wt16")
-
-
-class _Vec:
-    __slots__ = ("name", "p", "g", "shape")
-
-
-def _r4(n: int) -> int:
-    return (n + 3) // 4 * 4
-
-
-class MstctTrainer:
+class MstctTrainer(GemmTrainer):
     def __init__(self, inter_channels: Sequence[int] = (256, 384, 576, 864), num_block: int = 2, head: int = 8, mlp_ratio: int = 8,
                  in_feat_dim: int = 1536, final_embedding_dim: int = 512, loss_type: str = "i", lr: float = 0.1, weight_decay: float = 1e-5,
                  device: str = "cuda", process_group=None, operand_dtype: torch.dtype = torch.float32):
         assert loss_type in NCLS
+        super().__init__(lr, weight_decay, device, process_group)
         assert operand_dtype in (torch.float32, torch.bfloat16)
         # bfloat16: the nn.Linear GEMMs (forward, data and weight gradients) read bf16 copies of their operands -- activations are cast on the
         # way in (`mt4_cast_f32_bf16`), weights re-derived from the fp32 masters after every step -- and accumulate / store in fp32; everything
@@ -63,96 +51,52 @@ class MstctTrainer:
         self.inter, self.nb, self.H, self.ratio = tuple(inter_channels), num_block, head, mlp_ratio
         self.D, self.E, self.loss_type, self.K = in_feat_dim, final_embedding_dim, loss_type, NCLS[loss_type]
         self.KP = _r4(self.K)
-        self.lr, self.wd = lr, weight_decay
-        self.dev, self.pg = torch.device(device), process_group
-        self.exchange = True
         self._table = mstct_shapes(in_feat_dim, self.inter, num_block, mlp_ratio, final_embedding_dim, loss_type)
-        self.lins: Dict[str, _Lin] = {}
-        self.vecs: Dict[str, _Vec] = {}
-        self._graphs: Dict[tuple, object] = {}
 
     # ------------------------------------------------------------------ parameters
     def _specs(self):
-        """(kind, name, ...) in flat-buffer order.  lin: (cout, cin, taps, conv_shape flag); vec: shape"""
+        """in flat-buffer order: lin (name, cout, cin, taps), then vec (name, shape)"""
         lin, vec = [], []
         cin = self.D
         for s, c in enumerate(self.inter, start=1):
             m = f"TemporalEncoder.Temporal_Merging_Block{s}"
-            lin.append((m + ".proj", c, cin, 3, True))
+            lin.append((m + ".proj", c, cin, 3))
             vec += [(m + ".norm.weight", (c,)), (m + ".norm.bias", (c,))]
             for b in range(self.nb):
                 q = f"TemporalEncoder.block{s}.{b}"
                 g, l = q + ".Global_Relational_Block", q + ".Local_Relational_Block"
                 vec += [(q + ".norm1.weight", (c,)), (q + ".norm1.bias", (c,)), (q + ".norm2.weight", (c,)), (q + ".norm2.bias", (c,)),
                         (l + ".TC.weight", (self.ratio * c, 3)), (l + ".TC.bias", (self.ratio * c,))]
-                lin += [(g + ".q", c, c, 1, False), (g + ".kv", 2 * c, c, 1, False), (g + ".proj", c, c, 1, False),
-                        (l + ".linear1", self.ratio * c, c, 1, False), (l + ".linear2", c, self.ratio * c, 1, False)]
+                lin += [(g + ".q", c, c, 1), (g + ".kv", 2 * c, c, 1), (g + ".proj", c, c, 1), (l + ".linear1", self.ratio * c, c, 1),
+                        (l + ".linear2", c, self.ratio * c, 1)]
             vec += [(f"TemporalEncoder.norm{s}.weight", (c,)), (f"TemporalEncoder.norm{s}.bias", (c,))]
             cin = c
         for i, c in zip((4, 3, 2, 1), reversed(self.inter)):
-            lin.append((f"Temporal_Mixer.linear_f{i}.proj", self.E, c, 1, False))
+            lin.append((f"Temporal_Mixer.linear_f{i}.proj", self.E, c, 1))
         for i in range(1, 10):
-            lin.append((f"Temporal_Mixer.linear{i}", self.E, self.E, 1, True))
+            lin.append((f"Temporal_Mixer.linear{i}", self.E, self.E, 1))
         q = f"classifier_{self.loss_type}"
-        lin += [(q + ".linear_fuse", self.E, 4 * self.E, 1, True), (q + ".linear_pred", self.K, self.E, 1, True)]
+        lin += [(q + ".linear_fuse", self.E, 4 * self.E, 1), (q + ".linear_pred", self.K, self.E, 1)]
         return lin, vec
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
         names = [k for k, _ in self._table]
         assert all(k in sd for k in names), "state dict incomplete"
         lin, vec = self._specs()
-        total = 0
-        for name, cout, cin, taps, _ in lin:
-            total += _r4(cout) * ops.packed_k(cin, 1, taps, F32) + _r4(cout)
+        # every derived matrix -- the fp32 transposed (tap-flipped) weights of the data gradients and, in the bf16-operand mode, the bf16 forward /
+        # transposed copies of the eligible nn.Linear layers -- comes from ONE launch over a table after each parameter change
+        fp = FlatParams(self.dev, self.op16)
+        for name, cout, cin, taps in lin:
+            fp.lin(name, cout, cin, taps=taps, dgrad=not name.endswith("Block1.proj"))   # (the first merge conv needs no data gradient)
         for name, shp in vec:
-            total += _r4(int(torch.tensor(shp).prod()))
-        self.P = torch.zeros(total, dtype=F32, device=self.dev)
-        self.G = torch.zeros(total, dtype=F32, device=self.dev)
-        off = 0
-        for name, cout, cin, taps, conv_shape in lin:
-            c = _Lin()
-            c.name, c.cout_real, c.cout, c.cin, c.taps, c.conv_shape = name, cout, _r4(cout), cin, taps, conv_shape
-            c.kpad = ops.packed_k(cin, 1, taps, F32)
-            nw = c.cout * c.kpad
-            c.w, c.gw = self.P[off:off + nw].view(c.cout, c.kpad), self.G[off:off + nw].view(c.cout, c.kpad)
-            c.b, c.gb = self.P[off + nw:off + nw + c.cout], self.G[off + nw:off + nw + c.cout]
-            off += nw + c.cout
-            w = sd[name + ".weight"].float()
-            w3 = w.reshape(cout, cin, taps)                                   # Linear [N,K] -> [N,K,1]; Conv1d [N,K,taps]
-            if c.cout != cout:
-                w3 = torch.cat([w3, torch.zeros(c.cout - cout, cin, taps)], 0)
-            c.w.copy_(ops.pack_conv_weight(w3.to(self.dev).unsqueeze(2), None, F32))
-            c.b[:cout].copy_(sd[name + ".bias"].float().to(self.dev))
-            c.wt = None if name.endswith("Block1.proj") else True          # (the first merge conv needs no data gradient; filled below)
-            c.w16 = c.wt16 = None
-            self.lins[name] = c
-        for name, shp in vec:
-            v = _Vec()
-            n = int(torch.tensor(shp).prod())
-            v.name, v.shape = name, shp
-            v.p, v.g = self.P[off:off + n].view(*shp), self.G[off:off + n].view(*shp)
-            off += _r4(n)
-            src = sd[name].float()
-            v.p.copy_((src[:, 0, :] if name.endswith("TC.weight") else src).to(self.dev))
-            self.vecs[name] = v
-        assert off == total
+            fp.vec(name, shp)
+        self.fp = fp.build(sd)
+        self.lins = fp.L
         E = self.E
         kp = ops.packed_k(E, 1, 1, F32)
         self._wsum = torch.zeros((3, E, kp), dtype=F32, device=self.dev)       # summed 1x1 mixer weights of scales 3, 2, 1
         self._bsum = torch.zeros((3, E), dtype=F32, device=self.dev)
         self._wsum_t = torch.zeros((3, E, ops.packed_k(E, 1, 1, F32)), dtype=F32, device=self.dev)
-        # every derived matrix -- the fp32 transposed (tap-flipped) weights of the data gradients and, in the bf16-operand mode, the bf16 forward /
-        # transposed copies of the eligible nn.Linear layers -- comes from ONE launch over a table after each parameter change
-        self._tab = ops.RefreshTable(self.dev)
-        for c in self.lins.values():
-            if c.wt is not None:
-                c.wt = self._tab.add(c.w, c.cout, c.cin, F32, True, [c.taps - 1 - i for i in range(c.taps)])
-            if self.op16 and c.taps == 1 and c.cin % 8 == 0 and c.cout % 8 == 0 and c.cout >= 64:
-                c.w16 = self._tab.add(c.w, c.cout, c.cin, torch.bfloat16, False, [0])
-                if c.wt is not None:
-                    c.wt16 = self._tab.add(c.w, c.cout, c.cin, torch.bfloat16, True, [0])
-        self._c16: Dict[tuple, tuple] = {}
-        self._dy16 = None
         self._refresh()
         return self
 
@@ -160,7 +104,7 @@ class MstctTrainer:
 
     def _refresh(self):
         """derived copies after a parameter change: transposed weights for the data gradients, summed mixer weights"""
-        self._tab.run()
+        self.fp.tab.run()
         for j, (_, ids) in enumerate(self._MIX):
             for n, i in enumerate(ids):
                 l = self.lins[f"Temporal_Mixer.linear{i}"]
@@ -168,30 +112,13 @@ class MstctTrainer:
                 ops.axpby_(l.b, self._bsum[j], 1.0, 0.0 if n == 0 else 1.0)
             ops.transpose_pack_conv1d(self._wsum[j], self.E, self.E, 1, out=self._wsum_t[j])
 
-    def _unpack(self, c: _Lin, packed: torch.Tensor, bias: torch.Tensor):
-        w = packed[:c.cout_real, :c.taps * c.cin].reshape(c.cout_real, c.taps, c.cin).permute(0, 2, 1).contiguous().cpu()
-        if not c.conv_shape:
-            w = w[:, :, 0].contiguous()
-        return w, bias[:c.cout_real].clone().cpu()
-
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """reference layout and key names (`Temporal_mstct/network.py`), on the CPU"""
-        out = {}
-        for name, c in self.lins.items():
-            out[name + ".weight"], out[name + ".bias"] = self._unpack(c, c.w, c.b)
-        for name, v in self.vecs.items():
-            t = v.p.clone().cpu()
-            out[name] = t.unsqueeze(1) if name.endswith("TC.weight") else t
+        out = self.fp.export("p")
         return {k: out[k] for k, _ in self._table}
 
     def grads(self) -> Dict[str, torch.Tensor]:
-        out = {}
-        for name, c in self.lins.items():
-            out[name + ".weight"], out[name + ".bias"] = self._unpack(c, c.gw, c.gb)
-        for name, v in self.vecs.items():
-            t = v.g.clone().cpu()
-            out[name] = t.unsqueeze(1) if name.endswith("TC.weight") else t
-        return out
+        return self.fp.export("g")
 
     # ------------------------------------------------------------------ randomness
     def draw_masks(self, b: int, t: int, generator: Optional[torch.Generator] = None) -> dict:
@@ -207,48 +134,19 @@ class MstctTrainer:
                 "feat_rows": ops.dropout_mask((b * t, self.E), seed, 2 * step + 1, 0.5, self.dev)}
 
     # ------------------------------------------------------------------ building blocks
-    def _cast(self, x2d, grad=False):
-        """bf16 copy of a GEMM operand.  Forward activations: made once per step and kept with their source (the copy also serves the weight
-        gradient; holding the source keeps the allocator from handing its address to another tensor).  Gradients are short-lived: only the
-        latest one is remembered (a layer's data and weight gradient ask for the same tensor back to back)."""
-        key = (x2d.data_ptr(), tuple(x2d.shape))
-        if grad:
-            if self._dy16 is not None and self._dy16[0] == key:
-                return self._dy16[2]
-            y = ops.cast_bf16(x2d)
-            self._dy16 = (key, x2d, y)
-            return y
-        hit = self._c16.get(key)
-        if hit is None:
-            hit = self._c16[key] = (x2d, ops.cast_bf16(x2d))
-        return hit[1]
-
-    def _fwd(self, x2d, c: _Lin, residual=None, act=None, out=None):
-        if c.w16 is not None:
-            x2d = x2d if x2d.is_contiguous() else x2d.contiguous()
-            return ops.linear(self._cast(x2d), c.w16, c.b, residual=residual, act=act, out=out, out_dtype=F32)
-        return ops.linear(x2d, c.w, c.b, residual=residual, act=act, out=out)
-
-    def _dgrad(self, dy2d, c: _Lin, residual=None):
+    def _dgrad(self, dy2d, c: Lin, residual=None):
         if c.wt16 is not None:
             dy2d = dy2d if dy2d.is_contiguous() else dy2d.contiguous()
             return ops.linear(self._cast(dy2d, grad=True), c.wt16, None, residual=residual, out_dtype=F32)
         return ops.linear(dy2d, c.wt, None, residual=residual)
 
-    def _wgrad(self, dy2d, x2d, c: _Lin):
+    def _wgrad(self, dy2d, x2d, c: Lin):
         m = dy2d.shape[0]
         if c.w16 is not None and m % 16 == 0 and dy2d.is_contiguous() and x2d.is_contiguous():    # rows as a [M / 16, 16] pixel grid of one image
             ops.wgrad_conv2d_bf16(self._cast(dy2d, grad=True).view(1, m // 16, 16, c.cout), self._cast(x2d).view(1, m // 16, 16, c.cin), c.gw, 1, 1)
             ops.colsum(dy2d, c.gb, accumulate=True)
         else:   # (G is zeroed once per step; the bias gradient rides in the weight gradient's launch)
             ops.wgrad_conv1d(dy2d, x2d, c.gw, batch=1, t=m, taps=1, dil=1, pad=0, accumulate=True, bias_grad=c.gb)
-
-    def _ln(self, x, name):
-        return ops.layernorm(x, self.vecs[name + ".weight"].p, self.vecs[name + ".bias"].p)
-
-    def _ln_bwd(self, dy, x, name, dx=None, accumulate=False):
-        return ops.layernorm_bwd(dy, x, self.vecs[name + ".weight"].p, self.vecs[name + ".weight"].g, self.vecs[name + ".bias"].g, dx=dx,
-                                 accumulate_dx=accumulate)
 
     def _attention_fwd(self, q, kv, b, t, c):
         hd, H = c // self.H, self.H
@@ -282,9 +180,7 @@ class MstctTrainer:
         """x [B,T,D] frame-major, z [B*T,K] multi-hot fp32, masks as ROWS ([B*T,D] / [B*T,E]) or None.  Returns per-column loss sums [K]."""
         b, t, d = x_btd.shape
         M, E, L = b * t, self.E, self.lins
-        self.G.zero_()
-        self._c16.clear()
-        self._dy16 = None
+        self._begin_step()
         x = x_btd.contiguous().view(M, d)
         if mask_in is not None:
             x = ops.mul_add(x, mask_in)
@@ -305,7 +201,7 @@ class MstctTrainer:
                 x_mid = self._fwd(o, L[g_ + ".proj"], residual=y)
                 n2 = self._ln(x_mid, q_ + ".norm2")
                 h1 = self._fwd(n2, L[l_ + ".linear1"])
-                h2 = ops.dwconv1d_k3(h1.view(b, t, -1), self.vecs[l_ + ".TC.weight"].p, self.vecs[l_ + ".TC.bias"].p, act="none").view(M, -1)
+                h2 = ops.dwconv1d_k3(h1.view(b, t, -1), self.fp.V[l_ + ".TC.weight"].p, self.fp.V[l_ + ".TC.bias"].p, act="none").view(M, -1)
                 h3 = ops.gelu(h2)
                 y_out = self._fwd(h3, L[l_ + ".linear2"], residual=x_mid)
                 st["blocks"].append(dict(x_in=y, n1=n1, q=q, kv=kv, P=P, o=o, x_mid=x_mid, n2=n2, h1=h1, h2=h2, h3=h3))
@@ -373,8 +269,8 @@ class MstctTrainer:
                 self._wgrad(g, blk["h3"], L[l_ + ".linear2"])
                 dh3 = self._dgrad(g, L[l_ + ".linear2"])
                 dh2 = ops.gelu_bwd(dh3, blk["h2"], out=dh3)
-                dh1 = ops.dwconv1d_k3_bwd(dh2.view(b, t, -1), blk["h1"].view(b, t, -1), self.vecs[l_ + ".TC.weight"].p,
-                                          self.vecs[l_ + ".TC.weight"].g, self.vecs[l_ + ".TC.bias"].g).view(M, -1)
+                dh1 = ops.dwconv1d_k3_bwd(dh2.view(b, t, -1), blk["h1"].view(b, t, -1), self.fp.V[l_ + ".TC.weight"].p,
+                                          self.fp.V[l_ + ".TC.weight"].g, self.fp.V[l_ + ".TC.bias"].g).view(M, -1)
                 self._wgrad(dh1, blk["n2"], L[l_ + ".linear1"])
                 dn2 = self._dgrad(dh1, L[l_ + ".linear1"])
                 self._ln_bwd(dn2, blk["x_mid"], q_ + ".norm2", dx=g, accumulate=True)
@@ -430,29 +326,18 @@ class MstctTrainer:
         mi = masks["input_rows"] if "input_rows" in masks else rows(masks["input"]) if masks.get("input") is not None else None
         mf = masks["feat_rows"] if "feat_rows" in masks else rows(masks["feat"]) if masks.get("feat") is not None else None
         if use_graph:
-            key = (b, t, mi is not None, mf is not None)
-            g = self._graphs.get(key)
             ins = [x_btd, z] + ([mi] if mi is not None else []) + ([mf] if mf is not None else [])
-            if g is None:
-                from .graph import GraphedForward
 
-                def fn(xx, zz, *ms):
-                    ms = list(ms)
-                    return self._fwd_bwd(xx, zz, ms.pop(0) if mi is not None else None, ms.pop(0) if mf is not None else None)
-                g = self._graphs[key] = GraphedForward(fn, ins)
-            col_loss = g(*ins)
+            def fn(xx, zz, *ms):
+                ms = list(ms)
+                return self._fwd_bwd(xx, zz, ms.pop(0) if mi is not None else None, ms.pop(0) if mf is not None else None)
+            col_loss = self._graph_step((b, t, mi is not None, mf is not None), fn, ins)
         else:
             col_loss = self._fwd_bwd(x_btd, z, mi, mf)
         loss = float(col_loss.sum().item()) / (b * t * self.K)
         if apply_update:
             self.apply_update()
         return loss
-
-    def apply_update(self):
-        """DDP exchange (one all-reduce of the flat gradient buffer, mean over ranks) + SGD + refresh of the derived copies"""
-        scale = allreduce_sum_flat(self.G, self.pg) if self.exchange else 1.0
-        ops.sgd_step(self.P, self.G, self.lr, self.wd, scale)
-        self._refresh()
 
 
 # ------------------------------------------------------------------------------------------------ Temporal_mstct/run.py -t

@@ -22,7 +22,7 @@ Randomness (DropPath per block and sample, the transformer's dropouts) is passed
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import torch
 
@@ -31,7 +31,7 @@ from .shapes import SWIN_CFG, q2l_param_shapes, swin_window
 from .spatial_transformer import _merge_row_map, _rel_pos_index, _shift_mask, _window_row_map, sine_position_rows
 from .synth import IMAGENET_MEAN, IMAGENET_STD
 from .spatial_cnn_train import TARGET_W, TOOL_W, VERB_W
-from .tenco_train import allreduce_sum_flat
+from .flatparams import FlatParams, GemmTrainer, Lin
 
 F32 = torch.float32
 NCLS = {"i": 6, "v": 10, "t": 15, "ivt": 100}
@@ -40,107 +40,7 @@ POS_W = {"i": TOOL_W, "v": VERB_W, "t": TARGET_W}                               
 NHEAD, FFN = 4, 8192                                                               # `transformer.py:347-359` (build_transformer)
 
 
-def _r4(n: int) -> int:
-    return (n + 3) // 4 * 4
-
-
-class _Lin:
-    """a GEMM weight (packed) + bias with gradient views; `wt` = transposed packed copy for the data gradient"""
-    __slots__ = ("name", "wkey", "bkey", "cout", "cin", "w", "b", "gw", "gb", "wt", "shape", "w16", "wt16")
-
-
-class _Vec:
-    __slots__ = ("key", "p", "g", "shape")
-
-
-class FlatParams:
-    """all trained tensors in ONE flat parameter buffer P and ONE flat gradient buffer G (packed GEMM layouts), plus the derived transposed
-    copies; state-dict in / out in the reference's key names and shapes"""
-
-    def __init__(self, device, op16: bool = False):
-        self.dev, self.op16 = device, op16
-        self.tab = ops.RefreshTable(device)          # every derived matrix (transposed fp32, bf16 copies) from one launch per refresh
-        self._lin: List[tuple] = []
-        self._vec: List[tuple] = []
-        self.L: Dict[str, _Lin] = {}
-        self.V: Dict[str, _Vec] = {}
-        self._slices: List[tuple] = []
-
-    def lin(self, name, wkey, bkey, cout, cin, need_dgrad=True):
-        self._lin.append((name, wkey, bkey, cout, cin, need_dgrad))
-
-    def vec(self, key, shape):
-        self._vec.append((key, tuple(shape)))
-
-    def build(self, sd):
-        total = sum(c * ops.packed_k(ci, 1, 1, F32) + _r4(c) for _, _, _, c, ci, _ in self._lin) + sum(_r4(int(torch.tensor(s).prod())) for _, s in self._vec)
-        self.P = torch.zeros(total, dtype=F32, device=self.dev)
-        self.G = torch.zeros(total, dtype=F32, device=self.dev)
-        off = 0
-        for name, wkey, bkey, cout, cin, need_dgrad in self._lin:
-            assert cout % 4 == 0 and cin % 4 == 0, (name, cout, cin)
-            l = _Lin()
-            l.name, l.wkey, l.bkey, l.cout, l.cin = name, wkey, bkey, cout, cin
-            kp = ops.packed_k(cin, 1, 1, F32)
-            n = cout * kp
-            l.w, l.gw = self.P[off:off + n].view(cout, kp), self.G[off:off + n].view(cout, kp)
-            l.b, l.gb = (self.P[off + n:off + n + cout], self.G[off + n:off + n + cout]) if bkey else (None, None)
-            off += n + _r4(cout)
-            w = sd[wkey].float()
-            l.shape = tuple(w.shape)
-            l.w.copy_(ops.pack_linear_weight(w.reshape(cout, cin).to(self.dev), F32))
-            if bkey:
-                l.b.copy_(sd[bkey].float().to(self.dev))
-            self._derive(l, need_dgrad)
-            self.L[name] = l
-        for key, shape in self._vec:
-            v = _Vec()
-            n = int(torch.tensor(shape).prod())
-            v.key, v.shape = key, tuple(sd[key].shape)
-            v.p, v.g = self.P[off:off + n].view(*shape), self.G[off:off + n].view(*shape)
-            off += _r4(n)
-            v.p.copy_(sd[key].float().reshape(shape).to(self.dev))
-            self.V[key] = v
-        assert off == total
-        self.refresh()
-        return self
-
-    def _derive(self, l: _Lin, need_dgrad: bool):
-        """the matrices the kernels read besides the master weight: the transposed copy for the data gradient (fp32) and, in the bf16-operand
-        mode, bf16 copies of both for the GEMMs whose channel counts allow it"""
-        l.wt = self.tab.add(l.w, l.cout, l.cin, F32, True, [0]) if need_dgrad else None
-        l.w16 = l.wt16 = None
-        if self.op16 and l.cin % 8 == 0 and l.cout % 8 == 0 and l.cout >= 64:
-            l.w16 = self.tab.add(l.w, l.cout, l.cin, torch.bfloat16, False, [0])
-            if need_dgrad:
-                l.wt16 = self.tab.add(l.w, l.cout, l.cin, torch.bfloat16, True, [0])
-
-    def rows(self, name: str, lo: int, hi: int) -> _Lin:
-        """a row slice of a packed weight (nn.MultiheadAttention's in_proj split into q / k / v) with its own transposed copy"""
-        src = self.L[name]
-        l = _Lin()
-        l.name, l.cout, l.cin = f"{name}[{lo}:{hi}]", hi - lo, src.cin
-        l.w, l.gw, l.b, l.gb = src.w[lo:hi], src.gw[lo:hi], src.b[lo:hi], src.gb[lo:hi]
-        self._derive(l, True)
-        self._slices.append(l)
-        return l
-
-    def refresh(self):
-        self.tab.run()
-
-    def _export(self, which: str) -> Dict[str, torch.Tensor]:
-        out = {}
-        for l in self.L.values():
-            wsrc, bsrc = (l.w, l.b) if which == "p" else (l.gw, l.gb)
-            out[l.wkey] = wsrc[:, :l.cin].reshape(l.shape).clone().cpu()
-            if l.bkey:
-                out[l.bkey] = bsrc.clone().cpu()
-        for v in self.V.values():
-            out[v.key] = (v.p if which == "p" else v.g).reshape(v.shape).clone().cpu()
-        return out
-
-
-class Q2LTrainer:
+class Q2LTrainer(GemmTrainer):
     def __init__(self, backbone: str = "swin_L_384_22k", img_size: int = 384, hidden_dim: int = 1536, loss_type: str = "i", lr: float = 0.01,
                  weight_decay: float = 1e-5, drop_path_rate: float = 0.1, device: str = "cuda", process_group=None,
                  operand_dtype: torch.dtype = torch.float32, teacher_dim: int = 512, rates=(1.0, 0.0, 0.1), temp: float = 4.0):
@@ -152,14 +52,11 @@ class Q2LTrainer:
         self.teacher_dim, self.rates, self.temp = int(teacher_dim), tuple(float(r) for r in rates), float(temp)   # `run.py:66,70` (--rates default 1 0 0.1)
         self.cfg = SWIN_CFG[backbone]
         assert self.d == self.cfg["embed_dim"] * 8, "hidden_dim is the backbone's final width (backbone.py:188-201)"
-        self.lr, self.wd, self.dev, self.pg = lr, weight_decay, torch.device(device), process_group
+        super().__init__(lr, weight_decay, device, process_group)
         assert operand_dtype in (torch.float32, torch.bfloat16)
         # bfloat16: the nn.Linear / patch-embedding GEMMs (forward, data and weight gradients) read bf16 copies of their operands; activations,
         # accumulation, everything between the GEMMs and the master weights stay fp32 (as in `MstctTrainer`)
         self.op16 = operand_dtype == torch.bfloat16
-        self._c16: Dict[tuple, tuple] = {}
-        self._dy16 = None
-        self.exchange = True
         self._table = q2l_param_shapes(backbone, self.S, self.d, loss_type, teacher_dim=self.teacher_dim)
         nblk = sum(self.cfg["depths"])
         self.drop_probs = [drop_path_rate * i / max(1, nblk - 1) for i in range(nblk)]     # `swin_transformer.py:517` (linspace 0 .. rate)
@@ -168,8 +65,11 @@ class Q2LTrainer:
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
         assert all(k in sd for k, _ in self._table), "state dict incomplete"
         fp, pre, C0, d = FlatParams(self.dev, self.op16), "backbone.0.", self.cfg["embed_dim"], self.d
-        fp.lin("pe", pre + "patch_embed.proj.weight", pre + "patch_embed.proj.bias", C0, 48, need_dgrad=False)
-        fp.vec(pre + "patch_embed.norm.weight", (C0,)); fp.vec(pre + "patch_embed.norm.bias", (C0,))
+        vecs = []                                     # (the layout: every GEMM weight first, then the vectors in declaration order)
+        vec = lambda key, shape: vecs.append((key, shape))
+        lin = lambda name, wkey, bkey, cout, cin, dgrad=True: fp.lin(name, cout, cin, wkey=wkey, bkey=bkey, bias=bkey is not None, dgrad=dgrad)
+        lin("pe", pre + "patch_embed.proj.weight", pre + "patch_embed.proj.bias", C0, 48, dgrad=False)
+        vec(pre + "patch_embed.norm.weight", (C0,)); vec(pre + "patch_embed.norm.bias", (C0,))
         self.stages = []
         for s, (depth, nh) in enumerate(zip(self.cfg["depths"], self.cfg["num_heads"])):
             ws, res = swin_window(self.backbone, self.S, s)
@@ -179,58 +79,59 @@ class Q2LTrainer:
                 q = f"{pre}layers.{s}.blocks.{b}."
                 shift = 0 if (b % 2 == 0 or res <= self.cfg["window_size"]) else self.cfg["window_size"] // 2
                 for n_ in ("norm1", "norm2"):
-                    fp.vec(q + n_ + ".weight", (C,)); fp.vec(q + n_ + ".bias", (C,))
-                fp.vec(q + "attn.relative_position_bias_table", ((2 * ws - 1) ** 2, nh))
-                fp.lin(q + "qkv", q + "attn.qkv.weight", q + "attn.qkv.bias", 3 * C, C)
-                fp.lin(q + "proj", q + "attn.proj.weight", q + "attn.proj.bias", C, C)
-                fp.lin(q + "fc1", q + "mlp.fc1.weight", q + "mlp.fc1.bias", 4 * C, C)
-                fp.lin(q + "fc2", q + "mlp.fc2.weight", q + "mlp.fc2.bias", C, 4 * C)
+                    vec(q + n_ + ".weight", (C,)); vec(q + n_ + ".bias", (C,))
+                vec(q + "attn.relative_position_bias_table", ((2 * ws - 1) ** 2, nh))
+                lin(q + "qkv", q + "attn.qkv.weight", q + "attn.qkv.bias", 3 * C, C)
+                lin(q + "proj", q + "attn.proj.weight", q + "attn.proj.bias", C, C)
+                lin(q + "fc1", q + "mlp.fc1.weight", q + "mlp.fc1.bias", 4 * C, C)
+                lin(q + "fc2", q + "mlp.fc2.weight", q + "mlp.fc2.bias", C, 4 * C)
                 blocks.append(dict(q=q, shift=shift, row_map=_window_row_map(res, ws, shift).to(self.dev),
                                    mask=_shift_mask(res, ws, shift).to(self.dev) if shift > 0 else None))
             st = dict(res=res, ws=ws, nh=nh, C=C, blocks=blocks, idx=_rel_pos_index(ws).reshape(-1).to(torch.int32).to(self.dev))
             if s < 3:
                 q = f"{pre}layers.{s}.downsample."
-                fp.vec(q + "norm.weight", (4 * C,)); fp.vec(q + "norm.bias", (4 * C,))
-                fp.lin(q + "red", q + "reduction.weight", None, 2 * C, 4 * C)
+                vec(q + "norm.weight", (4 * C,)); vec(q + "norm.bias", (4 * C,))
+                lin(q + "red", q + "reduction.weight", None, 2 * C, 4 * C)
+                fp.reserve(2 * C)                    # (the layout keeps a bias slot)
                 st["merge"] = dict(q=q, row_map=_merge_row_map(res).to(self.dev))
             self.stages.append(st)
-        fp.vec(pre + "norm.weight", (d,)); fp.vec(pre + "norm.bias", (d,))
+        vec(pre + "norm.weight", (d,)); vec(pre + "norm.bias", (d,))
         for task in self.tasks:
             dq, K = f"decoder_{task}.", NCLS[task]
-            fp.lin("in_proj." + task, dq + "input_proj.weight", dq + "input_proj.bias", d, d)
-            fp.vec(dq + "query_embed.weight", (K, d)); fp.vec(dq + "fc.W", (K, d)); fp.vec(dq + "fc.b", (K,))
+            lin("in_proj." + task, dq + "input_proj.weight", dq + "input_proj.bias", d, d)
+            vec(dq + "query_embed.weight", (K, d)); vec(dq + "fc.W", (K, d)); vec(dq + "fc.b", (K,))
         if self.loss_type == "all":              # KD adaptors (`network.py:75-80`): Conv1d(k = 1) on [B, C, 1] = linear layers
             for n in ("wi", "wv", "wt"):
-                fp.lin(n, n + ".weight", n + ".bias", self.teacher_dim, d)
+                lin(n, n + ".weight", n + ".bias", self.teacher_dim, d)
             for n in ("mi", "mv", "mt"):
-                fp.lin(n, n + ".weight", n + ".bias", d, self.teacher_dim, need_dgrad=False)
+                lin(n, n + ".weight", n + ".bias", d, self.teacher_dim, dgrad=False)
         t = self.tprefix = f"decoder_{self.tasks[0]}.transformer."     # the ONE Transformer (`named_parameters()` lists it under its first owner)
         layers = [("enc", t + "encoder.layers.0", "self_attn", ("norm1", "norm2"))] + \
                  [(f"dec{i}", f"{t}decoder.layers.{i}", "multihead_attn", ("norm2", "norm3")) for i in range(2)]
         for tag, lp, att, norms in layers:
-            fp.lin(tag + ".in", f"{lp}.{att}.in_proj_weight", f"{lp}.{att}.in_proj_bias", 3 * d, d, need_dgrad=False)
-            fp.lin(tag + ".out", f"{lp}.{att}.out_proj.weight", f"{lp}.{att}.out_proj.bias", d, d)
-            fp.lin(tag + ".l1", lp + ".linear1.weight", lp + ".linear1.bias", FFN, d)
-            fp.lin(tag + ".l2", lp + ".linear2.weight", lp + ".linear2.bias", d, FFN)
+            lin(tag + ".in", f"{lp}.{att}.in_proj_weight", f"{lp}.{att}.in_proj_bias", 3 * d, d, dgrad=False)
+            lin(tag + ".out", f"{lp}.{att}.out_proj.weight", f"{lp}.{att}.out_proj.bias", d, d)
+            lin(tag + ".l1", lp + ".linear1.weight", lp + ".linear1.bias", FFN, d)
+            lin(tag + ".l2", lp + ".linear2.weight", lp + ".linear2.bias", d, FFN)
             for n_ in norms:
-                fp.vec(f"{lp}.{n_}.weight", (d,)); fp.vec(f"{lp}.{n_}.bias", (d,))
-        fp.vec(t + "decoder.norm.weight", (d,)); fp.vec(t + "decoder.norm.bias", (d,))
-        fp.build(sd)
-        self.fp, self.P, self.G = fp, fp.P, fp.G
+                vec(f"{lp}.{n_}.weight", (d,)); vec(f"{lp}.{n_}.bias", (d,))
+        vec(t + "decoder.norm.weight", (d,)); vec(t + "decoder.norm.bias", (d,))
+        for key, shape in vecs:
+            fp.vec(key, shape)
+        self.fp = fp.build(sd)
         self.att = {tag: tuple(fp.rows(tag + ".in", i * d, (i + 1) * d) for i in range(3)) for tag, *_ in layers}
-        fp.refresh()                                   # (the q / k / v row slices joined the table after build())
+        self._refresh()
         self.layer_prefix = {tag: lp for tag, lp, _, _ in layers}
         self.layer_norms = {tag: norms for tag, _, _, norms in layers}
         hh = self.S // 32
         self.pos = sine_position_rows(d, hh, hh).to(self.dev, F32)
         self.pos_w = {t: torch.tensor(POS_W[t], dtype=F32, device=self.dev) for t in self.tasks if t in POS_W}     # ivt: plain BCE (`run.py:342`)
-        self._graphs: Dict[tuple, object] = {}
         return self
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """the reference's parameter names and shapes; loss_type all: followed by the shared transformer's three alias entries per tensor
         (decoder_v / _t / _ivt.transformer.*), as the reference module's own `state_dict()` lists them (`run.py:266-277` saves that)"""
-        out = self.fp._export("p")
+        out = self.fp.export("p")
         sd = {k: out[k] for k, _ in self._table}
         if self.loss_type == "all":
             from .shapes import q2l_state_dict_aliases
@@ -239,7 +140,7 @@ class Q2LTrainer:
         return sd
 
     def grads(self) -> Dict[str, torch.Tensor]:
-        return self.fp._export("g")
+        return self.fp.export("g")
 
     # ------------------------------------------------------------------ randomness
     def mask_specs(self, b: int):
@@ -274,28 +175,7 @@ class Q2LTrainer:
         return {"droppath": dp, "tx": tx}
 
     # ------------------------------------------------------------------ building blocks
-    def _cast(self, x2d, grad=False):
-        """bf16 copy of a GEMM operand: forward activations once per step, kept with their source (the copy also serves the weight gradient, and
-        holding the source keeps the allocator from reusing its address); of the short-lived gradients only the latest is remembered"""
-        key = (x2d.data_ptr(), tuple(x2d.shape))
-        if grad:
-            if self._dy16 is not None and self._dy16[0] == key:
-                return self._dy16[2]
-            y = ops.cast_bf16(x2d)
-            self._dy16 = (key, x2d, y)
-            return y
-        hit = self._c16.get(key)
-        if hit is None:
-            hit = self._c16[key] = (x2d, ops.cast_bf16(x2d))
-        return hit[1]
-
-    def _fwd(self, x, l: _Lin, residual=None, act=None, out_row_map=None):
-        if l.w16 is not None:
-            x = x if x.is_contiguous() else x.contiguous()
-            return ops.linear(self._cast(x), l.w16, l.b, residual=residual, act=act, out_row_map=out_row_map, out_dtype=F32)
-        return ops.linear(x, l.w, l.b, residual=residual, act=act, out_row_map=out_row_map)
-
-    def _bwd(self, dy, x, l: _Lin, need_dx=True, residual=None, gate=None):
+    def _bwd(self, dy, x, l: Lin, need_dx=True, residual=None, gate=None):
         """parameter gradients of y = x W^T + b from dy; returns dx (+ residual; gate: ReLU of the layer below, `act=relu_gate`)"""
         m = dy.shape[0]
         mixed = l.w16 is not None and m % 16 == 0
@@ -317,13 +197,6 @@ class Q2LTrainer:
         if gate is not None:
             return ops.linear(dy, l.wt, None, residual=gate, act="relu_gate")
         return ops.linear(dy, l.wt, None, residual=residual)
-
-    def _ln(self, x, key):
-        return ops.layernorm(x, self.fp.V[key + ".weight"].p, self.fp.V[key + ".bias"].p)
-
-    def _ln_bwd(self, dy, x, key, dx=None, accumulate=False):
-        V = self.fp.V
-        return ops.layernorm_bwd(dy, x, V[key + ".weight"].p, V[key + ".weight"].g, V[key + ".bias"].g, dx=dx, accumulate_dx=accumulate)
 
     def _attn_fwd(self, q, k, v, nb, nh, nq, nk, sq, sk, sv, dout, scale, bias=None, index=None, mask=None, drop=None):
         """softmax(scale q k^T [+ bias + mask]) v on head slices: q rows [nb*nq] of pitch sq, k / v rows [nb*nk] of pitch sk / sv, head h at
@@ -554,9 +427,7 @@ class Q2LTrainer:
         masks = masks or {}
         tx = masks.get("tx") or {}
         allm = self.loss_type == "all"
-        self.G.zero_()
-        self._c16.clear()
-        self._dy16 = None
+        self._begin_step()
         feats, bb = self._backbone_fwd(img, B, masks.get("droppath"))
         # ---- decoders forward
         tms = {t: (lambda k, pk=(t + "/" if allm else ""): tx.get(pk + k)) for t in self.tasks}
@@ -652,8 +523,3 @@ class Q2LTrainer:
         if apply_update:
             self.apply_update()
         return terms
-
-    def apply_update(self):
-        scale = allreduce_sum_flat(self.G, self.pg) if self.exchange else 1.0
-        ops.sgd_step(self.P, self.G, self.lr, self.wd, scale)
-        self.fp.refresh()

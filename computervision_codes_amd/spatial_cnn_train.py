@@ -18,8 +18,8 @@ from typing import Dict, List, Sequence
 import torch
 
 from . import ops
+from .flatparams import FlatParams, FlatTrainer
 from .shapes import resnet_feat_dim, spatial_cnn_shapes
-from .tenco_train import allreduce_sum_flat
 
 _DEPTHS = {"resnet18": (2, 2, 2, 2), "resnet50": (3, 4, 6, 3)}
 _ALL_HEADS = (("i", 6), ("v", 10), ("t", 15), ("ivt", 100))
@@ -38,7 +38,7 @@ class _Unit:
                  "sums_f", "sums_b", "w16", "wt16", "phase_w16")
 
 
-class SpatialCnnTrainer:
+class SpatialCnnTrainer(FlatTrainer):
     op16 = False                # (class defaults: GEMM operands fp32; no derived-weight table built yet)
     _refresh_table = None
     def __init__(self, network: str = "resnet50", lr: float = 0.01, weight_decay: float = 1e-5, rates: Sequence[float] = (1.0, 1.0, 1.0),
@@ -58,11 +58,9 @@ class SpatialCnnTrainer:
         self.heads = _ALL_HEADS if loss_type == "all" else tuple(h for h in _ALL_HEADS if h[0] == loss_type)
         self.NH = sum(k for _, k in self.heads)
         self.NHP = (self.NH + 3) // 4 * 4
-        self.network, self.lr, self.wd, self.rates, self.temp = network, lr, weight_decay, tuple(rates), float(temp)
-        self.overlap = overlap            # DDP: all-reduce each gradient bucket as soon as the backward has written it (eager steps)
-        self._pending: list = []
-        self._capturing = False
-        self.dev, self.pg = torch.device(device), process_group
+        # overlap: each gradient bucket is all-reduced as soon as the backward has written it (DDP, `FlatTrainer`)
+        super().__init__(lr, weight_decay, device, process_group, overlap)
+        self.network, self.rates, self.temp = network, tuple(rates), float(temp)
         self.C = resnet_feat_dim(network)
         self.TD = int(teacher_dim)          # `--teacher_dim` (`Spatial_cnn/run.py:82`): width of the teachers' frame features
         self._table = spatial_cnn_shapes(network, self.C, self.TD, loss_type)
@@ -93,66 +91,36 @@ class SpatialCnnTrainer:
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
         assert all(k in sd for k, _ in self._table), "state dict incomplete"
-        dev, C = self.dev, self.C
+        dev, C, TD = self.dev, self.C, self.TD
         specs = self._unit_specs()
-        TD = self.TD
-        NH, NHP, _HEADS = self.NH, self.NHP, self.heads
-        lin = [("heads", NHP, C)]
-        if self.loss_type == "all":
-            lin += [("wi", TD, C), ("wv", TD, C), ("wt", TD, C), ("mi", C, TD), ("mv", C, TD), ("mt", C, TD)]
-        r4 = lambda n: (n + 3) // 4 * 4
-        total = sum(co * ops.packed_k(ci, k, k, F32) + 2 * r4(co) for _, _, ci, co, k, _, _ in specs)
-        total += sum(co * ops.packed_k(ci, 1, 1, F32) + r4(co) for _, co, ci in lin)
-        self.P, self.G = torch.zeros(total, dtype=F32, device=dev), torch.zeros(total, dtype=F32, device=dev)
-        off = 0
-
-        def take(n, shape=None):
-            nonlocal off
-            p, g = self.P[off:off + n], self.G[off:off + n]
-            off += r4(n)
-            return (p.view(shape), g.view(shape)) if shape else (p, g)
-
-        trained = set()
-        self._ranges: Dict[str, list] = {}     # flat-buffer range of every gradient bucket: "stem", "layer1".."layer4", "heads"
+        # gradient buckets: "stem", "layer1".."layer4", "heads" (heads + KD branch); a unit is its conv weight, BN gamma, BN beta
+        fp = FlatParams(dev)
         for conv, bn, ci, co, k, s, pad in specs:
-            bucket = conv.split(".")[2] if ".layer" in conv else "stem"
-            self._ranges.setdefault(bucket, [off, off])
+            fp.bucket(conv.split(".")[2] if ".layer" in conv else "stem")
+            stem = (torch.cat([sd[conv + ".weight"].float(), torch.zeros(co, 1, 7, 7)], 1), None) if ci == 4 else None
+            fp.lin(conv, co, ci, taps=k, kh=k, bias=False, src=stem)
+            fp.vec(bn + ".weight", (co,))
+            fp.vec(bn + ".bias", (co,))
+        fp.bucket("heads")
+        fp.lin("heads", self.NH, C, src=(torch.cat([sd[f"classifier_{t}.fc.weight"] for t, _ in self.heads], 0),
+                                         torch.cat([sd[f"classifier_{t}.fc.bias"] for t, _ in self.heads], 0)))
+        if self.loss_type == "all":
+            for name, co, ci in (("wi", TD, C), ("wv", TD, C), ("wt", TD, C), ("mi", C, TD), ("mv", C, TD), ("mt", C, TD)):
+                fp.lin(name, co, ci)
+        self.fp = fp.build(sd, derive=False)    # (the derived copies: `_refresh_transposed`)
+        trained = fp.keys() | {f"classifier_{t}.fc.{p}" for t, _ in self.heads for p in ("weight", "bias")}
+        for conv, bn, ci, co, k, s, pad in specs:
             u = _Unit()
             u.name, u.bn, u.cin, u.cout, u.k, u.stride, u.pad = conv, bn, ci, co, k, s, pad
-            kp = ops.packed_k(ci, k, k, F32)
-            u.w, u.gw = take(co * kp, (co, kp))
-            u.gamma, u.ggamma = take(co)
-            u.beta, u.gbeta = take(co)
-            w = sd[conv + ".weight"].float().to(dev)
-            if ci == 4 and k == 7:
-                w = torch.cat([w, torch.zeros(co, 1, 7, 7, device=dev)], 1)
-            u.w.copy_(ops.pack_conv_weight(w, None, F32))
-            u.gamma.copy_(sd[bn + ".weight"].float())
-            u.beta.copy_(sd[bn + ".bias"].float())
+            u.w, u.gw = fp.L[conv].w, fp.L[conv].gw
+            u.gamma, u.ggamma = fp.V[bn + ".weight"].p, fp.V[bn + ".weight"].g
+            u.beta, u.gbeta = fp.V[bn + ".bias"].p, fp.V[bn + ".bias"].g
             u.rmean, u.rvar = sd[bn + ".running_mean"].float().to(dev).clone(), sd[bn + ".running_var"].float().to(dev).clone()
             self.nbt[bn] = int(sd[bn + ".num_batches_tracked"])
             u.wt, u.phase_w = None, None
             u.w16, u.wt16, u.phase_w16 = None, None, None
             self.units[conv] = u
-            self._ranges[bucket][1] = off
-            trained |= {conv + ".weight", bn + ".weight", bn + ".bias", bn + ".running_mean", bn + ".running_var", bn + ".num_batches_tracked"}
-        self.lin: Dict[str, tuple] = {}
-        self._ranges["heads"] = [off, total]
-        for name, co, ci in lin:
-            kp = ops.packed_k(ci, 1, 1, F32)
-            w, gw = take(co * kp, (co, kp))
-            b, gb = take(co)
-            if name == "heads":
-                wsrc = torch.cat([sd[f"classifier_{t}.fc.weight"].float() for t, _ in _HEADS] + [torch.zeros(NHP - NH, C)], 0)
-                bsrc = torch.cat([sd[f"classifier_{t}.fc.bias"].float() for t, _ in _HEADS] + [torch.zeros(NHP - NH)], 0)
-                trained |= {f"classifier_{t}.fc.{p}" for t, _ in _HEADS for p in ("weight", "bias")}
-            else:
-                wsrc, bsrc = sd[name + ".weight"].float()[:, :, 0], sd[name + ".bias"].float()
-                trained |= {name + ".weight", name + ".bias"}
-            w.copy_(ops.pack_linear_weight(wsrc.to(dev), F32))
-            b.copy_(bsrc.to(dev))
-            self.lin[name] = (w, b, gw, gb, co, ci)
-        assert off == total
+            trained |= {bn + ".running_mean", bn + ".running_var", bn + ".num_batches_tracked"}
         # float64 scratch of every BatchNorm reduction of a step (forward 2C -- or its STAT_REPLICAS copies when the convolution's epilogue
         # fills them -- and backward 2C), zeroed once per step
         rep = ops.STAT_REPLICAS if self.epilogue_stats else 1
@@ -206,6 +174,8 @@ class SpatialCnnTrainer:
         self._refresh_table.run()
         # (the linear layers' data gradients transpose their small weights on the fly in _linear_bwd)
 
+    _refresh = _refresh_transposed      # (what `FlatTrainer.apply_update` runs after the update)
+
     def running_stats(self) -> Dict[str, torch.Tensor]:
         """the BatchNorm buffers only (what a train-mode forward changes)"""
         out = {}
@@ -214,46 +184,23 @@ class SpatialCnnTrainer:
             out[u.bn + ".num_batches_tracked"] = torch.tensor(self.nbt[u.bn], dtype=torch.int64)
         return out
 
+    def _export(self, which: str) -> Dict[str, torch.Tensor]:
+        out = self.fp.export(which)
+        stem = "basemodel.basemodel.conv1.weight"
+        out[stem] = out[stem][:, :3].contiguous()            # (the image's 4th channel is padding)
+        w, b = out.pop("heads.weight"), out.pop("heads.bias")
+        o = 0
+        for t, k in self.heads:
+            out[f"classifier_{t}.fc.weight"], out[f"classifier_{t}.fc.bias"] = w[o:o + k].clone(), b[o:o + k].clone()
+            o += k
+        return out
+
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        out = dict(self._extra)
-        for u in self.units.values():
-            taps = u.k * u.k
-            tapw = (u.cin + 3) // 4 * 4
-            w = u.w[:, :taps * tapw].reshape(u.cout, u.k, u.k, tapw)[..., :u.cin].permute(0, 3, 1, 2).contiguous().cpu()
-            if u.cin == 4:
-                w = w[:, :3].contiguous()
-            out[u.name + ".weight"] = w
-            out[u.bn + ".weight"], out[u.bn + ".bias"] = u.gamma.clone().cpu(), u.beta.clone().cpu()
-            out[u.bn + ".running_mean"], out[u.bn + ".running_var"] = u.rmean.clone().cpu(), u.rvar.clone().cpu()
-            out[u.bn + ".num_batches_tracked"] = torch.tensor(self.nbt[u.bn], dtype=torch.int64)
-        for name, (w, b, gw, gb, co, ci) in self.lin.items():
-            ww, bb = w[:, :ci].clone().cpu(), b.clone().cpu()
-            if name == "heads":
-                o = 0
-                for t, k in self.heads:
-                    out[f"classifier_{t}.fc.weight"], out[f"classifier_{t}.fc.bias"] = ww[o:o + k].clone(), bb[o:o + k].clone()
-                    o += k
-            else:
-                out[name + ".weight"], out[name + ".bias"] = ww.unsqueeze(-1), bb
+        out = dict(self._extra, **self._export("p"), **self.running_stats())
         return {k: out[k] for k, _ in self._table}
 
     def grads(self) -> Dict[str, torch.Tensor]:
-        out = {}
-        for u in self.units.values():
-            taps, tapw = u.k * u.k, (u.cin + 3) // 4 * 4
-            g = u.gw[:, :taps * tapw].reshape(u.cout, u.k, u.k, tapw)[..., :u.cin].permute(0, 3, 1, 2).contiguous().cpu()
-            out[u.name + ".weight"] = g[:, :3].contiguous() if u.cin == 4 else g
-            out[u.bn + ".weight"], out[u.bn + ".bias"] = u.ggamma.clone().cpu(), u.gbeta.clone().cpu()
-        for name, (w, b, gw, gb, co, ci) in self.lin.items():
-            gg, gbb = gw[:, :ci].clone().cpu(), gb.clone().cpu()
-            if name == "heads":
-                o = 0
-                for t, k in self.heads:
-                    out[f"classifier_{t}.fc.weight"], out[f"classifier_{t}.fc.bias"] = gg[o:o + k].clone(), gbb[o:o + k].clone()
-                    o += k
-            else:
-                out[name + ".weight"], out[name + ".bias"] = gg.unsqueeze(-1), gbb
-        return out
+        return self._export("g")
 
     # ------------------------------------------------------------------ building blocks
     def _fwd_unit(self, u: _Unit, x, residual=None, relu=True, saved=None):
@@ -327,15 +274,15 @@ class SpatialCnnTrainer:
         return dx, (dres.view(z.shape) if dres is not None else None)
 
     def _linear_fwd(self, name, x):
-        w, b, _, _, co, ci = self.lin[name]
-        return ops.linear(x, w, b)
+        l = self.fp.L[name]
+        return ops.linear(x, l.w, l.b)
 
     def _linear_bwd(self, name, dy, x, need_dx=True):
-        w, b, gw, gb, co, ci = self.lin[name]
-        ops.wgrad_conv1d(dy, x, gw, batch=1, t=x.shape[0], taps=1, dil=1, pad=0, accumulate=True, bias_grad=gb)   # (G is zeroed once per step)
+        l = self.fp.L[name]
+        ops.wgrad_conv1d(dy, x, l.gw, batch=1, t=x.shape[0], taps=1, dil=1, pad=0, accumulate=True, bias_grad=l.gb)   # (G is zeroed once per step)
         if not need_dx:
             return None
-        wt = ops.transpose_pack_conv1d(w, co, ci, 1)
+        wt = ops.transpose_pack_conv1d(l.w, l.cout, l.cin, 1)
         return ops.linear(dy, wt, None)
 
     # ------------------------------------------------------------------ one step
@@ -354,39 +301,8 @@ class SpatialCnnTrainer:
         assert frames.is_cuda and tuple(z.shape) == (B, self.NH)
         self.bucket_order = []            # gradient buckets in the order their all-reduce was issued this step (DDP)
         if use_graph:
-            # data-parallel steps with bucket overlap: the backward is captured in SEGMENTS cut where a gradient bucket is complete
-            # (`_reduce_bucket`), and the bucket's all-reduce is issued between two replays -- one graph would leave ONE flat all-reduce
-            # behind the whole backward (171 MB for the ResNet-50 student)
-            seg = self.overlap and getattr(self, "exchange", True) and self._ddp_world() > 1
-            key = (tuple(frames.shape), frames.dtype, bool(seg))
-            g = self._graphs.get(key)
-            if g is None:
-                from .graph import GraphedForward, SegmentedGraph
-                keep = {n: (u.rmean.clone(), u.rvar.clone()) for n, u in self.units.items()}   # warm-up + capture runs must not count
-                self._capturing = True
-                try:
-                    fn = lambda f, zz, *t: self._fwd_bwd(f, zz, t[:3], t[3:])
-                    if seg:
-                        def fn_cut(cut, *a):
-                            self._cut = cut
-                            try:
-                                return fn(*a)
-                            finally:
-                                self._cut = None
-                        g = SegmentedGraph(fn_cut, [frames, z, *tp, *tf])
-                    else:
-                        g = GraphedForward(fn, [frames, z, *tp, *tf])
-                    self._graphs[key] = g
-                finally:
-                    self._capturing = False
-                    self._cut = None
-                for n, u in self.units.items():
-                    u.rmean.copy_(keep[n][0])
-                    u.rvar.copy_(keep[n][1])
-            if seg:
-                col_loss, soft, kdl = g(frames, z, *tp, *tf, on_cut=self._issue_bucket)
-            else:
-                col_loss, soft, kdl = g(frames, z, *tp, *tf)
+            col_loss, soft, kdl = self._graph_step((tuple(frames.shape), frames.dtype), lambda f, zz, *t: self._fwd_bwd(f, zz, t[:3], t[3:]),
+                                                   [frames, z, *tp, *tf])
         else:
             col_loss, soft, kdl = self._fwd_bwd(frames, z, tp, tf)
         for bn in self.nbt:
@@ -532,27 +448,13 @@ class SpatialCnnTrainer:
         self._reduce_bucket("stem")
         return col_loss, soft, kdl
 
-    def _ddp_world(self) -> int:
-        import torch.distributed as dist
-        return dist.get_world_size(self.pg) if (dist.is_available() and dist.is_initialized()) else 1
-
-    def _reduce_bucket(self, name: str):
-        """DDP overlap: the bucket's all-reduce is enqueued behind the kernels that wrote it and runs while the backward
-        of the earlier layers continues; `apply_update` waits for all of them.  Not inside a hipGraph capture."""
-        if self._capturing:
-            if getattr(self, "_cut", None) is not None:     # segmented capture: the graph is cut here, the all-reduce is issued at replay
-                self._cut(name)
-            return
-        if not self.overlap or not getattr(self, "exchange", True) or self._ddp_world() == 1:
-            return
-        self._issue_bucket(name)
-
-    def _issue_bucket(self, name: str):
-        import torch.distributed as dist
-        a, b = self._ranges[name]
-        self.bucket_order = getattr(self, "bucket_order", []) + [name]
-        if b > a:
-            self._pending.append(dist.all_reduce(self.G[a:b], op=dist.ReduceOp.SUM, group=self.pg, async_op=True))
+    def _capture(self, fn, inputs, seg):
+        keep = {n: (u.rmean.clone(), u.rvar.clone()) for n, u in self.units.items()}   # warm-up + capture runs must not count
+        g = super()._capture(fn, inputs, seg)
+        for n, u in self.units.items():
+            u.rmean.copy_(keep[n][0])
+            u.rvar.copy_(keep[n][1])
+        return g
 
     def _col_scale(self, B: int) -> torch.Tensor:
         if B not in self._col_scales:
@@ -563,16 +465,3 @@ class SpatialCnnTrainer:
     def relu_outputs(self) -> Dict[str, torch.Tensor]:
         """post-ReLU activations of the last step by BatchNorm name, NCHW on the host (tests: ReLU-gate comparison)"""
         return {u.bn: a.permute(0, 3, 1, 2).cpu() for (u, _, _, _, _, a, relu, _) in self.last_saved if relu}
-
-    def apply_update(self):
-        if self._pending:                                   # buckets were reduced during the backward
-            for h in self._pending:
-                h.wait()
-            self._pending = []
-            scale = 1.0 / self._ddp_world()
-        elif getattr(self, "exchange", True):
-            scale = allreduce_sum_flat(self.G, self.pg)
-        else:
-            scale = 1.0                                     # exchange=False: rank-local step (bench: the step without its exchange)
-        ops.sgd_step(self.P, self.G, self.lr, self.wd, scale)
-        self._refresh_transposed()

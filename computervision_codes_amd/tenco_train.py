@@ -20,6 +20,8 @@ from typing import Dict, List, Optional
 import torch
 
 from . import ops
+from .flatparams import FlatParams, FlatTrainer, Lin
+from .flatparams import allreduce_sum_flat  # noqa: F401  (its import path before it moved to flatparams)
 from .shapes import tenco_shapes
 
 HEADS = (("", 100, 1.0), ("_i", 6, 0.1), ("_v", 10, 0.1), ("_t", 15, 0.1))   # loss = 0.1 (i + v + t) + ivt (`run.py:212`)
@@ -27,28 +29,18 @@ NH = 131
 NHP = 132  # padded to a multiple of 4 (16-byte rows for the gradient GEMMs)
 
 
-class _Conv:
-    __slots__ = ("name", "cout", "cin", "taps", "w", "b", "gw", "gb", "wt", "kpad")
-
-
-class TencoTrainer:
+class TencoTrainer(FlatTrainer):
     def __init__(self, num_layers_PG=11, num_layers_R=10, num_R=3, num_f_maps=512, dim=512, num_classes=100, lr=0.1, weight_decay=1e-5,
                  device: str = "cuda", process_group=None, overlap: bool = True, hier: bool = False):
+        # overlap: a stage's gradients are all-reduced as soon as its backward has written them (DDP, `FlatTrainer`)
+        super().__init__(lr, weight_decay, device, process_group, overlap)
         # hier = `args.hier` (`network.py:147,154-155`): AvgPool1d(7, 3) behind every refinement stage, so level l has its own length T_l, the FPN
         # resamples (`:96`) and `fusion` scores every level against the labels resized to it (`run.py:159-179,196-212`)
         self.hier = bool(hier)
-        self.overlap = overlap            # DDP: all-reduce a stage's gradients as soon as its backward has written them (eager steps)
-        self._pending: list = []
-        self._capturing = False
         assert num_classes == 100 and num_R == 3, "the FPN training recipe (Scripts/train_fold1.sh:28) has PG + 3 refinement stages"
         self.LP, self.LR, self.R, self.C, self.D = num_layers_PG, num_layers_R, num_R, num_f_maps, dim
-        self.lr, self.wd = lr, weight_decay
-        self.dev = torch.device(device)
-        self.pg = process_group
         self._table = tenco_shapes(num_layers_PG, num_layers_R, num_R, num_f_maps, dim, 100, fpn=True)
         self._extra: Dict[str, torch.Tensor] = {}   # parameters outside the trained graph, kept verbatim
-        self.convs: Dict[str, _Conv] = {}
-        self._graphs: Dict[int, object] = {}
         self._scales: Dict[int, torch.Tensor] = {}
         self._label_idx: Dict[tuple, torch.Tensor] = {}
 
@@ -60,84 +52,43 @@ class TencoTrainer:
         names = [k for k, _ in self._table]
         assert all(k in sd for k in names), "state dict incomplete"
         C, D = self.C, self.D
-        specs = [("PG.conv_1x1", C, D, 1)]
+        # gradient buckets: "PG", "Rs.0".."Rs.2", "heads" (FPN lateral + heads); the derived copies are the transposed, tap-reversed
+        # data-gradient operators (a launch of `mt4_transpose_pack_conv1d_f32` per layer was 98 launches = 0.5 ms of an 8 ms whole-video step)
+        fp = FlatParams(self.dev)
+        fp.bucket("PG")
+        fp.lin("PG.conv_1x1", C, D, dgrad=False)          # (the input projection needs no data gradient)
         for prefix, n in self._stages():
+            fp.bucket(prefix)
             for i in range(n):
-                specs += [(f"{prefix}.layers.{i}.conv_dilated", C, C, 3), (f"{prefix}.layers.{i}.conv_1x1", C, C, 1)]
-        specs += [("fpn.latlayer1", C, C, 1), ("heads", NHP, C, 1)]
-        f32 = torch.float32
-        sizes = []
-        for name, cout, cin, taps in specs:
-            kp = ops.packed_k(cin, 1, taps, f32)
-            sizes.append(cout * kp + ((cout + 3) // 4) * 4)
-        total = sum(sizes)
-        self.P = torch.zeros(total, dtype=f32, device=self.dev)
-        self.G = torch.zeros(total, dtype=f32, device=self.dev)
-        self._tab = ops.RefreshTable(self.dev)   # the transposed, tap-reversed data-gradient operators: ONE launch after every update
-        off = 0
-        self._ranges: Dict[str, list] = {}     # flat-buffer range of every gradient bucket: "PG", "Rs.0".."Rs.2", "heads" (FPN lateral + heads)
-        for name, cout, cin, taps in specs:
-            bucket = name.split(".layers.")[0] if ".layers." in name else ("PG" if name == "PG.conv_1x1" else "heads")
-            self._ranges.setdefault(bucket, [off, off])
-            c = _Conv()
-            c.name, c.cout, c.cin, c.taps = name, cout, cin, taps
-            c.kpad = ops.packed_k(cin, 1, taps, f32)
-            nw = cout * c.kpad
-            c.w, c.gw = self.P[off:off + nw].view(cout, c.kpad), self.G[off:off + nw].view(cout, c.kpad)
-            c.b, c.gb = self.P[off + nw:off + nw + cout], self.G[off + nw:off + nw + cout]
-            off += nw + ((cout + 3) // 4) * 4
-            self._ranges[bucket][1] = off
-            if name == "heads":
-                w = torch.cat([sd[f"conv_out{s}.weight"] for s, _, _ in HEADS], 0).float()
-                b = torch.cat([sd[f"conv_out{s}.bias"] for s, _, _ in HEADS], 0).float()
-                w = torch.cat([w, torch.zeros(NHP - NH, cin, 1)], 0)
-                b = torch.cat([b, torch.zeros(NHP - NH)], 0)
-            else:
-                w, b = sd[name + ".weight"].float(), sd[name + ".bias"].float()
-            c.w.copy_(ops.pack_conv_weight(w.to(self.dev).unsqueeze(2), None, f32))
-            c.b.copy_(b.to(self.dev))
-            # (the input projection needs no data gradient)
-            c.wt = self._tab.add(c.w, cout, cin, f32, True, [taps - 1 - i for i in range(taps)]) if name != "PG.conv_1x1" else None
-            self.convs[name] = c
-        trained = {n + suffix for n, *_ in specs for suffix in (".weight", ".bias")} | \
-                  {f"conv_out{s}.{p}" for s, _, _ in HEADS for p in ("weight", "bias")}
+                fp.lin(f"{prefix}.layers.{i}.conv_dilated", C, C, taps=3)
+                fp.lin(f"{prefix}.layers.{i}.conv_1x1", C, C)
+        fp.bucket("heads")
+        fp.lin("fpn.latlayer1", C, C)
+        fp.lin("heads", NH, C, src=(torch.cat([sd[f"conv_out{s}.weight"] for s, _, _ in HEADS], 0),   # [131 (+1 zero row), C, 1]
+                                    torch.cat([sd[f"conv_out{s}.bias"] for s, _, _ in HEADS], 0)))
+        self.fp, self.convs = fp.build(sd), fp.L
+        trained = fp.keys() | {f"conv_out{s}.{p}" for s, _, _ in HEADS for p in ("weight", "bias")}
         self._extra = {k: sd[k].detach().clone() for k in names if k not in trained}
-        self._refresh_transposed()
+        self._refresh()
         return self
 
-    def _refresh_transposed(self):
-        """(a launch of `mt4_transpose_pack_conv1d_f32` per layer was 98 launches = 0.5 ms of an 8 ms whole-video step)"""
-        self._tab.run()
+    def _export(self, which: str) -> Dict[str, torch.Tensor]:
+        out = self.fp.export(which)
+        w, b = out.pop("heads.weight"), out.pop("heads.bias")
+        o = 0
+        for s, k, _ in HEADS:
+            out[f"conv_out{s}.weight"], out[f"conv_out{s}.bias"] = w[o:o + k].clone(), b[o:o + k].clone()
+            o += k
+        return out
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """reference layout and key names (`Temporal_tenco/network.py`), on the CPU"""
-        out = dict(self._extra)
-        for name, c in self.convs.items():
-            w = c.w[:, :c.taps * c.cin].reshape(c.cout, c.taps, c.cin).permute(0, 2, 1).contiguous().cpu()
-            b = c.b.clone().cpu()
-            if name == "heads":
-                o = 0
-                for s, k, _ in HEADS:
-                    out[f"conv_out{s}.weight"], out[f"conv_out{s}.bias"] = w[o:o + k].clone(), b[o:o + k].clone()
-                    o += k
-            else:
-                out[name + ".weight"], out[name + ".bias"] = w, b
+        out = dict(self._extra, **self._export("p"))
         return {k: out[k] for k, _ in self._table}
 
     def grads(self) -> Dict[str, torch.Tensor]:
         """gradients of the last step in reference layout (trained parameters only), on the CPU"""
-        out = {}
-        for name, c in self.convs.items():
-            g = c.gw[:, :c.taps * c.cin].reshape(c.cout, c.taps, c.cin).permute(0, 2, 1).contiguous().cpu()
-            gb = c.gb.clone().cpu()
-            if name == "heads":
-                o = 0
-                for s, k, _ in HEADS:
-                    out[f"conv_out{s}.weight"], out[f"conv_out{s}.bias"] = g[o:o + k].clone(), gb[o:o + k].clone()
-                    o += k
-            else:
-                out[name + ".weight"], out[name + ".bias"] = g, gb
-        return out
+        return self._export("g")
 
     def level_lengths(self, t: int) -> List[int]:
         """frames of the four FPN levels for a video of t frames: all t, or t -> (t - 7) // 3 + 1 per refinement stage with --hier"""
@@ -168,7 +119,7 @@ class TencoTrainer:
         return masks
 
     # ------------------------------------------------------------------ one step
-    def _conv(self, x, c: _Conv, dil=1, residual=None, act=None, transposed=False, cout=None):
+    def _conv(self, x, c: Lin, dil=1, residual=None, act=None, transposed=False, cout=None):
         w = c.wt if transposed else c.w
         b = None if transposed else (c.b if cout is None else c.b[:cout])
         pad = dil if c.taps == 3 else 0
@@ -186,31 +137,7 @@ class TencoTrainer:
         assert z.is_cuda and tuple(z.shape) == (T, NH) and z.dtype == torch.float32
         self.bucket_order = []            # gradient buckets in the order their all-reduce was issued this step (DDP)
         if use_graph and not masks:
-            # data-parallel steps with bucket overlap: the backward is captured in segments cut where a stage's gradients are complete, the
-            # stage's all-reduce is issued between two replays (`graph.SegmentedGraph`); otherwise one graph, one flat all-reduce behind it
-            seg = self.overlap and getattr(self, "exchange", True) and self._ddp_world() > 1
-            g = self._graphs.get((T, bool(seg)))
-            if g is None:
-                from .graph import GraphedForward, SegmentedGraph
-                self._capturing = True
-                try:
-                    if seg:
-                        def fn_cut(cut, xx, zz):
-                            self._cut = cut
-                            try:
-                                return self._fwd_bwd(xx, zz, None)
-                            finally:
-                                self._cut = None
-                        g = SegmentedGraph(fn_cut, [x, z])
-                    else:
-                        g = GraphedForward(lambda xx, zz: self._fwd_bwd(xx, zz, None), [x, z])
-                    self._graphs[(T, bool(seg))] = g
-                finally:
-                    self._capturing = False
-            if seg:
-                col_loss = g(x, z, on_cut=self._issue_bucket)
-            else:
-                col_loss = g(x, z)
+            col_loss = self._graph_step(T, lambda xx, zz: self._fwd_bwd(xx, zz, None), [x, z])
         else:
             col_loss = self._fwd_bwd(x, z, masks)
         cl = col_loss.cpu()                                  # [levels, 131]: BCE sums per level and column
@@ -327,29 +254,6 @@ class TencoTrainer:
         self._reduce_bucket("PG")
         return col_loss
 
-    def _ddp_world(self) -> int:
-        import torch.distributed as dist
-        return dist.get_world_size(self.pg) if (dist.is_available() and dist.is_initialized()) else 1
-
-    def _reduce_bucket(self, name: str):
-        """DDP overlap: the bucket's all-reduce is enqueued behind the kernels that wrote it and runs while the backward of the
-        earlier stages continues; `apply_update` waits for all of them.  Under graph replay the backward is replayed in segments cut at these
-        points (`train_step`)."""
-        if self._capturing:
-            if getattr(self, "_cut", None) is not None:     # segmented capture: the graph is cut here, the all-reduce is issued at replay
-                self._cut(name)
-            return
-        if not self.overlap or not getattr(self, "exchange", True) or self._ddp_world() == 1:
-            return
-        self._issue_bucket(name)
-
-    def _issue_bucket(self, name: str):
-        import torch.distributed as dist
-        a, b = self._ranges[name]
-        self.bucket_order = getattr(self, "bucket_order", []) + [name]
-        if b > a:
-            self._pending.append(dist.all_reduce(self.G[a:b], op=dist.ReduceOp.SUM, group=self.pg, async_op=True))
-
     def _level_labels(self, z: torch.Tensor, T: int, tl: int) -> torch.Tensor:
         """`fusion` (`run.py:169-175`): the labels of a level of tl != T frames are `F.interpolate(labels, size=tl, mode='nearest')` of the [T, K] rows:
         row j <- row min(floor(j * float32(T / tl)), T - 1) (torch's nearest index arithmetic, in float32)"""
@@ -368,28 +272,6 @@ class TencoTrainer:
         if cs is None:
             cs = self._scales[T] = torch.cat([torch.full((k,), w / (T * k)) for _, k, w in HEADS]).to(self.dev)
         return cs
-
-    def apply_update(self):
-        """DDP exchange (one all-reduce of the flat gradient buffer, mean over ranks) + SGD + refresh of the transposed copies"""
-        if self._pending:                                   # buckets were reduced during the backward
-            for h in self._pending:
-                h.wait()
-            self._pending = []
-            scale = 1.0 / self._ddp_world()
-        else:
-            scale = allreduce_sum_flat(self.G, self.pg) if getattr(self, "exchange", True) else 1.0   # exchange=False: rank-local step (bench only)
-        ops.sgd_step(self.P, self.G, self.lr, self.wd, scale)
-        self._refresh_transposed()
-
-
-def allreduce_sum_flat(flat_grad: torch.Tensor, group=None) -> float:
-    """The ONE exchange of a data-parallel step: sum the flat gradient buffer over ranks in place (RCCL on the GPU,
-    gloo in the CPU tests) and return the factor that turns the sum into the mean (1/world).  No-op for one rank."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-        return 1.0
-    dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=group)
-    return 1.0 / dist.get_world_size(group)
 
 
 def lr_at_epoch(epoch: int, lr: float, power: float, warmup: int, decay_rate: float) -> float:
