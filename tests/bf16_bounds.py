@@ -1,0 +1,132 @@
+"""Per-element error bounds for kernels that read bf16 operands, accumulate in fp32 and round once when they store.
+
+A correct kernel of that kind is, on every element, within half a bf16 ulp of the exact (float64) result of the operation on the same bf16
+operands, plus a small term for its fp32 accumulation.  A single tolerance scaled by the tensor's largest value allows several ulps at the largest
+element and far more near zero, so a truncating store, a bias read as bf16 or a K-split partial sum rounded to bf16 all pass it; these bounds
+do not (`test_bf16_bounds_cpu.py` shows both on CPU emulations of those bugs).
+
+`check_bf16` asserts, for every element,
+
+    |got - ref64| <= half_ulp_bf16(ref64) + sqrt(k) * ACC_EPS * acc64 + extra
+
+and, when the reference rounds in exactly the places the kernel does (`single_rounding`), that the outputs equal the round-to-nearest-even of the
+float64 result almost everywhere and that their signed error has no bias (these two catch truncation and one-sided errors at long K, where the
+accumulation term is loose).  `check_f32` is the same bound for fp32 outputs of bf16 operands, with an fp32 half-ulp in place of the bf16 one.
+
+This is a plain module imported by the GPU tests (`tests/` is on sys.path while pytest runs them), not a conftest.
+"""
+import json
+import math
+import os
+
+import numpy as np
+import torch
+
+# fp32 accumulation term per sqrt(K), times sum |a * b| (acc64).  The fp32 MFMA chain was measured at about 1-3.5e-7 * sum |a * b| for
+# K <= 4096 (one fp32 rounding per step, errors of random sign): sqrt(K) * 2^-24 is about ten times that.  How the bf16 MFMA sums inside one
+# instruction has not been measured here; if a correct kernel exceeds this term, and the fp32-output form of the same kernel does too, it is
+# raised here, once, with the measured worst ratio.
+ACC_EPS = 2.0 ** -24
+
+# gelu_erf (computervision_codes_amd/csrc/mt4_common.h): |gelu_erf - exact| < 9e-7 over [-10, 10] in fp32, documented in the header; and the
+# accumulation error of the argument reaches the output through gelu', whose largest value is 1.129 (at x = sqrt 2).
+GELU_APPROX_ERR = 1e-6
+GELU_MAX_SLOPE = 1.13
+
+# single-rounding statistics, over the outputs where the documented approximation (`extra`) is at most 1/16 ulp -- it cannot move their rounding
+# much (GELU: every output of magnitude >= 2^-9; below that gelu_erf's 9e-7 spans ulps, and outputs of x < -5 are all off by most of it):
+# at least this fraction of them equals RNE(float64) ...
+MIN_MATCH = 0.99
+# ... and the mean signed error (in ulps, towards larger magnitude) stays below this.  For n nonzero outputs the mean of n independent rounding
+# errors (uniform, sigma = 0.29 ulp) has a standard deviation of 0.29 / sqrt(n): below n = 576 the threshold is four of those, 1.2 / sqrt(n).
+MAX_MEAN_SIGNED = 0.05
+
+BF16_MIN_NORMAL_EXP = -126
+
+
+def _floor_log2(t64):
+    """floor(log2 |t|) of a float64 tensor, floored at the smallest normal exponent (0 maps there too)"""
+    _, e = torch.frexp(t64)                 # t = m * 2^e, 0.5 <= |m| < 1
+    e = torch.where(t64 == 0, torch.full_like(e, BF16_MIN_NORMAL_EXP + 1), e)
+    return torch.clamp(e.to(torch.float64) - 1.0, min=BF16_MIN_NORMAL_EXP)
+
+
+def half_ulp_bf16(ref):
+    """half a bf16 ulp of each element of `ref`: 2^(floor(log2 |ref|) - 8), floored at the smallest normal"""
+    return torch.pow(2.0, _floor_log2(ref.to(torch.float64)) - 8.0)
+
+
+def half_ulp_f32(ref):
+    """half an fp32 ulp of each element of `ref`: 2^(floor(log2 |ref|) - 24), floored at the smallest normal"""
+    return torch.pow(2.0, _floor_log2(ref.to(torch.float64)) - 24.0)
+
+
+def rne_bf16(t):
+    """round to bf16 with round-to-nearest-even, directly from float64 (no intermediate fp32 rounding), widened back to float64"""
+    t64 = t.to(torch.float64)
+    ulp = torch.pow(2.0, _floor_log2(t64) - 7.0)
+    return torch.round(t64 / ulp) * ulp     # torch.round: halves to even; t / ulp is exact (power-of-two scale)
+
+
+def _acc_term(acc64, k, ref64):
+    if acc64 is None:
+        return torch.zeros_like(ref64)
+    return math.sqrt(k) * ACC_EPS * acc64.to(torch.float64).cpu()
+
+
+def _log(stats):
+    """append the statistics of one check as a JSON line to $BF16_BOUNDS_LOG (when set): the measured ratios of a suite run in one file"""
+    path = os.environ.get("BF16_BOUNDS_LOG")
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps(stats) + "\n")
+
+
+def _check(got, ref64, bound_base, acc64, k, extra, single_rounding, what, kind):
+    got64 = got.detach().to(torch.float64).cpu()
+    ref64 = ref64.detach().to(torch.float64).cpu()
+    assert got64.shape == ref64.shape, (what, tuple(got64.shape), tuple(ref64.shape))
+    extra = extra.to(torch.float64).cpu() if torch.is_tensor(extra) else extra
+    bound = bound_base(ref64) + _acc_term(acc64, k, ref64) + extra
+    err = (got64 - ref64).abs()
+    ratio = err / bound
+    ratio = torch.where(torch.isnan(ratio), torch.full_like(ratio, math.inf), ratio)   # NaN output: worst possible
+    flat = int(torch.argmax(ratio.reshape(-1)))
+    idx = tuple(int(i) for i in np.unravel_index(flat, tuple(ref64.shape))) if ref64.dim() else ()
+    worst = float(ratio.reshape(-1)[flat]) if ratio.numel() else 0.0
+    stats = dict(what=what, kind=kind, n=int(ref64.numel()), k=k, worst_ratio=worst)
+    ok = worst <= 1.0
+    if single_rounding:
+        ulp = 2.0 * half_ulp_bf16(ref64)
+        sel = (extra <= ulp / 16) if torch.is_tensor(extra) or extra else torch.ones_like(ref64, dtype=torch.bool)
+        g_s, r_s, u_s = got64[sel], ref64[sel], ulp[sel]
+        n_nz = int((r_s != 0).sum())
+        mism = int((g_s != rne_bf16(r_s)).sum())
+        match = 1.0 - mism / max(1, r_s.numel())
+        signed = ((g_s - r_s) * torch.sign(r_s) / u_s).sum().item() / max(1, n_nz)
+        lim = max(MAX_MEAN_SIGNED, 1.2 / math.sqrt(max(1, n_nz)))
+        stats.update(match=match, mean_signed_ulp=signed)
+        ok = ok and (match >= MIN_MATCH or mism <= 1) and abs(signed) < lim
+    _log(stats)
+    if not ok:
+        gv, rv = got64.reshape(-1)[flat].item(), ref64.reshape(-1)[flat].item()
+        msg = (f"{what}: {kind} bound exceeded or biased; worst element {idx}: got {gv!r}, ref {rv!r}, |err| {abs(gv - rv):.3e}, "
+               f"bound {bound.reshape(-1)[flat].item():.3e}; worst err/bound {worst:.3f}")
+        if single_rounding:
+            msg += f"; outputs equal to RNE(ref) {stats['match']:.4f} (>= {MIN_MATCH}); mean signed error {stats['mean_signed_ulp']:+.4f} ulp (|.| < {lim:.3f})"
+        raise AssertionError(msg)
+    return stats
+
+
+def check_bf16(got, ref64, *, acc64=None, k=1, extra=0.0, single_rounding=True, what=""):
+    """bf16 output `got` against the float64 result `ref64` of the same operation on the same bf16 operands.
+
+    acc64: the same operation on absolute values (sum |a * b| of a GEMM, |bias|, |residual| ...), float64; k: the reduction length;
+    extra: an allowance (scalar or per element) for an approximation the kernel documents; single_rounding: the kernel rounds once, where the
+    reference does not round at all -- also require RNE agreement and no signed bias.  Returns the statistics (also logged, see `_log`)."""
+    return _check(got, ref64, half_ulp_bf16, acc64, k, extra, single_rounding, what, "bf16")
+
+
+def check_f32(got, ref64, *, acc64=None, k=1, extra=0.0, what=""):
+    """fp32 output of bf16 operands: no output rounding beyond fp32's own; bound = fp32 half-ulp + the same accumulation term + extra"""
+    return _check(got, ref64, half_ulp_f32, acc64, k, extra, False, what, "f32")

@@ -1,9 +1,14 @@
 """GPU: randomised shapes through `mt4_conv_nhwc` (fixed seed): every tile instantiation, FAST and generic staging, strides, dilations,
-paddings, ragged M / N, residual, activations, fp32 (exact MFMA chain, tight tolerance) and bf16, against torch's CPU conv2d."""
+paddings, ragged M / N, residual, activations, fp32 (exact MFMA chain, tight tolerance) and bf16, against torch's CPU conv2d.
+
+bf16 also element by element against float64 (`bf16_bounds`): the kernel starts its fp32 accumulators at the fp32 bias
+(igemm_conv.hip:198-209), adds the bf16 residual and applies ReLU / GELU in fp32, and rounds once when it stores (`pack_bf16x2` of the staged
+epilogue, `f32_to_bf16` of the direct one, igemm_conv.hip:591-668); the reference rounds nowhere after the operands."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+from bf16_bounds import GELU_APPROX_ERR, GELU_MAX_SLOPE, check_bf16
 
 pytestmark = pytest.mark.gpu
 
@@ -53,3 +58,12 @@ def test_conv_random_shapes(cuda, dtype):
         err = (got - ref).abs().max().item() / scale
         worst = max(worst, err)
         assert err < (2e-5 if dtype == torch.float32 else 1.2e-2), (it, c, err)
+        if dtype == torch.bfloat16:
+            act64 = {"none": lambda t: t, "relu": F.relu, "gelu": F.gelu}[c["act"]]
+            pre64 = F.conv2d(x.double(), wt.double(), bias.double(), c["s"], c["p"], c["d"])
+            acc64 = F.conv2d(x.double().abs(), wt.double().abs(), bias.double().abs(), c["s"], c["p"], c["d"])
+            if res is not None:
+                pre64, acc64 = pre64 + res.double(), acc64 + res.double().abs()
+            gelu = c["act"] == "gelu"
+            check_bf16(got, act64(pre64), acc64=acc64 * (GELU_MAX_SLOPE if gelu else 1.0), k=c["cin"] * c["kh"] * c["kw"] + 1,
+                       extra=GELU_APPROX_ERR if gelu else 0.0, what=f"conv fuzz {it} {c}")

@@ -1,8 +1,13 @@
-"""GPU: each C-ABI kernel against the CPU oracle op (torch fp32 on the host) on seeded inputs."""
+"""GPU: each C-ABI kernel against the CPU oracle op (torch fp32 on the host) on seeded inputs.
+
+The bf16 convolutions are also checked element by element against float64 (`bf16_bounds`): `mt4_conv_nhwc` starts its fp32 accumulators at
+the fp32 bias (igemm_conv.hip:198-209; K-split tiles: group 0 only, partial tiles added in fp32 in LDS), adds the bf16 residual and applies the
+activation in fp32, and rounds once when it stores (igemm_conv.hip:591-668); the reference rounds nowhere after the operands."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+from bf16_bounds import check_bf16, check_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -38,6 +43,14 @@ def _conv_case(cuda, B, H, W, Cin, Cout, kh, kw, stride, pad, dil, dtype, relu, 
     tol = 2e-5 if dtype == torch.float32 else 1.2e-2
     err = (got - ref).abs().max().item()
     assert err <= tol * max(1.0, ref.abs().max().item()), (err, ref.abs().max().item())
+    if dtype == torch.bfloat16:
+        geo = dict(stride=stride, padding=pad, dilation=dil)
+        ref64 = F.conv2d(x.double(), w.double(), bias.double(), **geo)
+        acc64 = F.conv2d(x.double().abs(), w.double().abs(), bias.double().abs(), **geo)
+        if use_res:
+            ref64, acc64 = ref64 + res.double(), acc64 + res.double().abs()
+        check_bf16(got, F.relu(ref64) if relu else ref64, acc64=acc64, k=Cin * kh * kw + 1,
+                   what=f"conv tile {tile} {(B, H, W, Cin, Cout, kh, kw, stride, pad, dil)} relu={relu} res={use_res}")
 
 
 CONV_SHAPES = [
@@ -197,6 +210,8 @@ def test_conv_bf16_in_f32_out(cuda):
                       None, kh=1, kw=1, out_dtype=torch.float32)
     assert y.dtype == torch.float32
     assert (y.cpu().permute(0, 3, 1, 2) - ref).abs().max().item() < 1e-4
+    check_f32(y.cpu().permute(0, 3, 1, 2), F.conv2d(x.double(), w.double()), acc64=F.conv2d(x.double().abs(), w.double().abs()), k=64,
+              what="conv bf16 in, fp32 out")
 
 
 def test_conv_rejects_bad_alignment(cuda):
@@ -227,6 +242,9 @@ def test_stem_path_matches_conv7x7(cuda, hw, dtype):
         (xp[..., :3].float().cpu()[:, 3:3 + h, 3:3 + w] - xn_ref.permute(0, 2, 3, 1)).abs().max() < (1e-6 if dtype == torch.float32 else 2e-2)
     assert (xp.float() - xp2.float()).abs().max().item() < (1e-6 if dtype == torch.float32 else 2e-2)
     assert xp[:, :3].abs().max().item() == 0 and xp[..., 3].abs().max().item() == 0
+    if dtype == torch.bfloat16:   # the same fp32 arithmetic as ToTensor + Normalize (misc_kernels.hip:40-43), one RNE: bit-equal
+        assert torch.equal(xp[..., :3].cpu()[:, 3:3 + h, 3:3 + w].view(torch.int16), xn.bfloat16().permute(0, 2, 3, 1).view(torch.int16))
+        assert torch.equal(xp.view(torch.int16), xp2.view(torch.int16))
     wp = ops.pack_stem_weight(wt.to(cuda), None, dtype)
     b, hp, wpd, _ = xp.shape
     y = ops.conv_nhwc(xp.view(b, hp, wpd // 2, 8), wp, bias.to(cuda), kh=7, kw=4, stride=(2, 1), relu=True)
@@ -234,6 +252,12 @@ def test_stem_path_matches_conv7x7(cuda, hw, dtype):
     assert got.shape == ref.shape
     tol = 2e-5 if dtype == torch.float32 else 2e-2
     assert (got - ref).abs().max().item() <= tol * ref.abs().max().item()
+    if dtype == torch.bfloat16:   # the conv on the operands it was given (the padded map above), fp32 bias in the accumulators, one rounding
+        x64 = xp[..., :3].double().cpu()[:, 3:3 + h, 3:3 + w].permute(0, 3, 1, 2)
+        w64 = wt.bfloat16().double()
+        ref64 = F.relu(F.conv2d(x64, w64, bias.double(), stride=2, padding=3))
+        acc64 = F.conv2d(x64.abs(), w64.abs(), bias.double().abs(), stride=2, padding=3)
+        check_bf16(got, ref64, acc64=acc64, k=3 * 49 + 1, what=f"stem {hw}")
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -321,6 +345,12 @@ def test_conv_with_second_k_source_is_conv3_plus_downsample(cuda, b, h2, w2, mid
     idt = ops.conv_nhwc(xb.to(cuda), wdp, bd.to(cuda), kh=1, kw=1, stride=(s, s), relu=False)
     two = ops.conv_nhwc(t2.to(cuda), w3p, b3.to(cuda), kh=1, kw=1, residual=idt, relu=True)
     assert float(((y.float() - two.float()).abs() / (two.float().abs() + 1.0)).max()) < 2 ** -6
+    # one fp32 sum over the concatenated K (bias b3 + bd added on the host in fp32), one rounding at the store
+    w3b, wdb = w3.view(cout, mid).to(bf).double(), wd.view(cout, c2).to(bf).double()
+    t64, x64, bsum = t2.double(), xb[:, ::s, ::s].double(), (b3 + bd).double()
+    ref64 = torch.relu(t64 @ w3b.T + x64 @ wdb.T + bsum)
+    acc64 = t64.abs() @ w3b.abs().T + x64.abs() @ wdb.abs().T + bsum.abs()
+    check_bf16(y.cpu(), ref64, acc64=acc64, k=mid + c2 + 1, what=f"conv3 + downsample {(b, h2, w2, mid, c2, cout, s)}")
 
 
 @pytest.mark.parametrize("b,h,w", [(3, 56, 56), (2, 16, 24), (1, 9, 15), (2, 8, 14), (1, 1, 1)])
@@ -386,6 +416,23 @@ def test_preprocess_u8_s2d_matches_torch(cuda, b, h, w):
     assert got.shape == ref.shape and torch.equal(got.view(torch.int16), ref.view(torch.int16))
 
 
+def _check_interp_bf16(x, u, t_out):
+    """`interp_linear_rows_kernel` (misc_kernels.hip:398-413): the source position src = (Tin / Tout) (w + 0.5) - 0.5 and the weights
+    1 - l, l are fp32 (as in torch), the blend is fp32, one rounding at the store.  Reference: the exact position in float64; the bound adds the
+    position's fp32 error, 4 * 2^-24 (src + 1) per unit of |x1 - x0|, to the accumulation term of the two-term blend."""
+    t_in = x.shape[1]
+    pos = ((torch.arange(t_out, dtype=torch.float64) + 0.5) * (t_in / t_out) - 0.5).clamp(min=0.0)
+    i0 = pos.floor().long().clamp(max=t_in - 1)
+    i1 = torch.where(i0 < t_in - 1, i0 + 1, i0)
+    l1 = (pos - i0.double()).view(1, -1, 1)
+    x64 = x.double()
+    a, v = x64[:, i0], x64[:, i1]
+    ref64 = (1.0 - l1) * a + l1 * v
+    acc64 = (1.0 - l1) * a.abs() + l1 * v.abs()
+    pos_err = 4 * 2.0 ** -24 * (pos.view(1, -1, 1) + 1.0) * (v - a).abs()
+    check_bf16(u, ref64, acc64=acc64, k=2, extra=pos_err, single_rounding=False, what=f"interp_linear_rows {tuple(x.shape)} -> {t_out}")
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("b,t,c", [(1, 301, 64), (2, 26, 512), (3, 7, 8)])
 def test_avgpool1d_and_linear_interpolation_rows(cuda, dtype, b, t, c):
@@ -398,10 +445,16 @@ def test_avgpool1d_and_linear_interpolation_rows(cuda, dtype, b, t, c):
     ref = F.avg_pool1d(x.float().permute(0, 2, 1), 7, 3).permute(0, 2, 1)
     assert tuple(y.shape) == tuple(ref.shape) == (b, (t - 7) // 3 + 1, c)
     assert (y.float().cpu() - ref).abs().max().item() <= tol * max(1.0, ref.abs().max().item())
+    if dtype == torch.bfloat16:   # fp32 sum of the 7 rows, / 7, one rounding (misc_kernels.hip:391-394)
+        x64 = x.double().permute(0, 2, 1)
+        check_bf16(y.cpu(), F.avg_pool1d(x64, 7, 3).permute(0, 2, 1), acc64=F.avg_pool1d(x64.abs(), 7, 3).permute(0, 2, 1), k=8,
+                   what=f"avgpool1d_rows {(b, t, c)}")
     for t_out in (t, 3 * t + 2, max(1, t // 2)):
         u = ops.interp_linear_rows(x.to(cuda), t_out)
         ref = F.interpolate(x.float().permute(0, 2, 1), size=t_out, mode="linear").permute(0, 2, 1)
         assert tuple(u.shape) == (b, t_out, c)
         assert (u.float().cpu() - ref).abs().max().item() <= tol * max(1.0, ref.abs().max().item())
+        if dtype == torch.bfloat16:
+            _check_interp_bf16(x, u.cpu(), t_out)
         if t_out == t:
             assert torch.equal(u.cpu(), x)                 # to the same length: the identity (what the non-hier FPN relies on)

@@ -1,10 +1,15 @@
 """GPU: the temporal-head latency path (`mt4_tcn_conv`, `mt4_tcn_dilated_residual_layer`, `mt4_tcn_stage`; csrc/tcn_kernels.hip) against
 torch's CPU conv1d -- every comb geometry (dilation below / at / above the tile span and the video length, ragged T, several videos per
-call, ragged channel counts), residual + ReLU epilogue, fp32 (exact MFMA chain: tight tolerance) and bf16."""
+call, ragged channel counts), residual + ReLU epilogue, fp32 (exact MFMA chain: tight tolerance) and bf16.
+
+bf16 also element by element against float64 (`bf16_bounds`): `mt4_tcn_conv` sums the taps in fp32 MFMA accumulators, adds the fp32 bias and
+the bf16 residual and applies ReLU in fp32 after the K loop, and rounds once when it stores (`pack_bf16x2` / `f32_to_bf16`,
+tcn_kernels.hip:312-344); its fp32-output form stores the same sum unrounded."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+from bf16_bounds import check_bf16, check_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -52,6 +57,13 @@ def test_tcn_conv_vs_torch(cuda, dtype):
             y32 = ops.tcn_conv(x.to(dtype).to(cuda), wp, bias.to(cuda), taps=taps, dilation=d, relu=relu, out_dtype=torch.float32)
             ref32 = _ref(x, w, bias, taps, d, None, relu)
             assert (y32.cpu() - ref32).abs().max().item() / max(1.0, ref32.abs().max().item()) < 2e-5
+            case = (b, t, cin, cout, taps, d)
+            x64, w64, b64 = x.double(), w.double(), bias.double()
+            acc_conv = _ref(x64.abs(), w64.abs(), b64.abs(), taps, d, None, False)
+            res64 = res.double() if use_res else None
+            check_bf16(y.cpu(), _ref(x64, w64, b64, taps, d, res64, relu),
+                       acc64=acc_conv + (res64.abs() if use_res else 0.0), k=cin * taps + 1, what=f"tcn_conv bf16 {case}")
+            check_f32(y32.cpu(), _ref(x64, w64, b64, taps, d, None, relu), acc64=acc_conv, k=cin * taps + 1, what=f"tcn_conv fp32 out {case}")
 
 
 def test_tcn_conv_matches_generic_kernel_and_is_batch_independent(cuda):

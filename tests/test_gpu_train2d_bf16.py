@@ -1,11 +1,14 @@
 """GPU: the bf16-operand training mode of the spatial stage -- its kernels against torch fp32 on the CPU evaluated on the SAME bf16-valued
 inputs (bf16 products are exact in fp32, so only the summation order and the final rounding differ), and the whole step against the fp32
-fixtures of the reference step at the tolerance the operand rounding allows."""
+fixtures of the reference step at the tolerance the operand rounding allows.
+
+The bf16 outputs of the BatchNorm and pooling kernels are also checked element by element against float64 (`bf16_bounds`)."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from bf16_bounds import GELU_APPROX_ERR, GELU_MAX_SLOPE, check_bf16, check_f32
 from computervision_codes_amd import shapes, synth
 from conftest import load_golden
 
@@ -47,7 +50,13 @@ def test_wgrad_conv2d_bf16_vs_autograd(cuda, b, h, w, cin, cout, k, s):
 @pytest.mark.parametrize("m,c,relu,res,xf32", [(200, 64, True, False, False), (1031, 128, True, True, False), (77, 256, False, False, False), (300, 64, True, False, True)])
 def test_batchnorm_bf16_fwd_bwd(cuda, m, c, relu, res, xf32):
     """train-mode BatchNorm with bf16 tensors (fp32 convolution output for the stem variant): statistics, output, and the three gradients against
-    torch on the same bf16-valued inputs; outputs are bf16, so one rounding of tolerance"""
+    torch on the same bf16-valued inputs; outputs are bf16, so one rounding of tolerance.
+
+    Per element against float64 (train2d_bf16.hip): the statistics are float64 sums, mean and invstd rounded to fp32 (:119-131);
+    `bn_apply_t_kernel` stores (x - mean) * invstd * gamma + beta (+ bf16 residual, ReLU) from fp32 arithmetic with one rounding (:152-158);
+    `bn_bwd_reduce_t_kernel` sums dy and dy * x_hat (x_hat in fp32) in float64, the ReLU gate read from the stored bf16 output (:176-222);
+    `bn_bwd_apply_t_kernel` stores gamma invstd (dy - mean(dy) - x_hat mean(dy x_hat)) in fp32 with one rounding (:248-265), the gated dy as dres
+    (exact), and dgamma / dbeta as the float64 sums rounded to fp32 (:241-242)."""
     from computervision_codes_amd import ops
     x = (_rand((m, c), 1, 2.0) + 0.3)
     x = x if xf32 else x.to(BF)
@@ -71,12 +80,33 @@ def test_batchnorm_bf16_fwd_bwd(cuda, m, c, relu, res, xf32):
     assert y.dtype == BF
     assert (rmd.cpu() - rm_t).abs().max() < 1e-5 and (rvd.cpu() - rv_t).abs().max() < 1e-5
     assert (y.float().cpu() - y_ref.detach()).abs().max().item() <= 2 ** -8 * max(1.0, y_ref.abs().max().item())
+    x64, g64, b64 = x.double(), g.double(), bta.double()
+    mu64 = x64.mean(0)
+    is64 = 1.0 / torch.sqrt(((x64 - mu64) ** 2).mean(0) + 1e-5)
+    xh64 = (x64 - mu64) * is64
+    y64 = xh64 * g64 + b64
+    acc_y = (x64.abs() + mu64.abs()) * is64 * g64.abs() + b64.abs()
+    if res:
+        y64, acc_y = y64 + r.double(), acc_y + r.double().abs()
+    check_bf16(y.cpu(), torch.relu(y64) if relu else y64, acc64=acc_y, k=4, what=f"bn_apply_t {(m, c, relu, res, xf32)}")
     # backward on the bf16 output the kernel produced (the ReLU gate is read from it)
     with torch.enable_grad():
         y_ref.backward(dy.float())
     dg, db = torch.zeros(c, device=cuda), torch.zeros(c, device=cuda)
     dx, dres = ops.bn_backward_t(dy.to(cuda), y if relu else None, x.to(cuda), mean, invstd, g.to(cuda), dg, db, relu=relu, want_dres=res, sums=sums[2 * c:])
     assert dx.dtype == x.dtype
+    dy64 = dy.double() * (y.cpu() > 0).double() if relu else dy.double()        # the kernel's gate: its own stored output
+    m1, m2 = dy64.mean(0), (dy64 * xh64).mean(0)
+    dx64 = g64 * is64 * (dy64 - m1 - xh64 * m2)
+    acc_dx = g64.abs() * is64 * (dy64.abs() + m1.abs() + (xh64.abs() + (x64.abs() + mu64.abs()) * is64) * (m2.abs() + (dy64 * xh64).abs().mean(0)))
+    if xf32:
+        check_f32(dx.cpu(), dx64, acc64=acc_dx, k=8, what=f"bn_backward_t dx fp32 {(m, c, relu, res)}")
+    else:
+        check_bf16(dx.cpu(), dx64, acc64=acc_dx, k=8, what=f"bn_backward_t dx {(m, c, relu, res)}")
+    check_f32(db.cpu(), dy64.sum(0), acc64=dy64.abs().sum(0), k=m, what=f"bn_backward_t dbeta {(m, c)}")
+    check_f32(dg.cpu(), (dy64 * xh64).sum(0), acc64=(dy64 * xh64).abs().sum(0), k=m, what=f"bn_backward_t dgamma {(m, c)}")
+    if res:
+        check_bf16(dres.cpu(), dy64, what=f"bn_backward_t dres {(m, c, relu)}")
     tol = 2 ** -8 if not xf32 else 1e-4
     assert (dx.float().cpu() - xt.grad).abs().max().item() <= tol * max(1.0, xt.grad.abs().max().item())
     assert (dg.cpu() - gt.grad).abs().max().item() <= 2e-3 * max(1.0, gt.grad.abs().max().item())
@@ -142,6 +172,17 @@ def test_conv_epilogue_statistics_refusals(cuda):
     assert float(sums.abs().max()) == 0.0
 
 
+def _check_maxpool_bwd(x, dy, dx):
+    """`maxpool3x3s2_bwd_bf16` (both kernels, train2d_bf16.hip:496-533 and the tiled one): the fp32 sum of the (up to 4) window gradients a
+    pixel takes, one rounding.  Reference: the same routing by float64 autograd (ties: the first maximum in scan order, as in torch)"""
+    xt = x.double().permute(0, 3, 1, 2).clone().requires_grad_()
+    xa = x.double().permute(0, 3, 1, 2).clone().requires_grad_()
+    with torch.enable_grad():
+        F.max_pool2d(xt, 3, 2, 1).backward(dy.double().permute(0, 3, 1, 2))
+        F.max_pool2d(xa, 3, 2, 1).backward(dy.double().abs().permute(0, 3, 1, 2))
+    check_bf16(dx.cpu(), xt.grad.permute(0, 2, 3, 1), acc64=xa.grad.permute(0, 2, 3, 1), k=4, what=f"maxpool3x3s2_bwd_bf16 {tuple(x.shape)}")
+
+
 @pytest.mark.parametrize("b,h,w,c", [(2, 13, 18, 64), (1, 40, 37, 128), (2, 13, 18, 8), (1, 32, 48, 64)])
 def test_maxpool_backward_bf16(cuda, b, h, w, c):
     """C % 64 == 0 runs the LDS-tiled kernel (several 16 x 16 tiles, ragged edges), other channel counts the per-pixel one"""
@@ -157,6 +198,7 @@ def test_maxpool_backward_bf16(cuda, b, h, w, c):
     dx = ops.maxpool3x3s2_bwd_bf16(x.to(cuda), dy.to(cuda))
     ref = xt.grad.permute(0, 2, 3, 1)
     assert (dx.float().cpu() - ref).abs().max().item() <= 2 ** -7 * max(1.0, ref.abs().max().item())
+    _check_maxpool_bwd(x, dy, dx)
 
 
 def test_pool_backward_and_repack_bf16(cuda):
@@ -172,9 +214,13 @@ def test_pool_backward_and_repack_bf16(cuda):
     dx = ops.maxpool3x3s2_bwd_bf16(x.to(cuda), dy.to(cuda))
     ref = xt.grad.permute(0, 2, 3, 1)
     assert (dx.float().cpu() - ref).abs().max().item() <= 2 ** -7 * max(1.0, ref.abs().max().item())
+    _check_maxpool_bwd(x, dy, dx)
     df = _rand((3, 128), 3)
     dxa = ops.avgpool_bwd_bf16(df.to(cuda), 3, 21, 128)
     assert (dxa.float().cpu() - (df / 21)[:, None, :].expand(3, 21, 128)).abs().max().item() <= 2 ** -8 * float(df.abs().max()) / 21
+    # fp32 df * fp32(1 / 21), one rounding (train2d_bf16.hip:538-547)
+    ref64 = (df.double() / 21)[:, None, :].expand(3, 21, 128)
+    check_bf16(dxa.cpu(), ref64, acc64=ref64.abs(), k=2, what="avgpool_bwd_bf16")
     # packed fp32 -> packed bf16 == packing the bf16-rounded weights directly
     wt = _rand((128, 64, 3, 3), 4).to(cuda)
     w32 = ops.pack_conv_weight(wt, None, torch.float32)
@@ -288,3 +334,14 @@ def test_mixed_precision_linear_fp32_residual(cuda, m, k, n, act):
         ref = pre + b + r
         ref = torch.relu(ref) if act == "relu" else (F.gelu(ref) if act == "gelu" else ref)
     assert (y.cpu() - ref).abs().max().item() <= 2e-5 * max(1.0, ref.abs().max().item()) + 1e-6 * (act == "gelu")
+    # fp32 output: the accumulators start at the bias, the fp32 residual / gate and the activation are applied in fp32, nothing is rounded to bf16
+    x64, w64, b64, r64 = x.to(BF).double(), w.to(BF).double(), b.double(), r.double()
+    pre64, acc64 = x64 @ w64.t(), x64.abs() @ w64.abs().t()
+    if act == "relu_gate":
+        ref64 = torch.where(r64 > 0, pre64, torch.zeros_like(pre64))
+    else:
+        ref64, acc64 = pre64 + b64 + r64, acc64 + b64.abs() + r64.abs()
+        ref64 = torch.relu(ref64) if act == "relu" else (F.gelu(ref64) if act == "gelu" else ref64)
+    gelu = act == "gelu"
+    check_f32(y.cpu(), ref64, acc64=acc64 * (GELU_MAX_SLOPE if gelu else 1.0), k=k + 2, extra=GELU_APPROX_ERR if gelu else 0.0,
+              what=f"mixed-precision linear {(m, k, n, act)}")

@@ -1,9 +1,12 @@
-"""GPU: the transformer-stage C-ABI kernels against torch-CPU fp32 oracle ops on seeded inputs."""
+"""GPU: the transformer-stage C-ABI kernels against torch-CPU fp32 oracle ops on seeded inputs.
+
+bf16 also element by element against float64 (`bf16_bounds`); each test's docstring names where its kernel rounds."""
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
+from bf16_bounds import GELU_APPROX_ERR, GELU_MAX_SLOPE, check_bf16, rne_bf16
 
 pytestmark = pytest.mark.gpu
 DT = [torch.float32, torch.bfloat16]
@@ -18,6 +21,17 @@ def _tol(dtype, f32=2e-5, bf16=2e-2):
     return f32 if dtype == torch.float32 else bf16
 
 
+def _ln64(x64, g, b, eps=1e-5):
+    """float64 LayerNorm over the last dim and its accumulation scale: `layernorm_kernel` (transformer_kernels.hip:44-90) sums the row in fp32,
+    then the squared deviations from that mean (two passes), and stores (x - mean) * rstd * gamma + beta with one rounding.  The fp32 error of
+    the mean reaches the output as |gamma| rstd mean|x|, that of rstd as |gamma x_hat|."""
+    mu = x64.mean(-1, keepdim=True)
+    r = 1.0 / torch.sqrt(((x64 - mu) ** 2).mean(-1, keepdim=True) + eps)
+    xh = (x64 - mu) * r
+    g64, b64 = g.double(), b.double()
+    return xh * g64 + b64, g64.abs() * (xh.abs() + r * x64.abs().mean(-1, keepdim=True)) + b64.abs()
+
+
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("c", [96, 128, 864, 1024, 4096])
 def test_layernorm_plain(cuda, c, dtype):
@@ -27,6 +41,13 @@ def test_layernorm_plain(cuda, c, dtype):
     ref = F.layer_norm(x, (c,), g, b, 1e-5)
     got = ops.layernorm(x.to(cuda, dtype), g.to(cuda), b.to(cuda)).float().cpu()
     assert (got - ref).abs().max().item() < _tol(dtype, 1e-5, 3e-2)
+    if dtype == torch.bfloat16:
+        ref64, acc64 = _ln64(x.double(), g, b)
+        check_bf16(got, ref64, acc64=acc64, k=c, what=f"layernorm C={c}")
+        # rows with mean / std ~ 100: a one-pass E[x^2] - E[x]^2 variance loses ~2^-24 * 100^2 * sqrt(C) of it; the two-pass kernel does not
+        xo = (_rand((37, c), 4) + 60.0).to(dtype)
+        ref64, acc64 = _ln64(xo.double(), g, b)
+        check_bf16(ops.layernorm(xo.to(cuda), g.to(cuda), b.to(cuda)).cpu(), ref64, acc64=acc64, k=c, what=f"layernorm C={c}, mean/std ~ 100")
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -45,6 +66,13 @@ def test_layernorm_window_gather_matches_roll_partition(cuda, res, ws, shift, dt
     rm = _window_row_map(res, ws, shift).to(cuda)
     got = ops.layernorm(x.view(-1, c).to(cuda, dtype), g.to(cuda), be.to(cuda), row_map=rm, group=1, l_out=res * res, l_in=res * res)
     assert (got.float().cpu() - ref).abs().max().item() < _tol(dtype, 1e-5, 3e-2)
+    if dtype == torch.bfloat16:   # (the gather moves rows; the arithmetic is that of the plain form)
+        y64, a64 = _ln64(x.double(), g, be)
+        y64, a64 = y64.view(b, res, res, c), a64.view(b, res, res, c)
+        if shift:
+            y64, a64 = torch.roll(y64, shifts=(-shift, -shift), dims=(1, 2)), torch.roll(a64, shifts=(-shift, -shift), dims=(1, 2))
+        check_bf16(got.cpu(), window_partition(y64, ws).reshape(-1, c), acc64=window_partition(a64, ws).reshape(-1, c), k=c,
+                   what=f"layernorm window gather {(res, ws, shift)}")
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -60,6 +88,11 @@ def test_layernorm_patch_merging_gather(cuda, dtype):
     got = ops.layernorm(x.view(-1, c).to(cuda, dtype), g.to(cuda), be.to(cuda), row_map=_merge_row_map(res).to(cuda), group=4,
                         l_out=(res // 2) ** 2, l_in=res * res, m_out=b * (res // 2) ** 2)
     assert (got.float().cpu() - ref).abs().max().item() < _tol(dtype, 1e-5, 3e-2)
+    if dtype == torch.bfloat16:
+        x64 = x.double().view(b, res, res, c)
+        cat64 = torch.cat([x64[:, 0::2, 0::2], x64[:, 1::2, 0::2], x64[:, 0::2, 1::2], x64[:, 1::2, 1::2]], -1).reshape(-1, 4 * c)
+        ref64, acc64 = _ln64(cat64, g, be)
+        check_bf16(got.cpu(), ref64, acc64=acc64, k=4 * c, what="layernorm patch-merging gather")
 
 
 def _attn_ref(q, k, v, scale, bias, mask, nw):
@@ -71,6 +104,42 @@ def _attn_ref(q, k, v, scale, bias, mask, nw):
         b = q.shape[0]
         s = (s.view(b // nw, nw, *s.shape[1:]) + mask.unsqueeze(1).unsqueeze(0)).view(*s.shape)
     return s.softmax(-1) @ v
+
+
+def _check_attn_bf16(out, q, k, v, scale, bias, mask, nw, *, mfma, region=False, what=""):
+    """`out` [B*N, H*hd] of a bf16 attention core against float64 on the same bf16 q / k / v ([B,H,N,hd]).
+
+    mfma: the matrix-unit kernels (mha_mfma_kernel, window_attention_mfma_kernel) multiply Q by the scale in fp32 and round it to bf16 before
+    the score MFMA (transformer_kernels.hip:351,1176) -- the reference rounds it there too; they round the unnormalised probabilities
+    p_j = exp(s_j - max) to bf16 as the B operand of the P.V MFMA while the normaliser is the fp32 sum of the unrounded p_j, and scale the fp32
+    result by 1 / sum before the one rounding of the store (:403-458, :1302-1337).  That P rounding is not emulated: it adds at most
+    2^-9 * sum_j p_j |v_j| per output, and the bound allows 2^-8 of it.  The generic kernel (attention_kernel, :179-307) keeps q * scale and P in
+    fp32 (online softmax, one rounding at the store): single rounding.
+    The fp32 score error (a dot product of hd terms, the bias / mask added, exp2 of s * log2 e - max * log2 e) reaches an output as
+    sum_j p_j |ds_j| (|v_j| + |o|): in the accumulation term with sum_d |q_d k_d| + |bias| + |mask| (+ 100 on the region form, which adds 100
+    where the regions are equal) + the row's largest such sum as the size of ds_j."""
+    q64, k64, v64 = q.double(), k.double(), v.double()
+    qs = rne_bf16(q.float() * scale) if mfma else q64 * scale
+    s = qs @ k64.transpose(-1, -2)
+    sa = qs.abs() @ k64.abs().transpose(-1, -2)
+    if bias is not None:
+        s, sa = s + bias.double().unsqueeze(0), sa + bias.double().abs().unsqueeze(0)
+    if mask is not None:
+        b = q.shape[0]
+        m64 = mask.double().unsqueeze(1).unsqueeze(0)
+        s = (s.view(b // nw, nw, *s.shape[1:]) + m64).view(*s.shape)
+        sa = (sa.view(b // nw, nw, *sa.shape[1:]) + m64.abs()).view(*sa.shape)
+    if region:
+        sa = sa + 100.0
+    sa = sa + sa.amax(-1, keepdim=True)
+    p = torch.softmax(s, -1)
+    o = p @ v64
+    pv = p @ v64.abs()
+    acc = pv + (p * sa) @ v64.abs() + (p * sa).sum(-1, keepdim=True) * o.abs()
+    B, H, N, hd = o.shape
+    flat = lambda t: t.permute(0, 2, 1, 3).reshape(B * N, H * hd)
+    kk = max(k.shape[2], hd)
+    check_bf16(out.cpu(), flat(o), acc64=flat(acc), k=kk, extra=flat(pv) * 2.0 ** -8 if mfma else 0.0, single_rounding=not mfma, what=what)
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -106,6 +175,9 @@ def test_attention_core(cuda, cfg, dtype):
     vf = kv.float()[:, c:].reshape(B, Nk, H, hd).permute(0, 2, 1, 3)
     ref = _attn_ref(qf, kf, vf, scale, bias, mask, cfg["nw"]).permute(0, 2, 1, 3).reshape(B * Nq, c)
     assert (out.float().cpu() - ref).abs().max().item() < _tol(dtype, 2e-5, 2e-2)
+    if dtype == torch.bfloat16:   # (mt4_attention's dispatch, transformer_kernels.hip:762: the matrix-unit core for hd 256 / 384 without bias / mask)
+        mfma = hd in (256, 384) and bias is None and mask is None and Nk <= 160
+        _check_attn_bf16(out, qf, kf, vf, scale, bias, mask, cfg["nw"], mfma=mfma, what=f"attention core {cfg}")
 
 
 @pytest.mark.parametrize("hd", [256, 384])
@@ -124,10 +196,12 @@ def test_mha_mfma_head_dim_256(cuda, B, H, Nq, Nk, hd):
     ref = _attn_ref(sp(q, Nq), sp(kv[:, :c], Nk), sp(kv[:, c:], Nk), scale, None, None, 0).permute(0, 2, 1, 3).reshape(B * Nq, c)
     assert torch.isfinite(out.float()).all()
     assert (out.float().cpu() - ref).abs().max().item() < 2e-2
+    _check_attn_bf16(out, sp(q, Nq), sp(kv[:, :c], Nk), sp(kv[:, c:], Nk), scale, None, None, 0, mfma=True, what=f"mha mfma {(B, H, Nq, Nk, hd)}")
     # sharper scores (a few keys dominate): the probabilities' bf16 rounding shows most here
     out2 = ops.attention(qd, kvd[:, :c], kvd[:, c:], batch=B, heads=H, nq=Nq, nk=Nk, hd=hd, q_stride=c, k_stride=2 * c, v_stride=2 * c, scale=1.0)
     ref2 = _attn_ref(sp(q, Nq), sp(kv[:, :c], Nk), sp(kv[:, c:], Nk), 1.0, None, None, 0).permute(0, 2, 1, 3).reshape(B * Nq, c)
     assert (out2.float().cpu() - ref2).abs().max().item() < 2e-2
+    _check_attn_bf16(out2, sp(q, Nq), sp(kv[:, :c], Nk), sp(kv[:, c:], Nk), 1.0, None, None, 0, mfma=True, what=f"mha mfma scale 1 {(B, H, Nq, Nk, hd)}")
 
 
 @pytest.mark.parametrize("B,H,Nq,Nk,hd", [(1, 8, 256, 256, 32), (1, 8, 256, 256, 48), (1, 8, 256, 256, 72), (1, 8, 256, 256, 108),
@@ -161,6 +235,10 @@ def test_linear_gelu_rowmap_and_column_slices(cuda, dtype):
     ref = F.gelu(F.linear(x, w, b))
     got = ops.linear(x.to(cuda, dtype), wp, b.to(cuda), act="gelu")
     assert (got.float().cpu() - ref).abs().max().item() < _tol(dtype, 2e-5, 2e-2)
+    bf = dtype == torch.bfloat16
+    lin64, acc64 = F.linear(x.double(), w.double(), b.double()), F.linear(x.double().abs(), w.double().abs(), b.double().abs())
+    if bf:
+        check_bf16(got.cpu(), F.gelu(lin64), acc64=acc64 * GELU_MAX_SLOPE, k=k + 1, extra=GELU_APPROX_ERR, what="linear + GELU")
     # scatter epilogue: out[perm[m]] = res[perm[m]] + x[m] @ W^T, per-"image" map of length 144
     perm = torch.randperm(144, generator=torch.Generator().manual_seed(3)).to(torch.int32)
     res = _rand((m, n), 24).to(dtype).float()
@@ -169,12 +247,18 @@ def test_linear_gelu_rowmap_and_column_slices(cuda, dtype):
     ref2[full] = res[full] + F.linear(x, w, b)
     got2 = ops.linear(x.to(cuda, dtype), wp, b.to(cuda), residual=res.to(cuda, dtype), out_row_map=perm.to(cuda))
     assert (got2.float().cpu() - ref2).abs().max().item() < _tol(dtype, 2e-5, 3e-2)
+    if bf:
+        r64 = res.double()
+        check_bf16(got2.cpu()[full], r64[full] + lin64, acc64=r64[full].abs() + acc64, k=k + 2, what="linear, scattered residual epilogue")
     # column-slice output and residual of wider buffers
     wide = torch.zeros((m, 3 * n), dtype=dtype, device=cuda)
     rwide = _rand((m, 2 * n), 25).to(dtype)
     ops.linear(x.to(cuda, dtype), wp, b.to(cuda), residual=rwide.to(cuda)[:, n:], out=wide[:, n:2 * n])
     ref3 = F.linear(x, w, b) + rwide.float()[:, n:]
     assert (wide[:, n:2 * n].float().cpu() - ref3).abs().max().item() < _tol(dtype, 2e-5, 3e-2)
+    if bf:
+        r64 = rwide.double()[:, n:]
+        check_bf16(wide[:, n:2 * n].cpu(), lin64 + r64, acc64=acc64 + r64.abs(), k=k + 2, what="linear, column-slice output and residual")
     assert wide[:, :n].abs().max().item() == 0 and wide[:, 2 * n:].abs().max().item() == 0
 
 
@@ -189,6 +273,9 @@ def test_patchify_matches_conv4x4(cuda, dtype):
         rows = ops.patchify(inp, 4, dtype, synth.IMAGENET_MEAN, synth.IMAGENET_STD)
         got = rows.float().cpu() @ w.view(16, 48).t()
         assert (got - ref).abs().max().item() < _tol(dtype, 1e-4, 5e-2)
+    if dtype == torch.bfloat16:   # float input: the rows are the fp32 pixels in (c, kh, kw) order, each rounded once (transformer_kernels.hip:854)
+        rows64 = F.unfold(xn.double(), 4, stride=4).transpose(1, 2).reshape(-1, 48)
+        check_bf16(ops.patchify(xn.to(cuda), 4, dtype).cpu(), rows64, what="patchify rows from float input")
     if dtype == torch.bfloat16:   # uint8 frames, P = 4, bf16 rows run a kernel of their own (12 bytes per thread, table-driven): the generic kernel's bits
         for (b, h, w_) in ((2, 32, 48), (3, 96, 100), (1, 384, 384)):
             fr = synth.synthetic_frames(b, h, w_, seed=h + w_).to(cuda)
@@ -203,6 +290,8 @@ def test_small_elementwise_pieces(cuda, dtype):
     p = _rand((10, 64), 42).to(dtype)
     got = ops.add_rowbcast(x.to(cuda), p.to(cuda)).float().cpu()
     assert (got - (x.float().view(3, 10, 64) + p.float()).view(-1, 64)).abs().max().item() < _tol(dtype, 1e-6, 2e-2)
+    if dtype == torch.bfloat16:   # fp32 add, one rounding (transformer_kernels.hip:941-956): torch's own bf16 add, bit for bit
+        assert torch.equal(ops.add_rowbcast(x.to(cuda), p.to(cuda)).cpu().view(torch.int16), (x.view(3, 10, 64) + p).view(-1, 64).view(torch.int16))
     hs = _rand((4 * 6, 256), 43).to(dtype)
     W, b = _rand((6, 256), 44), _rand((6,), 45)
     got = ops.groupwise_linear(hs.to(cuda), W.to(cuda), b.to(cuda), 4, 6).cpu()
@@ -213,6 +302,13 @@ def test_small_elementwise_pieces(cuda, dtype):
     got = ops.dwconv1d_k3(xd.to(cuda), wd.to(cuda), bd.to(cuda), act="gelu").float().cpu()
     ref = F.gelu(F.conv1d(xd.float().transpose(1, 2), wd.unsqueeze(1), bd, padding=1, groups=64)).transpose(1, 2)
     assert (got - ref).abs().max().item() < _tol(dtype, 1e-5, 2e-2)
+    if dtype == torch.bfloat16:   # three fp32 taps + fp32 bias, activation in fp32, one rounding (transformer_kernels.hip:1019-1025)
+        x64 = xd.double().transpose(1, 2)
+        pre64 = F.conv1d(x64, wd.double().unsqueeze(1), bd.double(), padding=1, groups=64).transpose(1, 2)
+        acc64 = F.conv1d(x64.abs(), wd.double().abs().unsqueeze(1), bd.double().abs(), padding=1, groups=64).transpose(1, 2)
+        check_bf16(ops.dwconv1d_k3(xd.to(cuda), wd.to(cuda), bd.to(cuda), act="gelu").cpu(), F.gelu(pre64), acc64=acc64 * GELU_MAX_SLOPE, k=4,
+                   extra=GELU_APPROX_ERR, what="dwconv1d_k3 + GELU")
+        check_bf16(ops.dwconv1d_k3(xd.to(cuda), wd.to(cuda), bd.to(cuda)).cpu(), pre64, acc64=acc64, k=4, what="dwconv1d_k3")
 
 
 def test_kd_mix_matches_reference_branch(cuda):
@@ -249,6 +345,7 @@ def test_window_attention_mfma_bf16(cuda, cfg):
     sp = lambda t: t.reshape(B, N, H, 32).permute(0, 2, 1, 3)
     ref = _attn_ref(sp(f[:, :c]), sp(f[:, c:2 * c]), sp(f[:, 2 * c:]), scale, bias, mask, cfg["nw"]).permute(0, 2, 1, 3).reshape(B * N, c)
     assert (out.float().cpu() - ref).abs().max().item() < 3e-2
+    _check_attn_bf16(out, sp(f[:, :c]), sp(f[:, c:2 * c]), sp(f[:, 2 * c:]), scale, bias, mask, cfg["nw"], mfma=True, what=f"window attention {cfg}")
     gen = ops.attention(d[:, :c], d[:, c:2 * c], d[:, 2 * c:], batch=B, heads=H, nq=N, nk=N, hd=32, q_stride=3 * c, k_stride=3 * c, v_stride=3 * c,
                         scale=scale, bias=bias.to(cuda), mask=mask.to(cuda) if mask is not None else None)
     assert (out.float() - gen.float()).abs().max().item() < 3e-2
@@ -276,6 +373,8 @@ def test_window_attention_from_relative_table_equals_expanded_tables(cuda, ws, H
                                     mask_padded=ops.pad_attention_bias(mask.to(cuda), 0.0) if shift else None, **kw)
     got = ops.window_attention_rel_bf16(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], ws=ws, rel_table=table.t().contiguous().to(cuda),
                                         region=_shift_regions(res, ws, shift).to(torch.int32).to(cuda) if shift else None, **kw)
+    q, k, v = [t.cpu().view(B, N, H, 32).permute(0, 2, 1, 3) for t in (qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:])]
+    _check_attn_bf16(got, q, k, v, scale, bias, mask, nwin, mfma=True, region=bool(shift), what=f"window attention rel table {(ws, H, res, shift)}")
     if not shift:
         assert torch.equal(got, ref)
         return
