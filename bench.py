@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Headline benchmark: spatial-extract frames/s (Spatial_cnn ResNet-50, 224x224, bf16, synthetic frames
-resident in HBM) + per-video TCN latency (Temporal_tenco), beside the CPU oracle timed on the host.
+resident in HBM); with --full also per-video TCN latency (Temporal_tenco) and the other sub-records, beside the CPU
+oracle timed on the host.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W            # headline only: set up, warm up, time K steps, print
+  python bench.py --gpus N --steps K --warmup W --full     # + every sub-record (see rank0_record, ddp_train_bench)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the extraction hot path over one batch of B frames per GPU: uint8 frames ->
@@ -44,16 +46,21 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--streams", type=int, default=1, help="HIP streams per GPU; every stream gets --batch frames of a step (round 3: one stream over 2672 "
                     "frames = two streams of 1336 within 1 %%, profiles/r03_stream_skew_ab.txt -- the launches of two parts do not overlap usefully)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-temporal", action="store_true")
-    ap.add_argument("--no-ddp-train", action="store_true", help="N > 1: skip the data-parallel training sub-record")
-    ap.add_argument("--ddp-timeout", type=float, default=300.0, help="N > 1: seconds after which the data-parallel training sub-record is given up and the headline line is printed without it")
-    ap.add_argument("--per-layer", default="", help="write a per-conv-layer timing table (json) to this path")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything beyond the headline: per-launch conv timings, "
+                    "temporal / Swin / training / end-to-end / fp32 parity-mode sub-records, the CPU baseline, and for N > 1 the data-parallel training "
+                    "sub-record.  Without it a run times the steps and prints the headline line only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle timings")
+    ap.add_argument("--no-temporal", action="store_true", help="--full: skip the single-GPU sub-records (temporal, Swin, training, end-to-end, parity mode)")
+    ap.add_argument("--no-ddp-train", action="store_true", help="--full, N > 1: skip the data-parallel training sub-record")
+    ap.add_argument("--ddp-timeout", type=float, default=300.0, help="--full, N > 1: seconds after which the data-parallel training sub-record is given up and the headline line is printed without it")
+    ap.add_argument("--per-layer", default="", help="--full: write a per-conv-layer timing table (json) to this path")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned (rank 0) "
                     "as DIR/<name>.npy, float32, at most 64 MB in all (see dump_outputs)")
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.per_layer and not a.full:
+        ap.error("--per-layer needs --full (the table comes from the per-launch timing passes)")
     return a
 
 
@@ -782,15 +789,13 @@ def main():
     fps = world * nstep * a.steps / dt
 
     def rank0_record():
-        """everything beyond the timed region that only rank 0 computes (per-launch roofline, single-GPU sub-records)"""
+        """the result line rank 0 prints: the headline and the roofline figures that follow from the timed steps alone; with --full also
+        everything that takes GPU or CPU runs of its own (per-launch roofline, per-layer table, single-GPU sub-records, CPU baseline)"""
         flops_frame = conv_flops_per_frame(model, a.height, a.width)
-        per_launch = time_conv_kernels(model, frames[:a.batch].contiguous())   # the launches of ONE stream's part of a step
-        conv_ms = sum(per_launch)
         peak = PEAK_BF16_TFLOPS if dtype == torch.bfloat16 else PEAK_F32_MFMA_TFLOPS
         # `achieved` / `frac` follow from the TIMED number: algorithmic conv FLOPs of the step's frames / ms_per_step (everything the step does --
-        # preprocess, avgpool, heads -- counts against it).  The conv-launches-only figure (HIP events around each launch) is kept beside it.
+        # preprocess, avgpool, heads -- counts against it).  With --full the conv-launches-only figure (HIP events around each launch) is kept beside it.
         achieved = flops_frame * nstep / (ms_per_step * 1e-3) / 1e12
-        achieved_conv = flops_frame * a.batch / (conv_ms * 1e-3) / 1e12
         # HBM bytes and MFMA-busy share of the same launches from rocprofv3 PMC passes (tools/collect_traffic.py, tools/collect_mfma_util.py;
         # commands in profiles/README.md), collected OFFLINE and committed: a figure is published only while the sources of the measured
         # kernels are the ones it was collected on (`kernels_sha`), and the line says which collection it is; null otherwise
@@ -820,14 +825,29 @@ def main():
         mfma_util, mfma_util_source = committed("mfma_util.json", "mfma_util", CONV_SOURCES, [(k, 1.0) for k, _ in keys])
         roofline = dict(bound="mfma", kernel="conv launches of one step (igemm_conv_kernel, conv3x3_patch_kernel, stem_pool_kernel, bottleneck64_fused_kernel, chain_gemm_kernel)", achieved=round(achieved, 2),
                         peak=peak, unit="TFLOP/s", frac=round(achieved / peak, 4), traffic=traffic, traffic_source=traffic_source,
-                        mfma_util_pmc=mfma_util, mfma_util_source=mfma_util_source,
-                        launches_per_step=len(per_launch), conv_ms_per_step=round(conv_ms, 4), ms_per_step=round(ms_per_step, 4),
-                        achieved_conv_launches=round(achieved_conv, 2), frac_conv_launches=round(achieved_conv / peak, 4),
-                        frames_in_conv_ms=a.batch,
+                        mfma_util_pmc=mfma_util, mfma_util_source=mfma_util_source, ms_per_step=round(ms_per_step, 4),
                         gflop_per_frame=round(flops_frame / 1e9, 3), traffic_unit="HBM bytes per step (all conv launches)",
-                        note="achieved / frac = algorithmic conv FLOPs of the step / ms_per_step (the timed region); *_conv_launches = the same FLOPs / the "
-                             "summed durations of the step's conv launches (HIP events on the launch stream, one pair per launch): "
-                             "conv_ms_per_step <= ms_per_step, the rest is preprocess + avgpool + heads")
+                        note="achieved / frac = algorithmic conv FLOPs of the step / ms_per_step (the timed region)")
+        res = {
+            "metric": METRIC,
+            "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": a.dtype, "data": "synthetic",
+            "config": {"workload": f"Spatial_cnn {a.network} extractor, {a.height}x{a.width} frames, {a.dtype}, eval "
+                                   f"(BASELINE configs[1])", "frames_per_gpu_per_step": nstep, "streams_per_gpu": a.streams,
+                       "frames_per_stream": a.batch, "global_frames_per_step": nstep * world,
+                       "parallelism": f"frame-sharded x{world}, no collective"},
+            "roofline": roofline,
+        }
+        if not a.full:
+            return res
+        per_launch = time_conv_kernels(model, frames[:a.batch].contiguous())   # the launches of ONE stream's part of a step
+        conv_ms = sum(per_launch)
+        achieved_conv = flops_frame * a.batch / (conv_ms * 1e-3) / 1e12
+        roofline.update(launches_per_step=len(per_launch), conv_ms_per_step=round(conv_ms, 4),
+                        achieved_conv_launches=round(achieved_conv, 2), frac_conv_launches=round(achieved_conv / peak, 4), frames_in_conv_ms=a.batch,
+                        note=roofline["note"] + "; *_conv_launches = the same FLOPs / the summed durations of the step's conv launches (HIP events on "
+                             "the launch stream, one pair per launch): conv_ms_per_step <= ms_per_step, the rest is preprocess + avgpool + heads")
         if a.per_layer:
             plan = model.conv_plan(a.height, a.width)
             groups = model.launch_groups(a.height, a.width)
@@ -846,17 +866,6 @@ def main():
                 rows.append(dict(rec, ms=round(ms, 4), tflops=round(fl / (ms * 1e-3) / 1e12, 1)))
             os.makedirs(os.path.dirname(os.path.abspath(a.per_layer)), exist_ok=True)
             json.dump(rows, open(a.per_layer, "w"), indent=1)
-        res = {
-            "metric": METRIC,
-            "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": a.dtype, "data": "synthetic",
-            "config": {"workload": f"Spatial_cnn {a.network} extractor, {a.height}x{a.width} frames, {a.dtype}, eval "
-                                   f"(BASELINE configs[1])", "frames_per_gpu_per_step": nstep, "streams_per_gpu": a.streams,
-                       "frames_per_stream": a.batch, "global_frames_per_step": nstep * world,
-                       "parallelism": f"frame-sharded x{world}, no collective"},
-            "roofline": roofline,
-        }
         if world == 1 and not a.no_temporal:
             res["temporal"] = temporal_bench(dev, do_cpu=not a.no_cpu_baseline)
             # the per-video latency half of the metric, where the driver's parsed record keeps it
@@ -907,7 +916,7 @@ def main():
                    "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype,
                    "data": "synthetic", "config": {"workload": f"Spatial_cnn {a.network} extractor, {a.height}x{a.width} frames, {a.dtype}, eval (BASELINE configs[1])"},
                    "roofline": None, "error": f"rank-0 sub-records failed: {type(e).__name__}: {e}"}
-    if world > 1 and not a.no_ddp_train:
+    if world > 1 and a.full and not a.no_ddp_train:
         # the headline line must survive the sub-record: an exception is caught below; a collective that never returns (the RCCL exchange has
         # not run on more than one GPU before the driver's scaling run) is cut by a timer -- rank 0 prints the line it has, every rank leaves
         def give_up():

@@ -33,3 +33,19 @@ def test_bench_under_torchrun_and_single_rank():
     assert rec["n_gpus"] == 2
     rec1 = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "0"])
     assert rec1["n_gpus"] == 1
+
+
+def test_bench_full_is_opt_in():
+    """a plain run measures the headline only: --full is off by default, and the per-layer table (from the per-launch timing passes of a
+    --full run) is refused without it instead of being silently skipped"""
+    import bench
+    argv, sys.argv = sys.argv, ["bench.py", "--steps", "2", "--warmup", "0"]
+    try:
+        assert bench.parse().full is False
+        sys.argv = ["bench.py", "--full", "--per-layer", "layers.json"]
+        a = bench.parse()
+        assert a.full and a.per_layer == "layers.json"
+    finally:
+        sys.argv = argv
+    p = subprocess.run([sys.executable, "bench.py", "--per-layer", "layers.json"], cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert p.returncode == 2 and "--per-layer needs --full" in p.stderr

@@ -8,10 +8,10 @@ cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out
 mkdir -p $O; rm -rf $O/pmc_fetch $O/pmc_write $O/prof_final $O/pmc_mfma $O/prof_tenco_f32 $O/prof_tenco_bf16 $O/pmc_tenco_FETCH_SIZE $O/pmc_tenco_WRITE_SIZE $O/prof_mstct_train $O/prof_q2l_train $O/prof_tenco2000_f32 $O/prof_tenco2000_bf16 $O/prof_swin
 cd $R
-timeout -k 10 900 python bench.py --per-layer gpurun_out/layers_final.json > gpurun_out/bench_final.json 2> gpurun_out/bench_final.err
+timeout -k 10 900 python bench.py --full --per-layer $O/layers_final.json > $O/bench_final.json 2> $O/bench_final.err
 echo bench done
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_final -o final -- python3 $R/bench.py --streams 1 --steps 10 --warmup 3 --no-cpu-baseline --no-temporal > $O/prof_final.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_final -o final -- python3 $R/bench.py --full --streams 1 --steps 10 --warmup 3 --no-cpu-baseline --no-temporal > $O/prof_final.log 2>&1
 echo stats done
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-temporal > $O/pmc_fetch.log 2>&1
 echo fetch done
