@@ -17,6 +17,7 @@ import torch
 
 from . import cholect, extract, featfile
 from .metrics import Recognition, final_report, gather_recognition, recognition_from
+from .trainloop import _barrier, _dist, _log, add_schedule_flags, deal, run_epochs
 
 
 def extraction_batch(img_size, device_batch):
@@ -47,30 +48,18 @@ def _common(p: argparse.ArgumentParser):
                    help="device: inflate + PNG unfiltering on the GPU (mt4_png_inflate / mt4_png_unfilter_rgb8), the host only reads the files")
 
 
-def _dist():
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_rank(), dist.get_world_size()
-    return 0, 1
-
-
-def _barrier():
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        dist.barrier()
-
-
 def _chlg(F) -> bool:
     """`set_chlg_eval` of the reference's drivers (`Spatial_cnn/run.py:122`): the challenge evaluation protocol (null triplets left out of the
     100-way AP) for the `*challenge*` dataset variants"""
     return "challenge" in str(getattr(F, "dataset_variant", ""))
 
 
-def _log(path: str, msg: str):
-    print(msg)
-    os.makedirs(os.path.dirname(path), exist_ok=True)
-    with open(path, "a+") as f:
-        print(msg, file=f)
+def _stem(F, kfold: int = None, task_dir: bool = False) -> str:
+    """`./__checkpoint__/run_<version>[_<task>]/<modelname>`, the stem of a run's log and checkpoints.  modelname: the spatial drivers'
+    `<model>_l<variant>_cholect<kfold>` when kfold is given, else the temporal drivers' `<model>_l8_cholect<variant>_k<kfold>_batchnorm_lowres`
+    (`Temporal_tenco/run.py:137-142`); task_dir: the task suffix of single-task runs (`Spatial_transformer/run.py:86-88`, `Temporal_mstct/run.py:88-90`)"""
+    name = f"{F.model}_l{F.dataset_variant}_cholect{kfold}" if kfold is not None else f"{F.model}_l8_cholect{F.dataset_variant}_k{F.kfold}_batchnorm_lowres"
+    return os.path.join(f"./__checkpoint__/run_{F.version}" + (f"_{F.loss_type}" if task_dir and F.loss_type != "all" else ""), name)
 
 
 def _sigmoid(x: torch.Tensor) -> np.ndarray:
@@ -132,10 +121,8 @@ def spatial_cnn_eval(argv=None) -> Dict[str, float]:
     F.train = False
     rank, world = _dist()
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
-    modelname = f"{F.model}_l{F.dataset_variant}_cholect{kfold}"
-    model_dir = f"./__checkpoint__/run_{F.version}"
-    logfile = os.path.join(model_dir, modelname + ".log")
-    ckpt = F.test_ckpt or os.path.join(model_dir, modelname + ".pth")
+    stem = _stem(F, kfold)
+    ckpt = F.test_ckpt or stem + ".pth"
     model = VideoNas(args=F, dtype=torch.float32 if F.dtype == "fp32" else torch.bfloat16).eval()
     model.load_state_dict(torch.load(ckpt, map_location="cpu"))
     _, _, videos = cholect.split_videos(F.dataset_variant, kfold)
@@ -146,7 +133,7 @@ def spatial_cnn_eval(argv=None) -> Dict[str, float]:
     res = {}
     try:
         if rank == 0:
-            res = _write_report(logfile, m, F.loss_type, _chlg(F), "spatial_cnn")
+            res = _write_report(stem + ".log", m, F.loss_type, _chlg(F), "spatial_cnn")
     finally:
         _barrier()
     return res
@@ -214,6 +201,43 @@ def load_train_frames_u8(data_dir, video, frame_ids, height, width, rng, aug_nam
     return out
 
 
+def _teacher_files(F, kfold):
+    """the teacher prediction / feature files of --loss_type all ({task: {video key: rows}} for i, v, t): the distillation losses read them
+    (`dataloader.py:216-238` loads them regardless; a single-task run never uses them)"""
+    if F.loss_type != "all":
+        return {}, {}
+    tdir = lambda ver, task, kind: featfile.feats_path("..", ver, kfold, task, kind)
+    return ({t: featfile.read_feats(tdir(F.teacher_pred_version, t, "pred")) for t in "ivt"},
+            {t: featfile.read_feats(tdir(F.teacher_feat_version, t, "feats")) for t in "ivt"})
+
+
+def _frame_batch(F, batch, labels, tpred, tfeat, size, rng):
+    """a training batch of (video, frame) samples -> (uint8 frames [B,H,W,3] on the GPU through the train transform at size = (H, W), the
+    labels of the i, v, t, ivt heads, the teacher predictions and features of i, v, t -- empty without teacher files)"""
+    frames = np.concatenate([load_train_frames_u8(F.data_dir, v, [labels[v]["ivt"][i, 0]], size[0], size[1], rng, F.augmentation_list)
+                             for v, i in batch])
+    lab = [torch.from_numpy(np.stack([labels[v][k][i, 1:] for v, i in batch])) for k in ("i", "v", "t", "ivt")]
+    rows = lambda files: [torch.from_numpy(np.stack([files[t][featfile.video_key(v)][i] for v, i in batch]).astype(np.float32))
+                          for t in "ivt"] if files else []
+    return torch.from_numpy(frames).cuda(), lab, rows(tpred), rows(tfeat)
+
+
+def _frame_validation(F, val_videos, labels, size, cap, forward):
+    """validation mAP of the task's head (`run.py:416-451`; ivt for --loss_type all) over the validation videos' frames in device batches of
+    max(--batch, min(--device_batch, cap)) (results do not depend on it); forward(uint8 frames) -> the head's logits"""
+    vt = F.loss_type if F.loss_type != "all" else "ivt"
+    m = Recognition({"i": 6, "v": 10, "t": 15, "ivt": 100}[vt])
+    vb = max(F.batch, min(F.device_batch, cap))
+    for v in val_videos:
+        lv = labels[v][vt]
+        for s0 in range(0, len(lv), vb):
+            fr = cholect.load_frames_device(F.data_dir, v, lv[s0:s0 + vb, 0], size[0], size[1], workers=F.decode_workers, decode=F.png_decode)
+            m.update(lv[s0:s0 + vb, 1:], _sigmoid(forward(fr)))
+        m.video_end()
+    score = float(m.compute_video_AP(ignore_null=_chlg(F))["mAP"]) if val_videos else 0.0
+    return score, f"{vt}: [{score:.5f}]"
+
+
 def spatial_cnn_train(argv=None) -> Dict[str, float]:
     """`Spatial_cnn/run.py -t` (:296-470): student distillation.  Shuffled frames of all training videos in batches of --batch; with
     torchrun every rank takes its own batch of a step (frame-DDP: global batch = world x --batch), BatchNorm statistics stay per
@@ -223,25 +247,18 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
 
     from .spatial_cnn import VideoNas
     from .spatial_cnn_train import SpatialCnnTrainer
-    from .tenco_train import lr_at_epoch
     from . import shapes, synth
     p = argparse.ArgumentParser()
     _common(p)
+    add_schedule_flags(p)
     p.add_argument("--network", type=str, default="resnet18")
     p.add_argument("--student_dim", type=int, default=512)
     p.add_argument("--teacher_dim", type=int, default=1536)
     p.add_argument("--teacher_feat_version", type=str, default="Q2L")
     p.add_argument("--teacher_pred_version", type=str, default="Q2LMSTCT")
     p.add_argument("--augmentation_list", type=str, nargs="*", default=["original", "vflip", "hflip", "contrast", "rot90"])
-    p.add_argument("--epochs", type=int, default=100)
-    p.add_argument("-w", "--warmups", type=int, nargs="+", default=[9, 18, 58])
-    p.add_argument("-l", "--initial_learning_rates", type=float, nargs="+", default=[0.01, 0.01, 0.01])
     p.add_argument("--rates", type=float, nargs="+", default=[1, 0, 0.1])
-    p.add_argument("--weight_decay", type=float, default=1e-5)
     p.add_argument("--temp", type=int, default=4)
-    p.add_argument("--decay_rate", type=float, default=0.99)
-    p.add_argument("--power", type=float, default=0.1)
-    p.add_argument("--val_interval", type=int, default=1)
     p.add_argument("--pretrain_dir", type=str, default="")
     p.add_argument("--operand_dtype", type=str, default="fp32", choices=["fp32", "bf16"],
                    help="bf16: the convolutions' GEMM operands in bf16 (activations, gradients, weight copies), master weights and sums fp32")
@@ -251,11 +268,8 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     single = F.loss_type != "all"
     rank, world = _dist()
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
-    modelname = f"{F.model}_l{F.dataset_variant}_cholect{kfold}"
-    model_dir = f"./__checkpoint__/run_{F.version}"
-    logfile = os.path.join(model_dir, modelname + ".log")
-    ckpt, latest = os.path.join(model_dir, modelname + ".pth"), os.path.join(model_dir, modelname + "_latest.pth")
-    val_interval = F.epochs - 1 if F.val_interval == -1 else F.val_interval
+    stem = _stem(F, kfold)
+    latest = stem + "_latest.pth"
     tr = SpatialCnnTrainer(F.network, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay, rates=F.rates, temp=float(F.temp),
                            teacher_dim=F.teacher_dim, loss_type=F.loss_type,
                            operand_dtype=torch.bfloat16 if F.operand_dtype == "bf16" else torch.float32)
@@ -267,59 +281,28 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     tr.load_state_dict(sd)
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, kfold)
     labels = {v: cholect.load_labels(F.data_dir, v) for v in train_videos + val_videos}
-    tdir = lambda ver, task, kind: featfile.feats_path("..", ver, kfold, task, kind)
-    # the teacher files feed the distillation losses only (`dataloader.py:216-238` loads them regardless; a single-task run never uses them)
-    tpred = {} if single else {t: featfile.read_feats(tdir(F.teacher_pred_version, t, "pred")) for t in "ivt"}
-    tfeat = {} if single else {t: featfile.read_feats(tdir(F.teacher_feat_version, t, "feats")) for t in "ivt"}
+    tpred, tfeat = _teacher_files(F, kfold)
     samples = [(v, i) for v in train_videos for i in range(len(labels[v]["ivt"]))]
     order_rng, aug_rng = random.Random(F.seed), random.Random(F.seed * 1000003 + rank)
+    size = (F.image_height, F.image_width)
     eval_args = argparse.Namespace(**vars(F))
     eval_args.train = False
-    best, last = 0.0, {}
-    for epoch in range(F.epochs):
-        tr.lr = lr_at_epoch(epoch, F.initial_learning_rates[2], F.power, F.warmups[2], F.decay_rate)
+
+    def train_epoch(epoch):
         order = list(samples)
         order_rng.shuffle(order)                             # the same permutation on every rank
-        nb = (len(order) + F.batch - 1) // F.batch
-        steps = (nb + world - 1) // world
-        t0, tot = time.time(), 0.0
-        for s in range(steps):
-            bi = (s * world + rank) % nb
-            batch = order[bi * F.batch:(bi + 1) * F.batch]
-            frames = np.concatenate([load_train_frames_u8(F.data_dir, v, [labels[v]["ivt"][i, 0]], F.image_height, F.image_width, aug_rng,
-                                                          F.augmentation_list) for v, i in batch])
-            lab = [torch.from_numpy(np.stack([labels[v][k][i, 1:] for v, i in batch])) for k in ("i", "v", "t", "ivt")]
-            key = lambda v: featfile.video_key(v)
-            tp = [] if single else [torch.from_numpy(np.stack([tpred[t][key(v)][i] for v, i in batch]).astype(np.float32)) for t in "ivt"]
-            tf = [] if single else [torch.from_numpy(np.stack([tfeat[t][key(v)][i] for v, i in batch]).astype(np.float32)) for t in "ivt"]
-            terms = tr.train_step(torch.from_numpy(frames).cuda(), lab, tp, tf)
-            tot += terms["loss"]
-        last = {"loss": tot / steps, "lr": tr.lr}
-        if rank == 0:
-            _log(logfile, f"Traning | lr: {tr.lr:.6f} | epoch {epoch} | loss {tot / steps:.4f} | {time.time() - t0:.2f} secs")
-        if epoch % val_interval == 0 and rank == 0:          # `weight_mgt`: latest every validation, best by triplet mAP
-            state = tr.state_dict()
-            torch.save(state, latest)
-            model = VideoNas(args=eval_args, dtype=torch.float32).eval()
-            model.load_state_dict(state)
-            vt = F.loss_type if single else "ivt"               # the head the validation mAP is taken on (`run.py:416-451`)
-            m = Recognition({"i": 6, "v": 10, "t": 15, "ivt": 100}[vt])
-            for v in val_videos:
-                lv = labels[v][vt]
-                vb = max(F.batch, min(getattr(F, "device_batch", F.batch), 256))     # validation passes in device batches (results do not depend on it)
-                for s0 in range(0, len(lv), vb):
-                    fr = cholect.load_frames_device(F.data_dir, v, lv[s0:s0 + vb, 0], F.image_height, F.image_width,
-                                                    workers=getattr(F, "decode_workers", 0), decode=getattr(F, "png_decode", "host"))
-                    m.update(lv[s0:s0 + vb, 1:], _sigmoid(model.extract_u8(fr)["ivt".index(vt) if single else 3][1]))
-                m.video_end()
-            score = float(m.compute_video_AP(ignore_null=_chlg(F))["mAP"]) if val_videos else 0.0
-            last["val_mAP_ivt"] = score
-            if score > best or not os.path.exists(ckpt):
-                best = max(best, score)
-                torch.save(state, ckpt)
-                _log(logfile, f">>> Saving checkpoint for epoch {epoch + 1} at {ckpt}, time {time.ctime()} ")
-            _log(logfile, f"\t\t\t\t\t\t\t video-wise | eta {time.time() - t0:.2f} secs | mAP => ivt: [{score:.5f}] ")
-    return last
+        mine, tot = deal(order, F.batch, world, rank), 0.0
+        for batch in mine:
+            tot += tr.train_step(*_frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng))["loss"]
+        return tot, len(mine)
+
+    def validate(state):
+        model = VideoNas(args=eval_args, dtype=torch.float32).eval()
+        model.load_state_dict(state)
+        gi = "ivt".index(F.loss_type) if single else 3
+        return _frame_validation(F, val_videos, labels, size, 256, lambda fr: model.extract_u8(fr)[gi][1])
+
+    return run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", latest, stem + ".pth", score_key="val_mAP_ivt")
 
 
 # ------------------------------------------------------------------------------------------------ Temporal_tenco/run.py -e
@@ -335,13 +318,7 @@ def tenco_eval(argv=None) -> Dict[str, float]:
     p.add_argument("--output", default=False, type=bool)
     p.add_argument("--hier", default=False, type=bool)
     p.add_argument("--input_dim", type=int, default=512)
-    p.add_argument("--epochs", type=int, default=100)
-    p.add_argument("-w", "--warmups", type=int, nargs="+", default=[9, 18, 58])
-    p.add_argument("-l", "--initial_learning_rates", type=float, nargs="+", default=[0.01, 0.01, 0.01])
-    p.add_argument("--weight_decay", type=float, default=1e-5)
-    p.add_argument("--decay_rate", type=float, default=0.99)
-    p.add_argument("--power", type=float, default=0.1)
-    p.add_argument("--val_interval", type=int, default=1)
+    add_schedule_flags(p)
     F, _ = p.parse_known_args(argv)
     if F.train:
         _tenco_train(F)
@@ -358,12 +335,11 @@ def tenco_eval(argv=None) -> Dict[str, float]:
 
 def _tenco_eval_rank0(F) -> Dict[str, float]:
     from .temporal_tenco import VideoNas
-    modelname = f"{F.model}_l8_cholect{F.dataset_variant}_k{F.kfold}_batchnorm_lowres"   # `run.py:137-142`
-    model_dir = f"./__checkpoint__/run_{F.version}"
-    logfile = os.path.join(model_dir, modelname + ".log")
-    ckpt = F.test_ckpt or os.path.join(model_dir, modelname + ".pth")
+    stem = _stem(F)
+    logfile = stem + ".log"
+    ckpt = F.test_ckpt or stem + ".pth"
     if not os.path.exists(ckpt):   # the shipped scripts always pass --test_ckpt ..._latest.pth (Scripts/test_fold1.sh)
-        ckpt = os.path.join(model_dir, modelname + "_latest.pth")
+        ckpt = stem + "_latest.pth"
     model = VideoNas(F, F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100).eval()
     sd = torch.load(ckpt, map_location="cpu")
     model.load_state_dict({k: v for k, v in sd.items() if k in dict(model._table)}, strict=False)   # `run.py:520`
@@ -373,7 +349,7 @@ def _tenco_eval_rank0(F) -> Dict[str, float]:
     m = recognition_from(_tenco_scores(model, feats, test_videos, F.data_dir), test_videos)     # (rank 0 alone runs this pass)
     _log(logfile, f"eta {time.time() - t0:.3f} secs")
     # `run.py:529-570`: the pickled metric objects, then head-wise ('singletest') and disentangled per-category AP and both mean-AP rows
-    res = _write_report(logfile, m, F.loss_type, _chlg(F), "temporal_tenco", pckl=os.path.join(model_dir, f"mAPs_k{F.kfold}.pckl"))
+    res = _write_report(logfile, m, F.loss_type, _chlg(F), "temporal_tenco", pckl=os.path.join(os.path.dirname(stem), f"mAPs_k{F.kfold}.pckl"))
     return res
 
 
@@ -395,11 +371,10 @@ def _tenco_train(F):
     to the ranks (one video per rank per step) and the flat gradient buffer is all-reduced over RCCL each step."""
     import random
 
-    from .tenco_train import TencoTrainer, lr_at_epoch
+    from .tenco_train import TencoTrainer
+    from .temporal_tenco import VideoNas
     rank, world = _dist()
-    modelname = f"{F.model}_l8_cholect{F.dataset_variant}_k{F.kfold}_batchnorm_lowres"
-    model_dir = f"./__checkpoint__/run_{F.version}"
-    logfile = os.path.join(model_dir, modelname + ".log")
+    stem = _stem(F)
     if not F.fpn:
         # the reference's own train loop cannot run a model without --fpn: `out_list_i / _v / _t` stay empty (`network.py:56-66`), so `loss_i`,
         # `loss_v`, `loss_t` stay the int 0 they start as (`run.py:190`) and `loss_i.item()` raises AttributeError at `run.py:214` in the first step
@@ -408,15 +383,13 @@ def _tenco_train(F):
     tr = TencoTrainer(F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                       hier=bool(getattr(F, "hier", False)))      # --hier True: pooled refinement levels (`network.py:147,154-155`, `run.py:159-179`)
     from . import shapes, synth
-    init = os.path.join(model_dir, modelname + "_latest.pth")
+    init = stem + "_latest.pth"
     if os.path.exists(init):
         tr.load_state_dict(torch.load(init, map_location="cpu"))
     else:   # no torch.nn init here: deterministic synthetic start (the reference starts from torch's default init)
         tr.load_state_dict(synth.fill_from_shapes(shapes.tenco_shapes(F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100, fpn=True),
                                                   seed=F.seed))
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, F.kfold)
-    val_interval = F.epochs - 1 if F.val_interval == -1 else max(1, F.val_interval)
-    best, best_path, vmodel = 0.0, os.path.join(model_dir, modelname + ".pth"), None
     feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, "all"))
     # features and labels of every training video are uploaded ONCE (a per-step pageable host->device copy stalls the step)
     xs, zs = {}, {}
@@ -426,42 +399,29 @@ def _tenco_train(F):
         zs[v] = tr.prepare_labels({k: torch.from_numpy(lab[n][:, 1:]) for k, n in (("", "ivt"), ("_i", "i"), ("_v", "v"), ("_t", "t"))})
     rng = random.Random(F.seed)
     gen = torch.Generator().manual_seed(F.seed + rank)
-    for epoch in range(F.epochs):
-        tr.lr = lr_at_epoch(epoch, F.initial_learning_rates[2], F.power, F.warmups[2], F.decay_rate)
+    vmodel = VideoNas(F, F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100).eval() if rank == 0 else None
+
+    def train_epoch(epoch):
         order = list(train_videos)
         rng.shuffle(order)                                         # same permutation on every rank
-        steps = (len(order) + world - 1) // world
-        t0, tot = time.time(), 0.0
-        for s in range(steps):
-            v = order[(s * world + rank) % len(order)]
+        mine, tot = deal(order, 1, world, rank), 0.0
+        for (v,) in mine:
             x = xs[v]
             masks = tr.draw_masks(x.shape[1], gen)                 # Dropout2d + per-layer Dropout are always on in train mode
             if not F.mask:                                         # (`network.py:123-127,194-196`); --mask gates the 75 % input mask only
                 masks["input_mask"] = None                         # (`network.py:43-48`)
-            loss, _ = tr.train_step(x, zs[v], masks=masks)
-            tot += loss
-        if rank == 0:
-            _log(logfile, f"Traning | lr: {tr.lr:.6f} | epoch {epoch} | loss {tot / steps:.4f} | {time.time() - t0:.2f} secs")
-            state = tr.state_dict()
-            torch.save(state, init + ".tmp")
-            os.replace(init + ".tmp", init)                        # readers never see a half-written checkpoint
-            if epoch % val_interval == 0:                          # validation + `weight_mgt` (`run.py:416-452,270-282`): best `.pth` by the triplet mAP
-                t1 = time.time()
-                if vmodel is None:
-                    from .temporal_tenco import VideoNas
-                    vmodel = VideoNas(F, F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100).eval()
-                vmodel.load_state_dict(state)
-                vm = recognition_from(_tenco_scores(vmodel, feats, val_videos, F.data_dir), val_videos) if val_videos else None
-                head = F.loss_type if F.loss_type in ("i", "v", "t") else "ivt"
-                score = float(vm[head].compute_video_AP()["mAP"]) if vm else 0.0
-                if score > best or not os.path.exists(best_path):
-                    best = max(best, score)
-                    torch.save(state, best_path + ".tmp")
-                    os.replace(best_path + ".tmp", best_path)
-                    _log(logfile, f">>> Saving checkpoint for epoch {epoch + 1} at {best_path}, time {time.ctime()} ")
-                ivt = float(vm["ivt"].compute_video_AP("ivt", ignore_null=_chlg(F))["mAP"]) if vm else 0.0
-                _log(logfile, f"\t\t\t\t\t\t\t video-wise | eta {time.time() - t1:.2f} secs | mAP => ivt: [{ivt:.5f}] ")
-    _barrier()                                                     # the last checkpoint is on disk before any rank goes on to -e
+            tot += tr.train_step(x, zs[v], masks=masks)[0]
+        return tot, len(mine)
+
+    def validate(state):                                           # (`run.py:416-452`): best `.pth` by the triplet mAP
+        vmodel.load_state_dict(state)
+        vm = recognition_from(_tenco_scores(vmodel, feats, val_videos, F.data_dir), val_videos) if val_videos else None
+        head = F.loss_type if F.loss_type in ("i", "v", "t") else "ivt"
+        score = float(vm[head].compute_video_AP()["mAP"]) if vm else 0.0
+        ivt = float(vm["ivt"].compute_video_AP("ivt", ignore_null=_chlg(F))["mAP"]) if vm else 0.0
+        return score, f"ivt: [{ivt:.5f}]"
+
+    run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", init, stem + ".pth", latest_every_epoch=True)
 
 
 # ------------------------------------------------------------------------------------------------ Spatial_transformer/test.py
@@ -540,11 +500,8 @@ def spatial_transformer_eval(argv=None) -> Dict[str, float]:
     F, _ = p.parse_known_args(argv)
     rank, world = _dist()
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
-    single = F.loss_type != "all"
-    modelname = f"{F.model}_l{F.dataset_variant}_cholect{kfold}"
-    model_dir = f"./__checkpoint__/run_{F.version}" + (f"_{F.loss_type}" if single else "")   # `run.py:86-88`
-    logfile = os.path.join(model_dir, modelname + ".log")
-    ckpt = F.test_ckpt or os.path.join(model_dir, modelname + ".pth")
+    stem = _stem(F, kfold, task_dir=True)
+    ckpt = F.test_ckpt or stem + ".pth"
     model = build_q2l(F, dtype=torch.float32 if F.dtype == "fp32" else torch.bfloat16).eval()
     model.load_state_dict(torch.load(ckpt, map_location="cpu"), strict=True)
     _, _, videos = cholect.split_videos(F.dataset_variant, kfold)
@@ -554,7 +511,7 @@ def spatial_transformer_eval(argv=None) -> Dict[str, float]:
     res = {}
     try:
         if rank == 0:
-            res = _write_report(logfile, m, F.loss_type, _chlg(F), "spatial_transformer")
+            res = _write_report(stem + ".log", m, F.loss_type, _chlg(F), "spatial_transformer")
     finally:
         _barrier()
     return res
@@ -571,9 +528,7 @@ def mstct_test(argv=None):
     F.in_feat_dim = F.input_dim
     # checkpoint directory: run_<version>_<task> for a single-task teacher (`test.py:88-90,131,326`); the feature / prediction files it
     # writes go to run_<version as given> (`test.py:342-366`) and its input comes from run_<version1> (`dataloader_test.py:220`)
-    model_dir = f"./__checkpoint__/run_{F.version}" + ("_" + F.loss_type if F.loss_type != "all" else "")
-    modelname = f"{F.model}_l8_cholect{F.dataset_variant}_k{F.kfold}_batchnorm_lowres"
-    ckpt = F.test_ckpt or os.path.join(model_dir, modelname + "latest.pth")              # no underscore (`run.py:268`)
+    ckpt = F.test_ckpt or _stem(F, task_dir=True) + "latest.pth"                              # no underscore (`run.py:268`)
     model = VideoNas(F, [256, 384, 576, 864], 2, 8, 8, F.input_dim, F.final_embedding_dim,
                      dtype=torch.float32 if F.dtype == "fp32" else torch.bfloat16).eval()
     model.load_state_dict(torch.load(ckpt, map_location="cpu"))
@@ -646,21 +601,77 @@ def mstct_eval(argv=None) -> Dict[str, float]:
         _barrier()
         return {}
     try:
-        model_dir = f"./__checkpoint__/run_{F.version}" + ("_" + F.loss_type if F.loss_type != "all" else "")
-        modelname = f"{F.model}_l8_cholect{F.dataset_variant}_k{F.kfold}_batchnorm_lowres"
-        logfile = os.path.join(model_dir, modelname + ".log")
-        ckpt = F.test_ckpt or os.path.join(model_dir, modelname + ".pth")
+        stem = _stem(F, task_dir=True)
+        ckpt = F.test_ckpt or stem + ".pth"
         if not os.path.exists(ckpt):
-            ckpt = os.path.join(model_dir, modelname + "latest.pth")                         # no underscore (`run.py:268`)
+            ckpt = stem + "latest.pth"                                                       # no underscore (`run.py:268`)
         model = VideoNas(F, [256, 384, 576, 864], 2, 8, 8, F.input_dim, F.final_embedding_dim,
                          dtype=torch.float32 if F.dtype == "fp32" else torch.bfloat16).eval()
         model.load_state_dict(torch.load(ckpt, map_location="cpu"))
         feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, F.loss_type))
         _, _, test_videos = cholect.split_videos(F.dataset_variant, F.kfold)
         m = recognition_from(_mstct_scores(model, feats, test_videos, F.data_dir, F.loss_type), test_videos)
-        return _write_report(logfile, m, F.loss_type, _chlg(F), "temporal_mstct", pckl="mAPs.pckl")
+        return _write_report(stem + ".log", m, F.loss_type, _chlg(F), "temporal_mstct", pckl="mAPs.pckl")
     finally:
         _barrier()
+
+
+def _mstct_train(F):
+    """`Temporal_mstct/run.py -t` (:147-235, :345-420): every epoch one random 256-frame window per training video, windows shuffled into
+    batches of --batch (31 in Scripts/train_fold1.sh), SGD without momentum under LinearLR warm-up -> ExponentialLR, checkpoint
+    `..._lowreslatest.pth` (no underscore: `run.py:268`) in run_<version>[_<task>] after every epoch.  Under torchrun every rank takes its
+    own batch of a step (window-DDP, global batch = world x --batch) and the flat gradient buffer is all-reduced over RCCL once per step."""
+    import random
+
+    from .mstct_train import NCLS, MstctTrainer, draw_windows
+    from .temporal_mstct import VideoNas
+    from . import shapes, synth
+    rank, world = _dist()
+    lt = F.loss_type
+    if lt not in NCLS:
+        raise ValueError("Temporal_mstct trains one task at a time: --loss_type i | v | t | ivt (Scripts/train_fold1.sh:16)")
+    stem = _stem(F, task_dir=True)
+    latest = stem + "latest.pth"                                                                  # no underscore (`run.py:268`)
+    tr = MstctTrainer((256, 384, 576, 864), 2, 8, 8, F.input_dim, F.final_embedding_dim, lt, lr=F.initial_learning_rates[2],
+                      weight_decay=F.weight_decay, operand_dtype=torch.bfloat16 if F.operand_dtype == "bf16" else torch.float32)
+    if os.path.exists(latest):
+        tr.load_state_dict(torch.load(latest, map_location="cpu"))
+    else:   # no torch.nn init here: deterministic synthetic start (the reference starts from its trunc_normal_ init)
+        tr.load_state_dict(synth.fill_from_shapes(shapes.mstct_shapes(F.input_dim, (256, 384, 576, 864), 2, 8, F.final_embedding_dim, lt), seed=F.seed))
+    train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, F.kfold)
+    feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, lt))                # `dataloader.py:220-222`
+    xs, zs = {}, {}
+    for v in train_videos:                                                                        # uploaded ONCE; windows are device slices
+        key = featfile.video_key(v)
+        if key not in feats:
+            key = v[3:]                                                                           # Spatial_transformer's key style
+        xs[v] = torch.from_numpy(feats[key]).to(tr.dev)
+        zs[v] = torch.from_numpy(cholect.load_labels(F.data_dir, v)[lt][:, 1:]).to(torch.float32).to(tr.dev)
+    lengths = {v: int(xs[v].shape[0]) for v in train_videos}
+    short = [v for v, n in lengths.items() if n <= F.num_clips]
+    if short:
+        raise ValueError(f"videos shorter than the {F.num_clips}-frame training window: {short[:3]} (the reference's sampler fails on them too)")
+    order_rng, win_rng = random.Random(F.seed), random.Random(F.seed * 7919 + 1)
+    vmodel = VideoNas(F, [256, 384, 576, 864], 2, 8, 8, F.input_dim, F.final_embedding_dim).eval() if rank == 0 else None
+
+    def train_epoch(epoch):
+        starts = draw_windows(lengths, win_rng, F.num_clips)                                       # same draw on every rank, before the shuffle
+        order = list(train_videos)
+        order_rng.shuffle(order)
+        mine, tot = deal(order, F.batch, world, rank), 0.0
+        for s, vids in enumerate(mine):
+            x = torch.stack([xs[v][starts[v]:starts[v] + F.num_clips] for v in vids])             # [B,T,D] frame-major
+            z = torch.cat([zs[v][starts[v]:starts[v] + F.num_clips] for v in vids])               # [B*T,K]
+            tot += tr.train_step_btd(x, z, masks=tr.draw_masks_device(len(vids), F.num_clips, F.seed + rank, epoch * len(mine) + s))
+        return tot, len(mine)
+
+    def validate(state):                                                                          # (`run.py:416-452`): best `.pth` by the task's mAP
+        vmodel.load_state_dict(state)
+        vm = recognition_from(_mstct_scores(vmodel, feats, val_videos, F.data_dir, lt), val_videos) if val_videos else None
+        score = float(vm[lt].compute_video_AP(ignore_null=_chlg(F))["mAP"]) if vm else 0.0
+        return score, f"{lt}: [{score:.5f}]"
+
+    run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", latest, stem + ".pth", latest_every_epoch=True)
 
 
 # ------------------------------------------------------------------------------------------------ teacher run.py entry points
@@ -686,21 +697,14 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
 
     from .q2l_train import Q2LTrainer
     from .spatial_transformer import build_q2l
-    from .tenco_train import lr_at_epoch
     from . import shapes, synth
     p = argparse.ArgumentParser()
     _common(p)
+    add_schedule_flags(p)
     p.add_argument("--backbone", type=str, default="swin_L_384_22k")
     p.add_argument("--img_size", type=int, default=384)
     p.add_argument("--hidden_dim", type=int, default=1536)
     p.add_argument("--augmentation_list", type=str, nargs="*", default=["original", "vflip", "hflip", "contrast", "rot90"])
-    p.add_argument("--epochs", type=int, default=100)
-    p.add_argument("-w", "--warmups", type=int, nargs="+", default=[9, 18, 58])
-    p.add_argument("-l", "--initial_learning_rates", type=float, nargs="+", default=[0.01, 0.01, 0.01])
-    p.add_argument("--weight_decay", type=float, default=1e-5)
-    p.add_argument("--decay_rate", type=float, default=0.99)
-    p.add_argument("--power", type=float, default=0.1)
-    p.add_argument("--val_interval", type=int, default=1)
     p.add_argument("--pretrain_dir", type=str, default="")
     p.add_argument("--drop_path_rate", type=float, default=0.1)          # `swin_transformer.py:488`
     p.add_argument("--operand_dtype", type=str, default="fp32", choices=["fp32", "bf16"],
@@ -719,11 +723,8 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     F.student_dim = F.hidden_dim                                             # `run.py:93`
     rank, world = _dist()
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
-    modelname = f"{F.model}_l{F.dataset_variant}_cholect{kfold}"
-    model_dir = f"./__checkpoint__/run_{F.version}" + (f"_{F.loss_type}" if single else "")   # `run.py:86-88`
-    logfile = os.path.join(model_dir, modelname + ".log")
-    ckpt, latest = os.path.join(model_dir, modelname + ".pth"), os.path.join(model_dir, modelname + "_latest.pth")
-    val_interval = F.epochs - 1 if F.val_interval == -1 else F.val_interval
+    stem = _stem(F, kfold, task_dir=True)
+    logfile, latest = stem + ".log", stem + "_latest.pth"
     tr = Q2LTrainer(F.backbone, F.img_size, F.hidden_dim, F.loss_type, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                     drop_path_rate=F.drop_path_rate, operand_dtype=torch.bfloat16 if F.operand_dtype == "bf16" else torch.float32,
                     teacher_dim=F.teacher_dim, rates=F.rates, temp=float(F.temp))
@@ -745,64 +746,32 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, kfold)
     labels = {v: cholect.load_labels(F.data_dir, v) for v in train_videos + val_videos}
     samples = [(v, i) for v in train_videos for i in range(len(labels[v]["ivt"]))]
-    tdir = lambda ver, task, kind: featfile.feats_path("..", ver, kfold, task, kind)
-    tpred = {} if single else {t: featfile.read_feats(tdir(F.teacher_pred_version, t, "pred")) for t in "ivt"}
-    tfeat = {} if single else {t: featfile.read_feats(tdir(F.teacher_feat_version, t, "feats")) for t in "ivt"}
+    tpred, tfeat = _teacher_files(F, kfold)
     order_rng, aug_rng = random.Random(F.seed), random.Random(F.seed * 1000003 + rank)
+    size = (F.img_size, F.img_size)
     eval_args = argparse.Namespace(**vars(F))
-    best, last, step_no = 0.0, {}, 0
-    for epoch in range(F.epochs):
-        tr.lr = lr_at_epoch(epoch, F.initial_learning_rates[2], F.power, F.warmups[2], F.decay_rate)
+
+    def train_epoch(epoch):
         order = list(samples)
         order_rng.shuffle(order)                             # the same permutation on every rank
-        nb = (len(order) + F.batch - 1) // F.batch
-        steps = (nb + world - 1) // world
-        t0, tot = time.time(), 0.0
-        for s in range(steps):
-            bi = (s * world + rank) % nb
-            batch = order[bi * F.batch:(bi + 1) * F.batch]
-            frames = np.concatenate([load_train_frames_u8(F.data_dir, v, [labels[v]["ivt"][i, 0]], F.img_size, F.img_size, aug_rng,
-                                                          F.augmentation_list) for v, i in batch])
-            masks = tr.draw_masks_device(len(batch), F.seed * 1000003 + rank, step_no)
+        mine, tot = deal(order, F.batch, world, rank), 0.0
+        for s, batch in enumerate(mine):
+            frames, lab, tp, tf = _frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng)
+            masks = tr.draw_masks_device(len(batch), F.seed * 1000003 + rank, epoch * len(mine) + s)     # (a running step count)
             if single:
-                lab = torch.from_numpy(np.stack([labels[v][F.loss_type][i, 1:] for v, i in batch]))
-                tot += tr.train_step(torch.from_numpy(frames).cuda(), lab, masks)
+                tot += tr.train_step(frames, lab["ivt".index(F.loss_type)], masks)
             else:
-                lab = [torch.from_numpy(np.stack([labels[v][k][i, 1:] for v, i in batch])) for k in ("i", "v", "t", "ivt")]
-                key = lambda v: featfile.video_key(v)
-                tp = [torch.from_numpy(np.stack([tpred[t][key(v)][i] for v, i in batch]).astype(np.float32)) for t in "ivt"]
-                tf = [torch.from_numpy(np.stack([tfeat[t][key(v)][i] for v, i in batch]).astype(np.float32)) for t in "ivt"]
-                tot += tr.train_step(torch.from_numpy(frames).cuda(), lab, masks, teacher_pred=tp, teacher_feat=tf)["loss"]
-            step_no += 1
-        last = {"loss": tot / steps, "lr": tr.lr}
-        if rank == 0:
-            _log(logfile, f"Traning | lr: {tr.lr:.6f} | epoch {epoch} | loss {tot / steps:.4f} | {time.time() - t0:.2f} secs")
-        if epoch % val_interval == 0 and rank == 0:          # `weight_mgt`: latest every validation, best by the task's mAP (:416-421)
-            state = tr.state_dict()
-            torch.save(state, latest)
-            model = build_q2l(eval_args, dtype=torch.float32).eval()
-            model.load_state_dict(state)
-            vt = F.loss_type if single else "ivt"                  # the head the validation mAP is taken on (`run.py:443-450`)
-            m = Recognition({"i": 6, "v": 10, "t": 15, "ivt": 100}[vt])
-            gi = ("i", "v", "t", "ivt").index(vt)
-            for v in val_videos:
-                lv = labels[v][vt]
-                vb = max(F.batch, min(getattr(F, "device_batch", F.batch), 128))     # validation passes in device batches (results do not depend on it)
-                for s0 in range(0, len(lv), vb):
-                    fr = cholect.load_frames_device(F.data_dir, v, lv[s0:s0 + vb, 0], F.img_size, F.img_size,
-                                                    workers=getattr(F, "decode_workers", 0), decode=getattr(F, "png_decode", "host"))
-                    zt = [] if single else [torch.zeros((fr.shape[0], F.teacher_dim), device=fr.device)] * 3   # (`dataloader.py:240-246`: zeros off the train split)
-                    m.update(lv[s0:s0 + vb, 1:], _sigmoid(model(fr, *zt)[gi][1]))
-                m.video_end()
-            score = float(m.compute_video_AP(ignore_null=_chlg(F))["mAP"]) if val_videos else 0.0
-            last["val_mAP"] = score
-            if score > best or not os.path.exists(ckpt):
-                best = max(best, score)
-                torch.save(state, ckpt)
-                _log(logfile, f">>> Saving checkpoint for epoch {epoch + 1} at {ckpt}, time {time.ctime()} ")
-            _log(logfile, f"\t\t\t\t\t\t\t video-wise | eta {time.time() - t0:.2f} secs | mAP => {vt}: [{score:.5f}] ")
-        _barrier()
-    return last
+                tot += tr.train_step(frames, lab, masks, teacher_pred=tp, teacher_feat=tf)["loss"]
+        return tot, len(mine)
+
+    def validate(state):                                     # the task's head (:416-421, 443-450)
+        model = build_q2l(eval_args, dtype=torch.float32).eval()
+        model.load_state_dict(state)
+        gi = "ivt".index(F.loss_type) if single else 3
+        zt = lambda fr: [] if single else [torch.zeros((fr.shape[0], F.teacher_dim), device=fr.device)] * 3   # (`dataloader.py:240-246`: zeros off the train split)
+        return _frame_validation(F, val_videos, labels, size, 128, lambda fr: model(fr, *zt(fr))[gi][1])
+
+    return run_epochs(F, tr, rank, train_epoch, validate, logfile, latest, stem + ".pth")
 
 
 def _wants_test(argv) -> bool:
@@ -828,8 +797,14 @@ def mstct_run(argv=None):
     """`Temporal_mstct/run.py`: -t trains the MS-TCT teacher on random 256-frame windows (`run.py:147-235`), -e evaluates the test split and
     writes the closing report + `mAPs.pckl` (`mstct_eval`, `run.py:527-580`); features / raw predictions for the student come from `test.py`
     (`mstct_test`)."""
-    last = None
     if _wants_train(argv):
-        from . import mstct_train
-        mstct_train.train_driver(sys.argv[1:] if argv is None else argv)
-    return mstct_eval(argv) if _wants_test(argv) else last
+        p = argparse.ArgumentParser()
+        _common(p)
+        add_schedule_flags(p)
+        p.add_argument("--input_dim", type=int, default=1536)
+        p.add_argument("--final_embedding_dim", type=int, default=512)
+        p.add_argument("--num_clips", type=int, default=256, help="window length (the reference hard-codes 256, dataloader.py:237)")
+        p.add_argument("--operand_dtype", type=str, default="fp32", choices=["fp32", "bf16"],
+                       help="bf16: the nn.Linear GEMMs on bf16 operand copies (fp32 activations, accumulation and master weights)")
+        _mstct_train(p.parse_known_args(argv)[0])
+    return mstct_eval(argv) if _wants_test(argv) else None

@@ -345,101 +345,3 @@ def draw_windows(lengths: Dict[str, int], rng, num_clips: int = 256) -> Dict[str
     """one random `num_clips`-frame window per training video and epoch (`Temporal_mstct/dataloader.py:225-245`: the dataset of a video has
     length 1 in train mode and its item starts at `random.choice(range(0, len - num_clips))`)"""
     return {v: rng.choice(range(0, n - num_clips)) for v, n in lengths.items()}
-
-
-def train_driver(argv=None):
-    """`Temporal_mstct/run.py -t` (:147-235, :345-420): every epoch one random 256-frame window per training video, windows shuffled into
-    batches of --batch (31 in Scripts/train_fold1.sh), SGD without momentum under LinearLR warm-up -> ExponentialLR, checkpoint
-    `..._lowreslatest.pth` (no underscore: `run.py:268`) in run_<version>[_<task>].  Under torchrun every rank takes its own batch of a
-    step (window-DDP, global batch = world x --batch) and the flat gradient buffer is all-reduced over RCCL once per step."""
-    import argparse
-    import os
-    import random
-    import time
-
-    from . import cholect, featfile, shapes, synth
-    from .drivers import _barrier, _common, _dist, _log
-    from .tenco_train import lr_at_epoch
-    p = argparse.ArgumentParser()
-    _common(p)
-    p.add_argument("--input_dim", type=int, default=1536)
-    p.add_argument("--final_embedding_dim", type=int, default=512)
-    p.add_argument("--epochs", type=int, default=100)
-    p.add_argument("-w", "--warmups", type=int, nargs="+", default=[9, 18, 58])
-    p.add_argument("-l", "--initial_learning_rates", type=float, nargs="+", default=[0.01, 0.01, 0.01])
-    p.add_argument("--weight_decay", type=float, default=1e-5)
-    p.add_argument("--decay_rate", type=float, default=0.99)
-    p.add_argument("--power", type=float, default=0.1)
-    p.add_argument("--val_interval", type=int, default=1)
-    p.add_argument("--num_clips", type=int, default=256, help="window length (the reference hard-codes 256, dataloader.py:237)")
-    p.add_argument("--operand_dtype", type=str, default="fp32", choices=["fp32", "bf16"],
-                   help="bf16: the nn.Linear GEMMs on bf16 operand copies (fp32 activations, accumulation and master weights)")
-    F, _ = p.parse_known_args(argv)
-    rank, world = _dist()
-    lt = F.loss_type
-    if lt not in NCLS:
-        raise ValueError("Temporal_mstct trains one task at a time: --loss_type i | v | t | ivt (Scripts/train_fold1.sh:16)")
-    model_dir = f"./__checkpoint__/run_{F.version}" + ("_" + lt if lt != "all" else "")          # `run.py:88-90,131`
-    modelname = f"{F.model}_l8_cholect{F.dataset_variant}_k{F.kfold}_batchnorm_lowres"
-    logfile = os.path.join(model_dir, modelname + ".log")
-    latest = os.path.join(model_dir, modelname + "latest.pth")
-    tr = MstctTrainer((256, 384, 576, 864), 2, 8, 8, F.input_dim, F.final_embedding_dim, lt, lr=F.initial_learning_rates[2],
-                      weight_decay=F.weight_decay, operand_dtype=torch.bfloat16 if F.operand_dtype == "bf16" else torch.float32)
-    if os.path.exists(latest):
-        tr.load_state_dict(torch.load(latest, map_location="cpu"))
-    else:   # no torch.nn init here: deterministic synthetic start (the reference starts from its trunc_normal_ init)
-        tr.load_state_dict(synth.fill_from_shapes(shapes.mstct_shapes(F.input_dim, (256, 384, 576, 864), 2, 8, F.final_embedding_dim, lt), seed=F.seed))
-    train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, F.kfold)
-    val_interval = F.epochs - 1 if F.val_interval == -1 else max(1, F.val_interval)
-    best, best_path, vmodel = 0.0, os.path.join(model_dir, modelname + ".pth"), None
-    feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, lt))                # `dataloader.py:220-222`
-    lab_name = {"i": "i", "v": "v", "t": "t", "ivt": "ivt"}[lt]
-    xs, zs = {}, {}
-    for v in train_videos:                                                                        # uploaded ONCE; windows are device slices
-        key = featfile.video_key(v)
-        if key not in feats:
-            key = v[3:]                                                                           # Spatial_transformer's key style
-        xs[v] = torch.from_numpy(feats[key]).to(tr.dev)
-        zs[v] = torch.from_numpy(cholect.load_labels(F.data_dir, v)[lab_name][:, 1:]).to(F32).to(tr.dev)
-    lengths = {v: int(xs[v].shape[0]) for v in train_videos}
-    short = [v for v, n in lengths.items() if n <= F.num_clips]
-    if short:
-        raise ValueError(f"videos shorter than the {F.num_clips}-frame training window: {short[:3]} (the reference's sampler fails on them too)")
-    order_rng, win_rng = random.Random(F.seed), random.Random(F.seed * 7919 + 1)
-    for epoch in range(F.epochs):
-        tr.lr = lr_at_epoch(epoch, F.initial_learning_rates[2], F.power, F.warmups[2], F.decay_rate)
-        starts = draw_windows(lengths, win_rng, F.num_clips)                                       # same draw on every rank
-        order = list(train_videos)
-        order_rng.shuffle(order)
-        batches = [order[i:i + F.batch] for i in range(0, len(order), F.batch)]                   # drop_last False
-        steps = (len(batches) + world - 1) // world
-        t0, tot = time.time(), 0.0
-        for s in range(steps):
-            vids = batches[(s * world + rank) % len(batches)]
-            x = torch.stack([xs[v][starts[v]:starts[v] + F.num_clips] for v in vids])             # [B,T,D] frame-major
-            z = torch.cat([zs[v][starts[v]:starts[v] + F.num_clips] for v in vids])               # [B*T,K]
-            tot += tr.train_step_btd(x, z, masks=tr.draw_masks_device(len(vids), F.num_clips, F.seed + rank, epoch * steps + s))
-        if rank == 0:
-            _log(logfile, f"Traning | lr: {tr.lr:.6f} | epoch {epoch} | loss {tot / steps:.4f} | {time.time() - t0:.2f} secs")
-            os.makedirs(model_dir, exist_ok=True)
-            state = tr.state_dict()
-            torch.save(state, latest + ".tmp")
-            os.replace(latest + ".tmp", latest)
-            if epoch % val_interval == 0:                          # validation + `weight_mgt` (`run.py:416-452,265-277`): best `.pth` by the task's mAP
-                from .drivers import _chlg, _mstct_scores
-                from .metrics import recognition_from
-                t1 = time.time()
-                if vmodel is None:
-                    from .temporal_mstct import VideoNas
-                    vmodel = VideoNas(F, [256, 384, 576, 864], 2, 8, 8, F.input_dim, F.final_embedding_dim).eval()
-                vmodel.load_state_dict(state)
-                vm = recognition_from(_mstct_scores(vmodel, feats, val_videos, F.data_dir, lt), val_videos) if val_videos else None
-                score = float(vm[lt].compute_video_AP(ignore_null=_chlg(F))["mAP"]) if vm else 0.0
-                if score > best or not os.path.exists(best_path):
-                    best = max(best, score)
-                    torch.save(state, best_path + ".tmp")
-                    os.replace(best_path + ".tmp", best_path)
-                    _log(logfile, f">>> Saving checkpoint for epoch {epoch + 1} at {best_path}, time {time.ctime()} ")
-                _log(logfile, f"\t\t\t\t\t\t\t video-wise | eta {time.time() - t1:.2f} secs | mAP => {lt}: [{score:.5f}] ")
-    _barrier()
-    return tr

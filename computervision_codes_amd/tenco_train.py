@@ -23,6 +23,7 @@ from . import ops
 from .flatparams import FlatParams, FlatTrainer, Lin
 from .flatparams import allreduce_sum_flat  # noqa: F401  (its import path before it moved to flatparams)
 from .shapes import tenco_shapes
+from .trainloop import lr_at_epoch  # noqa: F401  (its import path before it moved to trainloop)
 
 HEADS = (("", 100, 1.0), ("_i", 6, 0.1), ("_v", 10, 0.1), ("_t", 15, 0.1))   # loss = 0.1 (i + v + t) + ivt (`run.py:212`)
 NH = 131
@@ -272,13 +273,3 @@ class TencoTrainer(FlatTrainer):
         if cs is None:
             cs = self._scales[T] = torch.cat([torch.full((k,), w / (T * k)) for _, k, w in HEADS]).to(self.dev)
         return cs
-
-
-def lr_at_epoch(epoch: int, lr: float, power: float, warmup: int, decay_rate: float) -> float:
-    """The schedule of `Temporal_tenco/run.py:341-348` (same in Spatial_cnn): SGD(lr/power) under
-    SequentialLR([LinearLR(start_factor=power, total_iters=warmup), ExponentialLR(gamma)], milestones=[warmup+1]);
-    the value torch's schedulers hold during epoch `epoch` (0-based)."""
-    base = lr / power
-    if epoch <= warmup:
-        return base * (power + (1.0 - power) * min(epoch, warmup) / warmup)
-    return base * decay_rate ** (epoch - warmup - 1)
