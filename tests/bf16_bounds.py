@@ -11,7 +11,8 @@ do not (`test_bf16_bounds_cpu.py` shows both on CPU emulations of those bugs).
 
 and, when the reference rounds in exactly the places the kernel does (`single_rounding`), that the outputs equal the round-to-nearest-even of the
 float64 result almost everywhere and that their signed error has no bias (these two catch truncation and one-sided errors at long K, where the
-accumulation term is loose).  `check_f32` is the same bound for fp32 outputs of bf16 operands, with an fp32 half-ulp in place of the bf16 one.
+accumulation term is loose).  `check_f32` is the same bound for fp32 outputs (of bf16 or of fp32 operands), with an fp32 half-ulp in place of the
+bf16 one; its `single_rounding` asks the same of RNE-to-fp32.  `check_exact` is for kernels that only move data: every element bit for bit.
 
 This is a plain module imported by the GPU tests (`tests/` is on sys.path while pytest runs them), not a conftest.
 """
@@ -61,11 +62,30 @@ def half_ulp_f32(ref):
     return torch.pow(2.0, _floor_log2(ref.to(torch.float64)) - 24.0)
 
 
+def rne_f32(t):
+    """round to fp32 with round-to-nearest-even, directly from float64, widened back to float64 (torch's float64 -> float32 cast is RNE)"""
+    return t.to(torch.float64).to(torch.float32).to(torch.float64)
+
+
 def rne_bf16(t):
     """round to bf16 with round-to-nearest-even, directly from float64 (no intermediate fp32 rounding), widened back to float64"""
     t64 = t.to(torch.float64)
     ulp = torch.pow(2.0, _floor_log2(t64) - 7.0)
     return torch.round(t64 / ulp) * ulp     # torch.round: halves to even; t / ulp is exact (power-of-two scale)
+
+
+def pow2_ramp(n):
+    """operand scales 2^8 .. 2^-8 (powers of two: they add no rounding), descending with the index -- per channel or per row of a test operand, so
+    that the ragged tail tiles of a kernel hold the smallest values and a small-magnitude region has to be right on its own"""
+    return torch.pow(2.0, torch.round(torch.linspace(8.0, -8.0, n)))
+
+
+def sgd_ref64(p, g, lr, wd, gs):
+    """float64 of `p - lr * (g * gs + wd * p)` (mt4_sgd_step_f32) on fp32 p, g and the fp32 values of the scalars (the kernel's arguments are
+    floats); returns (ref64, acc64) with acc64 = lr (|g gs| + wd |p|), the terms inside the bracket whose roundings reach the result"""
+    lr, wd, gs = (float(torch.tensor(v, dtype=torch.float32)) for v in (lr, wd, gs))
+    p64, g64 = p.double(), g.double()
+    return p64 - lr * (g64 * gs + wd * p64), lr * (g64.abs() * abs(gs) + abs(wd) * p64.abs())
 
 
 def _acc_term(acc64, k, ref64):
@@ -82,7 +102,7 @@ def _log(stats):
             f.write(json.dumps(stats) + "\n")
 
 
-def _check(got, ref64, bound_base, acc64, k, extra, single_rounding, what, kind):
+def _check(got, ref64, bound_base, acc64, k, extra, single_rounding, what, kind, rne=rne_bf16):
     got64 = got.detach().to(torch.float64).cpu()
     ref64 = ref64.detach().to(torch.float64).cpu()
     assert got64.shape == ref64.shape, (what, tuple(got64.shape), tuple(ref64.shape))
@@ -97,11 +117,11 @@ def _check(got, ref64, bound_base, acc64, k, extra, single_rounding, what, kind)
     stats = dict(what=what, kind=kind, n=int(ref64.numel()), k=k, worst_ratio=worst)
     ok = worst <= 1.0
     if single_rounding:
-        ulp = 2.0 * half_ulp_bf16(ref64)
+        ulp = 2.0 * bound_base(ref64)
         sel = (extra <= ulp / 16) if torch.is_tensor(extra) or extra else torch.ones_like(ref64, dtype=torch.bool)
         g_s, r_s, u_s = got64[sel], ref64[sel], ulp[sel]
         n_nz = int((r_s != 0).sum())
-        mism = int((g_s != rne_bf16(r_s)).sum())
+        mism = int((g_s != rne(r_s)).sum())
         match = 1.0 - mism / max(1, r_s.numel())
         signed = ((g_s - r_s) * torch.sign(r_s) / u_s).sum().item() / max(1, n_nz)
         lim = max(MAX_MEAN_SIGNED, 1.2 / math.sqrt(max(1, n_nz)))
@@ -127,6 +147,31 @@ def check_bf16(got, ref64, *, acc64=None, k=1, extra=0.0, single_rounding=True, 
     return _check(got, ref64, half_ulp_bf16, acc64, k, extra, single_rounding, what, "bf16")
 
 
-def check_f32(got, ref64, *, acc64=None, k=1, extra=0.0, what=""):
-    """fp32 output of bf16 operands: no output rounding beyond fp32's own; bound = fp32 half-ulp + the same accumulation term + extra"""
-    return _check(got, ref64, half_ulp_f32, acc64, k, extra, False, what, "f32")
+def check_f32(got, ref64, *, acc64=None, k=1, extra=0.0, single_rounding=False, what=""):
+    """fp32 output (of bf16 or fp32 operands): bound = fp32 half-ulp + the same accumulation term + extra.
+
+    single_rounding: the kernel computes the element with exactly ONE fp32 rounding (one multiply, one FMA, or a sum of two values one of which
+    is exact in the other's ulp), so it must equal RNE-to-fp32 of the float64 result almost everywhere, with no signed bias.  hipcc contracts
+    `a * b + c` into an FMA by default; each call site says why one rounding holds."""
+    return _check(got, ref64, half_ulp_f32, acc64, k, extra, single_rounding, what, "f32", rne=rne_f32)
+
+
+def check_exact(got, want, *, what=""):
+    """kernels that only move data (transposes, packing, gathers, zero padding): every element equal to `want` bit for bit -- the bit patterns
+    are compared in `got`'s dtype, so -0.0 differs from +0.0 and a NaN never matches.  `want` may be wider (float64) but must hold values of
+    `got`'s dtype exactly.  Logged with kind "exact"; the failure message names the first differing element in the format of the other checks."""
+    g = got.detach().cpu().contiguous()
+    w = want.detach().cpu()
+    assert g.shape == w.shape, (what, tuple(g.shape), tuple(w.shape))
+    wn = w.to(g.dtype).contiguous()
+    assert torch.equal(wn.to(torch.float64).isnan(), w.to(torch.float64).isnan()) and \
+        bool(((wn.to(torch.float64) == w.to(torch.float64)) | w.to(torch.float64).isnan()).all()), (what, "want is not representable in", g.dtype)
+    ibits = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[g.element_size()]
+    bad = (g.view(ibits) != wn.view(ibits)) | g.to(torch.float64).isnan()
+    nbad = int(bad.sum())
+    _log(dict(what=what, kind="exact", n=int(w.numel()), mismatches=nbad))
+    if nbad:
+        flat = int(torch.nonzero(bad.reshape(-1))[0])
+        idx = tuple(int(i) for i in np.unravel_index(flat, tuple(w.shape))) if w.dim() else ()
+        gv, wv = g.reshape(-1)[flat].item(), wn.reshape(-1)[flat].item()
+        raise AssertionError(f"{what}: exact copy differs at {nbad} element(s); first differing element {idx}: got {gv!r}, want {wv!r}")

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from bf16_bounds import check_exact, check_f32
 from computervision_codes_amd import shapes, synth
 from conftest import load_golden
 
@@ -27,8 +28,12 @@ def _rand(shape, seed, scale=1.0):
 
 
 # ------------------------------------------------------------------------------------------------ kernels
-@pytest.mark.parametrize("m,c,relu,res", [(200, 64, True, False), (1031, 96, True, True), (77, 256, False, False)])
+@pytest.mark.parametrize("m,c,relu,res", [(200, 64, True, False), (1031, 96, True, True), (77, 256, False, False), (7, 100, True, False), (2, 36, True, True),
+                                          (20000, 196, True, True)])
 def test_batchnorm_train_fwd_bwd(cuda, m, c, relu, res):
+    """fp32 train-mode BatchNorm against torch, and per element against float64 as the bf16 family is checked (test_batchnorm_bf16_fwd_bwd: the
+    statistics are float64 sums, mean / invstd rounded to fp32; the output (x - mean) invstd gamma + beta (+ residual); dgamma / dbeta the
+    float64 sums rounded to fp32, k = M); C not a multiple of 64, M of 2, 7 and many row slabs"""
     from computervision_codes_amd import ops
     x, g, b = _rand((m, c), 1, 2.0) + 0.3, _rand((c,), 2) + 1.5, _rand((c,), 3)
     r = _rand((m, c), 4) if res else None
@@ -55,6 +60,32 @@ def test_batchnorm_train_fwd_bwd(cuda, m, c, relu, res):
     assert (dg.cpu() - gt.grad).abs().max() < tol(gt.grad) * 5 and (db.cpu() - bt.grad).abs().max() < tol(bt.grad) * 5
     if res:
         assert (dres.cpu() - rt.grad).abs().max() < 1e-6
+    x64, g64, b64 = x.double(), g.double(), b.double()
+    mu64 = x64.mean(0)
+    is64 = 1.0 / torch.sqrt(((x64 - mu64) ** 2).mean(0) + 1e-5)
+    xh64 = (x64 - mu64) * is64
+    y64 = xh64 * g64 + b64
+    acc_y = (x64.abs() + mu64.abs()) * is64 * g64.abs() + b64.abs()
+    if res:
+        y64, acc_y = y64 + r.double(), acc_y + r.double().abs()
+    what = f"bn f32 {(m, c, relu, res)}"
+    # bn_apply_kernel rounds five times before its store -- mean and invstd to fp32, x - mean, x invstd, and (with a residual) the FMA with gamma
+    # and beta -- each error at most 2^-24 x a term of acc_y (|mean| invstd |gamma|, |x - mean| invstd |gamma|, |x gamma invstd + beta|): the
+    # worst case is 5 x 2^-24 acc_y, k = 25 (sqrt(6) was exceeded, 1.11, on 3.9 M outputs with per-channel scales).  bn_bwd_apply_kernel: mean,
+    # invstd (twice), m1, m2 to fp32, x - mean, x invstd, x m2 (or its FMA), dy - m1, the subtraction, gamma invstd: k = 11 with independent
+    # signs (measured worst err/bound 0.82)
+    check_f32(y.cpu(), torch.relu(y64) if relu else y64, acc64=acc_y, k=25, what=what + " bn_apply")
+    gate = (y.cpu() > 0) if relu else torch.ones_like(dy, dtype=torch.bool)         # the kernel's gate: its own stored output
+    dy64 = torch.where(gate, dy.double(), torch.zeros((), dtype=torch.float64))
+    m1, m2 = dy64.mean(0), (dy64 * xh64).mean(0)
+    acc_dx = g64.abs() * is64 * (dy64.abs() + m1.abs() + (xh64.abs() + (x64.abs() + mu64.abs()) * is64) * (m2.abs() + (dy64 * xh64).abs().mean(0)))
+    check_f32(dx.cpu(), g64 * is64 * (dy64 - m1 - xh64 * m2), acc64=acc_dx, k=11, what=what + " bn_backward dx")
+    check_f32(db.cpu(), dy64.sum(0), acc64=dy64.abs().sum(0), k=m, what=what + " bn_backward dbeta")
+    # (x_hat is formed in fp32 from x, mean and invstd: its rounding is relative to (|x| + |mean|) invstd, not to |x_hat|)
+    check_f32(dg.cpu(), (dy64 * xh64).sum(0), acc64=(dy64.abs() * (xh64.abs() + (x64.abs() + mu64.abs()) * is64)).sum(0), k=m,
+              what=what + " bn_backward dgamma")
+    if res:
+        check_exact(dres.cpu(), dy64, what=what + " bn_backward dres")
     if relu and not res:   # the gate recomputed from x (the forward's own fp32 expression) == the gate read from the stored output, bit for bit
         dg2, db2 = torch.zeros(c, device=cuda), torch.zeros(c, device=cuda)
         dx2, _ = ops.bn_backward(dy.to(cuda), None, xd, mean, invstd, g.to(cuda), dg2, db2, relu=True, beta=b.to(cuda))
@@ -84,6 +115,14 @@ def test_conv2d_weight_and_data_gradients(cuda, b, h, w, cin, cout, k, s, p):
     got = u.gw[:, :k * k * cin].view(cout, k, k, cin).permute(0, 3, 1, 2).cpu()
     ref = wtt.grad
     assert (got - ref).abs().max() <= 3e-5 * ref.abs().max(), (got - ref).abs().max() / ref.abs().max()
+    # per element against float64 (k = the b * ho * wo pixels the weight gradient sums over; cin * k * k taps of the data gradient)
+    x64, w64, dy64 = x.double(), wt.double(), dy.double()
+    gw = lambda xx, gg: torch.nn.grad.conv2d_weight(xx, tuple(wt.shape), gg, s, p)
+    m = dy.shape[0] * dy.shape[2] * dy.shape[3]
+    what = f"conv2d {(b, h, w, cin, cout, k, s, p)}"
+    check_f32(got, gw(x64, dy64), acc64=gw(x64.abs(), dy64.abs()), k=m, what=what + " wgrad_conv2d_f32")
+    gx = lambda ww, gg: torch.nn.grad.conv2d_input(tuple(x.shape), ww, gg, s, p).permute(0, 2, 3, 1)
+    dx64, dxa64 = gx(w64, dy64), gx(w64.abs(), dy64.abs())
     if cin == 4:
         return
     tr = SpatialCnnTrainer.__new__(SpatialCnnTrainer)
@@ -93,6 +132,12 @@ def test_conv2d_weight_and_data_gradients(cuda, b, h, w, cin, cout, k, s, p):
         dx = tr._dgrad(u, dyd, xd.shape, residual)
         want = xt.grad.permute(0, 2, 3, 1) + (residual.cpu() if residual is not None else 0)
         assert (dx.cpu() - want).abs().max() <= 3e-5 * want.abs().max()
+        r64 = residual.cpu().double() if residual is not None else torch.zeros_like(dx64)
+        check_f32(dx.cpu(), dx64 + r64, acc64=dxa64 + r64.abs(), k=cout * k * k + 1, what=what + f" _dgrad residual={residual is not None}")
+        if s == 2 and k == 1:      # positions no stride-2 phase writes: the residual (or zero), bit for bit
+            odd = torch.ones(b, h, w, cin, dtype=torch.bool)
+            odd[:, ::2, ::2] = False
+            check_exact(dx.cpu()[odd], r64[odd], what=what + " _dgrad unwritten positions")
 
 
 def test_pool_backward_and_losses(cuda):

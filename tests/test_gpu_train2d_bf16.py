@@ -45,6 +45,12 @@ def test_wgrad_conv2d_bf16_vs_autograd(cuda, b, h, w, cin, cout, k, s):
     ref = wt.grad
     assert (got - ref).abs().max().item() <= 2e-5 * max(1.0, ref.abs().max().item()) + 1e-5, (got - ref).abs().max().item()
     assert float((dw.cpu() - base)[:, k * k * cin:].abs().max()) == 0.0 if kp > k * k * cin else True
+    # per element against float64 of the same bf16 operands: fp32 MFMA accumulation over the b * ho * wo pixels, added to the buffer
+    g64 = lambda xx, gg: torch.nn.grad.conv2d_weight(xx.permute(0, 3, 1, 2), (cout, cin, k, k), gg.permute(0, 3, 1, 2), s, pad).permute(0, 2, 3, 1).reshape(cout, -1)
+    x64, dy64 = x.double(), dy.double()
+    kk, b64 = k * k * cin, base[:, :k * k * cin].double()
+    check_f32(dw.cpu()[:, :kk], b64 + g64(x64, dy64), acc64=b64.abs() + g64(x64.abs(), dy64.abs()), k=b * ho * wo + 1,
+              what=f"wgrad_conv2d_bf16 {(b, h, w, cin, cout, k, s)}")
 
 
 @pytest.mark.parametrize("m,c,relu,res,xf32", [(200, 64, True, False, False), (1031, 128, True, True, False), (77, 256, False, False, False), (300, 64, True, False, True)])
