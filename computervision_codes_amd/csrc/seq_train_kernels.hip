@@ -278,7 +278,9 @@ __global__ void gelu_fwd_kernel(const float* __restrict__ x, float* __restrict__
 // y[t][c] = b[c] + sum_k w[c][k] x[t + k - 1][c] per sequence of T frames (zero padding).
 //   dx[t][c] = w[c][0] dy[t+1][c] + w[c][1] dy[t][c] + w[c][2] dy[t-1][c]
 //   dw[c][k] += sum_t dy[t][c] x[t + k - 1][c];   db[c] += sum_t dy[t][c]
-// One thread per channel over a slab of rows of one sequence (coalesced across channels); partial sums -> float atomics.
+// One thread per channel over a slab of rows of one sequence (coalesced across channels); partial sums -> float atomics.  The slab's sums run
+// in float64: one large product at the head of a slab (a sequence's first frame) would otherwise make each of the 31 later fp32 additions round
+// at its size -- measured 1.7 x sqrt(T) 2^-24 sum |dy x| on such rows; the kernel is bound by its loads and the four v_fma_f64 per row hide there.
 __global__ void dwconv1d_k3_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ w,
                                        float* __restrict__ dx, float* __restrict__ dw, float* __restrict__ db, int T, int C, int slab) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -287,7 +289,7 @@ __global__ void dwconv1d_k3_bwd_kernel(const float* __restrict__ dy, const float
     const int t1 = min(T, t0 + slab);
     const long long base = (long long)seq * T * C + c;
     const float w0 = w[c * 3 + 0], w1 = w[c * 3 + 1], w2 = w[c * 3 + 2];
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, ab = 0.f;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, ab = 0.0;
     float dprev = t0 > 0 ? dy[base + (long long)(t0 - 1) * C] : 0.f;
     float dcur = dy[base + (long long)t0 * C];
     float xprev = t0 > 0 ? x[base + (long long)(t0 - 1) * C] : 0.f;
@@ -296,17 +298,18 @@ __global__ void dwconv1d_k3_bwd_kernel(const float* __restrict__ dy, const float
         const float dnext = t + 1 < T ? dy[base + (long long)(t + 1) * C] : 0.f;
         const float xnext = t + 1 < T ? x[base + (long long)(t + 1) * C] : 0.f;
         dx[base + (long long)t * C] = w0 * dnext + w1 * dcur + w2 * dprev;
-        a0 += dcur * xprev;
-        a1 += dcur * xcur;
-        a2 += dcur * xnext;
-        ab += dcur;
+        const double dc = (double)dcur;
+        a0 += dc * xprev;
+        a1 += dc * xcur;
+        a2 += dc * xnext;
+        ab += dc;
         dprev = dcur; dcur = dnext;
         xprev = xcur; xcur = xnext;
     }
-    atomicAdd(dw + c * 3 + 0, a0);
-    atomicAdd(dw + c * 3 + 1, a1);
-    atomicAdd(dw + c * 3 + 2, a2);
-    atomicAdd(db + c, ab);
+    atomicAdd(dw + c * 3 + 0, (float)a0);
+    atomicAdd(dw + c * 3 + 1, (float)a1);
+    atomicAdd(dw + c * 3 + 2, (float)a2);
+    atomicAdd(db + c, (float)ab);
 }
 
 // y = a * x + b * y   (gradient fan-in, summed mixer weights)

@@ -906,6 +906,7 @@ def bce_logits_pw(y, z, pos_weight, col_scale, dy, col_loss):
 
 def distill_kl(y_s, t_pred, dy_s, loss, temp, grad_scale, accumulate=True):
     b, k = t_pred.shape
+    assert t_pred.is_contiguous() and t_pred.shape == y_s.shape      # the kernel reads t_pred with pitch K; y_s / dy_s carry their own pitches
     check(lib.mt4_distill_kl_f32(y_s.data_ptr(), t_pred.data_ptr(), dy_s.data_ptr(), loss.data_ptr(), b, k, y_s.stride(0), dy_s.stride(0), temp,
                                  grad_scale, 1 if accumulate else 0, _stream()), "mt4_distill_kl_f32")
 

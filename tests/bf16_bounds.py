@@ -34,6 +34,23 @@ ACC_EPS = 2.0 ** -24
 GELU_APPROX_ERR = 1e-6
 GELU_MAX_SLOPE = 1.13
 
+# `__expf(x)` (one v_exp_f32 of x * log2(e)): the relative error allowed to it.  The product x * log2(e) is rounded once and the constant
+# log2(e) is itself rounded to fp32: each moves the argument of 2^y by up to |x| log2(e) 2^-24, i.e. the result by |x| 2^-24 relative
+# (d 2^y / 2^y = ln 2 dy): 2 |x| 2^-24 together.  The hardware exponential is ASSUMED good to one ulp (2^-23 relative = 2 x 2^-24) and as much
+# again is allowed for its input denormal handling and range reduction: the constant 4.  Not measured on this part; if a correct kernel
+# exceeds a bound because of it, the constant becomes 1.5 x the measured worst error and the measured value is written here.
+def FAST_EXP(x):
+    """relative error bound of `__expf(x)`: (4 + 2 |x|) 2^-24 (float64 tensor in, float64 tensor out)"""
+    return (4.0 + 2.0 * x.to(torch.float64).abs()) * ACC_EPS
+
+
+# gelu_bwd_kernel (csrc/seq_train_kernels.hip): dy * (Phi(x) + x phi(x)) with Phi from the Abramowitz-Stegun 7.1.26 erf.  Per unit of |dy|:
+# an fp32 emulation of that form against the exact derivative over 2 x 10^6 points of [-12, 12] is off by at most 3.2e-7 (at x = 0.06;
+# re-measured by test_seq_bounds_cpu.py::test_gelu_bwd_formula_error), and FAST_EXP reaches the result through 0.5 pl t + 0.399 |x|
+# (both multiply exp(-x^2 / 2), whose relative error is (4 + x^2) 2^-24) as at most 1.3e-7 (at |x| about 1.6).  3.2e-7 + 1.3e-7 -> 5e-7.
+GELU_BWD_ERR = 5e-7
+GELU_BWD_FORMULA_ERR = 3.7e-7          # = GELU_BWD_ERR - 1.3e-7: what the emulated formula alone may use
+
 # single-rounding statistics, over the outputs where the documented approximation (`extra`) is at most 1/16 ulp -- it cannot move their rounding
 # much (GELU: every output of magnitude >= 2^-9; below that gelu_erf's 9e-7 spans ulps, and outputs of x < -5 are all off by most of it):
 # at least this fraction of them equals RNE(float64) ...
@@ -86,6 +103,91 @@ def sgd_ref64(p, g, lr, wd, gs):
     lr, wd, gs = (float(torch.tensor(v, dtype=torch.float32)) for v in (lr, wd, gs))
     p64, g64 = p.double(), g.double()
     return p64 - lr * (g64 * gs + wd * p64), lr * (g64.abs() * abs(gs) + abs(wd) * p64.abs())
+
+
+def softmax_ref64(s, scale):
+    """`softmax_rows_kernel`: p = softmax(scale * s) over the last axis, float64 of the fp32 logits and the fp32 value of `scale`.
+    Returns (p64, extra): `extra` is the bound below without its half ulp, which `check_f32(extra=...)` adds itself.  The bound is RELATIVE
+    TO EACH p_i (not to the row maximum).  With u = 2^-24, v = scale s, x_i = v_i - max v:
+      rho_i = u (|v_i| + |max v| + |x_i|) + FAST_EXP(x_i)   -- the roundings of v_i, of max v and of their difference are absolute errors of
+              the exponent, i.e. relative errors of e_i = exp(x_i); then `__expf` itself
+      the sum of the e_j carries sum_j p_j rho_j (relative, propagated) and sqrt(cols) u of its own additions (16 strided terms per lane and
+      a 6-step butterfly: positive terms, so acc64 is the sum itself); 1 / sum, the product e_i * inv and slack: 4 u
+      bound_i = p_i (rho_i + sum_j p_j rho_j + (sqrt(cols) + 4) u) + half_ulp_f32(p_i) + 2^-126
+    (2^-126: an e_i below the smallest normal is flushed to zero by the hardware exponential)"""
+    scale = float(torch.tensor(scale, dtype=torch.float32))
+    v = scale * s.to(torch.float64)
+    mx = v.max(-1, keepdim=True).values
+    x = v - mx
+    e = torch.exp(x)
+    p = e / e.sum(-1, keepdim=True)
+    rho = ACC_EPS * (v.abs() + mx.abs() + x.abs()) + FAST_EXP(x)
+    rel = rho + (p * rho).sum(-1, keepdim=True) + (math.sqrt(s.shape[-1]) + 4.0) * ACC_EPS
+    return p, p * rel + 2.0 ** -126
+
+
+def softmax_bwd_ref64(p, dp, scale):
+    """`softmax_bwd_rows_kernel`: ds = scale p (dp - dot), dot = sum_j p_j dp_j, float64 of the fp32 p and dp.  Returns (ds64, extra), extra
+    being the bound without the half ulp that `check_f32` adds:
+      dot: sqrt(cols) u sum_j |p_j dp_j| (its additions) -- an ABSOLUTE error, which reaches ds_i multiplied by |scale| p_i
+      dp_i - dot: u |dot| covers the rounding of dot's own last additions seen from the difference, and the difference, the product with p_i
+      and the product with scale are three roundings relative to the result: 3 u |dp_i - dot|
+      bound_i = |scale| p_i (sqrt(cols) u sum_j |p_j dp_j| + u |dot| + 3 u |dp_i - dot|) + half_ulp_f32(ds_i) + 2^-149 (1 + |dp_i - dot|)
+    The last term is gradual underflow, which the relative terms do not model: a product below the smallest normal (a masked probability of
+    1e-42 times anything) lands on the denormal grid, off by up to 2^-150 whatever its size; scale p_i does, and is then multiplied by
+    dp_i - dot, and the final product does.  Taken twice (2^-149), because results ON that grid are off by up to the whole of the worst case."""
+    scale = float(torch.tensor(scale, dtype=torch.float32))
+    p64, d64 = p.to(torch.float64), dp.to(torch.float64)
+    dot = (p64 * d64).sum(-1, keepdim=True)
+    adot = (p64 * d64).abs().sum(-1, keepdim=True)
+    ref = scale * p64 * (d64 - dot)
+    bound = abs(scale) * p64.abs() * (math.sqrt(p.shape[-1]) * ACC_EPS * adot + ACC_EPS * dot.abs() + 3.0 * ACC_EPS * (d64 - dot).abs())
+    return ref, bound + 2.0 ** -149 * (1.0 + (d64 - dot).abs())
+
+
+def layernorm_bwd_ref64(dy, x, gamma, eps):
+    """`layernorm_bwd_kernel`: g = dy gamma; dx = rstd (g - mean(g) - xhat mean(g xhat)); dgamma = sum_rows dy xhat; dbeta = sum_rows dy, in
+    float64 on the fp32 dy [M, C], x [M, C], gamma [C] and the fp32 value of eps.  Returns (dx, bound_dx, dgamma, bound_dgamma, dbeta,
+    bound_dbeta); the bounds are `extra` arguments of `check_f32`, which adds the output's own half ulp.  First-order propagation, u = 2^-24,
+    s = sqrt(C) (the random-walk factor of a C-term fp32 sum), d = x - mean, xh = d rstd, sg = mean(g), sgx = mean(g xh):
+      A     = s u mean|x| + u |mean|                      the row mean: its C additions, and the product with 1 / C
+      rho   = (s + 8) u + 2 A mean|d| / (var + eps)       rstd, relative: half the relative error of var + eps (s u from the additions of
+                                                          d^2, 2 u from squaring rounded d's, the error A of the mean entering through
+                                                          d var = 2 A mean|d|) plus rsqrtf, ASSUMED good to one ulp, 1 / C and eps: the 8
+      dxh   = rstd (A + u |d|) + |xh| (rho + u)           xhat, absolute: the mean's error and the rounding of d, scaled; rstd's; the product
+      Esg   = s u mean|g| + 2 u |sg|                      mean(g): additions; g's own rounding and the product with 1 / C
+      Esgx  = s u mean|g xh| + mean(|g| dxh) + 2 u |sgx|  mean(g xh): the same, plus xhat's error through every term
+      inner = |g| + |sg| + |xh sgx|
+      bound_dx     = rstd (Esg + dxh |sgx| + |xh| Esgx + 4 u inner) + rho rstd inner     (4: g, xh sgx, the two subtractions ... and rstd x)
+      bound_dgamma = sqrt(M) u sum|dy xh| + sum(|dy| dxh) + u sum|dy xh|                 (additions over the rows; xhat's error; the products)
+      bound_dbeta  = (sqrt(M) + 2) u sum|dy|             (+ 2: a wave's own rows are few -- below 16 terms sqrt(n) is under the worst case --
+                                                          and the waves' partial sums are then added by atomics in any order)"""
+    eps = float(torch.tensor(eps, dtype=torch.float32))
+    u = ACC_EPS
+    dy64, x64, g64 = dy.to(torch.float64), x.to(torch.float64), gamma.to(torch.float64)
+    m, c = x64.shape
+    s = math.sqrt(c)
+    mean = x64.mean(-1, keepdim=True)
+    d = x64 - mean
+    var = (d * d).mean(-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xh = d * rstd
+    g = dy64 * g64
+    sg = g.mean(-1, keepdim=True)
+    sgx = (g * xh).mean(-1, keepdim=True)
+    dx = rstd * (g - sg - xh * sgx)
+    dgamma, dbeta = (dy64 * xh).sum(0), dy64.sum(0)
+    A = s * u * x64.abs().mean(-1, keepdim=True) + u * mean.abs()
+    rho = (s + 8.0) * u + 2.0 * A * d.abs().mean(-1, keepdim=True) / (var + eps)
+    dxh = rstd * (A + u * d.abs()) + xh.abs() * (rho + u)
+    esg = s * u * g.abs().mean(-1, keepdim=True) + 2.0 * u * sg.abs()
+    esgx = s * u * (g * xh).abs().mean(-1, keepdim=True) + (g.abs() * dxh).mean(-1, keepdim=True) + 2.0 * u * sgx.abs()
+    inner = g.abs() + sg.abs() + (xh * sgx).abs()
+    b_dx = rstd * (esg + dxh * sgx.abs() + xh.abs() * esgx + 4.0 * u * inner) + rho * rstd * inner
+    adx = (dy64 * xh).abs().sum(0)
+    b_dg = math.sqrt(m) * u * adx + (dy64.abs() * dxh).sum(0) + u * adx
+    b_db = (math.sqrt(m) + 2.0) * u * dy64.abs().sum(0)
+    return dx, b_dx, dgamma, b_dg, dbeta, b_db
 
 
 def _acc_term(acc64, k, ref64):
