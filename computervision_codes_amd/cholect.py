@@ -84,6 +84,12 @@ def load_frames_device(data_dir: str, video: str, frame_ids, height: int = 256, 
     of one native size go through one launch pair; a video mixing sizes falls back to one group per size.  workers > 1: the PNGs
     are decoded by that many threads (Pillow releases the GIL while it inflates; the reference's loader has 3 worker processes,
     `Spatial_cnn/test.py:240-241`)."""
+    paths = [os.path.join(data_dir, "data", video, "{}.png".format(str(int(fid)).zfill(6))) for fid in frame_ids]
+    return load_files_device(paths, height, width, device=device, workers=workers, decode=decode)
+
+
+def load_files_device(paths, height: int = 256, width: int = 448, device="cuda", workers: int = 0, decode: str = "host"):
+    """`load_frames_device` over PNG paths (the frames of a shuffled training batch come from many videos)"""
     import struct
 
     import torch
@@ -91,13 +97,12 @@ def load_frames_device(data_dir: str, video: str, frame_ids, height: int = 256, 
 
     from . import _lib, ops
 
-    if len(frame_ids) == 0:
+    if len(paths) == 0:
         return torch.empty((0, height, width, 3), dtype=torch.uint8, device=device)
     if decode == "device":
         # decode = "device": the files are only read; inflate + unfiltering run on the GPU (`pngdec.decode_batch`, 8-bit RGB non-interlaced PNGs --
         # what the dataset ships; anything else raises `pngdec.UnsupportedPng`).  Same bytes as the Pillow path.
         from . import pngdec
-        paths = [os.path.join(data_dir, "data", video, "{}.png".format(str(int(fid)).zfill(6))) for fid in frame_ids]
         try:
             try:      # one frame size (a video): the files go to the device as they lie on disk, no host copy of the compressed bytes
                 x = pngdec.decode_files(paths, device, workers=max(8, workers))
@@ -129,15 +134,15 @@ def load_frames_device(data_dir: str, video: str, frame_ids, height: int = 256, 
             decode = "host"
     assert decode == "host"
 
-    def decode_one(fid):
-        with Image.open(os.path.join(data_dir, "data", video, "{}.png".format(str(int(fid)).zfill(6)))) as im:
+    def decode_one(path):
+        with Image.open(path) as im:
             return np.asarray(im.convert("RGB"))
-    if workers > 1 and len(frame_ids) > 1:
+    if workers > 1 and len(paths) > 1:
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=workers) as ex:
-            raw = list(ex.map(decode_one, frame_ids))
+            raw = list(ex.map(decode_one, paths))
     else:
-        raw = [decode_one(fid) for fid in frame_ids]
+        raw = [decode_one(p) for p in paths]
     out = torch.empty((len(raw), height, width, 3), dtype=torch.uint8, device=device)
     groups: Dict[tuple, List[int]] = {}
     for i, a in enumerate(raw):

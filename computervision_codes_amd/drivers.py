@@ -211,15 +211,45 @@ def _teacher_files(F, kfold):
             {t: featfile.read_feats(tdir(F.teacher_feat_version, t, "feats")) for t in "ivt"})
 
 
+def _add_train_transform_flag(p: argparse.ArgumentParser):
+    p.add_argument("--train_transform", type=str, default="host", choices=["host", "device"],
+                   help="device: flips, autocontrast, rotation and the second Resize of the train transform on the GPU (mt4_aug_*), the same bytes "
+                        "as Pillow for the same draws; the PNGs are decoded as --png_decode says")
+
+
+_WARNED_TRANSFORM = False
+
+
+def _device_transform(F) -> bool:
+    """--train_transform device, unless the augmentation list has no device form ('contrast' after 'rot90': the black fill of the rotation
+    would enter the histogram; 'contrast' or 'rot90' named twice) -- such a run keeps the host transform; said once"""
+    if getattr(F, "train_transform", "host") != "device":
+        return False
+    from . import augment
+    if augment.supported(F.augmentation_list):
+        return True
+    global _WARNED_TRANSFORM
+    if not _WARNED_TRANSFORM:
+        print(f"[drivers] --train_transform device: the augmentation list {list(F.augmentation_list)} has no device form ('contrast' after "
+              "'rot90', or 'contrast' / 'rot90' twice); the train transform runs in Pillow on the host", flush=True)
+        _WARNED_TRANSFORM = True
+    return False
+
+
 def _frame_batch(F, batch, labels, tpred, tfeat, size, rng):
     """a training batch of (video, frame) samples -> (uint8 frames [B,H,W,3] on the GPU through the train transform at size = (H, W), the
     labels of the i, v, t, ivt heads, the teacher predictions and features of i, v, t -- empty without teacher files)"""
-    frames = np.concatenate([load_train_frames_u8(F.data_dir, v, [labels[v]["ivt"][i, 0]], size[0], size[1], rng, F.augmentation_list)
-                             for v, i in batch])
+    if _device_transform(F):
+        from . import augment
+        frames = augment.load_train_batch_device(F.data_dir, [(v, labels[v]["ivt"][i, 0]) for v, i in batch], size[0], size[1], rng,
+                                                 F.augmentation_list, decode=F.png_decode, workers=F.decode_workers)
+    else:
+        frames = torch.from_numpy(np.concatenate([load_train_frames_u8(F.data_dir, v, [labels[v]["ivt"][i, 0]], size[0], size[1], rng,
+                                                                       F.augmentation_list) for v, i in batch])).cuda()
     lab = [torch.from_numpy(np.stack([labels[v][k][i, 1:] for v, i in batch])) for k in ("i", "v", "t", "ivt")]
     rows = lambda files: [torch.from_numpy(np.stack([files[t][featfile.video_key(v)][i] for v, i in batch]).astype(np.float32))
                           for t in "ivt"] if files else []
-    return torch.from_numpy(frames).cuda(), lab, rows(tpred), rows(tfeat)
+    return frames, lab, rows(tpred), rows(tfeat)
 
 
 def _frame_validation(F, val_videos, labels, size, cap, forward):
@@ -257,6 +287,7 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     p.add_argument("--teacher_feat_version", type=str, default="Q2L")
     p.add_argument("--teacher_pred_version", type=str, default="Q2LMSTCT")
     p.add_argument("--augmentation_list", type=str, nargs="*", default=["original", "vflip", "hflip", "contrast", "rot90"])
+    _add_train_transform_flag(p)
     p.add_argument("--rates", type=float, nargs="+", default=[1, 0, 0.1])
     p.add_argument("--temp", type=int, default=4)
     p.add_argument("--pretrain_dir", type=str, default="")
@@ -705,6 +736,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     p.add_argument("--img_size", type=int, default=384)
     p.add_argument("--hidden_dim", type=int, default=1536)
     p.add_argument("--augmentation_list", type=str, nargs="*", default=["original", "vflip", "hflip", "contrast", "rot90"])
+    _add_train_transform_flag(p)
     p.add_argument("--pretrain_dir", type=str, default="")
     p.add_argument("--drop_path_rate", type=float, default=0.1)          # `swin_transformer.py:488`
     p.add_argument("--operand_dtype", type=str, default="fp32", choices=["fp32", "bf16"],

@@ -233,6 +233,29 @@ int mt4_png_read_files(const char* const* paths, const int64_t* sizes, const int
  * axis 1: height.  Bit-exact with Pillow when the horizontal pass runs first. */
 int mt4_resize_pass_u8(const void* in, void* out, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, int32_t B, int32_t Hin,
                        int32_t Win, int32_t Hout, int32_t Wout, int32_t C, int32_t axis, void* stream);
+/* The train transform of the frame trainers on the device (Spatial_cnn/dataloader.py:89-100,153-162: Resize -> vflip -> hflip -> autocontrast
+ * -> rotation by a random angle with expand -> Resize), byte-identical to Pillow for the same draws.  Every frame has one parameter row of
+ * MT4_AUG_PARAMS int32: {vflip, hflip, a0, a1, a2, a3, a4, a5, nw, nh, contrast, 0} -- a0..a5 the 16.16 fixed-point inverse affine map of the
+ * rotation, nw x nh the size of the rotated image (augment.draw_params builds them on the host in float64).
+ *   mt4_aug_channel_luts: frames uint8 [B][H][W][3] -> luts uint8 [B][3][256], the autocontrast table of every channel (smallest value -> 0,
+ *     largest -> 255, int(i * scale + offset) in float64 with two roundings; identity when the channel is constant or the frame's contrast
+ *     flag is 0).  minmax: int32 [B][3][2] scratch, left holding (min, max) of the frames whose flag is set.
+ *   mt4_aug_flip_lut_rotate: canvas uint8 [B][Hc][Wc][3]; pixel (X, Y), X < nw and Y < nh, = lut[source pixel ((a2 + X a0 + Y a1) >> 16,
+ *     (a5 + X a3 + Y a4) >> 16) of the flipped frame], 0 when that lies outside the frame; 0 outside nw x nh.  Hc >= max nh, Wc >= max nw.
+ *   mt4_aug_resize_pass_u8: mt4_resize_pass_u8 (C = 3) where frame b's image is the top-left nh x nw corner of its canvas and its tables lie in
+ *     the int32 `pool` at the offsets of frame_tab [B][8] = {h bounds, h coeffs, h ksize, nw, v bounds, v coeffs, v ksize, nh} (bounds
+ *     [n_out][2], coeffs [n_out][ksize]; ksize_max sizes the LDS copy of a frame's horizontal table, a frame with a larger ksize reads the
+ *     pool directly).  axis 0: [B][Hc][Wc][3] -> [B][Hc][Wout][3] (Hout == Hc, Wc % 4 == 0, rows >= nh are not written); axis 1:
+ *     [B][Hc][Wout][3] -> [B][Hout][Wout][3] (Wc == Wout).
+ * Image, LUT and canvas pointers must be 4-byte aligned (MT4_EINVAL otherwise); H, W <= 4096 and Hc, Wc <= 8192 in mt4_aug_flip_lut_rotate,
+ * with |a2|, |a5| < 2^30, so that the 16.16 sums stay inside int32. */
+#define MT4_AUG_PARAMS 12
+int mt4_aug_channel_luts(const uint8_t* frames, const int32_t* params, int32_t* minmax, uint8_t* luts, int32_t B, int32_t H, int32_t W,
+                         void* stream);
+int mt4_aug_flip_lut_rotate(const uint8_t* frames, const uint8_t* luts, const int32_t* params, uint8_t* canvas, int32_t B, int32_t H, int32_t W,
+                            int32_t Hc, int32_t Wc, void* stream);
+int mt4_aug_resize_pass_u8(const uint8_t* in, uint8_t* out, const int32_t* pool, const int32_t* frame_tab, int32_t B, int32_t Hc, int32_t Wc,
+                           int32_t Hout, int32_t Wout, int32_t ksize_max, int32_t axis, void* stream);
 /* MaxPool2d(3, stride 2, pad 1) channels-last (resnet.py:149). C*esize % 16 == 0. */
 int mt4_maxpool3x3s2_nhwc(const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
                           void* stream);

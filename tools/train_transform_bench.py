@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""The train transform on the device against the Pillow path (GPU box).  Steps, each a command of its own (run every GPU step under its own
+`timeout` and chain them with `&&`, see tools/README.md):
+
+  make-data DIR [frames per video]        a CholecT45-shaped dataset of 480 x 854 PNGs under DIR (CPU only)
+  kernels B H W                           the device transform and the bf16 ResNet-50 student step at the same batch: event-timed ms per call and
+                                          the bytes each kernel must move; run it under `rocprofv3 --kernel-trace --stats` for the per-kernel table
+  loader DIR [B H W]                      frames/s of `drivers._frame_batch` alone, --train_transform host against device (--png_decode device),
+                                          median of 7 batches each, alternating
+  epoch DIR host|device [B]               frames/s of the second epoch of `Spatial_cnn/run.py -t` (ResNet-50, bf16 operands, --loss_type i)
+
+Every step prints one JSON line."""
+import json
+import os
+import random
+import statistics
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
+NAMES = ["original", "vflip", "hflip", "contrast", "rot90"]
+HBM_TBS = 6.3           # the achievable HBM bandwidth VERDICT.md uses
+
+
+def _one_png(args):
+    from PIL import Image
+    path, seed = args
+    g = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:480, 0:854]
+    base = np.stack([96 + 80 * np.sin(xx / (37.0 + seed % 11) + c) * np.cos(yy / (29.0 + seed % 7)) for c in range(3)], -1)
+    Image.fromarray(np.clip(base + g.normal(0, 6, base.shape), 10, 245).astype(np.uint8)).save(path)      # (smooth + sensor-like noise)
+
+
+def make_data(d, n_frames=16):
+    from concurrent.futures import ProcessPoolExecutor
+    from computervision_codes_amd import cholect
+    g = np.random.default_rng(3)
+    vids = cholect.extraction_videos("cholect45-crossval", 1)
+    jobs = []
+    for sub in ("triplet", "instrument", "verb", "target"):
+        os.makedirs(os.path.join(d, sub), exist_ok=True)
+    for vi, v in enumerate(vids):
+        os.makedirs(os.path.join(d, "data", v), exist_ok=True)
+        for sub, k in (("triplet", 100), ("instrument", 6), ("verb", 10), ("target", 15)):
+            lab = np.concatenate([np.arange(n_frames)[:, None], (g.random((n_frames, k)) < 0.15).astype(int)], 1)
+            np.savetxt(os.path.join(d, sub, v + ".txt"), lab, fmt="%d", delimiter=",")
+        jobs += [(os.path.join(d, "data", v, f"{i:06d}.png"), vi * 1000 + i) for i in range(n_frames)]
+    with ProcessPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
+        list(ex.map(_one_png, jobs, chunksize=8))
+    size = sum(os.path.getsize(p) for p, _ in jobs)
+    print(json.dumps({"step": "make-data", "dir": d, "videos": len(vids), "frames": len(jobs), "mean_png_bytes": size // len(jobs)}))
+
+
+def _event_ms(fn, iters):
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def kernels(B, H, W):
+    import torch
+    from computervision_codes_amd import augment, shapes, synth
+    from computervision_codes_amd.spatial_cnn_train import SpatialCnnTrainer
+    dev = torch.device("cuda:0")
+    x = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (B, H, W, 3), dtype=np.uint8)).to(dev)
+    rng = random.Random(47)
+    plist = [augment.draw_params(rng, NAMES, B, H, W) for _ in range(8)]
+    for p in plist:                                            # (fills the table pool)
+        augment.train_transform_device(x, p)
+    it = iter(range(10 ** 9))
+    ms_t = _event_ms(lambda: augment.train_transform_device(x, plist[next(it) % 8]), 24)
+    # the bytes every kernel MUST move, mean over the drawn batches: range = the frames with the contrast flag once; gather = the frames once in,
+    # the canvas once out; resize = canvas image in, h-pass image out and in again, frame out
+    fr = H * W * 3
+    nbytes = {"minmax": 0.0, "gather": 0.0, "resize_h": 0.0, "resize_v": 0.0}
+    for p in plist:
+        hc, wc = augment.canvas_dims(p)
+        nbytes["minmax"] += float(p.table[:, 10].sum()) * fr / 8
+        nbytes["gather"] += (B * fr + B * hc * wc * 3) / 8
+        nbytes["resize_h"] += sum(nh * nw * 3 + nh * W * 3 for nh, nw in p.sizes()) / 8
+        nbytes["resize_v"] += sum(nh * W * 3 + fr for nh, _ in p.sizes()) / 8
+    sd = synth.fill_from_shapes(shapes.spatial_cnn_shapes("resnet50"), seed=47)
+    z = (torch.rand(B, 131, device=dev) < 0.1).float()
+    tp = [torch.randn(B, k, device=dev) for k in (6, 10, 15)]
+    tf = [torch.randn(B, 1536, device=dev) for _ in range(3)]
+    tr = SpatialCnnTrainer("resnet50", lr=0.001, operand_dtype=torch.bfloat16).load_state_dict(sd)
+    tr.exchange = False
+    ms_s = _event_ms(lambda: tr.train_step(x, z, tp, tf), 5)
+    print(json.dumps({"step": "kernels", "batch": B, "size": [H, W], "transform_ms_per_call": round(ms_t, 4), "transform_us_per_frame": round(ms_t / B * 1e3, 3),
+                      "student_bf16_step_ms": round(ms_s, 3), "transform_share_of_step": round(ms_t / ms_s, 5),
+                      "must_move_bytes_per_call": {k: int(v) for k, v in nbytes.items()},
+                      "us_per_call_at_%.1f_TBs" % HBM_TBS: {k: round(v / (HBM_TBS * 1e12) * 1e6, 3) for k, v in nbytes.items()}}))
+
+
+def _namespace(d, mode):
+    import argparse
+    return argparse.Namespace(data_dir=d, augmentation_list=NAMES, png_decode="device", decode_workers=8, train_transform=mode)
+
+
+def loader(d, B=64, H=256, W=448, reps=7):
+    import torch
+    from computervision_codes_amd import cholect, drivers
+    vids, _, _ = cholect.split_videos("cholect45-crossval", 1)
+    labels = {v: cholect.load_labels(d, v) for v in vids}
+    samples = [(v, i) for v in vids for i in range(len(labels[v]["ivt"]))]
+    random.Random(1).shuffle(samples)
+    batches = [samples[k * B:(k + 1) * B] for k in range(len(samples) // B)]
+    assert batches, "dataset smaller than one batch"
+    times = {"host": [], "device": []}
+    for r in range(reps + 1):                                  # (round 0 warms both paths up: library load, table pool, file cache)
+        for mode in ("host", "device"):
+            F, rng = _namespace(d, mode), random.Random(r)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fr = drivers._frame_batch(F, batches[r % len(batches)], labels, {}, {}, (H, W), rng)[0]
+            torch.cuda.synchronize()
+            if r:
+                times[mode].append(time.perf_counter() - t0)
+            assert tuple(fr.shape) == (B, H, W, 3)
+    fps = {m: B / statistics.median(t) for m, t in times.items()}
+    print(json.dumps({"step": "loader", "batch": B, "size": [H, W], "png_decode": "device", "reps": reps,
+                      "host_frames_per_s": round(fps["host"], 1), "device_frames_per_s": round(fps["device"], 1),
+                      "host_s": [round(t, 4) for t in times["host"]], "device_s": [round(t, 4) for t in times["device"]]}))
+
+
+def epoch(d, mode, B=64):
+    from computervision_codes_amd import cholect, drivers
+    vids, _, _ = cholect.split_videos("cholect45-crossval", 1)
+    n = sum(len(cholect.load_labels(d, v)["ivt"]) for v in vids)
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as work:
+        os.chdir(work)
+        try:
+            drivers.spatial_cnn_train(["-t", "--network", "resnet50", "--student_dim", "2048", "--loss_type", "i", "--operand_dtype", "bf16", "--epochs", "2",
+                                       "--val_interval", "2", "--batch", str(B), "--version", "B", "--data_dir", d, "--kfold", "1", "--png_decode", "device",
+                                       "--train_transform", mode])
+            log = open(os.path.join(work, "__checkpoint__", "run_B", "rendezvous_lcholect45-crossval_cholect1.log")).read()
+        finally:
+            os.chdir(cwd)
+    secs = [float(ln.split("|")[-1].split()[0]) for ln in log.splitlines() if "Traning | lr:" in ln]
+    print(json.dumps({"step": "epoch", "train_transform": mode, "batch": B, "frames_per_epoch": n, "epoch_s": secs,
+                      "second_epoch_frames_per_s": round(n / secs[1], 1)}))
+
+
+if __name__ == "__main__":
+    cmd, a = sys.argv[1], sys.argv[2:]
+    if cmd == "make-data":
+        make_data(a[0], *[int(v) for v in a[1:2]])
+    elif cmd == "kernels":
+        kernels(*[int(v) for v in a[:3]])
+    elif cmd == "loader":
+        loader(a[0], *[int(v) for v in a[1:4]])
+    elif cmd == "epoch":
+        epoch(a[0], a[1], *[int(v) for v in a[2:3]])
+    else:
+        sys.exit(__doc__)
