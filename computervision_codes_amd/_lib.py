@@ -56,6 +56,13 @@ class TcnDesc(C.Structure):
     ]
 
 
+class TakeSeg(C.Structure):
+    """mirror of `mt4_take_seg` (include/mt4hip.h)"""
+    _fields_ = [("table", C.c_void_p), ("out", C.c_void_p), ("C", C.c_int32), ("nrows", C.c_int32)]
+
+
+TAKE_MAX_SEGS = 16      # MT4_TAKE_MAX_SEGS
+
 _vp, _i32 = C.c_void_p, C.c_int32
 _FLOAT3 = C.c_float * 3
 
@@ -82,6 +89,7 @@ SIGNATURES = {
     "mt4_aug_channel_luts": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "mt4_aug_flip_lut_rotate": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mt4_aug_resize_pass_u8": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "mt4_take_rows_f32": (C.c_int, [C.POINTER(TakeSeg), _i32, _vp, C.c_int64, _vp]),
     "mt4_maxpool3x3s2_nhwc": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mt4_stem_maxpool_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mt4_global_avgpool_nhwc": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),

@@ -272,9 +272,12 @@ def flip_lut_rotate_device(frames, luts, table_dev, hc: int, wc: int):
 def frame_tables(params: Params, device):
     """the per-frame rows `mt4_aug_resize_pass_u8` reads ([B,8] int32 on the device), the table pool's buffer and the largest (h, v) ksize"""
     import torch
-    pool = _POOLS.get(device)
+    # one pool per (device, stream): a pool's uploads and the kernels that read it are ordered by that stream alone, so loads that run on side
+    # streams of their own (`loader.FrameLoader`) neither share a buffer across streams nor grow one under another thread's feet
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    pool = _POOLS.get(key)
     if pool is None:
-        pool = _POOLS[device] = TablePool(device)
+        pool = _POOLS[key] = TablePool(device)
     sizes = params.sizes()
     offs = pool.offsets([(nw, params.w) for _, nw in sizes] + [(nh, params.h) for nh, _ in sizes])
     b = len(sizes)

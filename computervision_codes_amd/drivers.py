@@ -217,6 +217,13 @@ def _add_train_transform_flag(p: argparse.ArgumentParser):
                         "as Pillow for the same draws; the PNGs are decoded as --png_decode says")
 
 
+def _add_prefetch_flag(p: argparse.ArgumentParser):
+    p.add_argument("--prefetch", type=int, default=0,
+                   help="K > 0: training batches come from `loader.FrameLoader` -- chunks of up to K batches (at most 1024 frames) decoded, transformed "
+                        "and gathered per call on helper threads and side streams while the step runs, labels and teacher rows resident on the device; "
+                        "the same batches as 0 (the synchronous loader), only faster")
+
+
 _WARNED_TRANSFORM = False
 
 
@@ -252,6 +259,15 @@ def _frame_batch(F, batch, labels, tpred, tfeat, size, rng):
     return frames, lab, rows(tpred), rows(tfeat)
 
 
+def _sample_tables(F, labels, tpred, tfeat, videos):
+    """--prefetch K > 0: the label and teacher rows of the training videos on the device, built once per run (`loader.SampleTables`:
+    N x (131 + 31 + 3 x teacher_dim) x 4 bytes with teacher files); None for --prefetch 0, which keeps the synchronous `_frame_batch` path"""
+    if getattr(F, "prefetch", 0) <= 0:
+        return None
+    from .loader import SampleTables
+    return SampleTables(labels, tpred, tfeat, videos=videos)
+
+
 def _frame_validation(F, val_videos, labels, size, cap, forward):
     """validation mAP of the task's head (`run.py:416-451`; ivt for --loss_type all) over the validation videos' frames in device batches of
     max(--batch, min(--device_batch, cap)) (results do not depend on it); forward(uint8 frames) -> the head's logits"""
@@ -260,8 +276,9 @@ def _frame_validation(F, val_videos, labels, size, cap, forward):
     vb = max(F.batch, min(F.device_batch, cap))
     for v in val_videos:
         lv = labels[v][vt]
-        for s0 in range(0, len(lv), vb):
-            fr = cholect.load_frames_device(F.data_dir, v, lv[s0:s0 + vb, 0], size[0], size[1], workers=F.decode_workers, decode=F.png_decode)
+        load = lambda s0, v=v, lv=lv: cholect.load_frames_device(F.data_dir, v, lv[s0:s0 + vb, 0], size[0], size[1], workers=F.decode_workers, decode=F.png_decode)
+        spans = [(s0,) for s0 in range(0, len(lv), vb)]
+        for (s0,), fr in zip(spans, extract.iter_chunks(spans, load, 1 if getattr(F, "prefetch", 0) > 0 else 0)):      # --prefetch: the next span loads meanwhile
             m.update(lv[s0:s0 + vb, 1:], _sigmoid(forward(fr)))
         m.video_end()
     score = float(m.compute_video_AP(ignore_null=_chlg(F))["mAP"]) if val_videos else 0.0
@@ -288,6 +305,7 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     p.add_argument("--teacher_pred_version", type=str, default="Q2LMSTCT")
     p.add_argument("--augmentation_list", type=str, nargs="*", default=["original", "vflip", "hflip", "contrast", "rot90"])
     _add_train_transform_flag(p)
+    _add_prefetch_flag(p)
     p.add_argument("--rates", type=float, nargs="+", default=[1, 0, 0.1])
     p.add_argument("--temp", type=int, default=4)
     p.add_argument("--pretrain_dir", type=str, default="")
@@ -319,10 +337,18 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     eval_args = argparse.Namespace(**vars(F))
     eval_args.train = False
 
+    tables = _sample_tables(F, labels, tpred, tfeat, train_videos)
+
     def train_epoch(epoch):
         order = list(samples)
         order_rng.shuffle(order)                             # the same permutation on every rank
         mine, tot = deal(order, F.batch, world, rank), 0.0
+        if tables is not None:                               # --prefetch K: the same batches, loaded ahead in chunks (`loader.FrameLoader`)
+            from .loader import FrameLoader
+            with FrameLoader(F, mine, labels, tables, size, aug_rng, prefetch=F.prefetch) as batches:
+                for fb in batches:
+                    tot += tr.train_step(*fb)["loss"]
+            return tot, len(mine)
         for batch in mine:
             tot += tr.train_step(*_frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng))["loss"]
         return tot, len(mine)
@@ -737,6 +763,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     p.add_argument("--hidden_dim", type=int, default=1536)
     p.add_argument("--augmentation_list", type=str, nargs="*", default=["original", "vflip", "hflip", "contrast", "rot90"])
     _add_train_transform_flag(p)
+    _add_prefetch_flag(p)
     p.add_argument("--pretrain_dir", type=str, default="")
     p.add_argument("--drop_path_rate", type=float, default=0.1)          # `swin_transformer.py:488`
     p.add_argument("--operand_dtype", type=str, default="fp32", choices=["fp32", "bf16"],
@@ -783,17 +810,25 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     size = (F.img_size, F.img_size)
     eval_args = argparse.Namespace(**vars(F))
 
+    tables = _sample_tables(F, labels, tpred, tfeat, train_videos)
+
     def train_epoch(epoch):
+        from contextlib import nullcontext
         order = list(samples)
         order_rng.shuffle(order)                             # the same permutation on every rank
         mine, tot = deal(order, F.batch, world, rank), 0.0
-        for s, batch in enumerate(mine):
-            frames, lab, tp, tf = _frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng)
-            masks = tr.draw_masks_device(len(batch), F.seed * 1000003 + rank, epoch * len(mine) + s)     # (a running step count)
-            if single:
-                tot += tr.train_step(frames, lab["ivt".index(F.loss_type)], masks)
-            else:
-                tot += tr.train_step(frames, lab, masks, teacher_pred=tp, teacher_feat=tf)["loss"]
+        if tables is not None:                               # --prefetch K: the same batches, loaded ahead in chunks (`loader.FrameLoader`)
+            from .loader import FrameLoader
+            source = FrameLoader(F, mine, labels, tables, size, aug_rng, prefetch=F.prefetch)
+        else:
+            source = nullcontext(_frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng) for batch in mine)
+        with source as loaded:
+            for s, (batch, (frames, lab, tp, tf)) in enumerate(zip(mine, loaded)):
+                masks = tr.draw_masks_device(len(batch), F.seed * 1000003 + rank, epoch * len(mine) + s)     # (a running step count)
+                if single:
+                    tot += tr.train_step(frames, lab["ivt".index(F.loss_type)], masks)
+                else:
+                    tot += tr.train_step(frames, lab, masks, teacher_pred=tp, teacher_feat=tf)["loss"]
         return tot, len(mine)
 
     def validate(state):                                     # the task's head (:416-421, 443-450)

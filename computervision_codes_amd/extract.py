@@ -55,7 +55,17 @@ import atexit  # noqa: E402
 atexit.register(_shutdown_pools)
 
 
-def iter_chunks(spans: Sequence[tuple], load_chunk: Callable[[int, int], torch.Tensor], prefetch=1):
+def _record_stream(x, stream):
+    """`record_stream` on every device tensor of a load's result (a tensor, or tuples / lists of them)"""
+    if torch.is_tensor(x):
+        if x.is_cuda:
+            x.record_stream(stream)
+    elif isinstance(x, (tuple, list)):
+        for y in x:
+            _record_stream(y, stream)
+
+
+def iter_chunks(spans: Sequence[tuple], load_chunk: Callable[..., torch.Tensor], prefetch=1, prepare: Callable = None):
     """Yield `load_chunk(s, e)` for every span in order.  With `prefetch` = k > 0 the next k spans are read and decoded on helper threads
     while the caller works on this one (the reference's DataLoader workers run ahead of the model the same way, `Spatial_cnn/test.py:240-241`);
     k = 2 lets the host part of one load (file reads, gathering the compressed bytes) overlap the device part of the load before it.
@@ -64,11 +74,15 @@ def iter_chunks(spans: Sequence[tuple], load_chunk: Callable[[int, int], torch.T
     unfilter, resize -- co-run: the inflate is latency-bound per frame, 75 ms per call however many frames ride along).  A chunk is handed over
     with an event the CALLER'S CURRENT stream waits on (and `record_stream` for that stream): a consumer that fans out over streams of its own
     (`extract_u8(streams > 1)`) must order them behind the current stream, as `VideoNas.extract_u8` does (`st.wait_stream(main)`).
-    `spans` are argument tuples of `load_chunk`."""
+    `spans` are argument tuples of `load_chunk`; a load may return a tensor or tuples / lists of tensors.
+    `prepare(*span)`, when given, runs on the CALLER'S thread, span by span in order, right before that span's load is handed to a helper thread;
+    what it returns is passed to `load_chunk` as one more argument.  State that must advance in span order whatever the helpers do -- the
+    augmentation draws of `loader.FrameLoader` -- belongs there."""
     depth = int(prefetch)
+    extra = (lambda sp: ()) if prepare is None else (lambda sp: (prepare(*sp),))
     if depth <= 0 or len(spans) < 2 or not torch.cuda.is_available():
         for sp in spans:
-            yield load_chunk(*sp)
+            yield load_chunk(*sp, *extra(sp))
         return
     dev, cur = torch.cuda.current_device(), torch.cuda.current_stream()
     depth = min(depth, len(spans))
@@ -78,26 +92,30 @@ def iter_chunks(spans: Sequence[tuple], load_chunk: Callable[[int, int], torch.T
     if sides is None:
         sides = _SIDE_STREAMS[(dev, depth)] = [torch.cuda.Stream() for _ in range(depth)]
 
-    def ahead(i):
+    def ahead(i, args):
         torch.cuda.set_device(dev)
         st = sides[i % depth]
         with torch.cuda.stream(st):
-            fr = load_chunk(*spans[i])
+            fr = load_chunk(*args)
             ev = torch.cuda.Event()
             ev.record(st)
         return fr, ev
+
+    def submit(i):
+        return pool.submit(ahead, i, tuple(spans[i]) + extra(spans[i]))
     pool = _POOLS.get((dev, depth))
     if pool is None:
         pool = _POOLS[(dev, depth)] = ThreadPoolExecutor(depth, thread_name_prefix=f"mt4-load-{dev}")
-    pending = [pool.submit(ahead, i) for i in range(depth)]
+    pending = []
     try:
+        for i in range(depth):
+            pending.append(submit(i))
         for i in range(len(spans)):
             fr, ev = pending.pop(0).result()
             if i + depth < len(spans):
-                pending.append(pool.submit(ahead, i + depth))
+                pending.append(submit(i + depth))
             cur.wait_event(ev)
-            if torch.is_tensor(fr) and fr.is_cuda:
-                fr.record_stream(cur)           # allocated on a side stream, consumed on the caller's
+            _record_stream(fr, cur)             # allocated on a side stream, consumed on the caller's
             yield fr
     finally:
         for f in pending:                       # (the consumer stopped early: let the loads in flight finish before their buffers go)

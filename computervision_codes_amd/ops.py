@@ -1242,6 +1242,23 @@ def gather_rows(x: torch.Tensor, row_map: torch.Tensor, *, l_out: int, l_in: int
     return y
 
 
+def take_rows(tables, rows: torch.Tensor):
+    """[t[rows] for t in tables] from ONE launch (`mt4_take_rows_f32`): tables = up to 16 contiguous fp32 [N_s, C_s] device tensors, rows int64 [n] on
+    the device -> a list of contiguous fp32 [n, C_s] tensors.  The caller guarantees 0 <= rows < N_s (`loader.SampleTables` checks on the host);
+    n == 0 returns empty tensors without a launch."""
+    tables = list(tables)
+    _need_cuda(rows, *tables)
+    if not 1 <= len(tables) <= _lib.TAKE_MAX_SEGS:
+        raise _lib.Mt4Error(f"take_rows: 1..{_lib.TAKE_MAX_SEGS} tables per launch, got {len(tables)}")
+    assert rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous()
+    assert all(t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and t.device == rows.device for t in tables)
+    n = rows.numel()
+    outs = [torch.empty((n, t.shape[1]), dtype=torch.float32, device=t.device) for t in tables]
+    segs = (_lib.TakeSeg * len(tables))(*[_lib.TakeSeg(t.data_ptr(), o.data_ptr(), t.shape[1], t.shape[0]) for t, o in zip(tables, outs)])
+    check(lib.mt4_take_rows_f32(segs, len(tables), rows.data_ptr(), n, _stream()), "mt4_take_rows_f32")
+    return outs
+
+
 def scatter_rows(y: torch.Tensor, row_map: torch.Tensor, *, l_out: int, l_in: int, group: int = 1, m_in: Optional[int] = None) -> torch.Tensor:
     """the inverse of `gather_rows` (the maps are bijections): x[(m // l_out) * l_in + map[...]] = y[m][g*C:(g+1)*C]"""
     _need_cuda(y, row_map)

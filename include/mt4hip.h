@@ -256,6 +256,24 @@ int mt4_aug_flip_lut_rotate(const uint8_t* frames, const uint8_t* luts, const in
                             int32_t Hc, int32_t Wc, void* stream);
 int mt4_aug_resize_pass_u8(const uint8_t* in, uint8_t* out, const int32_t* pool, const int32_t* frame_tab, int32_t B, int32_t Hc, int32_t Wc,
                            int32_t Hout, int32_t Wout, int32_t ksize_max, int32_t axis, void* stream);
+/* The sample rows of a training batch gathered on the device.  The reference's dataset assembles, per sample and on the host, the label rows of
+ * the four heads and (--loss_type all) the teacher prediction and feature rows of i, v, t (Spatial_cnn/dataloader.py:216-261); here those tables
+ * are fp32 [nrows][C] arrays uploaded once per run (loader.SampleTables) and a batch -- or a chunk of batches -- is ONE launch:
+ *   out_s[r][c] = table_s[rows[r]][c]   for every segment s < nseg, r < n, c < C_s
+ * segs: HOST array of nseg (1..MT4_TAKE_MAX_SEGS) descriptors, copied into the kernel arguments (nothing is uploaded, the array may be freed when
+ * the call returns); rows: DEVICE int64 [n].  C >= 1 and nrows >= 1 per segment, n >= 0 (n == 0 launches nothing).  Tables and outputs are
+ * contiguous and 4-byte aligned (MT4_EALIGN otherwise); a segment with C % 4 == 0 and 16-byte aligned pointers (C = 100, 1536) moves 16 bytes per
+ * access, any other (C = 6, 10, 15: rows that are not 16-byte aligned) one dword.  Plain stores, no atomics: every output element is written by
+ * exactly one thread.  The caller guarantees 0 <= rows[r] < nrows (SampleTables checks on the host, where the index is built); an index outside
+ * writes a zero row and reads nothing. */
+#define MT4_TAKE_MAX_SEGS 16
+typedef struct mt4_take_seg {
+    const float* table; /* [nrows][C] on the device */
+    float* out;         /* [n][C] on the device */
+    int32_t C;
+    int32_t nrows;
+} mt4_take_seg;
+int mt4_take_rows_f32(const mt4_take_seg* segs, int32_t nseg, const int64_t* rows, int64_t n, void* stream);
 /* MaxPool2d(3, stride 2, pad 1) channels-last (resnet.py:149). C*esize % 16 == 0. */
 int mt4_maxpool3x3s2_nhwc(const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
                           void* stream);

@@ -7,7 +7,11 @@
                                           the bytes each kernel must move; run it under `rocprofv3 --kernel-trace --stats` for the per-kernel table
   loader DIR [B H W]                      frames/s of `drivers._frame_batch` alone, --train_transform host against device (--png_decode device),
                                           median of 7 batches each, alternating
-  epoch DIR host|device [B]               frames/s of the second epoch of `Spatial_cnn/run.py -t` (ResNet-50, bf16 operands, --loss_type i)
+  loader DIR [B H W] --prefetch K,K,...   frames/s of a whole pass over the training batches, --train_transform device --png_decode device, for every K of
+                                          the list: K = 0 is `drivers._frame_batch` batch after batch, K > 0 `loader.FrameLoader(prefetch=K)` consumed as
+                                          fast as it delivers; median of 7 passes each, alternating; [--batches N] bounds the pass
+  epoch DIR host|device [B]               frames/s of the second epoch of `Spatial_cnn/run.py -t` (ResNet-50, bf16 operands, --loss_type i);
+                                          [--prefetch K] passes the flag on
 
 Every step prints one JSON line."""
 import json
@@ -133,7 +137,42 @@ def loader(d, B=64, H=256, W=448, reps=7):
                       "host_s": [round(t, 4) for t in times["host"]], "device_s": [round(t, 4) for t in times["device"]]}))
 
 
-def epoch(d, mode, B=64):
+def loader_prefetch(d, ks, B=64, H=256, W=448, reps=7, max_batches=None):
+    import torch
+    from computervision_codes_amd import cholect, drivers
+    from computervision_codes_amd.loader import FrameLoader, SampleTables
+    vids, _, _ = cholect.split_videos("cholect45-crossval", 1)
+    labels = {v: cholect.load_labels(d, v) for v in vids}
+    samples = [(v, i) for v in vids for i in range(len(labels[v]["ivt"]))]
+    random.Random(1).shuffle(samples)
+    batches = [samples[k:k + B] for k in range(0, len(samples), B)][:max_batches]
+    frames = sum(len(b) for b in batches)
+    tables = SampleTables(labels, videos=vids)
+    F = _namespace(d, "device")
+    times, stats = {k: [] for k in ks}, {}
+    for r in range(reps + 1):                                  # (round 0 warms up: library load, table pools, file cache, pinned staging)
+        for k in ks:
+            rng = random.Random(r)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if k == 0:
+                for b in batches:
+                    drivers._frame_batch(F, b, labels, {}, {}, (H, W), rng)
+            else:
+                with FrameLoader(F, batches, labels, tables, (H, W), rng, prefetch=k) as fl:
+                    for fb in fl:
+                        pass
+                stats[k] = dict(fl.stats)
+            torch.cuda.synchronize()
+            if r:
+                times[k].append(time.perf_counter() - t0)
+    print(json.dumps({"step": "loader-prefetch", "batch": B, "size": [H, W], "png_decode": "device", "train_transform": "device", "reps": reps,
+                      "batches_per_pass": len(batches), "frames_per_pass": frames,
+                      "frames_per_s": {str(k): round(frames / statistics.median(t), 1) for k, t in times.items()},
+                      "pass_s": {str(k): [round(v, 4) for v in t] for k, t in times.items()}, "stats": {str(k): v for k, v in stats.items()}}))
+
+
+def epoch(d, mode, B=64, prefetch=0):
     from computervision_codes_amd import cholect, drivers
     vids, _, _ = cholect.split_videos("cholect45-crossval", 1)
     n = sum(len(cholect.load_labels(d, v)["ivt"]) for v in vids)
@@ -143,24 +182,33 @@ def epoch(d, mode, B=64):
         try:
             drivers.spatial_cnn_train(["-t", "--network", "resnet50", "--student_dim", "2048", "--loss_type", "i", "--operand_dtype", "bf16", "--epochs", "2",
                                        "--val_interval", "2", "--batch", str(B), "--version", "B", "--data_dir", d, "--kfold", "1", "--png_decode", "device",
-                                       "--train_transform", mode])
+                                       "--train_transform", mode, "--prefetch", str(prefetch)])
             log = open(os.path.join(work, "__checkpoint__", "run_B", "rendezvous_lcholect45-crossval_cholect1.log")).read()
         finally:
             os.chdir(cwd)
     secs = [float(ln.split("|")[-1].split()[0]) for ln in log.splitlines() if "Traning | lr:" in ln]
-    print(json.dumps({"step": "epoch", "train_transform": mode, "batch": B, "frames_per_epoch": n, "epoch_s": secs,
+    print(json.dumps({"step": "epoch", "train_transform": mode, "prefetch": prefetch, "batch": B, "frames_per_epoch": n, "epoch_s": secs,
                       "second_epoch_frames_per_s": round(n / secs[1], 1)}))
 
 
 if __name__ == "__main__":
     cmd, a = sys.argv[1], sys.argv[2:]
+    opts = {}
+    for flag in ("--prefetch", "--batches"):                   # (the two optional flags of `loader` / `epoch`)
+        if flag in a:
+            i = a.index(flag)
+            opts[flag] = a[i + 1]
+            del a[i:i + 2]
     if cmd == "make-data":
         make_data(a[0], *[int(v) for v in a[1:2]])
     elif cmd == "kernels":
         kernels(*[int(v) for v in a[:3]])
+    elif cmd == "loader" and "--prefetch" in opts:
+        loader_prefetch(a[0], [int(k) for k in opts["--prefetch"].split(",")], *[int(v) for v in a[1:4]],
+                        max_batches=int(opts["--batches"]) if "--batches" in opts else None)
     elif cmd == "loader":
         loader(a[0], *[int(v) for v in a[1:4]])
     elif cmd == "epoch":
-        epoch(a[0], a[1], *[int(v) for v in a[2:3]])
+        epoch(a[0], a[1], *[int(v) for v in a[2:3]], prefetch=int(opts.get("--prefetch", 0)))
     else:
         sys.exit(__doc__)
