@@ -62,6 +62,7 @@ class TakeSeg(C.Structure):
 
 
 TAKE_MAX_SEGS = 16      # MT4_TAKE_MAX_SEGS
+SELECT_SCRATCH_BYTES = 8448   # MT4_SELECT_SCRATCH_BYTES
 
 _vp, _i32 = C.c_void_p, C.c_int32
 _FLOAT3 = C.c_float * 3
@@ -166,6 +167,9 @@ SIGNATURES = {
     "mt4_sum_over_batch_f32": (C.c_int, [_vp, _vp, _i32, C.c_int64, _i32, _vp]),
     "mt4_dropout_mask_f32": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_float, _vp]),
     "mt4_axpby_f32": (C.c_int, [_vp, _vp, C.c_int64, C.c_float, C.c_float, _vp]),
+    "mt4_dropout_mul_add_f32": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _i32, C.c_float, _vp]),
+    "mt4_select_kth_key_u64": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _i32, _vp, _vp]),
+    "mt4_tenco_input_draw_f32": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),
 }
 
 

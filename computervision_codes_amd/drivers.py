@@ -375,6 +375,10 @@ def tenco_eval(argv=None) -> Dict[str, float]:
     p.add_argument("--output", default=False, type=bool)
     p.add_argument("--hier", default=False, type=bool)
     p.add_argument("--input_dim", type=int, default=512)
+    # (not in the reference) device: the step's random pieces are drawn by HIP kernels from (seed, step) and whole-video steps replay as
+    # hipGraphs; host: drawn with torch's generator and uploaded.  reference: `Temporal_tenco/dataloader.py:219-222` sub-clip sampling
+    p.add_argument("--mask_draw", choices=("host", "device"), default="host")
+    p.add_argument("--subclip", choices=("off", "reference"), default="off")
     add_schedule_flags(p)
     F, _ = p.parse_known_args(argv)
     if F.train:
@@ -425,8 +429,17 @@ def _tenco_scores(model, feats, vids, data_dir):
 def _tenco_train(F):
     """`Temporal_tenco/run.py -t` (:181-235, :341-348, :260-271): whole-video batch 1, SGD without momentum, LinearLR warm-up ->
     ExponentialLR per epoch, `_latest.pth` after every epoch.  With torchrun the shuffled videos of an epoch are dealt round-robin
-    to the ranks (one video per rank per step) and the flat gradient buffer is all-reduced over RCCL each step."""
+    to the ranks (one video per rank per step) and the flat gradient buffer is all-reduced over RCCL each step.
+
+    --mask_draw device: the draws of step i of an epoch are those of `tenco_draws.host_masks(F.seed + rank, epoch * steps_per_epoch + i, ...)`,
+    made on the device (`TencoTrainer.train_step(draws=...)`); whole-video steps replay as one hipGraph per length.
+    --subclip reference: a training item is `tenco_draws.tenco_clip` of the video (`dataloader.py:219-222`), drawn from a `random.Random(F.seed)`
+    of its own for EVERY video of the epoch in shuffled order on every rank (a rank's clips do not depend on the world size); features and label
+    rows are sliced on the device (row ranges: no copy) and a clipped step runs eagerly (its length is new almost every time).  Taken whole
+    instead: videos of <= 10 frames (`tenco_clip`) and, with --hier, clips too short for the pooled levels (`TencoTrainer.level_lengths`)."""
     import random
+
+    from .tenco_draws import tenco_clip
 
     from .tenco_train import TencoTrainer
     from .temporal_tenco import VideoNas
@@ -455,19 +468,41 @@ def _tenco_train(F):
         xs[v] = torch.from_numpy(feats[featfile.video_key(v)]).unsqueeze(0).cuda()
         zs[v] = tr.prepare_labels({k: torch.from_numpy(lab[n][:, 1:]) for k, n in (("", "ivt"), ("_i", "i"), ("_v", "v"), ("_t", "t"))})
     rng = random.Random(F.seed)
+    clip_rng = random.Random(F.seed)
+    device_draw, subclip = F.mask_draw == "device", F.subclip == "reference"
+    clipped = [0, 0]                                               # this rank's steps of the epoch: on a clip, all
     gen = torch.Generator().manual_seed(F.seed + rank)
     vmodel = VideoNas(F, F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100).eval() if rank == 0 else None
+
+    def clip(length):                                              # (start, frames) of a training item
+        s, n = tenco_clip(clip_rng, length)
+        if n != length and tr.hier:
+            try:
+                tr.level_lengths(n)
+            except ValueError:
+                return 0, length
+        return s, n
 
     def train_epoch(epoch):
         order = list(train_videos)
         rng.shuffle(order)                                         # same permutation on every rank
         mine, tot = deal(order, 1, world, rank), 0.0
-        for (v,) in mine:
-            x = xs[v]
-            masks = tr.draw_masks(x.shape[1], gen)                 # Dropout2d + per-layer Dropout are always on in train mode
+        clips = {v: clip(xs[v].shape[1]) for v in order} if subclip else {}
+        clipped[:] = [0, len(mine)]
+        for i, (v,) in enumerate(mine):
+            x, z, whole = xs[v], zs[v], True
+            if subclip:
+                s, n = clips[v]
+                whole = n == x.shape[1]
+                clipped[0] += not whole
+                x, z = x[:, s:s + n], z[s:s + n]
+            if device_draw:                                        # Dropout2d + per-layer Dropout are always on in train mode
+                tot += tr.train_step(x, z, draws=(F.seed + rank, epoch * len(mine) + i), input_mask=bool(F.mask), use_graph=whole)[0]
+                continue
+            masks = tr.draw_masks(x.shape[1], gen)
             if not F.mask:                                         # (`network.py:123-127,194-196`); --mask gates the 75 % input mask only
                 masks["input_mask"] = None                         # (`network.py:43-48`)
-            tot += tr.train_step(x, zs[v], masks=masks)[0]
+            tot += tr.train_step(x, z, masks=masks)[0]
         return tot, len(mine)
 
     def validate(state):                                           # (`run.py:416-452`): best `.pth` by the triplet mAP
@@ -478,7 +513,10 @@ def _tenco_train(F):
         ivt = float(vm["ivt"].compute_video_AP("ivt", ignore_null=_chlg(F))["mAP"]) if vm else 0.0
         return score, f"ivt: [{ivt:.5f}]"
 
-    run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", init, stem + ".pth", latest_every_epoch=True)
+    run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", init, stem + ".pth", latest_every_epoch=True,
+               epoch_note=(lambda: f" | clips {clipped[0]}/{clipped[1]}") if subclip else None)
+    if rank == 0 and device_draw:
+        _log(stem + ".log", f"mask_draw device | subclip {F.subclip} | cached graphs {len(tr._graphs)} | reserved bytes added {tr.graph_reserved_bytes}")
 
 
 # ------------------------------------------------------------------------------------------------ Spatial_transformer/test.py

@@ -179,6 +179,7 @@ class FlatTrainer:
         self._capturing = False
         self._cut = None
         self._graphs: Dict[tuple, object] = {}
+        self.graph_reserved_bytes = 0               # what the captures added to the allocator's reserved memory (their private pools)
 
     @property
     def P(self) -> torch.Tensor:
@@ -217,11 +218,16 @@ class FlatTrainer:
         """`fn(*inputs)` (a step's device part) replayed from the hipGraph captured for `key` on first use.  Data-parallel steps with bucket
         overlap are captured in segments cut at `_reduce_bucket`, a bucket's all-reduce issued between two replays (`graph.SegmentedGraph`);
         otherwise one graph, one flat all-reduce behind it."""
-        seg = bool(self.overlap and self.exchange and self._ddp_world() > 1)
+        seg = self._segmented()
         g = self._graphs.get((key, seg))
         if g is None:
+            before = torch.cuda.memory_reserved(self.dev)
             g = self._graphs[(key, seg)] = self._capture(fn, inputs, seg)
+            self.graph_reserved_bytes += max(0, torch.cuda.memory_reserved(self.dev) - before)
         return g(*inputs, on_cut=self._issue_bucket) if seg else g(*inputs)
+
+    def _segmented(self) -> bool:
+        return bool(self.overlap and self.exchange and self._ddp_world() > 1)
 
     def _capture(self, fn, inputs: List[torch.Tensor], seg: bool):
         from .graph import GraphedForward, SegmentedGraph

@@ -1230,6 +1230,58 @@ def dropout_mask(shape, seed: int, stream_id: int, p: float = 0.5, device="cuda"
     return out
 
 
+# ----------------------------------------------------------------------------------------- Temporal_tenco draws on the device
+def wrap_int64(v: int) -> int:
+    """v modulo 2^64 as the int64 with the same bits"""
+    return ((int(v) + (1 << 63)) % (1 << 64)) - (1 << 63)
+
+
+def draw_state(seed: int, step: int, device="cuda") -> torch.Tensor:
+    """the {seed, step} pair the three entry points below read from device memory (int64 [2]; values are taken modulo 2^64)"""
+    return torch.tensor([wrap_int64(seed), wrap_int64(step)], dtype=torch.int64).to(device)
+
+
+def _check_state(state: torch.Tensor):
+    _need_cuda(state)
+    assert state.dtype == torch.int64 and state.numel() == 2 and state.is_contiguous()
+
+
+def dropout_mul_add(a: torch.Tensor, state: torch.Tensor, slot: int, p: float = 0.5, c: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = a * m (+ c), m the nn.Dropout(p) keep mask of draw (`state`, slot) over a's elements in memory order (`mt4_dropout_mul_add_f32`)"""
+    _need_cuda(a, c, out)
+    _check_state(state)
+    assert a.is_contiguous() and a.dtype == torch.float32 and (c is None or (c.is_contiguous() and c.dtype == torch.float32 and c.numel() == a.numel()))
+    y = torch.empty_like(a) if out is None else out
+    check(lib.mt4_dropout_mul_add_f32(a.data_ptr(), c.data_ptr() if c is not None else None, y.data_ptr(), a.numel(), state.data_ptr(), slot, p,
+                                      _stream()), "mt4_dropout_mul_add_f32")
+    return y
+
+
+def select_kth_key(n: int, k: int, state: torch.Tensor, slot: int, thr: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the k-th smallest of the n keys of draw (`state`, slot) as an int64 [1] device tensor holding the uint64 bit pattern
+    (`mt4_select_kth_key_u64`); stays on the device"""
+    _check_state(state)
+    thr = torch.empty(1, dtype=torch.int64, device=state.device) if thr is None else thr
+    scratch = torch.empty(_lib.SELECT_SCRATCH_BYTES // 8, dtype=torch.int64, device=state.device)
+    check(lib.mt4_select_kth_key_u64(thr.data_ptr(), n, k, state.data_ptr(), slot, scratch.data_ptr(), _stream()), "mt4_select_kth_key_u64")
+    return thr
+
+
+def tenco_input_draw(x: torch.Tensor, state: torch.Tensor, slot_keys: int, thr: Optional[torch.Tensor], slot_chan: int,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [..., T, D] (contiguous) times the exact-count input mask (`thr` from `select_kth_key`, None: no mask) times Dropout2d per input
+    channel (`mt4_tenco_input_draw_f32`)"""
+    _need_cuda(x, thr, out)
+    _check_state(state)
+    assert x.is_contiguous() and x.dtype == torch.float32 and x.dim() >= 2
+    d = x.shape[-1]
+    y = torch.empty_like(x) if out is None else out
+    check(lib.mt4_tenco_input_draw_f32(x.data_ptr(), y.data_ptr(), x.numel() // d, d, state.data_ptr(), slot_keys,
+                                       thr.data_ptr() if thr is not None else None, slot_chan, _stream()), "mt4_tenco_input_draw_f32")
+    return y
+
+
 # ----------------------------------------------------------------------------------------- Swin / Q2L training pieces (fp32)
 def gather_rows(x: torch.Tensor, row_map: torch.Tensor, *, l_out: int, l_in: int, group: int = 1, m_out: Optional[int] = None) -> torch.Tensor:
     """y[m][g*C:(g+1)*C] = x[(m // l_out) * l_in + map[(m % l_out) * group + g]]  (`mt4_gather_rows_f32`)"""

@@ -9,7 +9,9 @@ backward and SGD, as `Temporal_tenco/run.py:181-235` does with autograd -- here 
   buffer (packed layouts), so DDP is ONE all-reduce of the flat gradient buffer over RCCL (videos shard over ranks).
 
 Randomness (75 % input mask, Dropout2d, per-layer Dropout; `network.py:43-48,123-127,194-196`) is drawn on the host side
-of this class (`draw_masks`) or passed in explicitly, so that parity tests feed the oracle the same draw.
+of this class (`draw_masks`) or passed in explicitly, so that parity tests feed the oracle the same draw -- or, with
+`train_step(draws=(seed, step))`, drawn on the device from a counter generator (`tenco_draws`, csrc/tenco_draw_kernels.hip): nothing
+is drawn, transposed or uploaded by the host, and the step replays as a hipGraph whose {seed, step} input changes the draw.
 Parameters that the FPN configuration never reaches (PG.conv_out, Rs.*.conv_1x1, Rs.*.conv_out, fpn.latlayer2/3) get no
 gradient and, like torch.optim.SGD with `grad is None`, are left untouched.
 """
@@ -19,7 +21,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import ops
+from . import ops, tenco_draws
 from .flatparams import FlatParams, FlatTrainer, Lin
 from .flatparams import allreduce_sum_flat  # noqa: F401  (its import path before it moved to flatparams)
 from .shapes import tenco_shapes
@@ -32,18 +34,22 @@ NHP = 132  # padded to a multiple of 4 (16-byte rows for the gradient GEMMs)
 
 class TencoTrainer(FlatTrainer):
     def __init__(self, num_layers_PG=11, num_layers_R=10, num_R=3, num_f_maps=512, dim=512, num_classes=100, lr=0.1, weight_decay=1e-5,
-                 device: str = "cuda", process_group=None, overlap: bool = True, hier: bool = False):
+                 device: str = "cuda", process_group=None, overlap: bool = True, hier: bool = False, max_graphs: int = 64):
         # overlap: a stage's gradients are all-reduced as soon as its backward has written them (DDP, `FlatTrainer`)
         super().__init__(lr, weight_decay, device, process_group, overlap)
         # hier = `args.hier` (`network.py:147,154-155`): AvgPool1d(7, 3) behind every refinement stage, so level l has its own length T_l, the FPN
         # resamples (`:96`) and `fusion` scores every level against the labels resized to it (`run.py:159-179,196-212`)
         self.hier = bool(hier)
+        # max_graphs: how many captured steps (one per length and mode) are kept; a step whose graph would be one more runs eagerly
+        self.max_graphs = int(max_graphs)
         assert num_classes == 100 and num_R == 3, "the FPN training recipe (Scripts/train_fold1.sh:28) has PG + 3 refinement stages"
         self.LP, self.LR, self.R, self.C, self.D = num_layers_PG, num_layers_R, num_R, num_f_maps, dim
         self._table = tenco_shapes(num_layers_PG, num_layers_R, num_R, num_f_maps, dim, 100, fpn=True)
         self._extra: Dict[str, torch.Tensor] = {}   # parameters outside the trained graph, kept verbatim
         self._scales: Dict[int, torch.Tensor] = {}
         self._label_idx: Dict[tuple, torch.Tensor] = {}
+        self._slots = tenco_draws.stage_slots(self._stages())
+        self._state_host: Optional[torch.Tensor] = None     # pinned {seed, step}: every step ends in a device->host copy, so one buffer serves
 
     # ------------------------------------------------------------------ parameters
     def _stages(self):
@@ -128,19 +134,28 @@ class TencoTrainer(FlatTrainer):
 
     @ops.with_latency_tiles
     def train_step(self, x: torch.Tensor, labels: Dict[str, torch.Tensor], masks: Optional[dict] = None, apply_update: bool = True,
-                   use_graph: bool = False):
+                   use_graph: bool = False, draws: Optional[tuple] = None, input_mask: bool = True):
         """x [1,T,D] fp32 on the GPU; labels {'': [T,100], '_i': [T,6], '_v': [T,10], '_t': [T,15]} multi-hot.
         Returns (loss, {head: loss term}).  use_graph: replay a hipGraph of the whole forward+backward captured for this T
-        (no masks: the draw changes every step) -- ~900 launches become one."""
+        (not with explicit masks: those change every step) -- ~900 launches become one.
+        draws = (seed, step): the random pieces of `tenco_draws.host_masks(seed, step, ...)` drawn on the device instead of passed in `masks`
+        (one or the other); input_mask False leaves the 75 % mask out, as the driver does without --mask.  With draws a step does replay:
+        {seed, step} is an input of the graph next to x and the labels.  At most `max_graphs` graphs are kept; beyond, a step runs eagerly."""
         assert x.dim() == 3 and x.shape[0] == 1 and x.shape[2] == self.D
+        assert draws is None or not masks, "draws and masks are two ways to say the same thing: pass one"
         T, dev = x.shape[1], self.dev
         z = labels if torch.is_tensor(labels) else self.prepare_labels(labels)
         assert z.is_cuda and tuple(z.shape) == (T, NH) and z.dtype == torch.float32
         self.bucket_order = []            # gradient buckets in the order their all-reduce was issued this step (DDP)
-        if use_graph and not masks:
-            col_loss = self._graph_step(T, lambda xx, zz: self._fwd_bwd(xx, zz, None), [x, z])
+        state = self._draw_state(*draws) if draws is not None else None
+        key = T if draws is None else ("draws", T, bool(input_mask))
+        if use_graph and not masks and ((key, self._segmented()) in self._graphs or len(self._graphs) < self.max_graphs):
+            if draws is None:
+                col_loss = self._graph_step(key, lambda xx, zz: self._fwd_bwd(xx, zz, None), [x, z])
+            else:
+                col_loss = self._graph_step(key, lambda xx, zz, st: self._fwd_bwd(xx, zz, None, st, input_mask), [x, z, state])
         else:
-            col_loss = self._fwd_bwd(x, z, masks)
+            col_loss = self._fwd_bwd(x, z, masks, state, input_mask)
         cl = col_loss.cpu()                                  # [levels, 131]: BCE sums per level and column
         lens = self.level_lengths(T)
         terms, o = {}, 0
@@ -159,12 +174,28 @@ class TencoTrainer(FlatTrainer):
         z = torch.cat([labels[s].to(torch.float32) for s, _, _ in HEADS], 1).contiguous()
         return z.pin_memory().to(self.dev, non_blocking=True) if not z.is_cuda else z
 
-    def _fwd_bwd(self, x: torch.Tensor, z: torch.Tensor, masks: Optional[dict]) -> torch.Tensor:
-        """device part of a step (enqueue only): forward, loss, backward into self.G.  Returns the per-column loss sums."""
+    def _draw_state(self, seed: int, step: int) -> torch.Tensor:
+        """{seed, step} on the device (int64 [2], taken modulo 2^64) through one pinned buffer"""
+        if self._state_host is None:
+            self._state_host = torch.empty(2, dtype=torch.int64).pin_memory()
+        self._state_host[0], self._state_host[1] = ops.wrap_int64(seed), ops.wrap_int64(step)
+        return self._state_host.to(self.dev, non_blocking=True)
+
+    def _fwd_bwd(self, x: torch.Tensor, z: torch.Tensor, masks: Optional[dict], state: Optional[torch.Tensor] = None,
+                 input_mask: bool = True) -> torch.Tensor:
+        """device part of a step (enqueue only): forward, loss, backward into self.G.  Returns the per-column loss sums.
+        state: {seed, step} on the device -- the draws are made by the kernels of csrc/tenco_draw_kernels.hip (the layer masks regenerated in
+        the backward instead of stored) and `masks` is not looked at."""
         T, C, dev = x.shape[1], self.C, self.dev
         cv = self.convs
         to_rows = lambda m: m[0].transpose(0, 1).contiguous().to(dev)        # [1,C,T] -> [T,C]
         h0 = x.contiguous().view(1, 1, T, self.D)
+        sl = self._slots
+        if state is not None:
+            masks = None
+            n = T * self.D
+            thr = ops.select_kth_key(n, (3 * n) // 4, state, sl["input_keys"]) if input_mask else None     # `int(n * 0.75)` ones (`network.py:45`)
+            h0 = ops.tenco_input_draw(h0, state, sl["input_keys"], thr, sl["channel"])
         if masks and masks.get("input_mask") is not None:
             h0 = ops.mul_add(h0, to_rows(masks["input_mask"]).view_as(h0))
         if masks and masks.get("channel_mask") is not None:
@@ -182,7 +213,9 @@ class TencoTrainer(FlatTrainer):
                 p = f"{prefix}.layers.{i}"
                 d = 2 ** i
                 u = self._conv(f, cv[p + ".conv_dilated"], dil=d, act="relu")
-                if p in lm:
+                if state is not None:
+                    fn = ops.dropout_mul_add(self._conv(u, cv[p + ".conv_1x1"]), state, sl[p], 0.5, c=f)
+                elif p in lm:
                     o = self._conv(u, cv[p + ".conv_1x1"])
                     fn = ops.mul_add(o, lm[p], f)
                 else:
@@ -242,7 +275,7 @@ class TencoTrainer(FlatTrainer):
                 idx -= 1
                 p, d, zin, u, _ = saved[idx]
                 w1, wd = cv[p + ".conv_1x1"], cv[p + ".conv_dilated"]
-                do = ops.mul_add(df, lm[p]) if p in lm else df
+                do = ops.dropout_mul_add(df, state, sl[p], 0.5) if state is not None else ops.mul_add(df, lm[p]) if p in lm else df
                 ops.wgrad_conv1d(do.view(ts, C), u.view(ts, C), w1.gw, batch=1, t=ts, taps=1, dil=1, pad=0, accumulate=True, bias_grad=w1.gb)
                 du = self._conv(do, w1, transposed=True, residual=u, act="relu_gate")
                 ops.wgrad_conv1d(du.view(ts, C), zin.view(ts, C), wd.gw, batch=1, t=ts, taps=3, dil=d, pad=d, accumulate=True, bias_grad=wd.gb)

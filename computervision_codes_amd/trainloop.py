@@ -72,12 +72,13 @@ def save_atomic(state: Dict[str, torch.Tensor], path: str):
 
 
 def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]], validate: Callable[[dict], Tuple[float, str]],
-               logfile: str, latest: str, best: str, latest_every_epoch: bool = False, score_key: str = "val_mAP") -> Dict[str, float]:
+               logfile: str, latest: str, best: str, latest_every_epoch: bool = False, score_key: str = "val_mAP",
+               epoch_note: Callable[[], str] = None) -> Dict[str, float]:
     """--epochs epochs: `tr.lr` from the schedule, `train_epoch(epoch) -> (loss sum, steps)` runs the epoch's steps (it owns the data and
     every random draw), then rank 0 logs and runs `weight_mgt`, and all ranks meet at a barrier.  `weight_mgt` (`Spatial_cnn/run.py:258-269`,
     `Temporal_tenco/run.py:270-282`): every --val_interval epochs `validate(state) -> (score, "<head>: [<mAP>]")`, the best `.pth` by that
     score; `_latest` at validation epochs, or after every epoch with `latest_every_epoch`.  Returns the last epoch's loss and lr (+ its
-    validation score under `score_key`)."""
+    validation score under `score_key`).  `epoch_note()`, if given, is appended to the epoch's `Traning |` line."""
     val_interval = max(1, F.epochs - 1 if F.val_interval == -1 else F.val_interval)
     top, last = 0.0, {}
     for epoch in range(F.epochs):
@@ -86,7 +87,7 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
         tot, steps = train_epoch(epoch)
         last = {"loss": tot / steps, "lr": tr.lr}
         if rank == 0:
-            _log(logfile, f"Traning | lr: {tr.lr:.6f} | epoch {epoch} | loss {tot / steps:.4f} | {time.time() - t0:.2f} secs")
+            _log(logfile, f"Traning | lr: {tr.lr:.6f} | epoch {epoch} | loss {tot / steps:.4f} | {time.time() - t0:.2f} secs" + (epoch_note() if epoch_note else ""))
             val = epoch % val_interval == 0
             if val or latest_every_epoch:
                 state = tr.state_dict()

@@ -589,6 +589,33 @@ int mt4_dropout_mask_f32(float* out, int64_t n, int64_t seed, int64_t stream_id,
 int mt4_axpby_f32(const float* x, float* y, int64_t n, float a, float b, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The random pieces of a Temporal_tenco training step drawn on the device (csrc/tenco_draw_kernels.hip).  `state` points to {seed, step} in
+ * DEVICE memory and `slot` (0 <= slot < 4096) names the draw inside the step: element i uses
+ *     key_i = splitmix64(base + i),   base = splitmix64(seed * 0x100000001B3 + step * 4096 + slot)
+ * -- the generator of mt4_dropout_mask_f32 / synth.uniform01(seed, step * 4096 + slot, n).  Neither seed nor step is a kernel argument, so a
+ * captured hipGraph draws anew on every replay whose {seed, step} input was rewritten.  Enqueue only; nothing is read back.
+ */
+/* nn.Dropout(p) fused into the residual add of a DilatedResidualLayer (Temporal_tenco/network.py:194-196: `x + dropout(conv_1x1(...))`):
+ * y[i] = a[i] * m_i (+ c[i]), m_i = (key_i >> 11) * 2^-53 >= p ? 1/(1-p) : 0 (the comparison of mt4_dropout_mask_f32; one fused multiply-add).
+ * c may be NULL: the backward `do = df * m`, the mask regenerated instead of stored.  i runs over the row-major [T][C] buffer.
+ * n % 4 == 0, 16-byte aligned pointers. */
+int mt4_dropout_mul_add_f32(const float* a, const float* c, float* y, int64_t n, const int64_t* state, int32_t slot, float p, void* stream);
+/* *thr = the k-th smallest of key_0 .. key_{n-1} (1 <= k <= n): the threshold under which `key_i <= *thr` holds for exactly k elements --
+ * the count `int(n * 0.75)` of ones that Temporal_tenco/network.py:44-47 gets from a permutation.  The keys are distinct by construction
+ * (the splitmix64 finaliser is a bijection of the 64-bit integers and the base + i are distinct), so there is no tie and no tie rule.
+ * k == 0 writes 0, which selects nothing unless the key 0 itself is among the n (one chance in 2^64 / n).  Radix select over the 8 key
+ * bytes: per-pass histograms in LDS, the running prefix and the remaining k in `scratch` (MT4_SELECT_SCRATCH_BYTES, 8-byte aligned, cleared by
+ * a kernel of this call); the keys are regenerated in every pass.  n < 2^31. */
+#define MT4_SELECT_SCRATCH_BYTES 8448
+int mt4_select_kth_key_u64(uint64_t* thr, int64_t n, int64_t k, const int64_t* state, int32_t slot, void* scratch, void* stream);
+/* The input side of a training forward (Temporal_tenco/network.py:43-48 `x * mask` under --mask, :123-127 Dropout2d on [1, D, T, 1]):
+ * y[t][d] = x[t][d] * (key(t*D + d) <= *thr ? 1 : 0) * (u_d >= 0.5 ? 2 : 0), keys of slot_keys, u_d = (key_d >> 11) * 2^-53 of slot_chan.
+ * thr (device, from mt4_select_kth_key_u64 on the same state and slot_keys) NULL: no input mask.  Both factors are multiplications, as
+ * in the two mt4_mul_add_f32 calls they replace.  D % 4 == 0, T * D < 2^31, 16-byte aligned x / y. */
+int mt4_tenco_input_draw_f32(const float* x, float* y, int32_t T, int32_t D, const int64_t* state, int32_t slot_keys, const uint64_t* thr,
+                             int32_t slot_chan, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Backward pieces of the Swin + Query2Label teacher (what torch autograd derives inside Spatial_transformer/run.py:150-229 for
  * Spatial_transformer/models/swin_transformer.py and models/transformer.py).  float32.  LayerNorm / GELU / softmax / batched-GEMM
  * backward are the entry points above.
