@@ -27,8 +27,6 @@
 // the result is bit-identical to conv1 -> conv2 -> conv3 through mt4_conv_nhwc.
 #include "mt4_common.h"
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int TH = 8, TW = 14, NHALO = 160, NPX = 128;   // NPX: the 8 x 16 grid of phases 2 and 3 (14 of 16 columns are stored)
@@ -417,11 +415,8 @@ int launch(const BneckK& a, hipStream_t stream) {
     constexpr int LDS = NXS * XS_BYTES + T2_BYTES + (DS ? YS_BYTES : T1_BYTES);
     static_assert(LDS <= 80 * 1024, "two workgroups per CU");
     static_assert(!NEXT || LDS >= 2 * YS_BYTES, "both output passes stay in LDS");
-    auto fn = bottleneck64_fused_kernel<CIN, DS, NEXT>;
-    MT4_RAISE_LDS(fn);
     const long long nblk = (long long)a.B * a.tiles_h * a.tiles_w;
-    hipLaunchKernelGGL(fn, dim3((unsigned)nblk), dim3(256), LDS, stream, a);
-    return mt4_check_launch();
+    return mt4_launch<bottleneck64_fused_kernel<CIN, DS, NEXT>>(dim3((unsigned)nblk), dim3(256), LDS, stream, a);
 }
 
 }  // namespace

@@ -22,8 +22,6 @@
 // residuals are added to the fp32 accumulator before the activation.
 #include "mt4_common.h"
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 namespace {
 
 struct ChainK {
@@ -305,24 +303,16 @@ extern "C" int mt4_chain_gemm_bf16(const void* x, int64_t x_ld, int64_t M, int32
     // Bottleneck form: r1 + y1, ReLU after both convs, no r2; MLP form: GELU between, shortcut r2, no activation behind
     if (conv != (y1 != nullptr) || act1 != (conv ? 1 : 2) || act2 != (conv ? 1 : 0) || conv == (r2 != nullptr)) return MT4_EUNSUPPORTED;
     if (K1 != 128 && K1 != 256) return MT4_EUNSUPPORTED;
-#define MT4_CHAIN_LAUNCH(NT2_, NKS1_, CONV_, NCH_)                                                 \
-    do {                                                                                       \
-        auto fn = chain_gemm_kernel<NT2_, NKS1_, CONV_, NCH_>;                                 \
-        MT4_RAISE_LDS(fn);                                                                     \
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, (hipStream_t)stream, k);            \
-    } while (0)
     const int nch = N1 / CH;
+    hipStream_t s = (hipStream_t)stream;
     if (nch != 4 && nch != 8) return MT4_EUNSUPPORTED;
     if (conv) {
-        if (N2 == 256 && K1 == 256 && nch == 8) MT4_CHAIN_LAUNCH(2, 4, true, 8);          // ResNet-50 layer3: 256 -> 1024 -> 256
-        else if (N2 == 256 && K1 == 128 && nch == 4) MT4_CHAIN_LAUNCH(2, 2, true, 4);     // layer2.3 -> layer3.0: 128 -> 512 -> 256
-        else if (N2 == 128 && K1 == 128 && nch == 4) MT4_CHAIN_LAUNCH(1, 2, true, 4);     // layer2: 128 -> 512 -> 128
-        else return MT4_EUNSUPPORTED;
+        if (N2 == 256 && K1 == 256 && nch == 8) return mt4_launch<chain_gemm_kernel<2, 4, true, 8>>(dim3(grid), dim3(512), lds, s, k);  // ResNet-50 layer3: 256 -> 1024 -> 256
+        if (N2 == 256 && K1 == 128 && nch == 4) return mt4_launch<chain_gemm_kernel<2, 2, true, 4>>(dim3(grid), dim3(512), lds, s, k);  // layer2.3 -> layer3.0: 128 -> 512 -> 256
+        if (N2 == 128 && K1 == 128 && nch == 4) return mt4_launch<chain_gemm_kernel<1, 2, true, 4>>(dim3(grid), dim3(512), lds, s, k);  // layer2: 128 -> 512 -> 128
     } else {
-        if (N2 == 256 && K1 == 256 && nch == 8) MT4_CHAIN_LAUNCH(2, 4, false, 8);         // Swin-B stage 1: C = 256
-        else if (N2 == 128 && K1 == 128 && nch == 4) MT4_CHAIN_LAUNCH(1, 2, false, 4);    // Swin-B stage 0: C = 128
-        else return MT4_EUNSUPPORTED;
+        if (N2 == 256 && K1 == 256 && nch == 8) return mt4_launch<chain_gemm_kernel<2, 4, false, 8>>(dim3(grid), dim3(512), lds, s, k);  // Swin-B stage 1: C = 256
+        if (N2 == 128 && K1 == 128 && nch == 4) return mt4_launch<chain_gemm_kernel<1, 2, false, 4>>(dim3(grid), dim3(512), lds, s, k);  // Swin-B stage 0: C = 128
     }
-#undef MT4_CHAIN_LAUNCH
-    return mt4_check_launch();
+    return MT4_EUNSUPPORTED;
 }

@@ -15,61 +15,9 @@
 // Tiles are dealt to XCDs in contiguous ranges (n-tile fastest), so all column tiles of a pixel tile hit
 // one XCD's L2 and activations are fetched from HBM once.
 #include "mt4_common.h"
+#include <algorithm>
 #include <cstdlib>
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
-// raw buffer descriptor (stride 0, num_records = bytes, gfx9 data-format word) from wave-uniform values
-__device__ __forceinline__ v4u make_srd(const void* p, unsigned bytes) {
-    const unsigned long long u = (unsigned long long)p;
-    v4u r;
-    r.x = __builtin_amdgcn_readfirstlane((unsigned)u);
-    r.y = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32) & 0xffffu);
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000u;
-    return r;
-}
-
-// N LDS-DMA pieces in ONE asm statement (one M0 save/restore): piece i goes to LDS [lds_addr + i*STRIDE + lane*16) from
-// buffer offset voff[i] (per lane, range-checked: out-of-range lanes write zeros) + soff (wave-uniform, NOT range-checked).
-// STRIDE = bytes one staging pass of the whole workgroup covers (waves * 8 rows * 128 B).
-template <int N, int STRIDE>
-__device__ __forceinline__ void lds_dma16_group(v4u srd, const unsigned (&voff)[N], unsigned soff, unsigned lds_addr) {
-    unsigned keep;
-    if constexpr (N == 1) {
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff[0]), "s"(srd), "s"(soff), "s"(lds_addr) : "memory");
-    } else if constexpr (N == 2) {
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\t"
-                     "s_add_u32 m0, m0, %6\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff[0]), "v"(voff[1]), "s"(srd), "s"(soff), "s"(lds_addr), "n"(STRIDE) : "memory", "scc");
-    } else {
-        static_assert(N == 4, "1, 2 or 4 pieces");
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %7\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %5, %6 offen lds\n\t"
-                     "s_add_u32 m0, m0, %8\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %5, %6 offen lds\n\t"
-                     "s_add_u32 m0, m0, %8\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %5, %6 offen lds\n\t"
-                     "s_add_u32 m0, m0, %8\n\ts_nop 0\n\tbuffer_load_dwordx4 %4, %5, %6 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(srd), "s"(soff), "s"(lds_addr),
-                       "n"(STRIDE)
-                     : "memory", "scc");
-    }
-}
-
-// one LDS-DMA piece: 64 lanes x 16 B from buffer offset `voff` (per lane) to LDS [lds_addr + lane*16); out-of-range
-// lanes write zeros.  M0 (the DMA's LDS base) is compiler-reserved: saved, set and restored inside the statement.
-__device__ __forceinline__ void lds_dma16(v4u srd, unsigned voff, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(lds_addr)
-        : "memory");
-}
+#include <type_traits>
 
 struct ConvK {
     const char* x;
@@ -1414,147 +1362,114 @@ __global__ __launch_bounds__(512, 4) void stem_pool_kernel(const StemPoolK a) {
 // ------------------------------------------------------------------------------------------------ host side
 namespace {
 
-struct TileCfg {
-    int bm, bn;
-};
-// tile ids are 1-based in the C-ABI
-// ids 1-6: two operand stages; 7-12: deeper rings (3 for the 128-wide tiles, 4 for the small ones)
-// ids 13-16: 8-wave workgroups (one per CU): 256x128 with 2 / 3 stages, 256x256, 128x256 with 3 stages
-// id 20: 256x64 for the 64-channel layers (8 waves)
-// ids 17-19: 16-wave workgroups (four waves per SIMD, 64x64 / 64x32 wave tiles): 256x256, 256x128 with 2 / 3 stages
-// ids 21-32: the 3x3 patch kernel (bf16, stride 1, pad 1, Cin % 64 == 0), BM x BN / waves / weight stages:
-//   21: 256x64/8/4   22: 256x128/16/3   23: 256x256/16/2   24: 256x64/8/2   25: 256x128/16/4   26: 256x128/16/2
-//   27: 256x64/8/all 9 taps resident   28: 512x64/16/resident   29: 128x64/4/2   30: 128x128/4/2   31: 256x64/4/2   32: 256x128/8/2
-//   (auto: 24, 30, 23 by Cout; the others are the tuning record: deeper rings and the barrier-free resident variants are slower)
-constexpr TileCfg kTiles[] = {
-    {128, 128}, {128, 64}, {64, 64}, {64, 128}, {32, 64}, {32, 32},                                  // 1-6
-    {128, 128}, {64, 128}, {64, 64}, {32, 64}, {32, 32}, {128, 64},                                  // 7-12
-    {256, 128}, {256, 128}, {256, 256}, {128, 256}, {256, 256}, {256, 128}, {256, 128}, {256, 64},   // 13-20
-    {256, 64}, {256, 128}, {256, 256}, {256, 64}, {256, 128}, {256, 128},                            // 21-26: conv3x3_patch_kernel
-    {256, 64}, {512, 64}, {128, 64}, {128, 128}, {256, 64}, {256, 128},                              // 27-32: conv3x3_patch_kernel
-    {256, 64}, {256, 64},                                                                            // 33 / 34: stem patch kernel, persistent form
-    {32, 32}, {32, 64}, {32, 32}, {32, 32},                                                          // 35-38: generic kernel, K-split groups (4, 4, 8, 4 with 3 stages)
-    {64, 64}, {64, 64}, {64, 64}, {64, 128}};                                                        // 39-42: K-split groups on the 64-row tiles (2, 4, 2 with 3 stages, 2): whole-video TCN layers
-constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+// Every tile id of the C-ABI (1-based), one entry each; kTiles and the dispatch switches below are generated from this list.
+//   G(id, BM, BN, waves M, waves N, operand stages, K-split groups)   igemm_conv_kernel (the register-staged path always runs 2 stages)
+//   P(id, BM, BN, waves M, waves N, weight stages)   conv3x3_patch_kernel (bf16, 3x3, stride 1, pad 1, Cin % 64 == 0)
+//   S(id, BM, BN, waves M, waves N)                  stem_patch_kernel (the space-to-depth stem)
+//   R(id, BM, BN)                                    retired, the tuning record: MT4_EUNSUPPORTED
+#define MT4_CONV_TILES(G, P, S, R)                                                                                                                                                                          \
+    G(1, 128, 128, 2, 2, 2, 1) G(2, 128, 64, 2, 2, 2, 1) G(3, 64, 64, 2, 2, 2, 1)     /* 1-6: two operand stages */                                                                                         \
+    G(4, 64, 128, 2, 2, 2, 1) G(5, 32, 64, 1, 4, 2, 1) G(6, 32, 32, 2, 2, 2, 1)                                                                                                                             \
+    G(7, 128, 128, 2, 2, 3, 1) G(8, 64, 128, 2, 2, 3, 1) G(9, 64, 64, 2, 2, 4, 1)     /* 7-12: deeper rings (3 stages for the 128-wide tiles, 4 for the small ones) */                                      \
+    G(10, 32, 64, 1, 4, 4, 1) G(11, 32, 32, 2, 2, 4, 1) G(12, 128, 64, 2, 2, 3, 1)                                                                                                                          \
+    G(13, 256, 128, 4, 2, 2, 1) G(14, 256, 128, 4, 2, 3, 1)                           /* 13-16, 20: 8-wave workgroups (one per CU) */                                                                       \
+    G(15, 256, 256, 2, 4, 2, 1) G(16, 128, 256, 2, 4, 3, 1)                                                                                                                                                 \
+    G(17, 256, 256, 4, 4, 2, 1) G(18, 256, 128, 4, 4, 2, 1) G(19, 256, 128, 4, 4, 3, 1) /* 17-19: 16-wave workgroups (four waves per SIMD, 64x64 / 64x32 wave tiles) */                                     \
+    G(20, 256, 64, 4, 2, 2, 1)                                                        /* the 64-channel layers */                                                                                           \
+    R(21, 256, 64) R(22, 256, 128)                                                    /* 21-32: the patch kernel.  21: 8 waves, 4 weight stages; 22: 16 waves, 3 stages.  Auto takes 24, 30 / 32, 23 */     \
+    P(23, 256, 256, 4, 4, 2) P(24, 256, 64, 4, 2, 2)                                  /* by Cout; the retired ids are deeper weight rings and barrier-free weights-resident forms, every one */             \
+    R(25, 256, 128) P(26, 256, 128, 4, 4, 2)                                          /* measured slower (profiles/r01_tile_tuning_patch3x3.txt).  25: 16 waves, 4 stages */                                \
+    R(27, 256, 64) R(28, 512, 64)                                                     /* 27: 8 waves, all 9 taps resident; 28: 16 waves, resident */                                                        \
+    R(29, 128, 64) P(30, 128, 128, 2, 2, 2)                                           /* 29: 4 waves, 2 stages */                                                                                           \
+    R(31, 256, 64) P(32, 256, 128, 4, 2, 2)                                           /* 31: 4 waves, 2 stages */                                                                                           \
+    S(33, 256, 64, 4, 2) R(34, 256, 64)                                               /* 34: the persistent form of the stem patch kernel, measured no faster in the bench */                               \
+    G(35, 32, 32, 2, 2, 2, 4) G(36, 32, 64, 1, 4, 2, 4)                               /* 35-38: K-split groups on the 32-row tiles; 35 / 36: 4 groups (16 waves) */                                         \
+    G(37, 32, 32, 1, 2, 2, 8) G(38, 32, 32, 2, 2, 3, 4)                               /* 37: 8 groups of 2 waves; 38: 4 groups, 3 stages each */                                                            \
+    G(39, 64, 64, 2, 2, 2, 2) G(40, 64, 64, 2, 2, 2, 4)                               /* 39-42: K-split groups on the 64-row tiles (whole-video TCN layers): 2 / 4 groups of 4 waves */                     \
+    G(41, 64, 64, 2, 2, 3, 2) G(42, 64, 128, 2, 2, 2, 2)                              /* 41: 2 groups, 3 stages each; 42: 2 groups of 4 waves */
+#define MT4_SKIP(...)
 
-template <typename T, int BM, int BN, int WM_, int WN_, int STAGES, bool OUT_F32, int KS = 1>
-int launch_tile(const ConvK& k, bool fast, hipStream_t s) {
-    const int m_tiles = cdiv(k.M, BM);
+enum TileKind { GENERIC, PATCH, STEM, RETIRED };
+struct TileCfg {
+    int id, kind, bm, bn, waves, stages;
+};
+#define G(id, bm, bn, wm, wn, st, ks) {id, GENERIC, bm, bn, wm * wn * ks, st},
+#define P(id, bm, bn, wm, wn, ws) {id, PATCH, bm, bn, wm * wn, ws},
+#define S(id, bm, bn, wm, wn) {id, STEM, bm, bn, wm * wn, 0},
+#define R(id, bm, bn) {id, RETIRED, bm, bn, 0, 0},
+constexpr TileCfg kTiles[] = {MT4_CONV_TILES(G, P, S, R)};
+#undef G
+#undef P
+#undef S
+#undef R
+constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+constexpr bool tiles_in_order() {
+    for (int i = 0; i < kNumTiles; ++i)
+        if (kTiles[i].id != i + 1) return false;
+    return true;
+}
+static_assert(tiles_in_order(), "kTiles[id - 1] describes tile id");
+constexpr int kStemBM = kTiles[33 - 1].bm;
+
+// the launch's copy of the arguments for a grid of BM x BN tiles; `out_cols` = channels of the tensor the epilogue stores.
+// Outputs that fit the 256 MB Infinity Cache stay cacheable for the next layer (+0.8 % over always-nt; MT4_NT_MIN_MB overrides)
+ConvK with_grid(const ConvK& k, int out_cols, int BM, int BN) {
     ConvK kk = k;
+    kk.n_tiles = cdiv(k.Cout, BN);
+    kk.total_tiles = cdiv(k.M, BM) * kk.n_tiles;
+    kk.nt_epi = (long long)k.M * out_cols * 2 < (long long)MT4_NT_MIN_MB * 1000000LL ? 0 : 1;
+    return kk;
+}
+
+template <typename T, int BM, int BN, int WM_, int WN_, int STAGES, bool OUT_F32, int KS>
+int launch_tile(const ConvK& k, bool fast, hipStream_t s) {
     constexpr bool CAN_STATS = KS == 1 && WM_ * WN_ * BN * 16 <= (BM + BN) * 128;   // the staged epilogue's LDS holds the waves' partial rows
     if (k.stat_sums && (!CAN_STATS || (k.Cout % (OUT_F32 ? 4 : 8)) != 0)) return MT4_EUNSUPPORTED;
-    kk.n_tiles = cdiv(k.Cout, BN);
-    kk.total_tiles = m_tiles * kk.n_tiles;
-    kk.nt_epi = 1;
-    {   // outputs that fit the 256 MB Infinity Cache stay cacheable for the next layer (+0.8 % over always-nt; MT4_NT_MIN_MB overrides)
-        const long long min_mb = MT4_NT_MIN_MB;
-        if ((long long)k.M * k.Cout * 2 < min_mb * 1000000LL) kk.nt_epi = 0;
-    }
-    // LDS: two operand stages, or ONE when the whole K fits a single step (then only the epilogue staging may need
-    // more than a stage): the short-K layers are memory-bound and want as many workgroups per CU as possible
+    if (KS > 1 && !fast) return MT4_EUNSUPPORTED;   // K-split groups: LDS-DMA path only
+    const ConvK kk = with_grid(k, k.Cout, BM, BN);
+    // LDS: a ring of operand stages per K-split group (two stages on the register-staged path), or ONE stage when the whole K fits a single
+    // step (then only the epilogue staging may need more than a stage): the short-K layers are memory-bound and want as many workgroups
+    // per CU as possible
     constexpr int stage = (BM + BN) * 128;
-    constexpr int os = OUT_F32 ? 4 : 2;
     constexpr int rowb = BN * 4 + 16;
     constexpr int passes = (BM * rowb > 4 * stage) ? 4 : (BM * rowb > 2 * stage) ? 2 : 1;
     constexpr int epi = BM / passes * rowb;
-    constexpr int threads = WM_ * WN_ * 64;
-    (void)os;
-    if constexpr (KS > 1) {   // K-split groups (LDS-DMA path only): every group has its own ring of stages
-        if (!fast) return MT4_EUNSUPPORTED;
-        constexpr int lds_ks = KS * STAGES * stage > epi ? KS * STAGES * stage : epi;
-        auto fn = igemm_conv_kernel<T, BM, BN, WM_, WN_, STAGES, true, OUT_F32, KS>;
-        if (lds_ks > 65536) {
-            MT4_RAISE_LDS(fn);
-        }
-        hipLaunchKernelGGL(fn, dim3(kk.total_tiles), dim3(threads * KS), lds_ks, s, kk);
-        return mt4_check_launch();
-    } else {
-    const int lds = k.nsteps > 1 ? (fast ? STAGES : 2) * stage : (stage > epi ? stage : epi);
-    const int grid = kk.total_tiles;  // one tile per workgroup (see PERSIST in the kernel)
+    const int lds = KS > 1 ? std::max(KS * STAGES * stage, epi) : k.nsteps > 1 ? (fast ? STAGES : 2) * stage : std::max(stage, epi);
+    // one tile per workgroup (see PERSIST in the kernel).  The instantiations: the LDS-DMA form with the tile's stages, the register-staged
+    // form with two (K-split tiles have none), and both again with the channel sums where the tile can hold them
+    auto launch = [&](auto fast_c, auto stats_c) {
+        constexpr bool F = decltype(fast_c)::value, S = decltype(stats_c)::value;
+        return mt4_launch<igemm_conv_kernel<T, BM, BN, WM_, WN_, F ? STAGES : 2, F, OUT_F32, KS, false, S>>(
+            dim3(kk.total_tiles), dim3(WM_ * WN_ * 64 * KS), lds, s, kk);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
     if constexpr (CAN_STATS) {
-        if (k.stat_sums) {
-            if (fast) {
-                auto fn = igemm_conv_kernel<T, BM, BN, WM_, WN_, STAGES, true, OUT_F32, 1, false, true>;
-                if (lds > 65536) {
-                    MT4_RAISE_LDS(fn);
-                }
-                hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, s, kk);
-            } else {
-                auto fn = igemm_conv_kernel<T, BM, BN, WM_, WN_, 2, false, OUT_F32, 1, false, true>;
-                if (lds > 65536) {
-                    MT4_RAISE_LDS(fn);
-                }
-                hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, s, kk);
-            }
-            return mt4_check_launch();
-        }
+        if (k.stat_sums) return fast ? launch(yes, yes) : launch(no, yes);
     }
-    if (fast) {
-        auto fn = igemm_conv_kernel<T, BM, BN, WM_, WN_, STAGES, true, OUT_F32>;
-        if (lds > 65536) {
-            MT4_RAISE_LDS(fn);
-        }
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, s, kk);
-    } else {
-        auto fn = igemm_conv_kernel<T, BM, BN, WM_, WN_, 2, false, OUT_F32>;
-        if (lds > 65536) {
-            MT4_RAISE_LDS(fn);
-        }
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, s, kk);
+    if constexpr (KS == 1) {
+        if (!fast) return launch(no, no);
     }
-    return mt4_check_launch();
-    }
+    return launch(yes, no);
 }
 
 // tile 17 (bf16 256 x 256, 16 waves) with the second K source (ConvK::x2)
 int launch_dual(const ConvK& k, hipStream_t s) {
     constexpr int BM = 256, BN = 256, stage = (BM + BN) * 128;
-    ConvK kk = k;
-    kk.n_tiles = cdiv(k.Cout, BN);
-    kk.total_tiles = cdiv(k.M, BM) * kk.n_tiles;
-    kk.nt_epi = 1;
-    if ((long long)k.M * k.Cout * 2 < (long long)MT4_NT_MIN_MB * 1000000LL) kk.nt_epi = 0;
-    auto fn = igemm_conv_kernel<u16, BM, BN, 4, 4, 2, true, false, 1, true>;
-    MT4_RAISE_LDS(fn);
-    hipLaunchKernelGGL(fn, dim3(kk.total_tiles), dim3(1024), 2 * stage, s, kk);
-    return mt4_check_launch();
+    const ConvK kk = with_grid(k, k.Cout, BM, BN);
+    return mt4_launch<igemm_conv_kernel<u16, BM, BN, 4, 4, 2, true, false, 1, true>>(dim3(kk.total_tiles), dim3(1024), 2 * stage, s, kk);
 }
 
 template <typename T, bool OUT_F32>
-int launch_dtype(const ConvK& k, int tile, bool fast, hipStream_t s) {
+int launch_generic(const ConvK& k, int tile, bool fast, hipStream_t s) {
     switch (tile) {
-        case 1: return launch_tile<T, 128, 128, 2, 2, 2, OUT_F32>(k, fast, s);
-        case 2: return launch_tile<T, 128, 64, 2, 2, 2, OUT_F32>(k, fast, s);
-        case 3: return launch_tile<T, 64, 64, 2, 2, 2, OUT_F32>(k, fast, s);
-        case 4: return launch_tile<T, 64, 128, 2, 2, 2, OUT_F32>(k, fast, s);
-        case 5: return launch_tile<T, 32, 64, 1, 4, 2, OUT_F32>(k, fast, s);
-        case 6: return launch_tile<T, 32, 32, 2, 2, 2, OUT_F32>(k, fast, s);
-        case 7: return launch_tile<T, 128, 128, 2, 2, 3, OUT_F32>(k, fast, s);
-        case 8: return launch_tile<T, 64, 128, 2, 2, 3, OUT_F32>(k, fast, s);
-        case 9: return launch_tile<T, 64, 64, 2, 2, 4, OUT_F32>(k, fast, s);
-        case 10: return launch_tile<T, 32, 64, 1, 4, 4, OUT_F32>(k, fast, s);
-        case 11: return launch_tile<T, 32, 32, 2, 2, 4, OUT_F32>(k, fast, s);
-        case 12: return launch_tile<T, 128, 64, 2, 2, 3, OUT_F32>(k, fast, s);
-        case 13: return launch_tile<T, 256, 128, 4, 2, 2, OUT_F32>(k, fast, s);
-        case 14: return launch_tile<T, 256, 128, 4, 2, 3, OUT_F32>(k, fast, s);
-        case 15: return launch_tile<T, 256, 256, 2, 4, 2, OUT_F32>(k, fast, s);
-        case 16: return launch_tile<T, 128, 256, 2, 4, 3, OUT_F32>(k, fast, s);
-        case 17: return launch_tile<T, 256, 256, 4, 4, 2, OUT_F32>(k, fast, s);
-        case 18: return launch_tile<T, 256, 128, 4, 4, 2, OUT_F32>(k, fast, s);
-        case 19: return launch_tile<T, 256, 128, 4, 4, 3, OUT_F32>(k, fast, s);
-        case 20: return launch_tile<T, 256, 64, 4, 2, 2, OUT_F32>(k, fast, s);
-        case 35: return launch_tile<T, 32, 32, 2, 2, 2, OUT_F32, 4>(k, fast, s);   // K-split x4 (16 waves)
-        case 36: return launch_tile<T, 32, 64, 1, 4, 2, OUT_F32, 4>(k, fast, s);
-        case 37: return launch_tile<T, 32, 32, 1, 2, 2, OUT_F32, 8>(k, fast, s);   // 8 groups of 2 waves
-        case 38: return launch_tile<T, 32, 32, 2, 2, 3, OUT_F32, 4>(k, fast, s);   // 4 groups, 3 stages each
-        case 39: return launch_tile<T, 64, 64, 2, 2, 2, OUT_F32, 2>(k, fast, s);   // 2 groups of 4 waves
-        case 40: return launch_tile<T, 64, 64, 2, 2, 2, OUT_F32, 4>(k, fast, s);   // 4 groups of 4 waves
-        case 41: return launch_tile<T, 64, 64, 2, 2, 3, OUT_F32, 2>(k, fast, s);   // 2 groups, 3 stages each
-        case 42: return launch_tile<T, 64, 128, 2, 2, 2, OUT_F32, 2>(k, fast, s);  // 2 groups of 4 waves
+#define G(id, bm, bn, wm, wn, st, ks) \
+    case id: return launch_tile<T, bm, bn, wm, wn, st, OUT_F32, ks>(k, fast, s);
+        MT4_CONV_TILES(G, MT4_SKIP, MT4_SKIP, MT4_SKIP)
+#undef G
     }
     return MT4_EINVAL;
 }
-
 
 // geometry the patch kernel covers (everything else runs the generic kernel)
 bool patch3x3_ok(const mt4_conv_desc* d, const ConvK& k, bool fast) {
@@ -1564,55 +1479,45 @@ bool patch3x3_ok(const mt4_conv_desc* d, const ConvK& k, bool fast) {
            k.x_total_bytes + (long long)(2 * d->W + 1024) * k.pix_bytes < 0x7fffffffLL;
 }
 
+// dynamic LDS of a patch-kernel launch (and its patch rows `pra`), or 0 where the tile does not fit: the patch (double-buffered over channel
+// slices) + the weight ring within 160 KB, the next slice's patch pieces within the taps they ride along with, and the weights-resident
+// form (WS == 9) on single-slice layers only
+int patch3x3_lds(const ConvK& k, int BM, int BN, int waves, int WS, bool expand, int* pra_out) {
+    const int rpp = waves * 8;
+    const int pra = (BM + 2 * k.W + 2 + 2 + 7) / 8 * 8;      // + 2: the rows of zeros out-of-image taps read
+    const int epi = BM / (BN >= 256 ? 4 : 2) * (BN * 4 + 16);
+    int lds = (k.SPT > 1 ? 2 : 1) * pra * 128 + WS * BN * 128;
+    if (lds < epi) lds = epi;
+    if (expand && lds < 2 * BM * 128 + epi) lds = 2 * BM * 128 + epi;   // the bf16 tile (two 64-channel planes) + the staging of a pass
+    if (WS == 9 && k.SPT != 1) return 0;
+    if (lds > 160 * 1024 || (k.SPT > 1 && cdiv(pra, rpp) > 11 - WS)) return 0;   // (next-slice patch pieces ride along with taps 0..)
+    *pra_out = pra;
+    return lds;
+}
+
 template <int BM, int BN, int WM_, int WN_, int WS, bool EXPAND = false>
 int launch_patch3x3(const ConvK& k, hipStream_t s) {
-    ConvK kk = k;
-    kk.n_tiles = cdiv(k.Cout, BN);
-    kk.total_tiles = cdiv(k.M, BM) * kk.n_tiles;
-    kk.nt_epi = 1;
-    {
-        const long long min_mb = MT4_NT_MIN_MB;
-        if ((long long)k.M * (EXPAND ? k.f_cout : k.Cout) * 2 < min_mb * 1000000LL) kk.nt_epi = 0;
-    }
-    constexpr int threads = WM_ * WN_ * 64;
-    constexpr int rpp = threads / 8;
-    const int pra = (BM + 2 * k.W + 2 + 2 + 7) / 8 * 8;      // + 2: the rows of zeros out-of-image taps read
-    const int npatch = k.SPT > 1 ? 2 : 1;
-    constexpr int epi = BM / (BN >= 256 ? 4 : 2) * (BN * 4 + 16);
-    int lds = npatch * pra * 128 + WS * BN * 128;
-    if (lds < epi) lds = epi;
-    if (EXPAND && lds < 2 * BM * 128 + epi) lds = 2 * BM * 128 + epi;   // the bf16 tile (two 64-channel planes) + the staging of a pass
-    if (WS == 9 && k.SPT != 1) return MT4_EUNSUPPORTED;
-    if (lds > 160 * 1024 || (k.SPT > 1 && cdiv(pra, rpp) > 11 - WS)) return MT4_EUNSUPPORTED;   // (next-slice patch pieces ride along with taps 0..)
+    int pra = 0;
+    const int lds = patch3x3_lds(k, BM, BN, WM_ * WN_, WS, EXPAND, &pra);
+    if (!lds) return MT4_EUNSUPPORTED;
     if (k.stat_sums && (EXPAND || (k.Cout & 7))) return MT4_EUNSUPPORTED;
-    if constexpr (!EXPAND) {
-        if (k.stat_sums) {       // the train-mode launch: its own instantiation (float64 channel sums in the epilogue)
-            auto fs = conv3x3_patch_kernel<BM, BN, WM_, WN_, WS, false, true>;
-            if (lds > 65536) {
-                MT4_RAISE_LDS(fs);
-            }
-            hipLaunchKernelGGL(fs, dim3(kk.total_tiles), dim3(threads), lds, s, kk, pra, npatch);
-            return mt4_check_launch();
-        }
+    const ConvK kk = with_grid(k, EXPAND ? k.f_cout : k.Cout, BM, BN);
+    const dim3 grid(kk.total_tiles), block(WM_ * WN_ * 64);
+    const int npatch = k.SPT > 1 ? 2 : 1;
+    if constexpr (!EXPAND) {       // the train-mode launch: its own instantiation (float64 channel sums in the epilogue)
+        if (k.stat_sums) return mt4_launch<conv3x3_patch_kernel<BM, BN, WM_, WN_, WS, false, true>>(grid, block, lds, s, kk, pra, npatch);
     }
-    auto fn = conv3x3_patch_kernel<BM, BN, WM_, WN_, WS, EXPAND, false>;
-    if (lds > 65536) {
-        MT4_RAISE_LDS(fn);
-    }
-    hipLaunchKernelGGL(fn, dim3(kk.total_tiles), dim3(threads), lds, s, kk, pra, npatch);
-    return mt4_check_launch();
+    return mt4_launch<conv3x3_patch_kernel<BM, BN, WM_, WN_, WS, EXPAND, false>>(grid, block, lds, s, kk, pra, npatch);
 }
 
 int launch_patch_tile(const ConvK& k, int tile, hipStream_t s) {
     switch (tile) {
-        case 23: return launch_patch3x3<256, 256, 4, 4, 2>(k, s);
-        case 24: return launch_patch3x3<256, 64, 4, 2, 2>(k, s);
-        case 26: return launch_patch3x3<256, 128, 4, 4, 2>(k, s);
-        case 30: return launch_patch3x3<128, 128, 2, 2, 2>(k, s);
-        case 32: return launch_patch3x3<256, 128, 4, 2, 2>(k, s);
+#define P(id, bm, bn, wm, wn, ws) \
+    case id: return launch_patch3x3<bm, bn, wm, wn, ws>(k, s);
+        MT4_CONV_TILES(MT4_SKIP, P, MT4_SKIP, MT4_SKIP)
+#undef P
     }
-    return MT4_EUNSUPPORTED;   // ids 21, 22, 25, 27, 28, 29, 31: retired variants of the tuning record (deeper weight rings, weights-resident forms:
-                               // every one measured slower, profiles/r01_tile_tuning_patch3x3.txt)
+    return MT4_EINVAL;
 }
 
 // the space-to-depth stem: KH x 1 kernel over runs of 4 pixels x 16 channels, stride 1, valid, Cout <= 64
@@ -1623,33 +1528,30 @@ bool stem_patch_ok(const mt4_conv_desc* d, const ConvK& k, bool fast) {
            (d->Cout % 8) == 0 && k.HoWo >= 256 && k.nsteps == d->KH && k.x_total_bytes < 0x70000000LL;
 }
 
-int launch_stem_patch(const ConvK& k, hipStream_t s) {
-    constexpr int BM = 256;
-    ConvK kk = k;
-    kk.n_tiles = 1;
-    kk.total_tiles = cdiv(k.M, BM);
-    kk.nt_epi = 1;
-    {
-        const long long min_mb = MT4_NT_MIN_MB;
-        if ((long long)k.M * k.Cout * 2 < min_mb * 1000000LL) kk.nt_epi = 0;
-    }
-    // frame pixels a tile of 256 consecutive output pixels of ONE image can span: its own run, 3 extra pixels per output row it crosses,
-    // the KH-1 rows and 3 pixels of the kernel footprint
-    kk.n_tiles = cdiv(k.HoWo, BM);                 // tiles per image
-    kk.total_tiles = k.B * kk.n_tiles;
+// dynamic LDS of the stem patch kernel (and its patch runs `pra`), or 0 past 160 KB.  Frame pixels a tile of 256 consecutive output pixels
+// of ONE image can span: its own run, 3 extra pixels per output row it crosses, the KH-1 rows and 3 pixels of the kernel footprint
+int stem_patch_lds(const ConvK& k, int* pra_out) {
+    constexpr int BM = kStemBM, epi = BM / 2 * (64 * 4 + 16);
     const int rows_crossed = cdiv(BM, k.Wo) + 1;
     const int span = BM + 3 * rows_crossed + (k.KH - 1) * k.W + 4;
     const int pra = (span + 31) / 32 * 32;
     int lds = pra * 32 + k.KH * 64 * 128;
-    constexpr int epi = BM / 2 * (64 * 4 + 16);
     if (lds < epi) lds = epi;
-    if (lds > 160 * 1024) return MT4_EUNSUPPORTED;
-    auto fn = stem_patch_kernel<BM, 4, 2>;
-    if (lds > 65536) {
-        MT4_RAISE_LDS(fn);
-    }
-    hipLaunchKernelGGL(fn, dim3(kk.total_tiles), dim3(512), lds, s, kk, pra);
-    return mt4_check_launch();
+    *pra_out = pra;
+    return lds > 160 * 1024 ? 0 : lds;
+}
+
+int launch_stem_patch(const ConvK& k, hipStream_t s) {
+    constexpr int BM = kStemBM;
+    int pra = 0;
+    const int lds = stem_patch_lds(k, &pra);
+    if (!lds) return MT4_EUNSUPPORTED;
+    ConvK kk = with_grid(k, k.Cout, BM, 64);
+    kk.n_tiles = cdiv(k.HoWo, BM);                 // tiles per image: no tile spans two images
+    kk.total_tiles = k.B * kk.n_tiles;
+#define S(id, bm, bn, wm, wn) return mt4_launch<stem_patch_kernel<bm, wm, wn>>(dim3(kk.total_tiles), dim3(wm * wn * 64), lds, s, kk, pra);
+    MT4_CONV_TILES(MT4_SKIP, MT4_SKIP, S, MT4_SKIP)
+#undef S
 }
 
 int auto_tile(int M, int N, int nsteps, int es) {
@@ -1717,8 +1619,11 @@ extern "C" int64_t mt4_conv_packed_k(int32_t Cin, int32_t KH, int32_t KW, int32_
     return (int64_t)chunks * (16 / es);
 }
 
-extern "C" int mt4_conv_nhwc(const mt4_conv_desc* d, void* stream) {
-    mt4_clear_error();
+namespace {
+
+// the descriptor's checks, in the order that decides which error a descriptor failing several of them reports, and the kernel arguments;
+// *fast: the LDS-DMA path
+int fill_conv_args(const mt4_conv_desc* d, ConvK& k, bool* fast_out) {
     if (!d || !d->x || !d->w || !d->y) return MT4_EINVAL;
     if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->Cout <= 0 || d->KH <= 0 ||
         d->KW <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->dil_h <= 0 || d->dil_w <= 0)
@@ -1734,7 +1639,6 @@ extern "C" int mt4_conv_nhwc(const mt4_conv_desc* d, void* stream) {
     const long long M = (long long)d->B * d->Ho * d->Wo;
     if (M > 0x7fffffffLL || M * d->Cout * 4 > (1LL << 40)) return MT4_EUNSUPPORTED;
 
-    ConvK k{};
     k.x = (const char*)d->x; k.w = (const char*)d->w; k.bias = d->bias; k.res = (const char*)d->residual; k.y = (char*)d->y;
     k.B = d->B; k.H = d->H; k.W = d->W; k.Cin = d->Cin; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
     k.KH = d->KH; k.KW = d->KW; k.sh = d->stride_h; k.sw = d->stride_w; k.ph = d->pad_h; k.pw = d->pad_w;
@@ -1788,99 +1692,124 @@ extern "C" int mt4_conv_nhwc(const mt4_conv_desc* d, void* stream) {
         if (d->fuse_w || d->x2 || d->out_row_map || d->tile == -1 || d->tile == 33 || pix != d->Cin * es) return MT4_EUNSUPPORTED;
         k.stat_sums = d->stat_sums;
     }
-    if (d->fuse_w && d->fuse_expand) {
-        // the Bottleneck's conv3 + bn3 + add + ReLU behind its 3x3 conv, in the patch kernel: only where that kernel runs (many tiles: the
-        // caller launches the two convs otherwise -- the results are bit-identical either way)
-        if (!d->fuse_y || !d->fuse_bias || d->fuse_cout <= 0 || (d->fuse_cout % 128) != 0) return MT4_EINVAL;
-        if (((uintptr_t)d->fuse_w | (uintptr_t)d->fuse_y | (uintptr_t)d->fuse_bias) & 15) return MT4_EALIGN;
-        if (!(patch3x3_ok(d, k, fast) && d->Cin == 128 && d->Cout == 128 && d->tile == 0 && !d->x2 &&
-              (long long)cdiv(k.M, 256) * cdiv(d->fuse_cout, 256) >= 256))
-            return MT4_EUNSUPPORTED;
-        k.f_w = (const char*)d->fuse_w; k.f_bias = d->fuse_bias; k.f_y = (char*)d->fuse_y; k.f_cout = d->fuse_cout; k.f_relu = d->fuse_relu ? 1 : 0;
-        return d->W <= 31 ? launch_patch3x3<128, 128, 2, 2, 2, true>(k, (hipStream_t)stream) : launch_patch3x3<256, 128, 4, 2, 2, true>(k, (hipStream_t)stream);
-    }
-    if (d->fuse_w) return MT4_EUNSUPPORTED;   // (fuse_w exists with fuse_expand only; two dependent 1x1 convs in one launch: mt4_chain_gemm_bf16)
-    if (d->x2) {
-        // second K source: y = act([W | W2] . [x ; x2 gathered at stride x2_stride] + bias); w rows hold both K ranges back to back
-        if (d->x2_H <= 0 || d->x2_W <= 0 || d->x2_C <= 0 || d->x2_stride <= 0) return MT4_EINVAL;
-        if (!(fast && d->dtype == MT4_BF16 && d->out_dtype == MT4_BF16 && d->KH == 1 && d->KW == 1 && d->stride_h == 1 && d->stride_w == 1 &&
-              d->pad_h == 0 && d->pad_w == 0 && !d->out_row_map && !d->residual && d->relu <= 1 && d->tile == 0 && pix == d->Cin * es &&
-              (d->x2_C * 2) % 128 == 0 && (d->Cout % 8) == 0 && (k.y_ld * 2) % 16 == 0))
-            return MT4_EUNSUPPORTED;
-        if ((long long)(d->Ho - 1) * d->x2_stride >= d->x2_H || (long long)(d->Wo - 1) * d->x2_stride >= d->x2_W) return MT4_EINVAL;
-        if ((uintptr_t)d->x2 & 15) return MT4_EALIGN;
-        k.x2 = (const char*)d->x2;
-        k.x2_pix_bytes = d->x2_C * 2;
-        k.x2_img_bytes = (long long)d->x2_H * d->x2_W * k.x2_pix_bytes;
-        k.x2_total_bytes = (long long)d->B * k.x2_img_bytes;
-        k.x2_W = d->x2_W; k.x2_s = d->x2_stride; k.x2_HoWo = d->Ho * d->Wo; k.x2_Wo = d->Wo;
-        if (((long long)(256 / k.x2_HoWo) + 2) * k.x2_img_bytes >= 0x70000000LL) return MT4_EUNSUPPORTED;
-        k.nsteps1 = k.nsteps;
-        k.nsteps += d->x2_C * 2 / 128;
-        k.w_row_bytes = k.nsteps * 128;
-        const long long wb2 = (long long)d->Cout * k.w_row_bytes;
-        if (wb2 >= 0x7fffffffLL) return MT4_EUNSUPPORTED;
-        k.w_bytes = (unsigned)wb2;
-        return launch_dual(k, (hipStream_t)stream);
-    }
-    int tile = d->tile;
-    if (tile < -1 || tile > kNumTiles) return MT4_EINVAL;
-    const bool latency = tile == -1;   // automatic choice, K-split tiles allowed
-    if (latency) tile = 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (tile == 34) return MT4_EUNSUPPORTED;   // (retired id: the persistent form of the stem patch kernel, measured no faster in the bench)
-    if (tile == 33 || (tile == 0 && stem_patch_ok(d, k, fast))) {   // the space-to-depth stem
-        if (!stem_patch_ok(d, k, fast)) return MT4_EUNSUPPORTED;
-        const int rc = launch_stem_patch(k, s);
-        if (rc != MT4_EUNSUPPORTED || tile != 0) return rc;
-    }
-    if (tile >= 21 && tile <= 32) {   // explicit request for the 3x3 patch kernel
-        if (!patch3x3_ok(d, k, fast)) return MT4_EUNSUPPORTED;
-        return launch_patch_tile(k, tile, s);
-    }
-    if (tile == 0 && patch3x3_ok(d, k, fast) && (long long)cdiv(k.M, 256) * cdiv(k.Cout, 256) >= 256) {
+    *fast_out = fast;
+    return MT4_OK;
+}
+
+// fuse_w: the Bottleneck's conv3 + bn3 + add + ReLU behind its 3x3 conv, in the patch kernel: only where that kernel runs (many tiles: the
+// caller launches the two convs otherwise -- the results are bit-identical either way).  Completes k in place
+int launch_fuse_expand(const mt4_conv_desc* d, ConvK& k, bool fast, hipStream_t s) {
+    if (!d->fuse_expand) return MT4_EUNSUPPORTED;   // (fuse_w exists with fuse_expand only; two dependent 1x1 convs in one launch: mt4_chain_gemm_bf16)
+    if (!d->fuse_y || !d->fuse_bias || d->fuse_cout <= 0 || (d->fuse_cout % 128) != 0) return MT4_EINVAL;
+    if (((uintptr_t)d->fuse_w | (uintptr_t)d->fuse_y | (uintptr_t)d->fuse_bias) & 15) return MT4_EALIGN;
+    if (!(patch3x3_ok(d, k, fast) && d->Cin == 128 && d->Cout == 128 && d->tile == 0 && !d->x2 &&
+          (long long)cdiv(k.M, 256) * cdiv(d->fuse_cout, 256) >= 256))
+        return MT4_EUNSUPPORTED;
+    k.f_w = (const char*)d->fuse_w; k.f_bias = d->fuse_bias; k.f_y = (char*)d->fuse_y; k.f_cout = d->fuse_cout; k.f_relu = d->fuse_relu ? 1 : 0;
+    return d->W <= 31 ? launch_patch3x3<128, 128, 2, 2, 2, true>(k, s) : launch_patch3x3<256, 128, 4, 2, 2, true>(k, s);   // (the geometry of tiles 30 / 32)
+}
+
+// x2, the second K source: y = act([W | W2] . [x ; x2 gathered at stride x2_stride] + bias); w rows hold both K ranges back to back
+int launch_second_source(const mt4_conv_desc* d, ConvK& k, bool fast, hipStream_t s) {
+    if (d->x2_H <= 0 || d->x2_W <= 0 || d->x2_C <= 0 || d->x2_stride <= 0) return MT4_EINVAL;
+    if (!(fast && d->dtype == MT4_BF16 && d->out_dtype == MT4_BF16 && d->KH == 1 && d->KW == 1 && d->stride_h == 1 && d->stride_w == 1 &&
+          d->pad_h == 0 && d->pad_w == 0 && !d->out_row_map && !d->residual && d->relu <= 1 && d->tile == 0 && k.pix_bytes == d->Cin * 2 &&
+          (d->x2_C * 2) % 128 == 0 && (d->Cout % 8) == 0 && (k.y_ld * 2) % 16 == 0))
+        return MT4_EUNSUPPORTED;
+    if ((long long)(d->Ho - 1) * d->x2_stride >= d->x2_H || (long long)(d->Wo - 1) * d->x2_stride >= d->x2_W) return MT4_EINVAL;
+    if ((uintptr_t)d->x2 & 15) return MT4_EALIGN;
+    k.x2 = (const char*)d->x2;
+    k.x2_pix_bytes = d->x2_C * 2;
+    k.x2_img_bytes = (long long)d->x2_H * d->x2_W * k.x2_pix_bytes;
+    k.x2_total_bytes = (long long)d->B * k.x2_img_bytes;
+    k.x2_W = d->x2_W; k.x2_s = d->x2_stride; k.x2_HoWo = d->Ho * d->Wo; k.x2_Wo = d->Wo;
+    if (((long long)(256 / k.x2_HoWo) + 2) * k.x2_img_bytes >= 0x70000000LL) return MT4_EUNSUPPORTED;
+    k.nsteps1 = k.nsteps;
+    k.nsteps += d->x2_C * 2 / 128;
+    k.w_row_bytes = k.nsteps * 128;
+    const long long wb2 = (long long)d->Cout * k.w_row_bytes;
+    if (wb2 >= 0x7fffffffLL) return MT4_EUNSUPPORTED;
+    k.w_bytes = (unsigned)wb2;
+    return launch_dual(k, s);
+}
+
+struct TileChoice {
+    int kind;   // TileKind, or the MT4_E* code (< 0) of a request that cannot be served
+    int tile;
+};
+
+// which kernel family and tile a plain launch gets: d->tile when it names one, the tuned choice for 0, and for -1 (`latency`) the tuned
+// choice with the K-split tiles allowed.  Reads its arguments only.
+TileChoice choose_tile(const mt4_conv_desc* d, const ConvK& k, bool fast, bool latency) {
+    if (d->tile < -1 || d->tile > kNumTiles) return {MT4_EINVAL, 0};
+    int tile = latency ? 0 : d->tile;
+    int pra;
+    if (tile > 0 && kTiles[tile - 1].kind == RETIRED) return {MT4_EUNSUPPORTED, 0};
+    if (tile > 0 && kTiles[tile - 1].kind == STEM) return stem_patch_ok(d, k, fast) ? TileChoice{STEM, tile} : TileChoice{MT4_EUNSUPPORTED, 0};
+    if (tile > 0 && kTiles[tile - 1].kind == PATCH) return patch3x3_ok(d, k, fast) ? TileChoice{PATCH, tile} : TileChoice{MT4_EUNSUPPORTED, 0};
+    if (tile > 0) return {GENERIC, tile};
+    if (stem_patch_ok(d, k, fast) && stem_patch_lds(k, &pra)) return {STEM, 33};   // the space-to-depth stem (patch too large for LDS: generic tiles)
+    if (patch3x3_ok(d, k, fast) && (long long)cdiv(k.M, 256) * cdiv(k.Cout, 256) >= 256) {
         // 3x3 stride-1 layers at many rounds of the chip: the patch kernel (same-box sweep at 1336 frames,
         // profiles/r01_tile_tuning_patch3x3.txt: layer1 conv2 0.462 -> 0.375 ms (256x64), layer2 0.343 -> 0.300 (128x128, 4 waves with 64x64
         // wave tiles), layer3 0.242 -> 0.244 and layer4 0.232 -> 0.230 (256x256: even); ResNet-50 bench, alternating runs on one box:
         // 67.8 k frames/s generic, 69.0 k with the tiles below): 256x64 for Cout <= 64, 128x128 for Cout <= 128 (only while the 2W+2 halo stays
         // small -- W = 56 at 256x448 frames: tile 30 0.475 ms, tile 32 0.310, generic 0.325), 256x256 above
         const int pt = d->Cout <= 64 ? 24 : d->Cout <= 128 ? (d->W <= 31 ? 30 : 32) : 23;
-        const int rc = launch_patch_tile(k, pt, s);
-        if (rc != MT4_EUNSUPPORTED) return rc;   // (patch too large for LDS: generic tiles)
+        const TileCfg& t = kTiles[pt - 1];
+        if (patch3x3_lds(k, t.bm, t.bn, t.waves, t.stages, false, &pra)) return {PATCH, pt};   // (patch too large for LDS: generic tiles)
     }
-    if (tile == 0) {
-        tile = auto_tile(k.M, k.Cout, k.nsteps, d->dtype == MT4_F32 ? 4 : 2);
-        // few tiles and a long K: the 4-stage ring of the small tiles (10 / 11), or -- when the caller asked for latency (tile -1) and the
-        // geometry is on the LDS-DMA path -- eight K-split groups of two waves per workgroup (36 / 37)
-        // (measured, 4-stage TCN, fp32, T = 256: 1.23 ms with the rings, 1.07 with four groups, 0.96 with eight; config 1 0.357 -> 0.277;
-        //  with more than one workgroup per CU -- T = 2000 -- the 16-wave workgroups lose 27 %, and bf16 (half the K-steps; 0.640 -> 0.630 ms with eight groups: the 84 dependent launches are the floor) gains nothing:
-        //  fp32 launches of at most 256 tiles only)
-        if (latency && fast && d->dtype == MT4_F32 && (tile == 10 || tile == 11)) {
-            const int kt = tile == 11 ? 37 : 36;
-            if ((long long)cdiv(k.M, kTiles[kt - 1].bm) * cdiv(k.Cout, kTiles[kt - 1].bn) <= 256) tile = kt;
-        }
-        // a whole video (T ~ 2000 frames x 512 channels: `Temporal_tenco/run.py:369-379` runs batch 1 on full videos): 64 x 64 tiles are one
-        // round of the 256 CUs and pull the fewest operand bytes per CU ((BM + BN) x K, minimal for square tiles); what they lack is waves to
-        // hide the per-K-step DMA round trip -- K-split groups supply them.  Same-box sweep, 4-stage head, T = 2000, hipGraph replay
-        // (tools/tcn_long_sweep.py): fp32 2.35 ms (32 x 32, 4-stage ring) -> 2.13 (two groups) -> 2.04 (four groups, tile 40);
-        // bf16 1.00 -> 0.83 (tile 40) -> 0.74 (two groups with 3-stage rings, tile 41).  At T = 1000 (128 such tiles: half the chip) the
-        // small tiles stay, bf16 on the 4-stage 32 x 64 ring (0.74 -> 0.69 ms)
-        // several short videos per forward (the temporal head's throughput mode: 8192 rows x 512 channels at 32 videos): 128 x 128 tiles are a
-        // single round of 256 four-wave workgroups; 64 x 128 gives two per CU -- 36.1 -> 30.4 us (dilated conv), 24.4 -> 21.0 (1 x 1) in bf16,
-        // 135 -> 123 / 56.5 -> 51.8 in fp32 (profiles/r04_tcn_batched_tile_sweep.txt).  Latency callers only: the spatial paths keep their tuned table.
-        if (latency && tile == 1) {
-            const long long t128 = (long long)cdiv(k.M, 128) * cdiv(k.Cout, 128), t64 = (long long)cdiv(k.M, 64) * cdiv(k.Cout, 128);
-            if (t128 < 512 && t64 >= 256) tile = 4;
-        }
-        if (latency && fast && k.nsteps >= 8 && (tile == 5 || tile == 6 || tile == 10 || tile == 11 || tile == 3 || tile == 9)) {
-            const long long t64 = (long long)cdiv(k.M, 64) * cdiv(k.Cout, 64);
-            if (t64 >= 192 && t64 <= 512) tile = d->dtype == MT4_F32 ? 40 : 41;
-            else if (d->dtype == MT4_BF16 && tile == 11 && (long long)cdiv(k.M, 32) * cdiv(k.Cout, 64) >= 256) tile = 10;
-        }
+    tile = auto_tile(k.M, k.Cout, k.nsteps, d->dtype == MT4_F32 ? 4 : 2);
+    // few tiles and a long K: the 4-stage ring of the small tiles (10 / 11), or -- when the caller asked for latency (tile -1) and the
+    // geometry is on the LDS-DMA path -- eight K-split groups of two waves per workgroup (36 / 37)
+    // (measured, 4-stage TCN, fp32, T = 256: 1.23 ms with the rings, 1.07 with four groups, 0.96 with eight; config 1 0.357 -> 0.277;
+    //  with more than one workgroup per CU -- T = 2000 -- the 16-wave workgroups lose 27 %, and bf16 (half the K-steps; 0.640 -> 0.630 ms with eight groups: the 84 dependent launches are the floor) gains nothing:
+    //  fp32 launches of at most 256 tiles only)
+    if (latency && fast && d->dtype == MT4_F32 && (tile == 10 || tile == 11)) {
+        const int kt = tile == 11 ? 37 : 36;
+        if ((long long)cdiv(k.M, kTiles[kt - 1].bm) * cdiv(k.Cout, kTiles[kt - 1].bn) <= 256) tile = kt;
     }
-    if (d->dtype == MT4_F32) return launch_dtype<float, true>(k, tile, fast, s);
-    if (d->out_dtype == MT4_F32) return launch_dtype<u16, true>(k, tile, fast, s);
-    return launch_dtype<u16, false>(k, tile, fast, s);
+    // a whole video (T ~ 2000 frames x 512 channels: `Temporal_tenco/run.py:369-379` runs batch 1 on full videos): 64 x 64 tiles are one
+    // round of the 256 CUs and pull the fewest operand bytes per CU ((BM + BN) x K, minimal for square tiles); what they lack is waves to
+    // hide the per-K-step DMA round trip -- K-split groups supply them.  Same-box sweep, 4-stage head, T = 2000, hipGraph replay
+    // (tools/tcn_long_sweep.py): fp32 2.35 ms (32 x 32, 4-stage ring) -> 2.13 (two groups) -> 2.04 (four groups, tile 40);
+    // bf16 1.00 -> 0.83 (tile 40) -> 0.74 (two groups with 3-stage rings, tile 41).  At T = 1000 (128 such tiles: half the chip) the
+    // small tiles stay, bf16 on the 4-stage 32 x 64 ring (0.74 -> 0.69 ms)
+    // several short videos per forward (the temporal head's throughput mode: 8192 rows x 512 channels at 32 videos): 128 x 128 tiles are a
+    // single round of 256 four-wave workgroups; 64 x 128 gives two per CU -- 36.1 -> 30.4 us (dilated conv), 24.4 -> 21.0 (1 x 1) in bf16,
+    // 135 -> 123 / 56.5 -> 51.8 in fp32 (profiles/r04_tcn_batched_tile_sweep.txt).  Latency callers only: the spatial paths keep their tuned table.
+    if (latency && tile == 1) {
+        const long long t128 = (long long)cdiv(k.M, 128) * cdiv(k.Cout, 128), t64 = (long long)cdiv(k.M, 64) * cdiv(k.Cout, 128);
+        if (t128 < 512 && t64 >= 256) tile = 4;
+    }
+    if (latency && fast && k.nsteps >= 8 && (tile == 5 || tile == 6 || tile == 10 || tile == 11 || tile == 3 || tile == 9)) {
+        const long long t64 = (long long)cdiv(k.M, 64) * cdiv(k.Cout, 64);
+        if (t64 >= 192 && t64 <= 512) tile = d->dtype == MT4_F32 ? 40 : 41;
+        else if (d->dtype == MT4_BF16 && tile == 11 && (long long)cdiv(k.M, 32) * cdiv(k.Cout, 64) >= 256) tile = 10;
+    }
+    return {GENERIC, tile};
+}
+
+}  // namespace
+
+extern "C" int mt4_conv_nhwc(const mt4_conv_desc* d, void* stream) {
+    mt4_clear_error();
+    ConvK k{};
+    bool fast = false;
+    if (const int rc = fill_conv_args(d, k, &fast)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (d->fuse_w) return launch_fuse_expand(d, k, fast, s);
+    if (d->x2) return launch_second_source(d, k, fast, s);
+    const TileChoice c = choose_tile(d, k, fast, d->tile == -1);
+    switch (c.kind) {
+        case STEM: return launch_stem_patch(k, s);
+        case PATCH: return launch_patch_tile(k, c.tile, s);
+        case GENERIC:
+            if (d->dtype == MT4_F32) return launch_generic<float, true>(k, c.tile, fast, s);
+            if (d->out_dtype == MT4_F32) return launch_generic<u16, true>(k, c.tile, fast, s);
+            return launch_generic<u16, false>(k, c.tile, fast, s);
+    }
+    return c.kind;
 }
 
 // ------------------------------------------------------------------------------------------------ weight packing
@@ -1958,16 +1887,9 @@ extern "C" int mt4_stem_maxpool_bf16(const void* x_s2d, const void* w_packed, co
     if (lds < 5 * k.ctw * 128) lds = 5 * k.ctw * 128;
     if (lds > 80 * 1024) return MT4_EUNSUPPORTED;
     if ((long long)B * k.tiles_per_img > 0x7fffffffLL) return MT4_EUNSUPPORTED;
-    if (wide) {
-        auto fn = stem_pool_kernel<10, 2>;
-        MT4_RAISE_LDS(fn);
-        hipLaunchKernelGGL(fn, dim3((unsigned)(B * k.tiles_per_img)), dim3(512), lds, (hipStream_t)stream, k);
-    } else {
-        auto fn = stem_pool_kernel<9, 2>;      // (two passes also here: 1.17 -> 1.10 ms per 1336 frames of 224 x 224, same box)
-        if (lds > 65536) MT4_RAISE_LDS(fn);
-        hipLaunchKernelGGL(fn, dim3((unsigned)(B * k.tiles_per_img)), dim3(512), lds, (hipStream_t)stream, k);
-    }
-    return mt4_check_launch();
+    const dim3 grid((unsigned)(B * k.tiles_per_img));
+    if (wide) return mt4_launch<stem_pool_kernel<10, 2>>(grid, dim3(512), lds, (hipStream_t)stream, k);
+    return mt4_launch<stem_pool_kernel<9, 2>>(grid, dim3(512), lds, (hipStream_t)stream, k);      // (two passes also here: 1.17 -> 1.10 ms per 1336 frames of 224 x 224, same box)
 }
 
 // stem: [64][3][7][7] -> taps (kh, kwp) with 8-element slots (kw%2)*4 + c, kw = 2*kwp + slot/4

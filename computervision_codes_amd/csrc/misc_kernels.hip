@@ -368,16 +368,6 @@ extern "C" int mt4_linear_f32(const float* x, const float* w, const float* bias,
 // refinement stages (Temporal_tenco/network.py:147,154-155: nn.AvgPool1d(kernel_size=7, stride=3)) and the FPN's linear re-interpolation to the
 // lateral's length (network.py:96: F.interpolate(x, size=W, mode='linear'), align_corners False), both over the time axis of frame-major rows
 namespace {
-template <typename T> __device__ __forceinline__ float4 ldrow4(const T* p);
-template <> __device__ __forceinline__ float4 ldrow4<float>(const float* p) { return *(const float4*)p; }
-template <> __device__ __forceinline__ float4 ldrow4<u16>(const u16* p) {
-    const uint2 v = *(const uint2*)p;
-    return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
-}
-template <typename T> __device__ __forceinline__ void strow4(T* p, float4 v);
-template <> __device__ __forceinline__ void strow4<float>(float* p, float4 v) { *(float4*)p = v; }
-template <> __device__ __forceinline__ void strow4<u16>(u16* p, float4 v) { *(uint2*)p = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)); }
-
 template <typename T>
 __global__ void avgpool1d_rows_kernel(const T* __restrict__ x, T* __restrict__ y, int Tin, int Tout, int C, int k, int stride, long long n4) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -388,10 +378,10 @@ __global__ void avgpool1d_rows_kernel(const T* __restrict__ x, T* __restrict__ y
     const int to = (int)(r % Tout);
     const long long b = r / Tout;
     const T* src = x + (b * Tin + (long long)to * stride) * C + c;
-    float4 s = ldrow4<T>(src);
-    for (int j = 1; j < k; ++j) { const float4 v = ldrow4<T>(src + (long long)j * C); s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+    float4 s = ld4<T>(src);
+    for (int j = 1; j < k; ++j) { const float4 v = ld4<T>(src + (long long)j * C); s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
     const float d = (float)k;
-    strow4<T>(y + r * C + c, make_float4(s.x / d, s.y / d, s.z / d, s.w / d));
+    st4<T>(y + r * C + c, make_float4(s.x / d, s.y / d, s.z / d, s.w / d));
 }
 
 template <typename T>
@@ -408,8 +398,8 @@ __global__ void interp_linear_rows_kernel(const T* __restrict__ x, T* __restrict
     const int i0 = (int)src;
     const int i1 = i0 + (i0 < Tin - 1 ? 1 : 0);
     const float l1 = src - (float)i0, l0 = 1.f - l1;
-    const float4 a = ldrow4<T>(x + (b * Tin + i0) * C + c), v = ldrow4<T>(x + (b * Tin + i1) * C + c);
-    strow4<T>(y + r * C + c, make_float4(l0 * a.x + l1 * v.x, l0 * a.y + l1 * v.y, l0 * a.z + l1 * v.z, l0 * a.w + l1 * v.w));
+    const float4 a = ld4<T>(x + (b * Tin + i0) * C + c), v = ld4<T>(x + (b * Tin + i1) * C + c);
+    st4<T>(y + r * C + c, make_float4(l0 * a.x + l1 * v.x, l0 * a.y + l1 * v.y, l0 * a.z + l1 * v.z, l0 * a.w + l1 * v.w));
 }
 // adjoints of the two (fp32: the TCN trainer's dtype), both as deterministic gathers over the OUTPUT rows that touch an input row
 __global__ void avgpool1d_rows_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int Tin, int Tout, int C, int k, int stride, long long n4) {

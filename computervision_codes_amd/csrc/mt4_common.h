@@ -85,20 +85,152 @@ __device__ __forceinline__ void gelu_erf_n(float (&v)[N]) {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// allow > 64 KiB of dynamic LDS for kernel `fn` on the CURRENT device: once per device and call site (the attribute is per device; a
-// process-wide flag would leave the second GPU of a process at the 64 KiB default)
-#define MT4_RAISE_LDS(fn)                                                                                                   \
-    do {                                                                                                                    \
-        static bool raised_[64] = {};                                                                                       \
-        int dev_ = 0;                                                                                                       \
-        (void)hipGetDevice(&dev_);                                                                                          \
-        if (dev_ < 0 || dev_ >= 64 || !raised_[dev_]) {                                                                     \
-            (void)hipFuncSetAttribute((const void*)(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);           \
-            if (dev_ >= 0 && dev_ < 64) raised_[dev_] = true;                                                               \
-        }                                                                                                                   \
-    } while (0)
+// Launch kernel `Fn` and report the launch's error.  A launch that needs more than 64 KiB of dynamic LDS first raises the kernel's limit on
+// the CURRENT device, once per kernel and device: the attribute belongs to the kernel FUNCTION and the device, so the flag is keyed on the
+// function itself (a non-type template parameter: a helper templated on the function's TYPE would share one flag among all kernels of one
+// signature -- every igemm_conv_kernel<...> is void(ConvK) -- and a process-wide flag would leave a second GPU at the 64 KiB default)
+template <auto Fn, typename... Args>
+static inline int mt4_launch(dim3 grid, dim3 block, int lds, hipStream_t stream, const Args&... args) {
+    if (lds > 65536) {
+        static bool raised[64] = {};
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (dev < 0 || dev >= 64 || !raised[dev]) {
+            (void)hipFuncSetAttribute((const void*)Fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (dev >= 0 && dev < 64) raised[dev] = true;
+        }
+    }
+    hipLaunchKernelGGL(Fn, grid, block, lds, stream, args...);
+    return mt4_check_launch();
+}
 
 // output / residual rows are stored / loaded with the non-temporal bit when the launch's output exceeds this many MB (below it the map fits the
 // Infinity Cache and stays cacheable for the next layer; each byte is touched once per launch: +2.6 % frames/s on ResNet-50, +4.5 % on Swin-B,
 // same-box A/Bs of round 1)
 #define MT4_NT_MIN_MB 200
+
+// ------------------------------------------------------------------------------------------------ device helpers shared between the sources
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+
+// raw buffer descriptor (stride 0, num_records = bytes, gfx9 data-format word) from wave-uniform values
+__device__ __forceinline__ v4u make_srd(const void* p, unsigned bytes) {
+    const unsigned long long u = (unsigned long long)p;
+    v4u r;
+    r.x = __builtin_amdgcn_readfirstlane((unsigned)u);
+    r.y = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32) & 0xffffu);
+    r.z = __builtin_amdgcn_readfirstlane(bytes);
+    r.w = 0x00020000u;
+    return r;
+}
+
+// N LDS-DMA pieces in ONE asm statement (one M0 save/restore): piece i goes to LDS [lds_addr + i*STRIDE + lane*16) from
+// buffer offset voff[i] (per lane, range-checked: out-of-range lanes write zeros) + soff (wave-uniform, NOT range-checked).
+// STRIDE = bytes one staging pass of the whole workgroup covers (waves * 8 rows * 128 B).
+// M0 (the DMA's LDS base) is compiler-reserved: saved, set and restored inside the statement.
+template <int N, int STRIDE>
+__device__ __forceinline__ void lds_dma16_group(v4u srd, const unsigned (&voff)[N], unsigned soff, unsigned lds_addr) {
+    unsigned keep;
+    if constexpr (N == 1) {
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(voff[0]), "s"(srd), "s"(soff), "s"(lds_addr) : "memory");
+    } else if constexpr (N == 2) {
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\t"
+                     "s_add_u32 m0, m0, %6\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(voff[0]), "v"(voff[1]), "s"(srd), "s"(soff), "s"(lds_addr), "n"(STRIDE) : "memory", "scc");
+    } else {
+        static_assert(N == 4, "1, 2 or 4 pieces");
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %7\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %5, %6 offen lds\n\t"
+                     "s_add_u32 m0, m0, %8\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %5, %6 offen lds\n\t"
+                     "s_add_u32 m0, m0, %8\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %5, %6 offen lds\n\t"
+                     "s_add_u32 m0, m0, %8\n\ts_nop 0\n\tbuffer_load_dwordx4 %4, %5, %6 offen lds\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(srd), "s"(soff), "s"(lds_addr),
+                       "n"(STRIDE)
+                     : "memory", "scc");
+    }
+}
+
+// one LDS-DMA piece: 64 lanes x 16 B from buffer offset `voff` (per lane) to LDS [lds_addr + lane*16); out-of-range lanes write zeros
+__device__ __forceinline__ void lds_dma16(v4u srd, unsigned voff, unsigned lds_addr) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %3\n\t"
+        "s_nop 0\n\t"
+        "buffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voff), "s"(srd), "s"(lds_addr)
+        : "memory");
+}
+
+template <int N>
+__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// 4 consecutive elements of a float or bf16 row as float4, and back (bf16: round to nearest even)
+template <typename T> __device__ __forceinline__ float4 ld4(const T* p);
+template <> __device__ __forceinline__ float4 ld4<float>(const float* p) { return *(const float4*)p; }
+template <> __device__ __forceinline__ float4 ld4<u16>(const u16* p) {
+    const uint2 v = *(const uint2*)p;
+    return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
+}
+template <typename T> __device__ __forceinline__ void st4(T* p, float4 v);
+template <> __device__ __forceinline__ void st4<float>(float* p, float4 v) { *(float4*)p = v; }
+template <> __device__ __forceinline__ void st4<u16>(u16* p, float4 v) { *(uint2*)p = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)); }
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// the counter generator of every random draw (computervision_codes_amd/synth.py:uniform01 is the same function on the host side of the tests)
+__host__ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ULL;
+    unsigned long long z = x;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+// ------------------------------------------------------------------------------------------------ train-mode BatchNorm: the reduction both tensor types share
+// A thread owns 4 consecutive channels (one 16- or 8-byte load per row) and walks rows; the reductions run 1024-thread workgroups (64 channels
+// x 64 row phases), at most ~512 per launch: every workgroup ends in 128 float64 atomics on its slab's 128 addresses, and 2048 workgroups of
+// 256 threads on a 64-channel map made those same-address chains (~25 ns a link at the L2) longer than the stream itself -- 52-58 us for 59 MB
+// where the apply kernel moves twice the bytes in 20-29 us (profiles/r03_bn_training_kernels.txt)
+__device__ __forceinline__ void bn_block_reduce(double (&acc)[8], double* __restrict__ sums, int C, int c0) {
+    __shared__ double red[16][8][17];               // [wave][value][channel group], padded
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {                   // the 4 row phases of a wave
+        acc[j] += __shfl_xor(acc[j], 16);
+        acc[j] += __shfl_xor(acc[j], 32);
+    }
+    if (lane < 16) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[w][j][lane] = acc[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 128) {                        // 16 channel groups x 8 values
+        const int g = threadIdx.x & 15, j = threadIdx.x >> 4;
+        double t = 0.0;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) t += red[rr][j][g];
+        const int c = c0 + g * 4 + (j & 3);
+        if (c < C) atomicAdd(sums + (j >> 2) * C + c, t);
+    }
+}
+
+static inline int bn_reduce_slabs(long long M, int C) {                      // 64-row slabs of the 1024-thread reductions
+    long long gy = (M + 63) / 64;
+    const long long cap = (512 + cdiv(C, 64) - 1) / cdiv(C, 64);
+    if (gy > cap) gy = cap;
+    return gy < 1 ? 1 : (int)gy;
+}
+
+static inline int bn_row_slabs(long long M, int C) {                         // 16-row slabs of the 256-thread streaming kernels
+    long long gy = (M + 63) / 64;
+    const long long cap = (2048 + cdiv(C, 64) - 1) / cdiv(C, 64);
+    if (gy > cap) gy = cap;
+    return gy < 1 ? 1 : (int)gy;
+}

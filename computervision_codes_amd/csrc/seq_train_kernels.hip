@@ -325,13 +325,6 @@ __global__ void axpby_kernel(const float* __restrict__ x, float* __restrict__ y,
 // nn.Dropout(p) mask from a counter generator: element i = splitmix64(base + i), base = splitmix64(seed * 0x100000001B3 + stream) -- the
 // same function as computervision_codes_amd/synth.py:uniform01, so the host can reproduce a draw bit for bit.
 // out[i] = u_i >= p ? 1 / (1 - p) : 0
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ULL;
-    unsigned long long z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
 __global__ void dropout_mask_kernel(float* __restrict__ out, long long n, unsigned long long base, float p, float keep_scale) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -523,12 +516,7 @@ extern "C" int mt4_sum_over_batch_f32(const float* x, float* out, int32_t B, int
 extern "C" int mt4_dropout_mask_f32(float* out, int64_t n, int64_t seed, int64_t stream_id, float p, void* stream) {
     mt4_clear_error();
     if (!out || n <= 0 || p < 0.f || p >= 1.f) return MT4_EINVAL;
-    unsigned long long x = (unsigned long long)seed * 0x100000001B3ULL + (unsigned long long)stream_id;
-    x += 0x9E3779B97F4A7C15ULL;                     // (splitmix64 on the host: same arithmetic as the device function)
-    unsigned long long z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    const unsigned long long base = z ^ (z >> 31);
+    const unsigned long long base = splitmix64((unsigned long long)seed * 0x100000001B3ULL + (unsigned long long)stream_id);
     hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, (long long)n, base, p,
                        1.0f / (1.0f - p));
     return mt4_check_launch();

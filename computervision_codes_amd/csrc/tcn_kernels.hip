@@ -19,9 +19,6 @@
 // Arithmetic: fp32 = v_mfma_f32_16x16x4_f32 (exact fp32 FMA chain), bf16 = v_mfma_f32_16x16x32_bf16 with fp32 accumulate.
 #include "mt4_common.h"
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
 namespace {
 
 struct TcnK {
@@ -51,27 +48,6 @@ struct TcnK {
     float2* stat_out;
     int stat_parts;
 };
-
-__device__ __forceinline__ v4u tcn_make_srd(const void* p, unsigned bytes) {
-    const unsigned long long u = (unsigned long long)p;
-    v4u r;
-    r.x = __builtin_amdgcn_readfirstlane((unsigned)u);
-    r.y = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32) & 0xffffu);
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000u;
-    return r;
-}
-
-// one LDS-DMA piece: lane l fetches 16 B at buffer offset voff (range-checked: out-of-range lanes write ZEROS) + soff (wave-uniform)
-// into LDS [lds_addr + 16 l).  M0 is compiler-reserved: saved, set and restored inside the statement.
-__device__ __forceinline__ void tcn_dma16(v4u srd, unsigned voff, unsigned soff, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(srd), "s"(soff), "s"(lds_addr) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void tcn_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 constexpr int kTcnBM = 32, kTcnBN = 16, kTcnWaves = 8, kTcnRing = 2, kTcnMaxPieces = 8;
 
@@ -119,7 +95,7 @@ __global__ __launch_bounds__(kTcnWaves * 64) void tcn_conv_kernel(const TcnK a) 
 
     // source offset of every LDS position this lane fills: piece p, position (row s = 8p + lane/8, chunk c' = lane & 7) holds chunk
     // c' ^ (s & 7) of input slot s (XOR swizzle on the source side: the DMA destination is lane-linear)
-    const v4u rsx = tcn_make_srd(a.x, a.x_bytes);
+    const v4u rsx = make_srd(a.x, a.x_bytes);
     constexpr unsigned OOB = 0x80000000u;
     unsigned voff[kTcnMaxPieces];
     const int row_bytes = a.Cin * ES;
@@ -134,15 +110,19 @@ __global__ __launch_bounds__(kTcnWaves * 64) void tcn_conv_kernel(const TcnK a) 
     auto issue_x = [&](int cs, int ring) {
         const unsigned soff = (unsigned)__builtin_amdgcn_readfirstlane(cs * 128);
         const unsigned dst = my_lds + ring * region;
+        auto piece = [&](int p) {
+            const unsigned v[1] = {voff[p]};
+            lds_dma16_group<1, 0>(rsx, v, soff, dst + p * 1024);
+        };
 #pragma unroll
-        for (int p = 0; p < 4; ++p) tcn_dma16(rsx, voff[p], soff, dst + p * 1024);     // np >= 4
+        for (int p = 0; p < 4; ++p) piece(p);     // np >= 4
         if (np > 4) {
-            tcn_dma16(rsx, voff[4], soff, dst + 4 * 1024);
+            piece(4);
             if (np > 5) {
-                tcn_dma16(rsx, voff[5], soff, dst + 5 * 1024);
+                piece(5);
                 if (np > 6) {
-                    tcn_dma16(rsx, voff[6], soff, dst + 6 * 1024);
-                    tcn_dma16(rsx, voff[7], soff, dst + 7 * 1024);                     // np == 7 stages one spare piece of zeros
+                    piece(6);
+                    piece(7);                     // np == 7 stages one spare piece of zeros
                 }
             }
         }
@@ -255,12 +235,12 @@ __global__ __launch_bounds__(kTcnWaves * 64) void tcn_conv_kernel(const TcnK a) 
     };
     // wait until the OLDER of two slices in flight has landed: everything issued for the younger one may stay outstanding
     auto wait_older = [&](bool other_in_flight) {
-        if (!other_in_flight) { tcn_wait_vm<0>(); return; }
+        if (!other_in_flight) { wait_vm<0>(); return; }
         switch (np) {
-            case 4: tcn_wait_vm<4 + 2 * TAPS>(); break;
-            case 5: tcn_wait_vm<5 + 2 * TAPS>(); break;
-            case 6: tcn_wait_vm<6 + 2 * TAPS>(); break;
-            default: tcn_wait_vm<8 + 2 * TAPS>(); break;
+            case 4: wait_vm<4 + 2 * TAPS>(); break;
+            case 5: wait_vm<5 + 2 * TAPS>(); break;
+            case 6: wait_vm<6 + 2 * TAPS>(); break;
+            default: wait_vm<8 + 2 * TAPS>(); break;
         }
     };
 
@@ -373,10 +353,7 @@ template <typename T, int TAPS, bool OUT_F32, bool LN = false>
 int launch_tcn(const TcnK& k, hipStream_t s) {
     const int lds = kTcnWaves * kTcnRing * k.np * 1024 + kTcnWaves * 2 * 64 * 16;
     if (lds > 160 * 1024) return MT4_EUNSUPPORTED;
-    auto fn = tcn_conv_kernel<T, TAPS, OUT_F32, LN>;
-    if (lds > 65536) MT4_RAISE_LDS(fn);
-    hipLaunchKernelGGL(fn, dim3(8, k.TT, k.B * k.nnx), dim3(kTcnWaves * 64), lds, s, k);
-    return mt4_check_launch();
+    return mt4_launch<tcn_conv_kernel<T, TAPS, OUT_F32, LN>>(dim3(8, k.TT, k.B * k.nnx), dim3(kTcnWaves * 64), lds, s, k);
 }
 
 int tcn_conv_impl(const mt4_tcn_desc* d, hipStream_t s, const float* ln_colsum = nullptr, float ln_eps = 0.f, const float* stat_in = nullptr,

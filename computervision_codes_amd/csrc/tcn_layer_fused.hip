@@ -14,8 +14,6 @@
 // What bounds it: the 2 MB of weights a tile pulls through L2 -> CU (~29 us at the ~70 GB/s a CU takes in) against 15.6 us of MFMA time.
 #include "mt4_common.h"
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 namespace {
 
 struct TcnLayerK {
@@ -197,8 +195,5 @@ extern "C" int mt4_tcn_layer_fused_bf16(const void* x, const void* w1_frag, cons
     if (grid > 0x7fffffffLL) return MT4_EUNSUPPORTED;
     const int lds = 2 * STAGE + HBYTES;                              // 80 KB (>= the 64 x 1040-byte output tile)
     static_assert(2 * STAGE + HBYTES >= BM * OUT_PITCH, "the output tile overlays ring + h");
-    auto fn = tcn_layer_fused_kernel;
-    MT4_RAISE_LDS(fn);
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(512), lds, (hipStream_t)stream, k);
-    return mt4_check_launch();
+    return mt4_launch<tcn_layer_fused_kernel>(dim3((unsigned)grid), dim3(512), lds, (hipStream_t)stream, k);
 }

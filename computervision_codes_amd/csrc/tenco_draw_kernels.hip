@@ -14,18 +14,10 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned long long sm64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ULL;
-    unsigned long long z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
 // (uniform over the grid: the two loads are scalar loads, the finaliser runs once per wave)
 __device__ __forceinline__ unsigned long long draw_base(const long long* __restrict__ state, int slot) {
     const unsigned long long seed = (unsigned long long)state[0], step = (unsigned long long)state[1];
-    return sm64(seed * 0x100000001B3ULL + step * 4096ULL + (unsigned long long)slot);
+    return splitmix64(seed * 0x100000001B3ULL + step * 4096ULL + (unsigned long long)slot);
 }
 
 // ------------------------------------------------------------------------------------------------ nn.Dropout fused into a multiply(-add)
@@ -37,10 +29,10 @@ __global__ __launch_bounds__(256) void dropout_mul_add_kernel(const float* a, co
     if (i4 >= n4) return;
     const unsigned long long b = draw_base(state, slot) + 4ULL * (unsigned long long)i4;
     const float4 av = ((const float4*)a)[i4];
-    const float m0 = (sm64(b) >> 11) >= thr53 ? keep : 0.f;
-    const float m1 = (sm64(b + 1) >> 11) >= thr53 ? keep : 0.f;
-    const float m2 = (sm64(b + 2) >> 11) >= thr53 ? keep : 0.f;
-    const float m3 = (sm64(b + 3) >> 11) >= thr53 ? keep : 0.f;
+    const float m0 = (splitmix64(b) >> 11) >= thr53 ? keep : 0.f;
+    const float m1 = (splitmix64(b + 1) >> 11) >= thr53 ? keep : 0.f;
+    const float m2 = (splitmix64(b + 2) >> 11) >= thr53 ? keep : 0.f;
+    const float m3 = (splitmix64(b + 3) >> 11) >= thr53 ? keep : 0.f;
     float4 r;
     if (c) {
         const float4 cv = ((const float4*)c)[i4];
@@ -112,7 +104,7 @@ __global__ __launch_bounds__(256) void select_pass_kernel(long long n, const lon
     const int shift = 56 - 8 * p;
     const long long stride = (long long)gridDim.x * 256;
     for (long long i = (long long)blockIdx.x * 256 + tid; i < n; i += stride) {
-        const unsigned long long key = sm64(base + (unsigned long long)i);
+        const unsigned long long key = splitmix64(base + (unsigned long long)i);
         if ((key & himask) == prefix) atomicAdd(&h[(unsigned)(key >> shift) & 255u], 1u);
     }
     __syncthreads();
@@ -138,15 +130,15 @@ __global__ __launch_bounds__(256) void tenco_input_draw_kernel(const float* x, f
     float4 v = ((const float4*)x)[i4];
     if (thr) {
         const unsigned long long t = *thr, bk = draw_base(state, slot_keys) + i;
-        v.x *= sm64(bk) <= t ? 1.f : 0.f;
-        v.y *= sm64(bk + 1) <= t ? 1.f : 0.f;
-        v.z *= sm64(bk + 2) <= t ? 1.f : 0.f;
-        v.w *= sm64(bk + 3) <= t ? 1.f : 0.f;
+        v.x *= splitmix64(bk) <= t ? 1.f : 0.f;
+        v.y *= splitmix64(bk + 1) <= t ? 1.f : 0.f;
+        v.z *= splitmix64(bk + 2) <= t ? 1.f : 0.f;
+        v.w *= splitmix64(bk + 3) <= t ? 1.f : 0.f;
     }
-    v.x *= (sm64(bc) >> 11) >= half ? 2.f : 0.f;
-    v.y *= (sm64(bc + 1) >> 11) >= half ? 2.f : 0.f;
-    v.z *= (sm64(bc + 2) >> 11) >= half ? 2.f : 0.f;
-    v.w *= (sm64(bc + 3) >> 11) >= half ? 2.f : 0.f;
+    v.x *= (splitmix64(bc) >> 11) >= half ? 2.f : 0.f;
+    v.y *= (splitmix64(bc + 1) >> 11) >= half ? 2.f : 0.f;
+    v.z *= (splitmix64(bc + 2) >> 11) >= half ? 2.f : 0.f;
+    v.w *= (splitmix64(bc + 3) >> 11) >= half ? 2.f : 0.f;
     ((float4*)y)[i4] = v;
 }
 

@@ -6,49 +6,13 @@
 //   * pooling backward with bf16 gradients, and the fp32 -> bf16 copy of a packed weight matrix.
 #include "mt4_common.h"
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 namespace {
-
-// ------------------------------------------------------------------------------------------------ element access
-template <typename T> __device__ __forceinline__ float4 ld4(const T* p);
-template <> __device__ __forceinline__ float4 ld4<float>(const float* p) { return *(const float4*)p; }
-template <> __device__ __forceinline__ float4 ld4<u16>(const u16* p) {
-    const uint2 v = *(const uint2*)p;
-    return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
-}
-template <typename T> __device__ __forceinline__ void st4(T* p, float4 v);
-template <> __device__ __forceinline__ void st4<float>(float* p, float4 v) { *(float4*)p = v; }
-template <> __device__ __forceinline__ void st4<u16>(u16* p, float4 v) { *(uint2*)p = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)); }
 
 // ------------------------------------------------------------------------------------------------ BatchNorm2d (training), typed tensors
 // same arithmetic as train2d_kernels.hip: float64 per-channel reductions, a thread owns 4 consecutive channels.  The reductions run 1024-thread
 // blocks (64 channels x 64 row phases) and at most ~512 of them: every block ends in 128 fp64 atomics on its slab's 128 addresses, and with 2048
 // blocks of 256 threads on a 64-channel tensor those 2048-deep same-address chains (~25 ns a link at the L2) took longer than the stream --
 // 52-58 us for 59 MB where the apply kernel moves twice the bytes in 20-29 us (profiles/r03_bn_training_kernels.txt)
-__device__ __forceinline__ void bn_block_reduce(double (&acc)[8], double* __restrict__ sums, int C, int c0) {
-    __shared__ double red[16][8][17];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {                                            // the 4 row phases of a wave
-        acc[j] += __shfl_xor(acc[j], 16);
-        acc[j] += __shfl_xor(acc[j], 32);
-    }
-    if (lane < 16) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) red[w][j][lane] = acc[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 128) {
-        const int g = threadIdx.x & 15, j = threadIdx.x >> 4;
-        double t = 0.0;
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) t += red[rr][j][g];
-        const int c = c0 + g * 4 + (j & 3);
-        if (c < C) atomicAdd(sums + (j >> 2) * C + c, t);
-    }
-}
-
 template <typename TZ>
 __global__ __launch_bounds__(1024) void bn_stats_t_kernel(const TZ* __restrict__ x, double* __restrict__ sums, long long M, int C) {
     const int c0 = blockIdx.x * 64, c = c0 + (threadIdx.x & 15) * 4;
@@ -70,20 +34,6 @@ __global__ __launch_bounds__(1024) void bn_stats_t_kernel(const TZ* __restrict__
         for (; m < M; m += st) add(ld4<TZ>(x + m * C + c));
     }
     bn_block_reduce(acc, sums, C, c0);
-}
-
-int bn_reduce_slabs(long long M, int C) {                                      // 64-row slabs of the 1024-thread reductions
-    long long gy = (M + 63) / 64;
-    const long long cap = (512 + cdiv(C, 64) - 1) / cdiv(C, 64);
-    if (gy > cap) gy = cap;
-    return gy < 1 ? 1 : (int)gy;
-}
-
-int bn_row_slabs(long long M, int C) {
-    long long gy = (M + 63) / 64;
-    const long long cap = (2048 + cdiv(C, 64) - 1) / cdiv(C, 64);
-    if (gy > cap) gy = cap;
-    return gy < 1 ? 1 : (int)gy;
 }
 
 __global__ void bn_finalize_t_kernel(const double* __restrict__ sums, float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ run_mean,
@@ -478,10 +428,7 @@ int launch_wgrad(WgK a, hipStream_t stream) {
     if (nsplit > a.ntiles) nsplit = a.ntiles;
     if (nsplit < 1) nsplit = 1;
     a.nsplit = nsplit;
-    auto fn = wgrad_bf16_kernel<K, S, TH, BMT, BNT, OCC>;
-    MT4_RAISE_LDS(fn);
-    hipLaunchKernelGGL(fn, dim3((unsigned)(pairs * nsplit)), dim3(256), LDS, stream, a);
-    return mt4_check_launch();
+    return mt4_launch<wgrad_bf16_kernel<K, S, TH, BMT, BNT, OCC>>(dim3((unsigned)(pairs * nsplit)), dim3(256), LDS, stream, a);
 }
 
 // ------------------------------------------------------------------------------------------------ pooling backward, packed-weight copy

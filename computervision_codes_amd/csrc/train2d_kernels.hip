@@ -13,29 +13,6 @@
 // (64 channels x 64 row phases), at most ~512 per launch: every workgroup ends in 128 float64 atomics on its slab's 128 addresses, and 2048
 // workgroups of 256 threads on a 64-channel map made those same-address chains (~25 ns a link at the L2) longer than the stream itself
 // (profiles/r03_bn_training_kernels.txt; the bf16-tensor twins live in train2d_bf16.hip)
-__device__ __forceinline__ void bn_block_reduce(double (&acc)[8], double* __restrict__ sums, int C, int c0) {
-    __shared__ double red[16][8][17];               // [wave][value][channel group], padded
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {                   // the 4 row phases of a wave
-        acc[j] += __shfl_xor(acc[j], 16);
-        acc[j] += __shfl_xor(acc[j], 32);
-    }
-    if (lane < 16) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) red[w][j][lane] = acc[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 128) {                        // 16 channel groups x 8 values
-        const int g = threadIdx.x & 15, j = threadIdx.x >> 4;
-        double t = 0.0;
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) t += red[rr][j][g];
-        const int c = c0 + g * 4 + (j & 3);
-        if (c < C) atomicAdd(sums + (j >> 2) * C + c, t);
-    }
-}
-
 __global__ __launch_bounds__(1024) void bn_stats_kernel(const float* __restrict__ x, double* __restrict__ sums, long long M, int C) {
     const int c0 = blockIdx.x * 64, c = c0 + (threadIdx.x & 15) * 4;
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -53,20 +30,6 @@ __global__ __launch_bounds__(1024) void bn_stats_kernel(const float* __restrict_
         for (; m < M; m += st) add(*(const float4*)(x + m * C + c));
     }
     bn_block_reduce(acc, sums, C, c0);
-}
-
-static inline int bn_reduce_slabs(long long M, int C) {                      // 64-row slabs of the 1024-thread reductions
-    long long gy = (M + 63) / 64;
-    const long long cap = (512 + cdiv(C, 64) - 1) / cdiv(C, 64);
-    if (gy > cap) gy = cap;
-    return gy < 1 ? 1 : (int)gy;
-}
-
-static inline int bn_row_slabs(long long M, int C) {                         // 16-row slabs of the 256-thread streaming kernels
-    long long gy = (M + 63) / 64;
-    const long long cap = (2048 + cdiv(C, 64) - 1) / cdiv(C, 64);
-    if (gy > cap) gy = cap;
-    return gy < 1 ? 1 : (int)gy;
 }
 
 // pass 2: batch mean / biased variance -> (mean, invstd); running stats with momentum and the UNBIASED variance (torch)

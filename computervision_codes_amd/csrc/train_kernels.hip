@@ -3,12 +3,6 @@
 // (the reference trains in fp32); the data gradients reuse the forward implicit-GEMM kernel with transposed weights.
 #include "mt4_common.h"
 
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------ conv1d weight gradient
 // dW[co][tap*Cin + ci] (+)= sum_{b,t} dY[b,t][co] * X[b, t + tap*dil - pad][ci]        (zero outside [0,T))
 // The contraction index (time) is the ROW index of both operands, which is exactly the operand shape of the fp32 MFMA

@@ -31,12 +31,6 @@ template <typename T> __device__ __forceinline__ void st1(T* p, float v);
 template <> __device__ __forceinline__ void st1<float>(float* p, float v) { *p = v; }
 template <> __device__ __forceinline__ void st1<u16>(u16* p, float v) { *p = f32_to_bf16(v); }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------ LayerNorm (+ row gather)
 // y[m][0..G*C) = LN( concat_g x[src(m,g)][0..C) ), src(m,g) = (m / L_out) * L_in + map[(m % L_out) * G + g]  (map NULL:
 // identity, G = 1).  One wave per output row, values kept in registers (two-pass mean / variance in fp32).
@@ -299,7 +293,6 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ q,
     }
 }
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float wa_max3(float a, float b, float c) {      // (fmaxf chains compile to v_max_f32 + canonicalising copies: 47 instructions for 36 scores)
     float r;
@@ -1090,7 +1083,6 @@ extern "C" int mt4_kd_mix(const float* s, const float* tea_i, const float* tea_v
 // 4 consecutive keys per tile: the softmax row lives in 4 lanes (2 xor-shuffles), and the probabilities are already in
 // B-operand layout for O^T = V^T P^T (k-slot (q,e) of a 32-key block = key 16*kt + 4q + e for e < 4, the next tile's
 // for e >= 4; the V^T fragment is read in the same order), so P never touches LDS.
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 
 template <int NT, int NW = 4>  // key/query tiles of 16; waves per workgroup

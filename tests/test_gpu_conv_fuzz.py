@@ -2,8 +2,8 @@
 paddings, ragged M / N, residual, activations, fp32 (exact MFMA chain, tight tolerance) and bf16, against torch's CPU conv2d.
 
 bf16 also element by element against float64 (`bf16_bounds`): the kernel starts its fp32 accumulators at the fp32 bias
-(igemm_conv.hip:198-209), adds the bf16 residual and applies ReLU / GELU in fp32, and rounds once when it stores (`pack_bf16x2` of the staged
-epilogue, `f32_to_bf16` of the direct one, igemm_conv.hip:591-668); the reference rounds nowhere after the operands."""
+(igemm_conv.hip:146-157), adds the bf16 residual and applies ReLU / GELU in fp32, and rounds once when it stores (`pack_bf16x2` of the staged
+epilogue, `f32_to_bf16` of the direct one, igemm_conv.hip:539-616); the reference rounds nowhere after the operands."""
 import numpy as np
 import pytest
 import torch

@@ -1,8 +1,8 @@
 """GPU: each C-ABI kernel against the CPU oracle op (torch fp32 on the host) on seeded inputs.
 
 The bf16 convolutions are also checked element by element against float64 (`bf16_bounds`): `mt4_conv_nhwc` starts its fp32 accumulators at
-the fp32 bias (igemm_conv.hip:198-209; K-split tiles: group 0 only, partial tiles added in fp32 in LDS), adds the bf16 residual and applies the
-activation in fp32, and rounds once when it stores (igemm_conv.hip:591-668); the reference rounds nowhere after the operands."""
+the fp32 bias (igemm_conv.hip:146-157; K-split tiles: group 0 only, partial tiles added in fp32 in LDS), adds the bf16 residual and applies the
+activation in fp32, and rounds once when it stores (igemm_conv.hip:539-616); the reference rounds nowhere after the operands."""
 import numpy as np
 import pytest
 import torch
@@ -81,16 +81,16 @@ PATCH_SHAPES = [
 ]
 
 
-PATCH_TILES = {  # id: (BM, BN, waves, weight stages)   (igemm_conv.hip launch_patch_tile; the other ids of 21..32 are retired variants)
+PATCH_TILES = {  # id: (BM, BN, waves, weight stages)   (the P entries of igemm_conv.hip's MT4_CONV_TILES; the other ids of 21..32 are retired)
     23: (256, 256, 16, 2), 24: (256, 64, 8, 2), 26: (256, 128, 16, 2), 30: (128, 128, 4, 2), 32: (256, 128, 8, 2)}
 
 
 def _patch_tile_fits(tile, W, Cin):
-    """launch_patch3x3's own rule: the patch (double-buffered over channel slices) + the weight ring fit 160 KB of LDS, the next
+    """the library's own rule (igemm_conv.hip patch3x3_lds): the patch (double-buffered over channel slices) + the weight ring fit 160 KB of LDS, the next
     slice's patch pieces fit the taps they ride along with, and the weights-resident variants take single-slice layers only"""
     bm, bn, waves, ws = PATCH_TILES[tile]
     spt = Cin // 64
-    pra = (bm + 2 * W + 2 + 7) // 8 * 8
+    pra = (bm + 2 * W + 2 + 2 + 7) // 8 * 8        # + 2: the rows of zeros out-of-image taps read
     lds = (2 if spt > 1 else 1) * pra * 128 + ws * bn * 128
     if ws == 9 and spt != 1:
         return False
@@ -417,7 +417,7 @@ def test_preprocess_u8_s2d_matches_torch(cuda, b, h, w):
 
 
 def _check_interp_bf16(x, u, t_out):
-    """`interp_linear_rows_kernel` (misc_kernels.hip:398-413): the source position src = (Tin / Tout) (w + 0.5) - 0.5 and the weights
+    """`interp_linear_rows_kernel` (misc_kernels.hip:388-403): the source position src = (Tin / Tout) (w + 0.5) - 0.5 and the weights
     1 - l, l are fp32 (as in torch), the blend is fp32, one rounding at the store.  Reference: the exact position in float64; the bound adds the
     position's fp32 error, 4 * 2^-24 (src + 1) per unit of |x1 - x0|, to the accumulation term of the two-term blend."""
     t_in = x.shape[1]
@@ -445,7 +445,7 @@ def test_avgpool1d_and_linear_interpolation_rows(cuda, dtype, b, t, c):
     ref = F.avg_pool1d(x.float().permute(0, 2, 1), 7, 3).permute(0, 2, 1)
     assert tuple(y.shape) == tuple(ref.shape) == (b, (t - 7) // 3 + 1, c)
     assert (y.float().cpu() - ref).abs().max().item() <= tol * max(1.0, ref.abs().max().item())
-    if dtype == torch.bfloat16:   # fp32 sum of the 7 rows, / 7, one rounding (misc_kernels.hip:391-394)
+    if dtype == torch.bfloat16:   # fp32 sum of the 7 rows, / 7, one rounding (misc_kernels.hip:381-384)
         x64 = x.double().permute(0, 2, 1)
         check_bf16(y.cpu(), F.avg_pool1d(x64, 7, 3).permute(0, 2, 1), acc64=F.avg_pool1d(x64.abs(), 7, 3).permute(0, 2, 1), k=8,
                    what=f"avgpool1d_rows {(b, t, c)}")

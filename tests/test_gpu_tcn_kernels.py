@@ -4,7 +4,7 @@ call, ragged channel counts), residual + ReLU epilogue, fp32 (exact MFMA chain: 
 
 bf16 also element by element against float64 (`bf16_bounds`): `mt4_tcn_conv` sums the taps in fp32 MFMA accumulators, adds the fp32 bias and
 the bf16 residual and applies ReLU in fp32 after the K loop, and rounds once when it stores (`pack_bf16x2` / `f32_to_bf16`,
-tcn_kernels.hip:312-344); its fp32-output form stores the same sum unrounded."""
+tcn_kernels.hip:292-324); its fp32-output form stores the same sum unrounded."""
 import numpy as np
 import pytest
 import torch

@@ -179,7 +179,7 @@ def test_conv_epilogue_statistics_refusals(cuda):
 
 
 def _check_maxpool_bwd(x, dy, dx):
-    """`maxpool3x3s2_bwd_bf16` (both kernels, train2d_bf16.hip:496-533 and the tiled one): the fp32 sum of the (up to 4) window gradients a
+    """`maxpool3x3s2_bwd_bf16` (both kernels, train2d_bf16.hip:443-480 and the tiled one): the fp32 sum of the (up to 4) window gradients a
     pixel takes, one rounding.  Reference: the same routing by float64 autograd (ties: the first maximum in scan order, as in torch)"""
     xt = x.double().permute(0, 3, 1, 2).clone().requires_grad_()
     xa = x.double().permute(0, 3, 1, 2).clone().requires_grad_()
@@ -224,7 +224,7 @@ def test_pool_backward_and_repack_bf16(cuda):
     df = _rand((3, 128), 3)
     dxa = ops.avgpool_bwd_bf16(df.to(cuda), 3, 21, 128)
     assert (dxa.float().cpu() - (df / 21)[:, None, :].expand(3, 21, 128)).abs().max().item() <= 2 ** -8 * float(df.abs().max()) / 21
-    # fp32 df * fp32(1 / 21), one rounding (train2d_bf16.hip:538-547)
+    # fp32 df * fp32(1 / 21), one rounding (train2d_bf16.hip:485-494)
     ref64 = (df.double() / 21)[:, None, :].expand(3, 21, 128)
     check_bf16(dxa.cpu(), ref64, acc64=ref64.abs(), k=2, what="avgpool_bwd_bf16")
     # packed fp32 -> packed bf16 == packing the bf16-rounded weights directly

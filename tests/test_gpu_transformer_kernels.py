@@ -22,7 +22,7 @@ def _tol(dtype, f32=2e-5, bf16=2e-2):
 
 
 def _ln64(x64, g, b, eps=1e-5):
-    """float64 LayerNorm over the last dim and its accumulation scale: `layernorm_kernel` (transformer_kernels.hip:44-90) sums the row in fp32,
+    """float64 LayerNorm over the last dim and its accumulation scale: `layernorm_kernel` (transformer_kernels.hip:38-84) sums the row in fp32,
     then the squared deviations from that mean (two passes), and stores (x - mean) * rstd * gamma + beta with one rounding.  The fp32 error of
     the mean reaches the output as |gamma| rstd mean|x|, that of rstd as |gamma x_hat|."""
     mu = x64.mean(-1, keepdim=True)
@@ -110,7 +110,7 @@ def _check_attn_bf16(out, q, k, v, scale, bias, mask, nw, *, mfma, region=False,
     """`out` [B*N, H*hd] of a bf16 attention core against float64 on the same bf16 q / k / v ([B,H,N,hd]).
 
     mfma: the matrix-unit kernels (mha_mfma_kernel, window_attention_mfma_kernel) multiply Q by the scale in fp32 and round it to bf16 before
-    the score MFMA (transformer_kernels.hip:351,1176) -- the reference rounds it there too; they round the unnormalised probabilities
+    the score MFMA (transformer_kernels.hip:344,1176) -- the reference rounds it there too; they round the unnormalised probabilities
     p_j = exp(s_j - max) to bf16 as the B operand of the P.V MFMA while the normaliser is the fp32 sum of the unrounded p_j, and scale the fp32
     result by 1 / sum before the one rounding of the store (:403-458, :1302-1337).  That P rounding is not emulated: it adds at most
     2^-9 * sum_j p_j |v_j| per output, and the bound allows 2^-8 of it.  The generic kernel (attention_kernel, :179-307) keeps q * scale and P in
@@ -175,7 +175,7 @@ def test_attention_core(cuda, cfg, dtype):
     vf = kv.float()[:, c:].reshape(B, Nk, H, hd).permute(0, 2, 1, 3)
     ref = _attn_ref(qf, kf, vf, scale, bias, mask, cfg["nw"]).permute(0, 2, 1, 3).reshape(B * Nq, c)
     assert (out.float().cpu() - ref).abs().max().item() < _tol(dtype, 2e-5, 2e-2)
-    if dtype == torch.bfloat16:   # (mt4_attention's dispatch, transformer_kernels.hip:762: the matrix-unit core for hd 256 / 384 without bias / mask)
+    if dtype == torch.bfloat16:   # (mt4_attention's dispatch, transformer_kernels.hip:755: the matrix-unit core for hd 256 / 384 without bias / mask)
         mfma = hd in (256, 384) and bias is None and mask is None and Nk <= 160
         _check_attn_bf16(out, qf, kf, vf, scale, bias, mask, cfg["nw"], mfma=mfma, what=f"attention core {cfg}")
 
@@ -273,7 +273,7 @@ def test_patchify_matches_conv4x4(cuda, dtype):
         rows = ops.patchify(inp, 4, dtype, synth.IMAGENET_MEAN, synth.IMAGENET_STD)
         got = rows.float().cpu() @ w.view(16, 48).t()
         assert (got - ref).abs().max().item() < _tol(dtype, 1e-4, 5e-2)
-    if dtype == torch.bfloat16:   # float input: the rows are the fp32 pixels in (c, kh, kw) order, each rounded once (transformer_kernels.hip:854)
+    if dtype == torch.bfloat16:   # float input: the rows are the fp32 pixels in (c, kh, kw) order, each rounded once (transformer_kernels.hip:847)
         rows64 = F.unfold(xn.double(), 4, stride=4).transpose(1, 2).reshape(-1, 48)
         check_bf16(ops.patchify(xn.to(cuda), 4, dtype).cpu(), rows64, what="patchify rows from float input")
     if dtype == torch.bfloat16:   # uint8 frames, P = 4, bf16 rows run a kernel of their own (12 bytes per thread, table-driven): the generic kernel's bits
@@ -290,7 +290,7 @@ def test_small_elementwise_pieces(cuda, dtype):
     p = _rand((10, 64), 42).to(dtype)
     got = ops.add_rowbcast(x.to(cuda), p.to(cuda)).float().cpu()
     assert (got - (x.float().view(3, 10, 64) + p.float()).view(-1, 64)).abs().max().item() < _tol(dtype, 1e-6, 2e-2)
-    if dtype == torch.bfloat16:   # fp32 add, one rounding (transformer_kernels.hip:941-956): torch's own bf16 add, bit for bit
+    if dtype == torch.bfloat16:   # fp32 add, one rounding (transformer_kernels.hip:934-949): torch's own bf16 add, bit for bit
         assert torch.equal(ops.add_rowbcast(x.to(cuda), p.to(cuda)).cpu().view(torch.int16), (x.view(3, 10, 64) + p).view(-1, 64).view(torch.int16))
     hs = _rand((4 * 6, 256), 43).to(dtype)
     W, b = _rand((6, 256), 44), _rand((6,), 45)
@@ -302,7 +302,7 @@ def test_small_elementwise_pieces(cuda, dtype):
     got = ops.dwconv1d_k3(xd.to(cuda), wd.to(cuda), bd.to(cuda), act="gelu").float().cpu()
     ref = F.gelu(F.conv1d(xd.float().transpose(1, 2), wd.unsqueeze(1), bd, padding=1, groups=64)).transpose(1, 2)
     assert (got - ref).abs().max().item() < _tol(dtype, 1e-5, 2e-2)
-    if dtype == torch.bfloat16:   # three fp32 taps + fp32 bias, activation in fp32, one rounding (transformer_kernels.hip:1019-1025)
+    if dtype == torch.bfloat16:   # three fp32 taps + fp32 bias, activation in fp32, one rounding (transformer_kernels.hip:1012-1018)
         x64 = xd.double().transpose(1, 2)
         pre64 = F.conv1d(x64, wd.double().unsqueeze(1), bd.double(), padding=1, groups=64).transpose(1, 2)
         acc64 = F.conv1d(x64.abs(), wd.double().abs().unsqueeze(1), bd.double().abs(), padding=1, groups=64).transpose(1, 2)
