@@ -48,17 +48,94 @@ def _common(p: argparse.ArgumentParser):
                    help="device: inflate + PNG unfiltering on the GPU (mt4_png_inflate / mt4_png_unfilter_rgb8), the host only reads the files")
 
 
+def _flag(*names, **kw):
+    return names, kw
+
+
+# the flags of the two frame trainers (`Spatial_cnn/run.py`, `Spatial_transformer/run.py`: --rates `:66`, --temp `:70`).  The reference's
+# Spatial_transformer dataloader reads args.teacher_pred_version / teacher_feat_version (`dataloader.py:217-238`) though its run.py declares
+# neither flag: same names and defaults as the student's `Spatial_cnn/run.py`
+_OPERAND_DTYPE = _flag("--operand_dtype", type=str, default="fp32", choices=["fp32", "bf16"],
+                       help="bf16: the GEMM operands of the training step in bf16 (Spatial_cnn: the convolutions' activations, gradients and weight copies; "
+                            "the transformer stages: operand copies of the nn.Linear GEMMs), master weights, accumulation and sums fp32")
+_FRAME_TRAIN = [
+    _flag("--teacher_feat_version", type=str, default="Q2L"),
+    _flag("--teacher_pred_version", type=str, default="Q2LMSTCT"),
+    _flag("--augmentation_list", type=str, nargs="*", default=["original", "vflip", "hflip", "contrast", "rot90"]),
+    _flag("--train_transform", type=str, default="host", choices=["host", "device"],
+          help="device: flips, autocontrast, rotation and the second Resize of the train transform on the GPU (mt4_aug_*), the same bytes "
+               "as Pillow for the same draws; the PNGs are decoded as --png_decode says"),
+    _flag("--prefetch", type=int, default=0,
+          help="K > 0: training batches come from `loader.FrameLoader` -- chunks of up to K batches (at most 1024 frames) decoded, transformed "
+               "and gathered per call on helper threads and side streams while the step runs, labels and teacher rows resident on the device; "
+               "the same batches as 0 (the synchronous loader), only faster"),
+    _flag("--rates", type=float, nargs="+", default=[1, 0, 0.1]),
+    _flag("--temp", type=int, default=4),
+    _flag("--pretrain_dir", type=str, default=""),
+    _OPERAND_DTYPE,
+]
+# stage -> (the flags every entry point of the stage parses, the flags of its trainer alone), on top of `_common` and -- the trainer --
+# `add_schedule_flags`.  --teacher_dim: the student mixes in the 1536-wide Swin-L feature (`Spatial_cnn/run.py`), the transformer stage's
+# `loss_type all` variant the 512-wide ResNet-18 one (`Spatial_transformer/run.py:82`, `test.py:82`)
+_FLAGS = {
+    "spatial_cnn": ([_flag("--network", type=str, default="resnet18"),
+                     _flag("--student_dim", type=int, default=512),
+                     _flag("--teacher_dim", type=int, default=1536)], _FRAME_TRAIN),
+    "spatial_transformer": ([_flag("--backbone", type=str, default="swin_L_384_22k"),
+                             _flag("--img_size", type=int, default=384),
+                             _flag("--hidden_dim", type=int, default=1536),
+                             _flag("--teacher_dim", type=int, default=512)],
+                            _FRAME_TRAIN + [_flag("--drop_path_rate", type=float, default=0.1)]),          # `swin_transformer.py:488`
+    "mstct": ([_flag("--input_dim", type=int, default=1536),
+               _flag("--final_embedding_dim", type=int, default=512)],
+              [_flag("--num_clips", type=int, default=256, help="window length (the reference hard-codes 256, dataloader.py:237)"), _OPERAND_DTYPE]),
+    # --mask_draw / --subclip (not in the reference) device: the step's random pieces are drawn by HIP kernels from (seed, step) and whole-video
+    # steps replay as hipGraphs; host: drawn with torch's generator and uploaded.  reference: `Temporal_tenco/dataloader.py:219-222` sub-clip sampling
+    "tenco": ([_flag("--num_layers_PG", default=11, type=int),
+               _flag("--num_layers_R", default=10, type=int),
+               _flag("--num_R", default=3, type=int),
+               _flag("--fpn", action="store_true"),
+               _flag("--mask", action="store_true"),
+               _flag("--output", default=False, type=bool),
+               _flag("--hier", default=False, type=bool),
+               _flag("--input_dim", type=int, default=512)],
+              [_flag("--mask_draw", choices=("host", "device"), default="host"),
+               _flag("--subclip", choices=("off", "reference"), default="off")]),
+}
+_LATEST = {"spatial_cnn": "_latest.pth", "spatial_transformer": "_latest.pth", "tenco": "_latest.pth",
+           "mstct": "latest.pth"}                            # <stem> + this = the trainer's newest checkpoint; MS-TCT: no underscore (`Temporal_mstct/run.py:268`)
+_MSTCT_ARCH = ((256, 384, 576, 864), 2, 8, 8)               # inter_channels, num_block, head, mlp_ratio (`Temporal_mstct/run.py`)
+
+
+def _parser(stage: str, train: bool) -> argparse.ArgumentParser:
+    """the parser of a stage's entry points (of its trainer with `train`); they read it with `parse_known_args`: unknown flags are ignored"""
+    p = argparse.ArgumentParser()
+    _common(p)
+    if train:
+        add_schedule_flags(p)
+    own, train_only = _FLAGS[stage]
+    for names, kw in own + (train_only if train else []):
+        p.add_argument(*names, **kw)
+    return p
+
+
+def _dtype(name: str) -> torch.dtype:
+    return torch.float32 if name == "fp32" else torch.bfloat16
+
+
 def _chlg(F) -> bool:
     """`set_chlg_eval` of the reference's drivers (`Spatial_cnn/run.py:122`): the challenge evaluation protocol (null triplets left out of the
     100-way AP) for the `*challenge*` dataset variants"""
     return "challenge" in str(getattr(F, "dataset_variant", ""))
 
 
-def _stem(F, kfold: int = None, task_dir: bool = False) -> str:
+def _stem(F, kfold: int = None, task_dir: bool = False, model: str = None) -> str:
     """`./__checkpoint__/run_<version>[_<task>]/<modelname>`, the stem of a run's log and checkpoints.  modelname: the spatial drivers'
     `<model>_l<variant>_cholect<kfold>` when kfold is given, else the temporal drivers' `<model>_l8_cholect<variant>_k<kfold>_batchnorm_lowres`
-    (`Temporal_tenco/run.py:137-142`); task_dir: the task suffix of single-task runs (`Spatial_transformer/run.py:86-88`, `Temporal_mstct/run.py:88-90`)"""
-    name = f"{F.model}_l{F.dataset_variant}_cholect{kfold}" if kfold is not None else f"{F.model}_l8_cholect{F.dataset_variant}_k{F.kfold}_batchnorm_lowres"
+    (`Temporal_tenco/run.py:137-142`); task_dir: the task suffix of single-task runs (`Spatial_transformer/run.py:86-88`, `Temporal_mstct/run.py:88-90`);
+    model: instead of --model (the spatial `test.py` spell their checkpoint 'rendezvous' whatever --model says)"""
+    model = model or F.model
+    name = f"{model}_l{F.dataset_variant}_cholect{kfold}" if kfold is not None else f"{model}_l8_cholect{F.dataset_variant}_k{F.kfold}_batchnorm_lowres"
     return os.path.join(f"./__checkpoint__/run_{F.version}" + (f"_{F.loss_type}" if task_dir and F.loss_type != "all" else ""), name)
 
 
@@ -78,6 +155,49 @@ def _write_report(logfile: str, m, loss_type: str, chlg: bool, style: str, pckl:
     for ln in lines:
         _log(logfile, ln)
     return res
+
+
+def _eval_model(stage: str, F, src):
+    """the inference model of `stage` built from F with a checkpoint loaded.  src = a list of checkpoint files: --test_ckpt instead of the
+    first when given, then the first one on disk (the last if none is: the load names it), the model in --dtype; or a trainer's state dict
+    (validation): the fp32 model.  Strict loads, except a Temporal_tenco FILE: the model's own keys of it (`Temporal_tenco/run.py:520`)"""
+    from_file = not isinstance(src, dict)
+    dtype = _dtype(F.dtype) if from_file else torch.float32
+    if stage == "spatial_cnn":
+        from .spatial_cnn import VideoNas
+        model = VideoNas(args=argparse.Namespace(**{**vars(F), "train": False}), dtype=dtype)     # (args.train gates the KD branch, `network.py:47`)
+    elif stage == "spatial_transformer":
+        from .spatial_transformer import build_q2l
+        model = build_q2l(F, dtype=dtype)
+    elif stage == "mstct":
+        from .temporal_mstct import VideoNas
+        model = VideoNas(F, *_MSTCT_ARCH, F.input_dim, F.final_embedding_dim, dtype=dtype)
+    else:
+        from .temporal_tenco import VideoNas
+        model = VideoNas(F, F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100)         # (fp32 whatever --dtype says)
+    if from_file:
+        files = [F.test_ckpt or src[0]] + list(src[1:])
+        src = torch.load(next((f for f in files if os.path.exists(f)), files[-1]), map_location="cpu")
+        if stage == "tenco":
+            known = dict(model._table)
+            return model.eval().load_state_dict({k: v for k, v in src.items() if k in known}, strict=False)
+    return model.eval().load_state_dict(src, strict=True)
+
+
+def _labelled_share(F, videos):
+    """-> (the labels of `videos`, the videos of this rank under `extract.shard_videos` by frame count, in file order)"""
+    labels = {v: cholect.load_labels(F.data_dir, v) for v in videos}
+    mine = extract.shard_videos(videos, [len(labels[v]["ivt"]) for v in videos], *_dist())
+    return labels, [videos[vi] for vi in mine]
+
+
+def _on_rank0(fn):
+    """fn() on rank 0 alone ({} on the others); every rank meets at the barrier behind it, whatever fn raised: what rank 0 wrote is on disk
+    before any rank goes on to the next stage"""
+    try:
+        return fn() if _dist()[0] == 0 else {}
+    finally:
+        _barrier()
 
 
 # ------------------------------------------------------------------------------------------------ Spatial_cnn/test.py
@@ -111,55 +231,27 @@ def spatial_cnn_eval(argv=None) -> Dict[str, float]:
     mean-AP row (I / V / T disentangled from the 100-way triplet head when --loss_type all, head-wise otherwise, `:518-525`), top-5 / 10 / 20
     per component.  Under torchrun whole videos are sharded over the ranks and their (labels, scores) meet in one host-side gather, so N
     ranks log exactly the single-rank report; rank 0 writes it."""
-    from .spatial_cnn import VideoNas
-    p = argparse.ArgumentParser()
-    _common(p)
-    p.add_argument("--network", type=str, default="resnet18")
-    p.add_argument("--student_dim", type=int, default=512)
-    p.add_argument("--teacher_dim", type=int, default=1536)
-    F, _ = p.parse_known_args(argv)
-    F.train = False
-    rank, world = _dist()
+    F = _parser("spatial_cnn", False).parse_known_args(argv)[0]
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold)
-    ckpt = F.test_ckpt or stem + ".pth"
-    model = VideoNas(args=F, dtype=torch.float32 if F.dtype == "fp32" else torch.bfloat16).eval()
-    model.load_state_dict(torch.load(ckpt, map_location="cpu"))
+    model = _eval_model("spatial_cnn", F, [stem + ".pth"])
     _, _, videos = cholect.split_videos(F.dataset_variant, kfold)
-    labels = {v: cholect.load_labels(F.data_dir, v) for v in videos}
-    mine = extract.shard_videos(videos, [len(labels[v]["ivt"]) for v in videos], rank, world)
-    _, scores_local = _spatial_cnn_videos(F, model, [videos[vi] for vi in mine], labels)
+    labels, mine = _labelled_share(F, videos)
+    _, scores_local = _spatial_cnn_videos(F, model, mine, labels)
     m = gather_recognition(scores_local, videos)
-    res = {}
-    try:
-        if rank == 0:
-            res = _write_report(stem + ".log", m, F.loss_type, _chlg(F), "spatial_cnn")
-    finally:
-        _barrier()
-    return res
+    return _on_rank0(lambda: _write_report(stem + ".log", m, F.loss_type, _chlg(F), "spatial_cnn"))
 
 
 def spatial_cnn_test(argv=None) -> Dict[str, np.ndarray]:
-    from .spatial_cnn import VideoNas
-    p = argparse.ArgumentParser()
-    _common(p)
-    p.add_argument("--network", type=str, default="resnet18")
-    p.add_argument("--student_dim", type=int, default=512)
-    p.add_argument("--teacher_dim", type=int, default=1536)
-    F, _ = p.parse_known_args(argv)
-    F.train = False
+    F = _parser("spatial_cnn", False).parse_known_args(argv)[0]
     rank, world = _dist()
-    modelname = f"{F.model}_l{F.dataset_variant}_cholect{F.kfold}"   # `test.py:126-128`
-    model_dir = f"./__checkpoint__/run_{F.version}"
-    logfile = os.path.join(model_dir, modelname + ".log")
-    ckpt = F.test_ckpt or f"./__checkpoint__/run_{F.version}/rendezvous_l{F.dataset_variant}_cholect{F.kfold}.pth"
-    model = VideoNas(args=F, dtype=torch.float32 if F.dtype == "fp32" else torch.bfloat16).eval()
-    model.load_state_dict(torch.load(ckpt, map_location="cpu"))
+    # `test.py:126-128`: --kfold as given (no crossval rule), the checkpoint spelled 'rendezvous' whatever --model says
+    logfile = _stem(F, F.kfold) + ".log"
+    model = _eval_model("spatial_cnn", F, [_stem(F, F.kfold, model="rendezvous") + ".pth"])
     videos = cholect.extraction_videos(F.dataset_variant, F.kfold)
-    labels = {v: cholect.load_labels(F.data_dir, v) for v in videos}
-    mine = extract.shard_videos(videos, [len(labels[v]["ivt"]) for v in videos], rank, world)
+    labels, mine = _labelled_share(F, videos)
     t0 = time.time()
-    feats_local, scores_local = _spatial_cnn_videos(F, model, [videos[vi] for vi in mine], labels)
+    feats_local, scores_local = _spatial_cnn_videos(F, model, mine, labels)
     merged = extract.gather_feats(feats_local)
     m = gather_recognition(scores_local, videos)               # the videos of ALL ranks in file order: N ranks log the 1-rank numbers
     all_feats = {featfile.video_key(v): merged[featfile.video_key(v)] for v in videos}
@@ -209,19 +301,6 @@ def _teacher_files(F, kfold):
     tdir = lambda ver, task, kind: featfile.feats_path("..", ver, kfold, task, kind)
     return ({t: featfile.read_feats(tdir(F.teacher_pred_version, t, "pred")) for t in "ivt"},
             {t: featfile.read_feats(tdir(F.teacher_feat_version, t, "feats")) for t in "ivt"})
-
-
-def _add_train_transform_flag(p: argparse.ArgumentParser):
-    p.add_argument("--train_transform", type=str, default="host", choices=["host", "device"],
-                   help="device: flips, autocontrast, rotation and the second Resize of the train transform on the GPU (mt4_aug_*), the same bytes "
-                        "as Pillow for the same draws; the PNGs are decoded as --png_decode says")
-
-
-def _add_prefetch_flag(p: argparse.ArgumentParser):
-    p.add_argument("--prefetch", type=int, default=0,
-                   help="K > 0: training batches come from `loader.FrameLoader` -- chunks of up to K batches (at most 1024 frames) decoded, transformed "
-                        "and gathered per call on helper threads and side streams while the step runs, labels and teacher rows resident on the device; "
-                        "the same batches as 0 (the synchronous loader), only faster")
 
 
 _WARNED_TRANSFORM = False
@@ -292,36 +371,19 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     ExponentialLR per epoch, validation mAP every --val_interval epochs with `_latest.pth` / best `.pth` like `weight_mgt` (:258-269)."""
     import random
 
-    from .spatial_cnn import VideoNas
     from .spatial_cnn_train import SpatialCnnTrainer
     from . import shapes, synth
-    p = argparse.ArgumentParser()
-    _common(p)
-    add_schedule_flags(p)
-    p.add_argument("--network", type=str, default="resnet18")
-    p.add_argument("--student_dim", type=int, default=512)
-    p.add_argument("--teacher_dim", type=int, default=1536)
-    p.add_argument("--teacher_feat_version", type=str, default="Q2L")
-    p.add_argument("--teacher_pred_version", type=str, default="Q2LMSTCT")
-    p.add_argument("--augmentation_list", type=str, nargs="*", default=["original", "vflip", "hflip", "contrast", "rot90"])
-    _add_train_transform_flag(p)
-    _add_prefetch_flag(p)
-    p.add_argument("--rates", type=float, nargs="+", default=[1, 0, 0.1])
-    p.add_argument("--temp", type=int, default=4)
-    p.add_argument("--pretrain_dir", type=str, default="")
-    p.add_argument("--operand_dtype", type=str, default="fp32", choices=["fp32", "bf16"],
-                   help="bf16: the convolutions' GEMM operands in bf16 (activations, gradients, weight copies), master weights and sums fp32")
-    F, _ = p.parse_known_args(argv)
+    F = _parser("spatial_cnn", True).parse_known_args(argv)[0]
     if F.loss_type not in ("all", "i", "v", "t"):
         raise ValueError("--loss_type all | i | v | t (`Spatial_cnn/run.py:165-192`)")
     single = F.loss_type != "all"
     rank, world = _dist()
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold)
-    latest = stem + "_latest.pth"
+    latest = stem + _LATEST["spatial_cnn"]
     tr = SpatialCnnTrainer(F.network, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay, rates=F.rates, temp=float(F.temp),
                            teacher_dim=F.teacher_dim, loss_type=F.loss_type,
-                           operand_dtype=torch.bfloat16 if F.operand_dtype == "bf16" else torch.float32)
+                           operand_dtype=_dtype(F.operand_dtype))
     table = shapes.spatial_cnn_shapes(F.network, F.student_dim, F.teacher_dim, F.loss_type)
     sd = synth.fill_from_shapes(table, seed=F.seed)          # no torch.nn init here: deterministic synthetic start
     for src in (F.pretrain_dir, latest):                     # `load_model` (:272-278): keys present in the model, strict=False
@@ -334,9 +396,6 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     samples = [(v, i) for v in train_videos for i in range(len(labels[v]["ivt"]))]
     order_rng, aug_rng = random.Random(F.seed), random.Random(F.seed * 1000003 + rank)
     size = (F.image_height, F.image_width)
-    eval_args = argparse.Namespace(**vars(F))
-    eval_args.train = False
-
     tables = _sample_tables(F, labels, tpred, tfeat, train_videos)
 
     def train_epoch(epoch):
@@ -354,8 +413,7 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
         return tot, len(mine)
 
     def validate(state):
-        model = VideoNas(args=eval_args, dtype=torch.float32).eval()
-        model.load_state_dict(state)
+        model = _eval_model("spatial_cnn", F, state)
         gi = "ivt".index(F.loss_type) if single else 3
         return _frame_validation(F, val_videos, labels, size, 256, lambda fr: model.extract_u8(fr)[gi][1])
 
@@ -364,54 +422,25 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
 
 # ------------------------------------------------------------------------------------------------ Temporal_tenco/run.py -e
 def tenco_eval(argv=None) -> Dict[str, float]:
-    from .temporal_tenco import VideoNas
-    p = argparse.ArgumentParser()
-    _common(p)
-    p.add_argument("--num_layers_PG", default=11, type=int)
-    p.add_argument("--num_layers_R", default=10, type=int)
-    p.add_argument("--num_R", default=3, type=int)
-    p.add_argument("--fpn", action="store_true")
-    p.add_argument("--mask", action="store_true")
-    p.add_argument("--output", default=False, type=bool)
-    p.add_argument("--hier", default=False, type=bool)
-    p.add_argument("--input_dim", type=int, default=512)
-    # (not in the reference) device: the step's random pieces are drawn by HIP kernels from (seed, step) and whole-video steps replay as
-    # hipGraphs; host: drawn with torch's generator and uploaded.  reference: `Temporal_tenco/dataloader.py:219-222` sub-clip sampling
-    p.add_argument("--mask_draw", choices=("host", "device"), default="host")
-    p.add_argument("--subclip", choices=("off", "reference"), default="off")
-    add_schedule_flags(p)
-    F, _ = p.parse_known_args(argv)
+    F = _parser("tenco", True).parse_known_args(argv)[0]      # (this is the stage's `run.py`: -t trains first)
     if F.train:
         _tenco_train(F)
         if not F.test:
             return {}
-    if _dist()[0] != 0:      # under torchrun the evaluation, its log lines and the mAP pickle belong to rank 0 alone
-        _barrier()
-        return {}
-    try:
-        return _tenco_eval_rank0(F)
-    finally:
-        _barrier()
+    return _on_rank0(lambda: _tenco_eval_rank0(F))      # under torchrun the evaluation, its log lines and the mAP pickle belong to rank 0 alone
 
 
 def _tenco_eval_rank0(F) -> Dict[str, float]:
-    from .temporal_tenco import VideoNas
     stem = _stem(F)
     logfile = stem + ".log"
-    ckpt = F.test_ckpt or stem + ".pth"
-    if not os.path.exists(ckpt):   # the shipped scripts always pass --test_ckpt ..._latest.pth (Scripts/test_fold1.sh)
-        ckpt = stem + "_latest.pth"
-    model = VideoNas(F, F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100).eval()
-    sd = torch.load(ckpt, map_location="cpu")
-    model.load_state_dict({k: v for k, v in sd.items() if k in dict(model._table)}, strict=False)   # `run.py:520`
+    model = _eval_model("tenco", F, [stem + ".pth", stem + _LATEST["tenco"]])   # (the shipped scripts pass --test_ckpt ..._latest.pth, Scripts/test_fold1.sh)
     _, _, test_videos = cholect.split_videos(F.dataset_variant, F.kfold)
     feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, "all"))
     t0 = time.time()
     m = recognition_from(_tenco_scores(model, feats, test_videos, F.data_dir), test_videos)     # (rank 0 alone runs this pass)
     _log(logfile, f"eta {time.time() - t0:.3f} secs")
     # `run.py:529-570`: the pickled metric objects, then head-wise ('singletest') and disentangled per-category AP and both mean-AP rows
-    res = _write_report(logfile, m, F.loss_type, _chlg(F), "temporal_tenco", pckl=os.path.join(os.path.dirname(stem), f"mAPs_k{F.kfold}.pckl"))
-    return res
+    return _write_report(logfile, m, F.loss_type, _chlg(F), "temporal_tenco", pckl=os.path.join(os.path.dirname(stem), f"mAPs_k{F.kfold}.pckl"))
 
 
 def _tenco_scores(model, feats, vids, data_dir):
@@ -442,7 +471,6 @@ def _tenco_train(F):
     from .tenco_draws import tenco_clip
 
     from .tenco_train import TencoTrainer
-    from .temporal_tenco import VideoNas
     rank, world = _dist()
     stem = _stem(F)
     if not F.fpn:
@@ -453,7 +481,7 @@ def _tenco_train(F):
     tr = TencoTrainer(F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                       hier=bool(getattr(F, "hier", False)))      # --hier True: pooled refinement levels (`network.py:147,154-155`, `run.py:159-179`)
     from . import shapes, synth
-    init = stem + "_latest.pth"
+    init = stem + _LATEST["tenco"]
     if os.path.exists(init):
         tr.load_state_dict(torch.load(init, map_location="cpu"))
     else:   # no torch.nn init here: deterministic synthetic start (the reference starts from torch's default init)
@@ -472,7 +500,6 @@ def _tenco_train(F):
     device_draw, subclip = F.mask_draw == "device", F.subclip == "reference"
     clipped = [0, 0]                                               # this rank's steps of the epoch: on a clip, all
     gen = torch.Generator().manual_seed(F.seed + rank)
-    vmodel = VideoNas(F, F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100).eval() if rank == 0 else None
 
     def clip(length):                                              # (start, frames) of a training item
         s, n = tenco_clip(clip_rng, length)
@@ -506,7 +533,7 @@ def _tenco_train(F):
         return tot, len(mine)
 
     def validate(state):                                           # (`run.py:416-452`): best `.pth` by the triplet mAP
-        vmodel.load_state_dict(state)
+        vmodel = _eval_model("tenco", F, state)
         vm = recognition_from(_tenco_scores(vmodel, feats, val_videos, F.data_dir), val_videos) if val_videos else None
         head = F.loss_type if F.loss_type in ("i", "v", "t") else "ivt"
         score = float(vm[head].compute_video_AP()["mAP"]) if vm else 0.0
@@ -520,61 +547,47 @@ def _tenco_train(F):
 
 
 # ------------------------------------------------------------------------------------------------ Spatial_transformer/test.py
+def _q2l_chunks(F, v, ids, min_load: int = 1, prefetch: int = 1):
+    """the frames `ids` of video v in file order as device chunks of `extraction_batch(...)` frames (a frame's result does not depend on the
+    chunk it rides in).  They are loaded -- decoded on --decode_workers threads or on the device -- in whole chunks of at least `min_load`
+    frames, `prefetch` loads running ahead of the model (`extract.iter_chunks`)"""
+    step = extraction_batch(F.img_size, F.device_batch)
+    lb = ((min_load - 1) // step + 1) * step
+    load = lambda s, e: cholect.load_frames_device(F.data_dir, v, ids[s:e], F.img_size, F.img_size, workers=F.decode_workers, decode=F.png_decode)
+    for span in extract.iter_chunks([(s, min(len(ids), s + lb)) for s in range(0, len(ids), lb)], load, prefetch):
+        for s in range(0, span.shape[0], step):
+            yield span[s:s + step]
+
+
 def spatial_transformer_test(argv=None) -> Dict[str, np.ndarray]:
-    from .spatial_transformer import build_q2l
-    p = argparse.ArgumentParser()
-    _common(p)
-    p.add_argument("--backbone", type=str, default="swin_L_384_22k")
-    p.add_argument("--img_size", type=int, default=384)
-    p.add_argument("--hidden_dim", type=int, default=1536)
-    F, _ = p.parse_known_args(argv)
-    # only the CHECKPOINT directory carries the task suffix (`test.py:93-95`); the feature file goes to run_<version as given>
-    # (`test.py:364-372`: `version1`), which is where Temporal_mstct and the student's dataloader look for it
-    ckpt_version = F.version + ("_" + F.loss_type if F.loss_type != "all" else "")
-    ckpt = F.test_ckpt or f"./__checkpoint__/run_{ckpt_version}/rendezvous_l{F.dataset_variant}_cholect{F.kfold}.pth"
-    model = build_q2l(F, dtype=torch.float32 if F.dtype == "fp32" else torch.bfloat16).eval()
-    model.load_state_dict(torch.load(ckpt, map_location="cpu"), strict=True)
-    rank, world = _dist()
-    videos = cholect.extraction_videos(F.dataset_variant, F.kfold)
-    labels = {v: cholect.load_labels(F.data_dir, v) for v in videos}
-    mine = extract.shard_videos(videos, [len(labels[v]["ivt"]) for v in videos], rank, world)
+    F = _parser("spatial_transformer", False).parse_known_args(argv)[0]
+    # only the CHECKPOINT directory carries the task suffix (`test.py:93-95`; --kfold as given, spelled 'rendezvous'); the feature file goes to
+    # run_<version as given> (`test.py:364-372`: `version1`), which is where Temporal_mstct and the student's dataloader look for it
+    model = _eval_model("spatial_transformer", F, [_stem(F, F.kfold, task_dir=True, model="rendezvous") + ".pth"])
+    labels, mine = _labelled_share(F, cholect.extraction_videos(F.dataset_variant, F.kfold))
+    dev_dec = F.png_decode == "device"                         # (the device decoder wants >= 1024 frames per call; two loads run ahead)
     feats_local = {}
-    for vi in mine:
-        v, chunks = videos[vi], []
-        ids_all = labels[v]["ivt"][:, 0]
-        # device batches (a frame's feature does not depend on the batch it rides in), decode on --decode_workers threads (or on the device), the
-        # video's features stay on the GPU until its end: one D2H per video instead of one synchronous copy per --batch frames (`test.py:357-376`)
-        step = extraction_batch(F.img_size, F.device_batch)
-        load = lambda s, e: cholect.load_frames_device(F.data_dir, v, ids_all[s:e], F.img_size, F.img_size, workers=F.decode_workers,
-                                                       decode=F.png_decode)
-        dev_dec = F.png_decode == "device"                     # (the device decoder wants >= 1024 frames per call; two loads run ahead)
-        lb = (1023 // step + 1) * step if dev_dec else step
-        spans = [(s, min(len(ids_all), s + lb)) for s in range(0, len(ids_all), lb)]
-        for span in extract.iter_chunks(spans, load, 2 if dev_dec else 1):      # the next load is decoded while this one runs
-            for s in range(0, span.shape[0], step):
-                chunks.append(model(span[s:s + step])[3][0].float())
+    for v in mine:
+        # the video's features stay on the GPU until its end: one D2H per video instead of one synchronous copy per --batch frames (`test.py:357-376`)
+        chunks = [model(fr)[3][0].float() for fr in _q2l_chunks(F, v, labels[v]["ivt"][:, 0], 1024 if dev_dec else 1, 2 if dev_dec else 1)]
         feats_local[featfile.video_key(v, "transformer")] = torch.vstack(chunks).cpu().numpy()
     merged = extract.gather_feats(feats_local)
-    if rank == 0:
+    if _dist()[0] == 0:
         featfile.write_feats(featfile.feats_path("..", F.version, F.kfold, F.loss_type), merged)
     return merged
 
 
 def _q2l_scores(F, model, vids, labels):
-    """`test_loop` of `Spatial_transformer/run.py:231-262` over `vids`: device batches in file order, the teacher features the loader hands a
-    `loss_type all` model off the train split are zeros (`dataloader.py:240-246`) -> {video -> {head -> (labels, sigmoid scores)}}; heads the
-    model does not have score sigmoid(0) like the reference's zero logits (`network.py:84-89`)"""
+    """`test_loop` of `Spatial_transformer/run.py:231-262` over `vids`: device batches in file order (loads of one batch, one running ahead), the
+    teacher features the loader hands a `loss_type all` model off the train split are zeros (`dataloader.py:240-246`) -> {video -> {head ->
+    (labels, sigmoid scores)}}; heads the model does not have score sigmoid(0) like the reference's zero logits (`network.py:84-89`)"""
     out_scores = {}
     single = F.loss_type != "all"
     for v in vids:
-        ids_all = labels[v]["ivt"][:, 0]
-        step = extraction_batch(F.img_size, F.device_batch)
-        load = lambda s, e: cholect.load_frames_device(F.data_dir, v, ids_all[s:e], F.img_size, F.img_size, workers=F.decode_workers, decode=F.png_decode)
-        spans = [(s, min(len(ids_all), s + step)) for s in range(0, len(ids_all), step)]
         acc = {k: [] for k in ("i", "v", "t", "ivt")}
-        for span in extract.iter_chunks(spans, load, 1):
-            zt = [] if single else [torch.zeros((span.shape[0], F.teacher_dim), device=span.device)] * 3
-            o = model(span, *zt)
+        for fr in _q2l_chunks(F, v, labels[v]["ivt"][:, 0]):
+            zt = [] if single else [torch.zeros((fr.shape[0], F.teacher_dim), device=fr.device)] * 3
+            o = model(fr, *zt)
             for gi, key in enumerate(("i", "v", "t", "ivt")):
                 acc[key].append(_sigmoid(o[gi][1]))
         out_scores[v] = {key: (labels[v][key][:, 1:], np.concatenate(acc[key])) for key in acc}
@@ -585,81 +598,54 @@ def spatial_transformer_eval(argv=None) -> Dict[str, float]:
     """`Spatial_transformer/run.py -e` (:482-527): the TEST-split videos through the best checkpoint of run_<version>[_<task>]/ and the closing
     report (per-category AP, mean-AP row; I / V / T from the component heads for a single-task teacher, disentangled from the triplet head for
     --loss_type all).  Videos sharded over the ranks, (labels, scores) gathered on the host, rank 0 writes: N ranks log the 1-rank report."""
-    from .spatial_transformer import build_q2l
-    p = argparse.ArgumentParser()
-    _common(p)
-    p.add_argument("--backbone", type=str, default="swin_L_384_22k")
-    p.add_argument("--img_size", type=int, default=384)
-    p.add_argument("--hidden_dim", type=int, default=1536)
-    p.add_argument("--teacher_dim", type=int, default=512)
-    F, _ = p.parse_known_args(argv)
-    rank, world = _dist()
+    F = _parser("spatial_transformer", False).parse_known_args(argv)[0]
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold, task_dir=True)
-    ckpt = F.test_ckpt or stem + ".pth"
-    model = build_q2l(F, dtype=torch.float32 if F.dtype == "fp32" else torch.bfloat16).eval()
-    model.load_state_dict(torch.load(ckpt, map_location="cpu"), strict=True)
+    model = _eval_model("spatial_transformer", F, [stem + ".pth"])
     _, _, videos = cholect.split_videos(F.dataset_variant, kfold)
-    labels = {v: cholect.load_labels(F.data_dir, v) for v in videos}
-    mine = extract.shard_videos(videos, [len(labels[v]["ivt"]) for v in videos], rank, world)
-    m = gather_recognition(_q2l_scores(F, model, [videos[vi] for vi in mine], labels), videos)
-    res = {}
-    try:
-        if rank == 0:
-            res = _write_report(stem + ".log", m, F.loss_type, _chlg(F), "spatial_transformer")
-    finally:
-        _barrier()
-    return res
+    labels, mine = _labelled_share(F, videos)
+    m = gather_recognition(_q2l_scores(F, model, mine, labels), videos)
+    return _on_rank0(lambda: _write_report(stem + ".log", m, F.loss_type, _chlg(F), "spatial_transformer"))
 
 
 # ------------------------------------------------------------------------------------------------ Temporal_mstct/test.py
+def _mstct_windows(model, f: np.ndarray, full=None):
+    """the feature matrix f [N,D] in non-overlapping 256-frame chunks, each an independent window, through `model.forward_btd` (`Temporal_mstct/
+    test.py:146-174`, loader batch 256): yields its return per chunk.  `full(x)`, when given, runs the full chunks instead"""
+    for s in range(0, f.shape[0], 256):
+        x = torch.from_numpy(f[s:s + 256]).unsqueeze(0).cuda()
+        yield full(x) if full is not None and x.shape[1] == 256 else model.forward_btd(x)
+
+
 def mstct_test(argv=None):
-    from .temporal_mstct import VideoNas
-    p = argparse.ArgumentParser()
-    _common(p)
-    p.add_argument("--input_dim", type=int, default=1536)
-    p.add_argument("--final_embedding_dim", type=int, default=512)
-    F, _ = p.parse_known_args(argv)
-    F.in_feat_dim = F.input_dim
+    F = _parser("mstct", False).parse_known_args(argv)[0]
     # checkpoint directory: run_<version>_<task> for a single-task teacher (`test.py:88-90,131,326`); the feature / prediction files it
     # writes go to run_<version as given> (`test.py:342-366`) and its input comes from run_<version1> (`dataloader_test.py:220`)
-    ckpt = F.test_ckpt or _stem(F, task_dir=True) + "latest.pth"                              # no underscore (`run.py:268`)
-    model = VideoNas(F, [256, 384, 576, 864], 2, 8, 8, F.input_dim, F.final_embedding_dim,
-                     dtype=torch.float32 if F.dtype == "fp32" else torch.bfloat16).eval()
-    model.load_state_dict(torch.load(ckpt, map_location="cpu"))
+    model = _eval_model("mstct", F, [_stem(F, task_dir=True) + _LATEST["mstct"]])
     feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, F.loss_type))
     out_feats, out_preds = {}, {}
     gi = {"i": 0, "v": 1, "t": 2, "ivt": 3}[F.loss_type]
-    graphed = None                                                                         # full chunks: one hipGraph replay each (~100 launches, launch-bound)
+    graphed = []
+
+    def full(x):                                                                           # full chunks: one hipGraph replay each (~100 launches, launch-bound)
+        if not graphed:
+            from .graph import GraphedForward
+            graphed.append(GraphedForward(lambda xx: model.forward_btd(xx), [x]))
+        return graphed[0](x)
     # under torchrun (`Scripts/train_fold1.sh` with NGPU > 1 runs `run.py -t -e`) whole videos are sharded over the ranks like the spatial
     # extractors' (no data-path collective), the per-rank dicts meet in one host-side gather and rank 0 alone writes the two files
-    rank, world = _dist()
     keys = list(feats.keys())
-    mine = set(extract.shard_videos(keys, [feats[k].shape[0] for k in keys], rank, world))
-    for ki, (key, f) in enumerate(feats.items()):
-        if ki not in mine:
-            continue
-        fs, ps = [], []
-        for s in range(0, f.shape[0], 256):                                                # non-overlapping 256-frame chunks
-            x = torch.from_numpy(f[s:s + 256]).unsqueeze(0).cuda()
-            if x.shape[1] == 256:
-                if graphed is None:
-                    from .graph import GraphedForward
-                    graphed = GraphedForward(lambda xx: model.forward_btd(xx), [x])
-                o = graphed(x)
-            else:
-                o = model.forward_btd(x)
-            ps.append(o[gi][0][0].float().cpu())                                           # raw logits [T,K]
-            fs.append(o[3][1][0].transpose(0, 1).float().cpu())                            # concat feature [T,2048]
-        out_feats[key], out_preds[key] = torch.vstack(fs).numpy(), torch.vstack(ps).numpy()
+    for ki in extract.shard_videos(keys, [feats[k].shape[0] for k in keys], *_dist()):
+        outs = [(o[3][1][0].transpose(0, 1).float().cpu(), o[gi][0][0].float().cpu()) for o in _mstct_windows(model, feats[keys[ki]], full)]
+        out_feats[keys[ki]] = torch.vstack([fs for fs, _ in outs]).numpy()                 # concat feature [T,2048]
+        out_preds[keys[ki]] = torch.vstack([ps for _, ps in outs]).numpy()                 # raw logits [T,K]
     out_feats, out_preds = extract.gather_feats(out_feats), extract.gather_feats(out_preds)
     out_feats, out_preds = {k: out_feats[k] for k in keys}, {k: out_preds[k] for k in keys}      # file order = input order, whatever the sharding
-    try:
-        if rank == 0:
-            featfile.write_feats(featfile.feats_path("..", F.version, F.kfold, F.loss_type, "feats"), out_feats)
-            featfile.write_feats(featfile.feats_path("..", F.version, F.kfold, F.loss_type, "pred"), out_preds)
-    finally:
-        _barrier()                                                                         # the files exist before any rank goes on to the next stage
+
+    def write():                                                                           # the files exist before any rank goes on to the next stage
+        featfile.write_feats(featfile.feats_path("..", F.version, F.kfold, F.loss_type, "feats"), out_feats)
+        featfile.write_feats(featfile.feats_path("..", F.version, F.kfold, F.loss_type, "pred"), out_preds)
+    _on_rank0(write)
     return out_feats, out_preds
 
 
@@ -671,12 +657,7 @@ def _mstct_scores(model, feats, vids, data_dir, loss_type):
     for v in vids:
         lab = cholect.load_labels(data_dir, v)
         key = featfile.video_key(v)
-        f = feats[key] if key in feats else feats[v[3:]]
-        ps = []
-        for s in range(0, f.shape[0], 256):
-            o = model.forward_btd(torch.from_numpy(f[s:s + 256]).unsqueeze(0).cuda())
-            ps.append(_sigmoid(o[gi][0][0]))
-        p_own = np.concatenate(ps)
+        p_own = np.concatenate([_sigmoid(o[gi][0][0]) for o in _mstct_windows(model, feats[key] if key in feats else feats[v[3:]])])
         n = p_own.shape[0]                                          # (a feature file may hold fewer frames than the label file lists: the first n)
         out_scores[v] = {h: (lab[h][:n, 1:], p_own if h == loss_type else np.full(lab[h][:n, 1:].shape, 0.5)) for h in ("i", "v", "t", "ivt")}
     return out_scores
@@ -686,29 +667,16 @@ def mstct_eval(argv=None) -> Dict[str, float]:
     """`Temporal_mstct/run.py -e` (:527-580): the TEST-split videos in 256-frame chunks through the checkpoint of run_<version>[_<task>]/ (best
     `.pth`, else `latest.pth`), the pickled metric objects (`mAPs.pckl` in the working directory, `:546-549`) and the closing report.  Rank 0
     alone (a window takes < 1 ms)."""
-    from .temporal_mstct import VideoNas
-    p = argparse.ArgumentParser()
-    _common(p)
-    p.add_argument("--input_dim", type=int, default=1536)
-    p.add_argument("--final_embedding_dim", type=int, default=512)
-    F, _ = p.parse_known_args(argv)
-    if _dist()[0] != 0:
-        _barrier()
-        return {}
-    try:
+    F = _parser("mstct", False).parse_known_args(argv)[0]
+
+    def rank0():
         stem = _stem(F, task_dir=True)
-        ckpt = F.test_ckpt or stem + ".pth"
-        if not os.path.exists(ckpt):
-            ckpt = stem + "latest.pth"                                                       # no underscore (`run.py:268`)
-        model = VideoNas(F, [256, 384, 576, 864], 2, 8, 8, F.input_dim, F.final_embedding_dim,
-                         dtype=torch.float32 if F.dtype == "fp32" else torch.bfloat16).eval()
-        model.load_state_dict(torch.load(ckpt, map_location="cpu"))
+        model = _eval_model("mstct", F, [stem + ".pth", stem + _LATEST["mstct"]])
         feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, F.loss_type))
         _, _, test_videos = cholect.split_videos(F.dataset_variant, F.kfold)
         m = recognition_from(_mstct_scores(model, feats, test_videos, F.data_dir, F.loss_type), test_videos)
         return _write_report(stem + ".log", m, F.loss_type, _chlg(F), "temporal_mstct", pckl="mAPs.pckl")
-    finally:
-        _barrier()
+    return _on_rank0(rank0)
 
 
 def _mstct_train(F):
@@ -719,20 +687,19 @@ def _mstct_train(F):
     import random
 
     from .mstct_train import NCLS, MstctTrainer, draw_windows
-    from .temporal_mstct import VideoNas
     from . import shapes, synth
     rank, world = _dist()
     lt = F.loss_type
     if lt not in NCLS:
         raise ValueError("Temporal_mstct trains one task at a time: --loss_type i | v | t | ivt (Scripts/train_fold1.sh:16)")
     stem = _stem(F, task_dir=True)
-    latest = stem + "latest.pth"                                                                  # no underscore (`run.py:268`)
-    tr = MstctTrainer((256, 384, 576, 864), 2, 8, 8, F.input_dim, F.final_embedding_dim, lt, lr=F.initial_learning_rates[2],
-                      weight_decay=F.weight_decay, operand_dtype=torch.bfloat16 if F.operand_dtype == "bf16" else torch.float32)
+    latest = stem + _LATEST["mstct"]
+    tr = MstctTrainer(*_MSTCT_ARCH, F.input_dim, F.final_embedding_dim, lt, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
+                      operand_dtype=_dtype(F.operand_dtype))
     if os.path.exists(latest):
         tr.load_state_dict(torch.load(latest, map_location="cpu"))
     else:   # no torch.nn init here: deterministic synthetic start (the reference starts from its trunc_normal_ init)
-        tr.load_state_dict(synth.fill_from_shapes(shapes.mstct_shapes(F.input_dim, (256, 384, 576, 864), 2, 8, F.final_embedding_dim, lt), seed=F.seed))
+        tr.load_state_dict(synth.fill_from_shapes(shapes.mstct_shapes(F.input_dim, _MSTCT_ARCH[0], _MSTCT_ARCH[1], _MSTCT_ARCH[3], F.final_embedding_dim, lt), seed=F.seed))
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, F.kfold)
     feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, lt))                # `dataloader.py:220-222`
     xs, zs = {}, {}
@@ -747,7 +714,6 @@ def _mstct_train(F):
     if short:
         raise ValueError(f"videos shorter than the {F.num_clips}-frame training window: {short[:3]} (the reference's sampler fails on them too)")
     order_rng, win_rng = random.Random(F.seed), random.Random(F.seed * 7919 + 1)
-    vmodel = VideoNas(F, [256, 384, 576, 864], 2, 8, 8, F.input_dim, F.final_embedding_dim).eval() if rank == 0 else None
 
     def train_epoch(epoch):
         starts = draw_windows(lengths, win_rng, F.num_clips)                                       # same draw on every rank, before the shuffle
@@ -761,7 +727,7 @@ def _mstct_train(F):
         return tot, len(mine)
 
     def validate(state):                                                                          # (`run.py:416-452`): best `.pth` by the task's mAP
-        vmodel.load_state_dict(state)
+        vmodel = _eval_model("mstct", F, state)
         vm = recognition_from(_mstct_scores(vmodel, feats, val_videos, F.data_dir, lt), val_videos) if val_videos else None
         score = float(vm[lt].compute_video_AP(ignore_null=_chlg(F))["mAP"]) if vm else 0.0
         return score, f"{lt}: [{score:.5f}]"
@@ -769,12 +735,7 @@ def _mstct_train(F):
     run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", latest, stem + ".pth", latest_every_epoch=True)
 
 
-# ------------------------------------------------------------------------------------------------ teacher run.py entry points
-def _wants_train(argv) -> bool:
-    argv = list(sys.argv[1:] if argv is None else argv)
-    return "-t" in argv or "--train" in argv
-
-
+# ------------------------------------------------------------------------------------------------ Spatial_transformer/run.py -t
 # `Spatial_transformer/models/backbone.py:31-41` (get_model_path)
 SWIN_PRETRAIN_FILES = {"swin_L_384_22k": "swin_large_patch4_window12_384_22k.pth", "swin_B_384_22k": "swin_base_patch4_window12_384_22k.pth",
                        "swin_T_224_1k": "swin_tiny_patch4_window7_224.pth"}
@@ -791,29 +752,8 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     import random
 
     from .q2l_train import Q2LTrainer
-    from .spatial_transformer import build_q2l
     from . import shapes, synth
-    p = argparse.ArgumentParser()
-    _common(p)
-    add_schedule_flags(p)
-    p.add_argument("--backbone", type=str, default="swin_L_384_22k")
-    p.add_argument("--img_size", type=int, default=384)
-    p.add_argument("--hidden_dim", type=int, default=1536)
-    p.add_argument("--augmentation_list", type=str, nargs="*", default=["original", "vflip", "hflip", "contrast", "rot90"])
-    _add_train_transform_flag(p)
-    _add_prefetch_flag(p)
-    p.add_argument("--pretrain_dir", type=str, default="")
-    p.add_argument("--drop_path_rate", type=float, default=0.1)          # `swin_transformer.py:488`
-    p.add_argument("--operand_dtype", type=str, default="fp32", choices=["fp32", "bf16"],
-                   help="bf16: the nn.Linear GEMMs on bf16 operand copies (fp32 activations, accumulation and master weights)")
-    p.add_argument("--rates", type=float, nargs="+", default=[1, 0, 0.1])          # `run.py:66`
-    p.add_argument("--temp", type=int, default=4)                                 # `run.py:70`
-    p.add_argument("--teacher_dim", type=int, default=512)                        # `run.py:82`
-    # the reference's dataloader reads args.teacher_pred_version / teacher_feat_version (`dataloader.py:217-238`) though its run.py declares
-    # neither flag; same names and defaults as the student's `Spatial_cnn/run.py`
-    p.add_argument("--teacher_feat_version", type=str, default="Q2L")
-    p.add_argument("--teacher_pred_version", type=str, default="Q2LMSTCT")
-    F, _ = p.parse_known_args(argv)
+    F = _parser("spatial_transformer", True).parse_known_args(argv)[0]
     if F.loss_type not in ("i", "v", "t", "all"):
         raise ValueError("--loss_type i | v | t | all (`Spatial_transformer/run.py:168-197`)")
     single = F.loss_type != "all"
@@ -821,9 +761,9 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     rank, world = _dist()
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold, task_dir=True)
-    logfile, latest = stem + ".log", stem + "_latest.pth"
+    logfile, latest = stem + ".log", stem + _LATEST["spatial_transformer"]
     tr = Q2LTrainer(F.backbone, F.img_size, F.hidden_dim, F.loss_type, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
-                    drop_path_rate=F.drop_path_rate, operand_dtype=torch.bfloat16 if F.operand_dtype == "bf16" else torch.float32,
+                    drop_path_rate=F.drop_path_rate, operand_dtype=_dtype(F.operand_dtype),
                     teacher_dim=F.teacher_dim, rates=F.rates, temp=float(F.temp))
     table = shapes.q2l_param_shapes(F.backbone, F.img_size, F.hidden_dim, F.loss_type, teacher_dim=F.teacher_dim)
     sd = synth.fill_from_shapes(table, seed=F.seed)          # deterministic synthetic start when no pretrained file is on disk
@@ -846,8 +786,6 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     tpred, tfeat = _teacher_files(F, kfold)
     order_rng, aug_rng = random.Random(F.seed), random.Random(F.seed * 1000003 + rank)
     size = (F.img_size, F.img_size)
-    eval_args = argparse.Namespace(**vars(F))
-
     tables = _sample_tables(F, labels, tpred, tfeat, train_videos)
 
     def train_epoch(epoch):
@@ -870,8 +808,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
         return tot, len(mine)
 
     def validate(state):                                     # the task's head (:416-421, 443-450)
-        model = build_q2l(eval_args, dtype=torch.float32).eval()
-        model.load_state_dict(state)
+        model = _eval_model("spatial_transformer", F, state)
         gi = "ivt".index(F.loss_type) if single else 3
         zt = lambda fr: [] if single else [torch.zeros((fr.shape[0], F.teacher_dim), device=fr.device)] * 3   # (`dataloader.py:240-246`: zeros off the train split)
         return _frame_validation(F, val_videos, labels, size, 128, lambda fr: model(fr, *zt(fr))[gi][1])
@@ -879,37 +816,28 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     return run_epochs(F, tr, rank, train_epoch, validate, logfile, latest, stem + ".pth")
 
 
-def _wants_test(argv) -> bool:
+# ------------------------------------------------------------------------------------------------ run.py: -t, then -e
+def _run(argv, train, evaluate):
+    """a stage's `run.py`: -t trains, -e evaluates the test split and writes the closing report; -> the evaluation's result, else the training's"""
     argv = list(sys.argv[1:] if argv is None else argv)
-    return "-e" in argv or "--test" in argv
+    last = train(argv) if "-t" in argv or "--train" in argv else None
+    return evaluate(argv) if "-e" in argv or "--test" in argv else last
 
 
 def spatial_cnn_run(argv=None):
     """`Spatial_cnn/run.py`: -t trains the student (`spatial_cnn_train`), -e evaluates the test split and writes the closing report
     (`spatial_cnn_eval`, `run.py:503-560`); the extraction pass over all videos is `test.py` (`spatial_cnn_test`)."""
-    last = spatial_cnn_train(argv) if _wants_train(argv) else None
-    return spatial_cnn_eval(argv) if _wants_test(argv) else last
+    return _run(argv, spatial_cnn_train, spatial_cnn_eval)
 
 
 def spatial_transformer_run(argv=None):
     """`Spatial_transformer/run.py`: -t trains the teacher (`spatial_transformer_train`), -e evaluates the test split and writes the closing
     report (`spatial_transformer_eval`, `run.py:482-527`); the extraction pass over all videos is `test.py` (`spatial_transformer_test`)."""
-    last = spatial_transformer_train(argv) if _wants_train(argv) else None
-    return spatial_transformer_eval(argv) if _wants_test(argv) else last
+    return _run(argv, spatial_transformer_train, spatial_transformer_eval)
 
 
 def mstct_run(argv=None):
     """`Temporal_mstct/run.py`: -t trains the MS-TCT teacher on random 256-frame windows (`run.py:147-235`), -e evaluates the test split and
     writes the closing report + `mAPs.pckl` (`mstct_eval`, `run.py:527-580`); features / raw predictions for the student come from `test.py`
     (`mstct_test`)."""
-    if _wants_train(argv):
-        p = argparse.ArgumentParser()
-        _common(p)
-        add_schedule_flags(p)
-        p.add_argument("--input_dim", type=int, default=1536)
-        p.add_argument("--final_embedding_dim", type=int, default=512)
-        p.add_argument("--num_clips", type=int, default=256, help="window length (the reference hard-codes 256, dataloader.py:237)")
-        p.add_argument("--operand_dtype", type=str, default="fp32", choices=["fp32", "bf16"],
-                       help="bf16: the nn.Linear GEMMs on bf16 operand copies (fp32 activations, accumulation and master weights)")
-        _mstct_train(p.parse_known_args(argv)[0])
-    return mstct_eval(argv) if _wants_test(argv) else None
+    return _run(argv, lambda a: _mstct_train(_parser("mstct", True).parse_known_args(a)[0]), mstct_eval)

@@ -14,13 +14,14 @@ import torch
 
 from . import ops
 from .shapes import resnet_feat_dim, spatial_cnn_shapes
+from .statemodule import StateModule
 from .synth import IMAGENET_MEAN, IMAGENET_STD
 
 _DEPTHS = {"resnet18": (2, 2, 2, 2), "resnet50": (3, 4, 6, 3)}
 _HEADS = (("i", 6), ("v", 10), ("t", 15), ("ivt", 100))
 
 
-class VideoNas:
+class VideoNas(StateModule):
     """Drop-in for `Spatial_cnn.network.VideoNas` (eval / extraction path).
 
     args needs: network ('resnet18'|'resnet50'), loss_type, student_dim, teacher_dim, train."""
@@ -65,29 +66,12 @@ class VideoNas:
             self._trainer.load_state_dict(self.state_dict())
         return self._trainer
 
-    def eval(self):
-        self.training = False
-        return self
+    def _store(self, t: torch.Tensor) -> torch.Tensor:
+        return t.detach()             # (the checkpoint's dtype is kept: `_fold` widens)
 
-    def cuda(self):
-        return self
-
-    def state_dict(self):
-        return dict(self._sd)
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
-        names = [k for k, _ in self._table]
-        missing = [k for k in names if k not in sd]
-        if strict and (missing or len(sd) != len(names)):
-            raise KeyError(f"state dict mismatch: missing {missing[:4]}, unexpected {[k for k in sd if k not in names][:4]}")
-        for k, shp in self._table:
-            if k in sd:
-                if tuple(sd[k].shape) != tuple(shp):
-                    raise ValueError(f"{k}: shape {tuple(sd[k].shape)} != {shp}")
-                self._sd[k] = sd[k].detach()
+    def _loaded(self):
         self._trainer = None          # (the train-mode engine is rebuilt from the new parameters on first use)
         self._pack()
-        return self
 
     # ------------------------------------------------------------------ load-time packing (BN folding)
     def _fold(self, conv: str, bn: str, stem: bool = False):

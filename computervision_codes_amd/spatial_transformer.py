@@ -19,6 +19,7 @@ import torch
 
 from . import ops
 from .shapes import SWIN_BUFFER_SUFFIXES, SWIN_CFG, q2l_param_shapes, swin_window
+from .statemodule import StateModule
 from .synth import IMAGENET_MEAN, IMAGENET_STD
 
 _K = {"i": 6, "v": 10, "t": 15, "ivt": 100}
@@ -90,7 +91,7 @@ def sine_position_rows(hidden_dim: int, h: int, w: int) -> torch.Tensor:
     return torch.cat((py, px), dim=3).reshape(h * w, hidden_dim).contiguous()
 
 
-class Qeruy2Label:
+class Qeruy2Label(StateModule):
     """Drop-in for `Spatial_transformer.network.Qeruy2Label` as built by `build_q2l` (eval path).
 
     args needs: backbone ('swin_{T,B,L}_{224,384}_*'), img_size, hidden_dim (= 8*embed_dim), loss_type ('i'|'v'|'t'|'all'),
@@ -116,30 +117,9 @@ class Qeruy2Label:
         self._sd: Dict[str, torch.Tensor] = {}
         self._p: Dict[str, object] = {}
 
-    def eval(self):
-        self.training = False
-        return self
-
-    def cuda(self):
-        return self
-
-    def state_dict(self):
-        return dict(self._sd)
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
-        names = [k for k, _ in self._table]
+    def _tolerated(self, key: str) -> bool:
         # a reference `loss_type all` checkpoint lists the shared transformer under every decoder: the copies are aliases
-        extra = [k for k in sd if k not in names and not k.endswith(SWIN_BUFFER_SUFFIXES) and ".transformer." not in k]
-        missing = [k for k in names if k not in sd]
-        if strict and (missing or extra):
-            raise KeyError(f"state dict mismatch: missing {missing[:4]}, unexpected {extra[:4]}")
-        for k, shp in self._table:
-            if k in sd:
-                if tuple(sd[k].shape) != tuple(shp):
-                    raise ValueError(f"{k}: shape {tuple(sd[k].shape)} != {shp}")
-                self._sd[k] = sd[k].detach().float()
-        self._pack()
-        return self
+        return key.endswith(SWIN_BUFFER_SUFFIXES) or ".transformer." in key
 
     # ------------------------------------------------------------------ packing
     def _lin(self, key_w: str, key_b: Optional[str]):

@@ -18,11 +18,12 @@ import torch
 
 from . import ops
 from .shapes import mstct_shapes
+from .statemodule import StateModule
 
 _K = {"i": 6, "v": 10, "t": 15, "ivt": 100}
 
 
-class VideoNas:
+class VideoNas(StateModule):
     """Drop-in for `Temporal_mstct.network.VideoNas` (eval path).  args needs: loss_type ('i'|'v'|'t'|'ivt')."""
 
     def __init__(self, args, inter_channels, num_block, head, mlp_ratio, in_feat_dim, final_embedding_dim, num_tool=6, num_verb=10,
@@ -39,29 +40,6 @@ class VideoNas:
         self._table = mstct_shapes(in_feat_dim, self.inter, num_block, mlp_ratio, final_embedding_dim, self.loss_type)
         self._sd: Dict[str, torch.Tensor] = {}
         self._p: Dict[str, object] = {}
-
-    def eval(self):
-        self.training = False
-        return self
-
-    def cuda(self):
-        return self
-
-    def state_dict(self):
-        return dict(self._sd)
-
-    def load_state_dict(self, sd, strict: bool = True):
-        names = [k for k, _ in self._table]
-        missing = [k for k in names if k not in sd]
-        if strict and (missing or len(sd) != len(names)):
-            raise KeyError(f"state dict mismatch: missing {missing[:4]}, unexpected {[k for k in sd if k not in names][:4]}")
-        for k, shp in self._table:
-            if k in sd:
-                if tuple(sd[k].shape) != tuple(shp):
-                    raise ValueError(f"{k}: shape {tuple(sd[k].shape)} != {shp}")
-                self._sd[k] = sd[k].detach().float()
-        self._pack()
-        return self
 
     def _pack(self):
         dev, sd, dt = self.device, self._sd, self.dtype

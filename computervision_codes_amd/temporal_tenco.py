@@ -20,6 +20,7 @@ import torch
 
 from . import ops
 from .shapes import tenco_shapes
+from .statemodule import StateModule
 
 # rows (B*T) up to which a forward takes the latency path: above it the 128 x 128 tiles of the implicit-GEMM kernel move fewer operand
 # bytes per FLOP than 32 x 16.  Measured crossover, 4-stage head, hipGraph replay, ms (latency path | implicit GEMM):
@@ -27,7 +28,7 @@ from .shapes import tenco_shapes
 TCN_PATH_MAX_ROWS = {torch.float32: 896, torch.bfloat16: 640}
 
 
-class VideoNas:
+class VideoNas(StateModule):
     """Drop-in for `Temporal_tenco.network.VideoNas` (inference path; eval semantics).
 
     args needs: fpn, output, hier.  output=False is what every shipped script uses and the only form the reference itself can run at the
@@ -64,30 +65,7 @@ class VideoNas:
         # (profiles/r04_tcn_fused_layer_ab.txt: 24 ... 64 videos of 256 frames +2 ... +20 %, 8 whole videos of 2000 frames 2.98 -> 1.98 ms; 128 videos: even)
         self.fused_layer_min_tiles, self.fused_layer_max_tiles = 96, 384
 
-    # ------------------------------------------------------------------ nn.Module-like surface
-    def eval(self):
-        self.training = False
-        return self
-
-    def cuda(self):
-        return self
-
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        return dict(self._sd)
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
-        names = [k for k, _ in self._table]
-        missing = [k for k in names if k not in sd]
-        if strict and (missing or len(sd) != len(names)):
-            raise KeyError(f"state dict mismatch: missing {missing[:4]}, unexpected {[k for k in sd if k not in names][:4]}")
-        for k, shp in self._table:
-            if k in sd:
-                if tuple(sd[k].shape) != tuple(shp):
-                    raise ValueError(f"{k}: shape {tuple(sd[k].shape)} != {shp}")
-                self._sd[k] = sd[k].detach().to(torch.float32)
-        self._pack()
-        return self
-
+    # ------------------------------------------------------------------ load-time packing (the nn.Module-like surface: `StateModule`)
     def _pack(self):
         dev, p = self.device, {}
 
