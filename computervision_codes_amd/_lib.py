@@ -170,6 +170,9 @@ SIGNATURES = {
     "mt4_dropout_mul_add_f32": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _i32, C.c_float, _vp]),
     "mt4_select_kth_key_u64": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _i32, _vp, _vp]),
     "mt4_tenco_input_draw_f32": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),
+    "mt4_video_ap_max_rows": (C.c_int, []),
+    "mt4_video_ap_f32": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), _i32, _i32, _i32, _vp, _vp]),
+    "mt4_component_max_f32": (C.c_int, [_vp, C.POINTER(_i32), _i32, _vp, C.c_int64, _vp]),
 }
 
 

@@ -46,6 +46,9 @@ def _common(p: argparse.ArgumentParser):
     p.add_argument("--decode_workers", type=int, default=8, help="host threads decoding PNGs")
     p.add_argument("--png_decode", type=str, default="host", choices=["host", "device"],
                    help="device: inflate + PNG unfiltering on the GPU (mt4_png_inflate / mt4_png_unfilter_rgb8), the host only reads the files")
+    p.add_argument("--metrics", type=str, default="host", choices=["host", "device"],
+                   help="device: the video-wise AP of the trainers' validation and of the temporal closing reports on the GPU (mt4_video_ap_f32 / "
+                        "mt4_component_max_f32) from the fp32 scores where the model wrote them; top-K and the spatial -e / test.py passes stay on the host")
 
 
 def _flag(*names, **kw):
@@ -143,6 +146,32 @@ def _sigmoid(x: torch.Tensor) -> np.ndarray:
     return torch.sigmoid(x.float()).cpu().numpy()
 
 
+def _device_metrics(F) -> bool:
+    return getattr(F, "metrics", "host") == "device"
+
+
+def _scores(x: torch.Tensor, device: bool):
+    """sigmoid scores of logits x: the fp32 values `_sigmoid` copies down, left on the device for --metrics device"""
+    return torch.sigmoid(x.float()) if device else _sigmoid(x)
+
+
+def _label_rows(cache, v, lab, device: bool):
+    """{head -> label rows [N,K] of video v} (`lab()` reads the label files): for --metrics device fp32 on the GPU, uploaded once per video
+    and run -- `cache` outlives the epochs"""
+    if not device:
+        return {h: a[:, 1:] for h, a in lab().items() if h in ("i", "v", "t", "ivt")}
+    if v not in cache:
+        cache[v] = {h: torch.from_numpy(np.ascontiguousarray(a[:, 1:], dtype=np.float32)).cuda() for h, a in lab().items() if h in ("i", "v", "t", "ivt")}
+    return cache[v]
+
+
+def _recognition(scores, order, device: bool):
+    if device:
+        from .metrics_device import device_recognition_from
+        return device_recognition_from(scores, order)
+    return recognition_from(scores, order)
+
+
 def _write_report(logfile: str, m, loss_type: str, chlg: bool, style: str, pckl: str = None) -> Dict[str, float]:
     """the reference's closing report (`metrics.final_report`: per-category AP vectors, the mean-AP row with I / V / T disentangled from the
     triplet head, top-K rows) into the log file, and -- temporal drivers -- the pickled metric objects (`Temporal_tenco/run.py:529-533`:
@@ -150,7 +179,7 @@ def _write_report(logfile: str, m, loss_type: str, chlg: bool, style: str, pckl:
     if pckl:
         os.makedirs(os.path.dirname(os.path.abspath(pckl)), exist_ok=True)
         with open(pckl, "wb") as f:
-            pickle.dump({k: m[k] for k in ("ivt", "i", "v", "t")}, f)
+            pickle.dump({k: m[k].to_host() if hasattr(m[k], "to_host") else m[k] for k in ("ivt", "i", "v", "t")}, f)     # (--metrics device: the same type and arrays)
     lines, res = final_report(m, loss_type, chlg, style)
     for ln in lines:
         _log(logfile, ln)
@@ -347,18 +376,24 @@ def _sample_tables(F, labels, tpred, tfeat, videos):
     return SampleTables(labels, tpred, tfeat, videos=videos)
 
 
-def _frame_validation(F, val_videos, labels, size, cap, forward):
+def _frame_validation(F, val_videos, labels, size, cap, forward, label_cache=None):
     """validation mAP of the task's head (`run.py:416-451`; ivt for --loss_type all) over the validation videos' frames in device batches of
-    max(--batch, min(--device_batch, cap)) (results do not depend on it); forward(uint8 frames) -> the head's logits"""
+    max(--batch, min(--device_batch, cap)) (results do not depend on it); forward(uint8 frames) -> the head's logits.  --metrics device: the
+    scores stay on the GPU, the label rows come from `label_cache` (the caller's, one per run)"""
     vt = F.loss_type if F.loss_type != "all" else "ivt"
-    m = Recognition({"i": 6, "v": 10, "t": 15, "ivt": 100}[vt])
+    dev = _device_metrics(F)
+    if dev:
+        from .metrics_device import DeviceRecognition
+    m = (DeviceRecognition if dev else Recognition)({"i": 6, "v": 10, "t": 15, "ivt": 100}[vt])
     vb = max(F.batch, min(F.device_batch, cap))
+    label_cache = {} if label_cache is None else label_cache
     for v in val_videos:
         lv = labels[v][vt]
+        zv = _label_rows(label_cache, v, lambda v=v: labels[v], dev)[vt]
         load = lambda s0, v=v, lv=lv: cholect.load_frames_device(F.data_dir, v, lv[s0:s0 + vb, 0], size[0], size[1], workers=F.decode_workers, decode=F.png_decode)
         spans = [(s0,) for s0 in range(0, len(lv), vb)]
         for (s0,), fr in zip(spans, extract.iter_chunks(spans, load, 1 if getattr(F, "prefetch", 0) > 0 else 0)):      # --prefetch: the next span loads meanwhile
-            m.update(lv[s0:s0 + vb, 1:], _sigmoid(forward(fr)))
+            m.update(zv[s0:s0 + vb], _scores(forward(fr), dev))
         m.video_end()
     score = float(m.compute_video_AP(ignore_null=_chlg(F))["mAP"]) if val_videos else 0.0
     return score, f"{vt}: [{score:.5f}]"
@@ -412,10 +447,12 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
             tot += tr.train_step(*_frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng))["loss"]
         return tot, len(mine)
 
+    val_labels = {}                                          # (--metrics device: the validation label rows on the GPU, uploaded once)
+
     def validate(state):
         model = _eval_model("spatial_cnn", F, state)
         gi = "ivt".index(F.loss_type) if single else 3
-        return _frame_validation(F, val_videos, labels, size, 256, lambda fr: model.extract_u8(fr)[gi][1])
+        return _frame_validation(F, val_videos, labels, size, 256, lambda fr: model.extract_u8(fr)[gi][1], val_labels)
 
     return run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", latest, stem + ".pth", score_key="val_mAP_ivt")
 
@@ -437,21 +474,24 @@ def _tenco_eval_rank0(F) -> Dict[str, float]:
     _, _, test_videos = cholect.split_videos(F.dataset_variant, F.kfold)
     feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, "all"))
     t0 = time.time()
-    m = recognition_from(_tenco_scores(model, feats, test_videos, F.data_dir), test_videos)     # (rank 0 alone runs this pass)
+    dev = _device_metrics(F)
+    m = _recognition(_tenco_scores(model, feats, test_videos, F.data_dir, dev), test_videos, dev)     # (rank 0 alone runs this pass)
     _log(logfile, f"eta {time.time() - t0:.3f} secs")
     # `run.py:529-570`: the pickled metric objects, then head-wise ('singletest') and disentangled per-category AP and both mean-AP rows
     return _write_report(logfile, m, F.loss_type, _chlg(F), "temporal_tenco", pckl=os.path.join(os.path.dirname(stem), f"mAPs_k{F.kfold}.pckl"))
 
 
-def _tenco_scores(model, feats, vids, data_dir):
-    """`test_loop` of `Temporal_tenco/run.py:238-270`: whole video, batch 1, the finest FPN level's logits [K,T] -> sigmoid [T,K]"""
+def _tenco_scores(model, feats, vids, data_dir, device=False, label_cache=None):
+    """`test_loop` of `Temporal_tenco/run.py:238-270`: whole video, batch 1, the finest FPN level's logits [K,T] -> sigmoid [T,K].
+    device (--metrics device): scores and label rows are device tensors, the label rows uploaded once per video into `label_cache`"""
     out_scores = {}
+    label_cache = {} if label_cache is None else label_cache
     for v in vids:
-        lab = cholect.load_labels(data_dir, v)
+        lab = _label_rows(label_cache, v, lambda v=v: cholect.load_labels(data_dir, v), device)
         x = torch.from_numpy(feats[featfile.video_key(v)]).unsqueeze(0).cuda()
         out, out_i, out_v, out_t, _, _ = model(x, False)
         n = x.shape[1]
-        out_scores[v] = {key: (lab[key][:n, 1:], _sigmoid(lg[0][0].transpose(0, 1))) for key, lg in (("ivt", out), ("i", out_i), ("v", out_v), ("t", out_t))}
+        out_scores[v] = {key: (lab[key][:n], _scores(lg[0][0].transpose(0, 1), device)) for key, lg in (("ivt", out), ("i", out_i), ("v", out_v), ("t", out_t))}
     return out_scores
 
 
@@ -532,9 +572,11 @@ def _tenco_train(F):
             tot += tr.train_step(x, z, masks=masks)[0]
         return tot, len(mine)
 
+    dev_metrics, val_labels = _device_metrics(F), {}
+
     def validate(state):                                           # (`run.py:416-452`): best `.pth` by the triplet mAP
         vmodel = _eval_model("tenco", F, state)
-        vm = recognition_from(_tenco_scores(vmodel, feats, val_videos, F.data_dir), val_videos) if val_videos else None
+        vm = _recognition(_tenco_scores(vmodel, feats, val_videos, F.data_dir, dev_metrics, val_labels), val_videos, dev_metrics) if val_videos else None
         head = F.loss_type if F.loss_type in ("i", "v", "t") else "ivt"
         score = float(vm[head].compute_video_AP()["mAP"]) if vm else 0.0
         ivt = float(vm["ivt"].compute_video_AP("ivt", ignore_null=_chlg(F))["mAP"]) if vm else 0.0
@@ -649,17 +691,21 @@ def mstct_test(argv=None):
     return out_feats, out_preds
 
 
-def _mstct_scores(model, feats, vids, data_dir, loss_type):
+def _mstct_scores(model, feats, vids, data_dir, loss_type, device=False, label_cache=None):
     """`test_loop` of `Temporal_mstct/run.py:237-262` behind its batch-256 loaders (`:371,378`): non-overlapping 256-frame chunks, each an
-    independent window; the heads the single-task model lacks are zero logits (`network.py:85-99`) = sigmoid 0.5"""
+    independent window; the heads the single-task model lacks are zero logits (`network.py:85-99`) = sigmoid 0.5.
+    device (--metrics device): scores and label rows are device tensors, the label rows uploaded once per video into `label_cache`"""
     out_scores = {}
     gi = {"i": 0, "v": 1, "t": 2, "ivt": 3}[loss_type]
+    label_cache = {} if label_cache is None else label_cache
     for v in vids:
-        lab = cholect.load_labels(data_dir, v)
+        lab = _label_rows(label_cache, v, lambda v=v: cholect.load_labels(data_dir, v), device)
         key = featfile.video_key(v)
-        p_own = np.concatenate([_sigmoid(o[gi][0][0]) for o in _mstct_windows(model, feats[key] if key in feats else feats[v[3:]])])
+        parts = [_scores(o[gi][0][0], device) for o in _mstct_windows(model, feats[key] if key in feats else feats[v[3:]])]
+        p_own = torch.cat(parts) if device else np.concatenate(parts)
         n = p_own.shape[0]                                          # (a feature file may hold fewer frames than the label file lists: the first n)
-        out_scores[v] = {h: (lab[h][:n, 1:], p_own if h == loss_type else np.full(lab[h][:n, 1:].shape, 0.5)) for h in ("i", "v", "t", "ivt")}
+        half = (lambda a: torch.full(a.shape, 0.5, dtype=torch.float32, device=a.device)) if device else (lambda a: np.full(a.shape, 0.5))
+        out_scores[v] = {h: (lab[h][:n], p_own if h == loss_type else half(lab[h][:n])) for h in ("i", "v", "t", "ivt")}
     return out_scores
 
 
@@ -674,7 +720,8 @@ def mstct_eval(argv=None) -> Dict[str, float]:
         model = _eval_model("mstct", F, [stem + ".pth", stem + _LATEST["mstct"]])
         feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, F.loss_type))
         _, _, test_videos = cholect.split_videos(F.dataset_variant, F.kfold)
-        m = recognition_from(_mstct_scores(model, feats, test_videos, F.data_dir, F.loss_type), test_videos)
+        dev = _device_metrics(F)
+        m = _recognition(_mstct_scores(model, feats, test_videos, F.data_dir, F.loss_type, dev), test_videos, dev)
         return _write_report(stem + ".log", m, F.loss_type, _chlg(F), "temporal_mstct", pckl="mAPs.pckl")
     return _on_rank0(rank0)
 
@@ -726,9 +773,11 @@ def _mstct_train(F):
             tot += tr.train_step_btd(x, z, masks=tr.draw_masks_device(len(vids), F.num_clips, F.seed + rank, epoch * len(mine) + s))
         return tot, len(mine)
 
+    dev_metrics, val_labels = _device_metrics(F), {}
+
     def validate(state):                                                                          # (`run.py:416-452`): best `.pth` by the task's mAP
         vmodel = _eval_model("mstct", F, state)
-        vm = recognition_from(_mstct_scores(vmodel, feats, val_videos, F.data_dir, lt), val_videos) if val_videos else None
+        vm = _recognition(_mstct_scores(vmodel, feats, val_videos, F.data_dir, lt, dev_metrics, val_labels), val_videos, dev_metrics) if val_videos else None
         score = float(vm[lt].compute_video_AP(ignore_null=_chlg(F))["mAP"]) if vm else 0.0
         return score, f"{lt}: [{score:.5f}]"
 
@@ -807,11 +856,13 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
                     tot += tr.train_step(frames, lab, masks, teacher_pred=tp, teacher_feat=tf)["loss"]
         return tot, len(mine)
 
+    val_labels = {}                                          # (--metrics device: the validation label rows on the GPU, uploaded once)
+
     def validate(state):                                     # the task's head (:416-421, 443-450)
         model = _eval_model("spatial_transformer", F, state)
         gi = "ivt".index(F.loss_type) if single else 3
         zt = lambda fr: [] if single else [torch.zeros((fr.shape[0], F.teacher_dim), device=fr.device)] * 3   # (`dataloader.py:240-246`: zeros off the train split)
-        return _frame_validation(F, val_videos, labels, size, 128, lambda fr: model(fr, *zt(fr))[gi][1])
+        return _frame_validation(F, val_videos, labels, size, 128, lambda fr: model(fr, *zt(fr))[gi][1], val_labels)
 
     return run_epochs(F, tr, rank, train_epoch, validate, logfile, latest, stem + ".pth")
 

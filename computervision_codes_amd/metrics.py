@@ -49,6 +49,23 @@ def disentangle(x: np.ndarray, component: str) -> np.ndarray:
     return np.stack([x[:, idx == c].max(axis=1) for c in np.unique(idx)], axis=1)
 
 
+def component_table(component: str):
+    """(col_of_triplet int32 [100], K): triplet id -> column of `disentangle(x, component)` (ascending unique component id) -- the table
+    `ops.component_max` takes"""
+    idx = _component_index(component)
+    uniq = np.unique(idx)
+    return np.searchsorted(uniq, idx).astype(np.int32), int(len(uniq))
+
+
+def video_mean(per_video, num_class: int):
+    """per-video AP vectors ([K] each, NaN = class without positives in the video) -> {"AP": nan-mean over videos per class, "mAP": nan-mean
+    over classes}; shared by `Recognition.compute_video_AP` and `metrics_device.DeviceRecognition.compute_video_AP`"""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        ap = np.nanmean(np.stack(per_video, 0), axis=0) if len(per_video) else np.full(num_class, np.nan)
+        return {"AP": ap, "mAP": float(np.nanmean(ap)) if np.isfinite(ap).any() else float("nan")}
+
+
 class Recognition:
     def __init__(self, num_class: int = 100):
         self.num_class = num_class
@@ -89,10 +106,7 @@ class Recognition:
         cut = (lambda a: a[:, :a.shape[1] - drop]) if drop else (lambda a: a)
         per_video = [self._ap_per_class(cut(disentangle(t, component)), cut(disentangle(p, component)))
                      for t, p in zip(self.global_targets, self.global_predictions)]
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", category=RuntimeWarning)
-            ap = np.nanmean(np.stack(per_video, 0), axis=0) if per_video else np.full(self.num_class, np.nan)
-            return {"AP": ap, "mAP": float(np.nanmean(ap)) if np.isfinite(ap).any() else float("nan")}
+        return video_mean(per_video, self.num_class)
 
     def topK(self, k: int = 5, component: str = "ivt") -> float:
         """`mAP.topK(k, component)` (`Spatial_cnn/run.py:543-548`) as the reference spells it out itself in `Temporal_mstct/run.py:507-523`

@@ -1282,6 +1282,42 @@ def tenco_input_draw(x: torch.Tensor, state: torch.Tensor, slot_keys: int, thr: 
     return y
 
 
+# ----------------------------------------------------------------------------------------- validation metric
+def video_ap_max_rows() -> int:
+    """the longest video `video_ap` takes (`mt4_video_ap_max_rows`)"""
+    return int(lib.mt4_video_ap_max_rows())
+
+
+def video_ap(scores: torch.Tensor, targets: torch.Tensor, row_offsets, k: Optional[int] = None) -> torch.Tensor:
+    """float64 [V, k] on the device: the average precision of the first k columns of scores / targets (fp32 [N, ld], targets 0 or 1) over the
+    rows [row_offsets[v], row_offsets[v+1]) of each of the V videos; NaN without positives (`mt4_video_ap_f32`).  row_offsets: host ints"""
+    _need_cuda(scores, targets)
+    assert scores.dtype == torch.float32 and targets.dtype == torch.float32 and scores.dim() == 2 and scores.shape == targets.shape
+    assert scores.is_contiguous() and targets.is_contiguous()
+    offs = [int(o) for o in row_offsets]
+    if len(offs) < 2 or offs[-1] > scores.shape[0]:
+        raise _lib.Mt4Error(f"video_ap: row offsets {offs[:3]}..{offs[-1:]} do not lie in the {scores.shape[0]} rows")
+    ld = scores.shape[1]
+    k = ld if k is None else int(k)
+    out = torch.empty((len(offs) - 1, k), dtype=torch.float64, device=scores.device)
+    check(lib.mt4_video_ap_f32(scores.data_ptr(), targets.data_ptr(), (C.c_int64 * len(offs))(*offs), len(offs) - 1, k, ld, out.data_ptr(), _stream()),
+          "mt4_video_ap_f32")
+    return out
+
+
+def component_max(x: torch.Tensor, col_of_triplet, kc: int) -> torch.Tensor:
+    """[rows, 100] fp32 triplet scores or labels -> [rows, kc]: column c = max over the triplets j with col_of_triplet[j] == c
+    (`mt4_component_max_f32`; `metrics.disentangle`).  col_of_triplet: 100 host ints"""
+    _need_cuda(x)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == 100 and x.is_contiguous() and len(col_of_triplet) == 100
+    out = torch.empty((x.shape[0], int(kc)), dtype=torch.float32, device=x.device)
+    if x.shape[0] == 0:
+        return out
+    check(lib.mt4_component_max_f32(x.data_ptr(), (C.c_int32 * 100)(*[int(c) for c in col_of_triplet]), int(kc), out.data_ptr(), x.shape[0], _stream()),
+          "mt4_component_max_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- Swin / Q2L training pieces (fp32)
 def gather_rows(x: torch.Tensor, row_map: torch.Tensor, *, l_out: int, l_in: int, group: int = 1, m_out: Optional[int] = None) -> torch.Tensor:
     """y[m][g*C:(g+1)*C] = x[(m // l_out) * l_in + map[(m % l_out) * group + g]]  (`mt4_gather_rows_f32`)"""

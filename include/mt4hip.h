@@ -616,6 +616,29 @@ int mt4_tenco_input_draw_f32(const float* x, float* y, int32_t T, int32_t D, con
                              int32_t slot_chan, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The validation metric on the device (Spatial_cnn/run.py:331-338,426-451: ivtmetrics' `Recognition.update / video_end /
+ * compute_video_AP`, which every driver of the reference calls; restated on the host in computervision_codes_amd/metrics.py).
+ */
+/* Longest video (rows) mt4_video_ap_f32 takes: a workgroup holds its column as 8-byte words in LDS. */
+int mt4_video_ap_max_rows(void);
+/* ap_out[v][c] = average precision of column c over the rows [row_offsets[v], row_offsets[v+1]) of video v, by the definition of sklearn's
+ * `average_precision_score`: the distinct scores in descending order are the thresholds, AP = sum over them of (recall step) x precision,
+ * equal scores are ONE threshold (-0.0 and +0.0 too).  NaN for a column without positives and for a video of 0 rows.
+ *   scores, targets  float32 [N_total][ld] on the device; the first k columns are read; targets hold exactly 0 or 1; scores are finite
+ *   row_offsets      int64 [n_videos + 1] in HOST memory, non-decreasing from >= 0 (checked here; they travel as kernel arguments)
+ *   ap_out           float64 [n_videos][k] on the device
+ * One launch of (k, n_videos) workgroups (one more per 255 videos); sums in float64 in a fixed order: a repeated call gives the same bits.
+ * MT4_EINVAL: null pointer, n_videos <= 0, k <= 0, ld < k, a negative or decreasing offset; MT4_EUNSUPPORTED: a video longer than
+ * mt4_video_ap_max_rows() -- both before any launch. */
+int mt4_video_ap_f32(const float* scores, const float* targets, const int64_t* row_offsets, int32_t n_videos, int32_t k, int32_t ld,
+                     double* ap_out, void* stream);
+/* out[r][c] = max over the triplets j with col_of_triplet[j] == c of x[r][j]: a component's score / label from the 100-way triplet
+ * rows (`compute_video_AP('i' | 'v' | 't' | 'iv' | 'it')`, Spatial_cnn/run.py:438-444).  x [rows][100], out [rows][kc] float32 on the device;
+ * col_of_triplet int32 [100] in HOST memory, every entry in [0, kc) (else MT4_EINVAL, before the launch); a column no triplet maps to
+ * gets -inf. */
+int mt4_component_max_f32(const float* x, const int32_t* col_of_triplet, int32_t kc, float* out, int64_t rows, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Backward pieces of the Swin + Query2Label teacher (what torch autograd derives inside Spatial_transformer/run.py:150-229 for
  * Spatial_transformer/models/swin_transformer.py and models/transformer.py).  float32.  LayerNorm / GELU / softmax / batched-GEMM
  * backward are the entry points above.

@@ -73,20 +73,27 @@ def step_times(args):
         torch.cuda.empty_cache()
 
 
-def driver_times(args):
-    d = os.path.abspath(args.driver)
+def make_driver_tree(d, frames, root=ROOT):
+    """a synthetic CholecT45-shaped dataset of `frames` frames per video and the Spatial_cnn feature file of run_S under d (emptied first), beside
+    a copy of `root`'s MT4MTLKD/ scripts -> (tree, data)"""
     shutil.rmtree(d, ignore_errors=True)
     tree, data = os.path.join(d, "MT4MTLKD"), os.path.join(d, "CholecT45")
-    shutil.copytree(os.path.join(ROOT, "MT4MTLKD"), tree)
+    shutil.copytree(os.path.join(root, "MT4MTLKD"), tree)
     rng = np.random.default_rng(3)
     vids = cholect.extraction_videos("cholect45-crossval", 1)
     for sub, k in (("triplet", 100), ("instrument", 6), ("verb", 10), ("target", 15)):
         os.makedirs(os.path.join(data, sub))
         for v in vids:
-            lab = np.concatenate([np.arange(args.frames)[:, None], (rng.random((args.frames, k)) < 0.15).astype(int)], 1)
+            lab = np.concatenate([np.arange(frames)[:, None], (rng.random((frames, k)) < 0.15).astype(int)], 1)
             np.savetxt(os.path.join(data, sub, v + ".txt"), lab, fmt="%d", delimiter=",")
     featfile.write_feats(os.path.join(tree, "0-5fold", "data_feats", "run_S", "k1_feats.pkl"),
-                         {v[-2:]: rng.standard_normal((args.frames, 512)).astype(np.float32) for v in vids})
+                         {v[-2:]: rng.standard_normal((frames, 512)).astype(np.float32) for v in vids})
+    return tree, data
+
+
+def driver_times(args):
+    d = os.path.abspath(args.driver)
+    tree, data = make_driver_tree(d, args.frames)
     env = dict(os.environ, PYTHONPATH=ROOT)
     for mode in ("host", "device"):
         r = subprocess.run([sys.executable, "run.py", "-t", "--fpn", "--mask", "--mask_draw", mode, "--input_dim", "512", "--loss_type", "all", "--epochs",
