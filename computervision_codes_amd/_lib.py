@@ -75,6 +75,8 @@ SIGNATURES = {
     "mt4_last_hip_error": (C.c_int, []),
     "mt4_conv_nhwc": (C.c_int, [C.POINTER(ConvDesc), _vp]),
     "mt4_conv_tile_count": (C.c_int, []),
+    "mt4_conv_tile_info": (C.c_int, [_i32] + [C.POINTER(_i32)] * 6),
+    "mt4_conv_plan": (C.c_int, [C.POINTER(ConvDesc)] + [C.POINTER(_i32)] * 3),
     "mt4_conv_packed_k": (C.c_int64, [_i32, _i32, _i32, _i32]),
     "mt4_pack_conv_weight": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mt4_pack_stem_weight": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),

@@ -1390,13 +1390,14 @@ namespace {
 #define MT4_SKIP(...)
 
 enum TileKind { GENERIC, PATCH, STEM, RETIRED };
+static_assert(GENERIC == MT4_TILE_GENERIC && PATCH == MT4_TILE_PATCH && STEM == MT4_TILE_STEM && RETIRED == MT4_TILE_RETIRED, "mt4_conv_tile_info reports these");
 struct TileCfg {
-    int id, kind, bm, bn, waves, stages;
+    int id, kind, bm, bn, waves, stages, ksplit;   // waves: of the whole workgroup (all K-split groups); ksplit: 1 = one group, 0 for retired ids
 };
-#define G(id, bm, bn, wm, wn, st, ks) {id, GENERIC, bm, bn, wm * wn * ks, st},
-#define P(id, bm, bn, wm, wn, ws) {id, PATCH, bm, bn, wm * wn, ws},
-#define S(id, bm, bn, wm, wn) {id, STEM, bm, bn, wm * wn, 0},
-#define R(id, bm, bn) {id, RETIRED, bm, bn, 0, 0},
+#define G(id, bm, bn, wm, wn, st, ks) {id, GENERIC, bm, bn, wm * wn * ks, st, ks},
+#define P(id, bm, bn, wm, wn, ws) {id, PATCH, bm, bn, wm * wn, ws, 1},
+#define S(id, bm, bn, wm, wn) {id, STEM, bm, bn, wm * wn, 0, 1},
+#define R(id, bm, bn) {id, RETIRED, bm, bn, 0, 0, 0},
 constexpr TileCfg kTiles[] = {MT4_CONV_TILES(G, P, S, R)};
 #undef G
 #undef P
@@ -1421,11 +1422,19 @@ ConvK with_grid(const ConvK& k, int out_cols, int BM, int BN) {
     return kk;
 }
 
+// a generic tile takes the channel sums (stat_sums) when it has one wave group and the staged epilogue's LDS holds the waves' partial rows
+constexpr bool tile_can_stats(int bm, int bn, int waves, int ks) { return ks == 1 && waves * bn * 16 <= (bm + bn) * 128; }
+
+// what a generic tile refuses before it launches (launch_generic and mt4_conv_plan both ask here)
+int generic_tile_refusal(const TileCfg& t, const ConvK& k, bool fast, bool out_f32) {
+    if (k.stat_sums && (!tile_can_stats(t.bm, t.bn, t.waves, t.ksplit) || (k.Cout % (out_f32 ? 4 : 8)) != 0)) return MT4_EUNSUPPORTED;
+    if (t.ksplit > 1 && !fast) return MT4_EUNSUPPORTED;   // K-split groups: LDS-DMA path only
+    return MT4_OK;
+}
+
 template <typename T, int BM, int BN, int WM_, int WN_, int STAGES, bool OUT_F32, int KS>
-int launch_tile(const ConvK& k, bool fast, hipStream_t s) {
-    constexpr bool CAN_STATS = KS == 1 && WM_ * WN_ * BN * 16 <= (BM + BN) * 128;   // the staged epilogue's LDS holds the waves' partial rows
-    if (k.stat_sums && (!CAN_STATS || (k.Cout % (OUT_F32 ? 4 : 8)) != 0)) return MT4_EUNSUPPORTED;
-    if (KS > 1 && !fast) return MT4_EUNSUPPORTED;   // K-split groups: LDS-DMA path only
+int launch_tile(const ConvK& k, bool fast, hipStream_t s) {   // (after generic_tile_refusal)
+    constexpr bool CAN_STATS = tile_can_stats(BM, BN, WM_ * WN_ * KS, KS);
     const ConvK kk = with_grid(k, k.Cout, BM, BN);
     // LDS: a ring of operand stages per K-split group (two stages on the register-staged path), or ONE stage when the whole K fits a single
     // step (then only the epilogue staging may need more than a stage): the short-K layers are memory-bound and want as many workgroups
@@ -1462,6 +1471,7 @@ int launch_dual(const ConvK& k, hipStream_t s) {
 
 template <typename T, bool OUT_F32>
 int launch_generic(const ConvK& k, int tile, bool fast, hipStream_t s) {
+    if (const int rc = generic_tile_refusal(kTiles[tile - 1], k, fast, OUT_F32)) return rc;
     switch (tile) {
 #define G(id, bm, bn, wm, wn, st, ks) \
     case id: return launch_tile<T, bm, bn, wm, wn, st, OUT_F32, ks>(k, fast, s);
@@ -1495,12 +1505,19 @@ int patch3x3_lds(const ConvK& k, int BM, int BN, int waves, int WS, bool expand,
     return lds;
 }
 
+// what a patch-kernel launch refuses before it launches (launch_patch3x3 and mt4_conv_plan both ask here); else its LDS bytes and patch rows
+int patch_tile_refusal(const ConvK& k, int BM, int BN, int waves, int WS, bool expand, int* lds_out, int* pra_out) {
+    const int lds = patch3x3_lds(k, BM, BN, waves, WS, expand, pra_out);
+    if (!lds) return MT4_EUNSUPPORTED;
+    if (k.stat_sums && (expand || (k.Cout & 7))) return MT4_EUNSUPPORTED;
+    *lds_out = lds;
+    return MT4_OK;
+}
+
 template <int BM, int BN, int WM_, int WN_, int WS, bool EXPAND = false>
 int launch_patch3x3(const ConvK& k, hipStream_t s) {
-    int pra = 0;
-    const int lds = patch3x3_lds(k, BM, BN, WM_ * WN_, WS, EXPAND, &pra);
-    if (!lds) return MT4_EUNSUPPORTED;
-    if (k.stat_sums && (EXPAND || (k.Cout & 7))) return MT4_EUNSUPPORTED;
+    int pra = 0, lds = 0;
+    if (const int rc = patch_tile_refusal(k, BM, BN, WM_ * WN_, WS, EXPAND, &lds, &pra)) return rc;
     const ConvK kk = with_grid(k, EXPAND ? k.f_cout : k.Cout, BM, BN);
     const dim3 grid(kk.total_tiles), block(WM_ * WN_ * 64);
     const int npatch = k.SPT > 1 ? 2 : 1;
@@ -1541,11 +1558,18 @@ int stem_patch_lds(const ConvK& k, int* pra_out) {
     return lds > 160 * 1024 ? 0 : lds;
 }
 
+// what the stem patch kernel refuses before it launches (launch_stem_patch and mt4_conv_plan both ask here); else its LDS bytes and patch runs
+int stem_tile_refusal(const ConvK& k, int* lds_out, int* pra_out) {
+    const int lds = stem_patch_lds(k, pra_out);
+    if (!lds) return MT4_EUNSUPPORTED;
+    *lds_out = lds;
+    return MT4_OK;
+}
+
 int launch_stem_patch(const ConvK& k, hipStream_t s) {
     constexpr int BM = kStemBM;
-    int pra = 0;
-    const int lds = stem_patch_lds(k, &pra);
-    if (!lds) return MT4_EUNSUPPORTED;
+    int pra = 0, lds = 0;
+    if (const int rc = stem_tile_refusal(k, &lds, &pra)) return rc;
     ConvK kk = with_grid(k, k.Cout, BM, 64);
     kk.n_tiles = cdiv(k.HoWo, BM);                 // tiles per image: no tile spans two images
     kk.total_tiles = k.B * kk.n_tiles;
@@ -1611,6 +1635,18 @@ int auto_tile(int M, int N, int nsteps, int es) {
 }  // namespace
 
 extern "C" int mt4_conv_tile_count(void) { return kNumTiles; }
+
+extern "C" int mt4_conv_tile_info(int32_t id, int32_t* kind, int32_t* bm, int32_t* bn, int32_t* waves, int32_t* stages, int32_t* ksplit) {
+    if (id < 1 || id > kNumTiles) return MT4_EINVAL;
+    const TileCfg& t = kTiles[id - 1];
+    if (kind) *kind = t.kind;
+    if (bm) *bm = t.bm;
+    if (bn) *bn = t.bn;
+    if (waves) *waves = t.waves;
+    if (stages) *stages = t.stages;
+    if (ksplit) *ksplit = t.ksplit;
+    return MT4_OK;
+}
 
 extern "C" int64_t mt4_conv_packed_k(int32_t Cin, int32_t KH, int32_t KW, int32_t dtype) {
     const int es = dtype == MT4_BF16 ? 2 : 4;
@@ -1810,6 +1846,26 @@ extern "C" int mt4_conv_nhwc(const mt4_conv_desc* d, void* stream) {
             return launch_generic<u16, false>(k, c.tile, fast, s);
     }
     return c.kind;
+}
+
+// the host side of mt4_conv_nhwc up to (not including) the launch: the same checks in the same order, through the same functions
+extern "C" int mt4_conv_plan(const mt4_conv_desc* d, int32_t* kind, int32_t* tile, int32_t* fast_out) {
+    ConvK k{};
+    bool fast = false;
+    if (const int rc = fill_conv_args(d, k, &fast)) return rc;
+    if (fast_out) *fast_out = fast ? 1 : 0;
+    if (d->fuse_w || d->x2) return MT4_EUNSUPPORTED;   // launch_fuse_expand / launch_second_source: not planned here
+    const TileChoice c = choose_tile(d, k, fast, d->tile == -1);
+    if (c.kind < 0) return c.kind;
+    const TileCfg& t = kTiles[c.tile - 1];
+    int lds = 0, pra = 0;
+    const int rc = c.kind == STEM    ? stem_tile_refusal(k, &lds, &pra)
+                   : c.kind == PATCH ? patch_tile_refusal(k, t.bm, t.bn, t.waves, t.stages, false, &lds, &pra)
+                                     : generic_tile_refusal(t, k, fast, d->out_dtype == MT4_F32);
+    if (rc) return rc;
+    if (kind) *kind = c.kind;
+    if (tile) *tile = c.tile;
+    return MT4_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ weight packing

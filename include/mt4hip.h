@@ -79,7 +79,7 @@ typedef struct mt4_conv_desc {
                            NOT added but gates the result (y = residual > 0 ? conv : 0; the saved forward activation) */
     int32_t dtype;      /* MT4_F32 / MT4_BF16 : x, w, residual */
     int32_t out_dtype;  /* MT4_F32 / MT4_BF16 : y */
-    int32_t tile;       /* 0 = auto; -1 = auto preferring latency: may take the K-split tiles 35-38 (groups of waves share a tile's K loop;
+    int32_t tile;       /* 0 = auto; -1 = auto preferring latency: may take the K-split tiles 35-42 (groups of waves share a tile's K loop;
                            the K summation order then differs from the other tiles' by fp32 reassociation -- the temporal heads use it);
                            else a tile id 1..mt4_conv_tile_count() (for tuning/tests).  Ids 21-32 (3x3 patch kernel) and 33-34
                            (space-to-depth stem kernels) cover one geometry each: MT4_EUNSUPPORTED for any other */
@@ -129,6 +129,26 @@ typedef struct mt4_conv_desc {
 
 int mt4_conv_nhwc(const mt4_conv_desc* d, void* stream);
 int mt4_conv_tile_count(void);
+/* Host only, no reference counterpart: what the tile ids are and what a descriptor would launch, so that the tile choice can be asserted on a
+ * machine without a GPU instead of being read off a kernel trace.  (Added without an ABI version step, as the metrics functions were.)
+ * mt4_conv_tile_info: the entry of tile `id`: its kernel family, the BM x BN output tile, the waves of a workgroup (all K-split groups together),
+ * the operand stages of the LDS-DMA ring (patch kernel: weight stages; 0 for the stem kernel) and the K-split groups (1 = one group walks K in
+ * order; > 1: LDS-DMA geometries only).  Retired ids report waves = stages = ksplit = 0.  Any output pointer may be NULL.
+ * MT4_EINVAL outside 1..mt4_conv_tile_count(), nothing written. */
+#define MT4_TILE_GENERIC 0 /* igemm_conv_kernel */
+#define MT4_TILE_PATCH 1   /* the 3x3 patch kernel */
+#define MT4_TILE_STEM 2    /* the space-to-depth stem kernel */
+#define MT4_TILE_RETIRED 3 /* kept as a tuning record: MT4_EUNSUPPORTED */
+int mt4_conv_tile_info(int32_t id, int32_t* kind, int32_t* bm, int32_t* bn, int32_t* waves, int32_t* stages, int32_t* ksplit);
+/* mt4_conv_plan: every check mt4_conv_nhwc makes on `d` before it launches, in the same order and through the same code -- the descriptor's own
+ * checks, the tile choice (d->tile, the tuned table for 0, the latency table for -1) and the chosen launcher's refusals (a K-split tile on a
+ * geometry off the LDS-DMA path, stat_sums on a tile that cannot hold them, a patch or stem tile whose LDS does not fit) -- and nothing else: no
+ * launch, no HIP call, and no access to the memory behind the descriptor's pointers (they are checked for NULL and alignment only).
+ * Returns the code mt4_conv_nhwc returns for every descriptor it refuses, MT4_OK where it would launch; then *kind (MT4_TILE_*) and *tile (the id)
+ * say what.  *fast (1: the LDS-DMA path, Cin * esize % 128 == 0 and KH, KW <= 8 on tensors whose tiles span < 2 GiB) is written whenever the
+ * descriptor's own checks pass.  Any output pointer may be NULL.
+ * Out of scope: descriptors with fuse_w or x2 (their launchers choose no tile): MT4_EUNSUPPORTED here whatever mt4_conv_nhwc does with them. */
+int mt4_conv_plan(const mt4_conv_desc* d, int32_t* kind, int32_t* tile, int32_t* fast);
 
 /* One stride-1 ResNet Bottleneck of 64 mid channels (layer1 of ResNet-50) in ONE launch: conv1 1x1 + bn1 + ReLU, conv2 3x3 + bn2 + ReLU,
  * conv3 1x1 + bn3 + residual + ReLU (Spatial_transformer/models/resnet.py:101-121; what Spatial_cnn/network.py:25-31 runs through

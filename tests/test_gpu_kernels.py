@@ -3,11 +3,16 @@
 The bf16 convolutions are also checked element by element against float64 (`bf16_bounds`): `mt4_conv_nhwc` starts its fp32 accumulators at
 the fp32 bias (igemm_conv.hip:146-157; K-split tiles: group 0 only, partial tiles added in fp32 in LDS), adds the bf16 residual and applies the
 activation in fp32, and rounds once when it stores (igemm_conv.hip:539-616); the reference rounds nowhere after the operands."""
+import ctypes
+import functools
+
+import conv_tiles as ct
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
-from bf16_bounds import check_bf16, check_f32
+from bf16_bounds import GELU_APPROX_ERR, GELU_MAX_SLOPE, check_bf16, check_f32
+from conv_tiles import PATCH_TILES
 
 pytestmark = pytest.mark.gpu
 
@@ -17,8 +22,10 @@ def _rand(shape, seed, scale=1.0):
     return (torch.rand(shape, generator=g) * 2 - 1) * scale
 
 
-def _conv_case(cuda, B, H, W, Cin, Cout, kh, kw, stride, pad, dil, dtype, relu, use_res, tile, seed):
+def _conv_case(cuda, B, H, W, Cin, Cout, kh, kw, stride, pad, dil, dtype, relu, use_res, tile, seed, gelu=False):
+    """one launch against F.conv2d: the max-error tolerance, then every element against float64 (`check_bf16` / `check_f32`)"""
     from computervision_codes_amd import ops
+    assert not (relu and gelu)
     x = _rand((B, Cin, H, W), seed)
     w = _rand((Cout, Cin, kh, kw), seed + 1, scale=(3.0 / (Cin * kh * kw)) ** 0.5)
     bias = _rand((Cout,), seed + 2, 0.1)
@@ -34,23 +41,26 @@ def _conv_case(cuda, B, H, W, Cin, Cout, kh, kw, stride, pad, dil, dtype, relu, 
         ref = ref + res
     if relu:
         ref = F.relu(ref)
+    if gelu:
+        ref = F.gelu(ref)
     xd = x.permute(0, 2, 3, 1).contiguous().to(cuda, dtype)
     wp = ops.pack_conv_weight(w.to(cuda), None, dtype)
     rd = res.permute(0, 2, 3, 1).contiguous().to(cuda, dtype) if use_res else None
-    y = ops.conv_nhwc(xd, wp, bias.to(cuda), kh=kh, kw=kw, stride=stride, pad=pad, dil=dil, residual=rd, relu=relu, tile=tile)
+    y = ops.conv_nhwc(xd, wp, bias.to(cuda), kh=kh, kw=kw, stride=stride, pad=pad, dil=dil, residual=rd, relu=relu, act="gelu" if gelu else None, tile=tile)
     torch.cuda.synchronize()
     got = y.float().cpu().permute(0, 3, 1, 2)
     tol = 2e-5 if dtype == torch.float32 else 1.2e-2
     err = (got - ref).abs().max().item()
     assert err <= tol * max(1.0, ref.abs().max().item()), (err, ref.abs().max().item())
-    if dtype == torch.bfloat16:
-        geo = dict(stride=stride, padding=pad, dilation=dil)
-        ref64 = F.conv2d(x.double(), w.double(), bias.double(), **geo)
-        acc64 = F.conv2d(x.double().abs(), w.double().abs(), bias.double().abs(), **geo)
-        if use_res:
-            ref64, acc64 = ref64 + res.double(), acc64 + res.double().abs()
-        check_bf16(got, F.relu(ref64) if relu else ref64, acc64=acc64, k=Cin * kh * kw + 1,
-                   what=f"conv tile {tile} {(B, H, W, Cin, Cout, kh, kw, stride, pad, dil)} relu={relu} res={use_res}")
+    geo = dict(stride=stride, padding=pad, dilation=dil)
+    ref64 = F.conv2d(x.double(), w.double(), bias.double(), **geo)
+    acc64 = F.conv2d(x.double().abs(), w.double().abs(), bias.double().abs(), **geo)
+    if use_res:
+        ref64, acc64 = ref64 + res.double(), acc64 + res.double().abs()
+    ref64 = F.relu(ref64) if relu else F.gelu(ref64) if gelu else ref64
+    check = check_bf16 if dtype == torch.bfloat16 else check_f32      # fp32: the exact-fp32 MFMA chain, the same accumulation term
+    check(got, ref64, acc64=acc64 * (GELU_MAX_SLOPE if gelu else 1.0), k=Cin * kh * kw + 1, extra=GELU_APPROX_ERR if gelu else 0.0,
+          what=f"conv tile {tile} {(B, H, W, Cin, Cout, kh, kw, stride, pad, dil)} {str(dtype)[6:]} relu={relu} gelu={gelu} res={use_res}")
 
 
 CONV_SHAPES = [
@@ -79,10 +89,6 @@ PATCH_SHAPES = [
     (300, 1, 1, 64, 64),      # 1x1 images: only the centre tap is ever valid
     (4, 2, 2, 192, 136),      # three slices, tiny images
 ]
-
-
-PATCH_TILES = {  # id: (BM, BN, waves, weight stages)   (the P entries of igemm_conv.hip's MT4_CONV_TILES; the other ids of 21..32 are retired)
-    23: (256, 256, 16, 2), 24: (256, 64, 8, 2), 26: (256, 128, 16, 2), 30: (128, 128, 4, 2), 32: (256, 128, 8, 2)}
 
 
 def _patch_tile_fits(tile, W, Cin):
@@ -123,12 +129,22 @@ def test_conv3x3_patch_kernel(cuda, shape, tile):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("tile", [35, 36, 37, 38])
+@pytest.mark.parametrize("tile", ct.KSPLIT_TILES)
 def test_conv_ksplit_tiles(cuda, tile, dtype):
-    """tiles 35 / 36: four K-split wave groups per workgroup (each runs every 4th K-step of the same output tile, partial tiles added
-    in LDS in fixed order): TCN-shaped layers -- long K, few pixels -- against F.conv2d; K-step counts that do not divide by 4, a single
-    K-step, ragged T, the 131-wide heads (direct epilogue) and residual + ReLU; deterministic and independent of what else is in the batch"""
+    """every tile with K-split wave groups (2, 4 or 8 per workgroup; group g runs the K-steps g, g + KS, ... of the same output tile, partial
+    tiles added in LDS in fixed order), the 64-row tiles 39-42 of the whole-video layers included: TCN-shaped layers -- long K, few pixels --
+    against F.conv2d; K-step counts that do not divide by the group count, a single K-step, ragged T over several 32- and 64-row tiles, the
+    131-wide heads (direct epilogue), Cout ragged against 64 and 128, residual + ReLU and GELU; deterministic and independent of what else is in
+    the batch; a geometry off the LDS-DMA path is refused, by the planner first"""
     from computervision_codes_amd import ops
+    es = 4 if dtype == torch.float32 else 2
+    d = ct.descriptor(1, 1, 40, 48, 64, 1, 1, "f32" if es == 4 else "bf16", tile=tile)          # Cin 48: 192 / 96 bytes per pixel
+    assert ct.plan(d)[0] == ct.MT4_EUNSUPPORTED and ct.plan(d)[3] == 0
+    with pytest.raises(RuntimeError):
+        _conv_case(cuda, 1, 1, 40, 48, 64, 1, 1, (1, 1), (0, 0), (1, 1), dtype, relu=False, use_res=False, tile=tile, seed=50)
+    _conv_case(cuda, 2, 1, 200, 256, 320, 1, 3, (1, 1), (0, 2), (1, 2), dtype, relu=True, use_res=True, tile=tile, seed=59)     # M 400: 7 tiles of 64, 24 / 12 steps
+    _conv_case(cuda, 1, 1, 77, 128, 96, 1, 3, (1, 1), (0, 1), (1, 1), dtype, relu=False, use_res=False, tile=tile, seed=60, gelu=True)   # 12 / 6 steps, GELU
+    _conv_case(cuda, 2, 1, 200, 128, 131, 1, 1, (1, 1), (0, 0), (1, 1), dtype, relu=True, use_res=True, tile=tile, seed=61)    # direct epilogue + residual, 4 / 2 steps
     _conv_case(cuda, 1, 1, 256, 512, 512, 1, 3, (1, 1), (0, 4), (1, 4), dtype, relu=True, use_res=False, tile=tile, seed=51)     # 48 / 24 K-steps
     _conv_case(cuda, 1, 1, 77, 512, 512, 1, 1, (1, 1), (0, 0), (1, 1), dtype, relu=False, use_res=True, tile=tile, seed=52)      # ragged T
     _conv_case(cuda, 2, 1, 100, 448, 131, 1, 1, (1, 1), (0, 0), (1, 1), dtype, relu=False, use_res=False, tile=tile, seed=53)    # 14 / 7 steps, ragged Cout
@@ -189,7 +205,7 @@ def test_conv_nhwc_auto_tile(cuda, shape, dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("tile", list(range(1, 21)))
+@pytest.mark.parametrize("tile", ct.SEQ_TILES)
 def test_conv_nhwc_every_tile(cuda, tile, dtype):
     # M = 2*13*11 = 286 (ragged vs every BM), N = 96 (ragged vs 64/128), both K modes
     _conv_case(cuda, 2, 13, 11, 64, 96, 3, 3, (1, 1), (1, 1), (1, 1), dtype, relu=False, use_res=False, tile=tile, seed=5)
@@ -199,6 +215,78 @@ def test_conv_nhwc_every_tile(cuda, tile, dtype):
     _conv_case(cuda, 1, 1, 40, 128, 32, 1, 3, (1, 1), (0, 2), (1, 2), dtype, relu=False, use_res=True, tile=tile, seed=8)
     if tile >= 13:   # 8-wave tiles: several 256-row tiles with ragged edges in both directions, 4-pass epilogue
         _conv_case(cuda, 3, 17, 19, 64, 320, 3, 3, (1, 1), (1, 1), (1, 1), dtype, relu=True, use_res=True, tile=tile, seed=9)
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_operands(dt, n, taps):
+    """operands and float64 references of one K-step sweep row, shared by every tile (read only): M = 70 pixels, Cout = 40 (staged epilogue,
+    ragged against every BM and BN), nsteps = n K-steps of 128 bytes; bias of order 1, so a K-split group that added it again would be off by
+    more than any bound.  taps 1: 1x1 with Cin = n * 128 / es; taps 3: 1x3, dilation 2, Cin = n * 128 / (3 es)"""
+    dtype = torch.float32 if dt == "f32" else torch.bfloat16
+    cin = n * (32 if dt == "f32" else 64) // taps
+    x = _rand((1, cin, 1, 70), 7000 + n).to(dtype).float()
+    w = _rand((40, cin, 1, taps), 7100 + n, scale=(3.0 / (cin * taps)) ** 0.5).to(dtype).float()
+    bias = _rand((40,), 7200 + n, 0.5) + 1.0
+    geo = dict(padding=(0, 2 * (taps // 2)), dilation=(1, 2))
+    ref64 = F.conv2d(x.double(), w.double(), bias.double(), **geo)
+    acc64 = F.conv2d(x.double().abs(), w.double().abs(), bias.double().abs(), **geo)
+    return x, w, bias, ref64, acc64, cin
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("tile", ct.RING_TILES)
+def test_conv_kstep_sweep(cuda, tile, dt):
+    """the edge counts of K-steps of the DMA rings (3 / 4 stages) and the K-split loops (igemm_conv.hip:316-373): every nsteps from 1 to
+    groups * stages + 2 -- fewer steps than stages, fewer steps than groups (idle groups contribute neither products nor bias), one more and one
+    fewer than fill the rings -- and a long count (37); then a dilated 1x3 layer of 12 K-steps, where a group's walk (advancing by the group
+    count) crosses tap and channel-slice boundaries.  Every element against float64."""
+    from computervision_codes_amd import ops
+    bm, bn, stages, ks = ct.GENERIC_TILES[tile]
+    dtype = torch.float32 if dt == "f32" else torch.bfloat16
+    check = check_f32 if dt == "f32" else check_bf16
+    for n, taps in [(n, 1) for n in list(range(1, ks * stages + 3)) + [37]] + [(12, 3)]:
+        x, w, bias, ref64, acc64, cin = _sweep_operands(dt, n, taps)
+        d = ct.descriptor(1, 1, 70, cin, 40, 1, taps, dt, tile=tile, pad=(0, 2 * (taps // 2)), dil=(1, 2))
+        assert ct.plan(d) == (ct.MT4_OK, ct.GENERIC, tile, 1)
+        y = ops.conv_nhwc(x.permute(0, 2, 3, 1).contiguous().to(cuda, dtype), ops.pack_conv_weight(w.to(cuda), None, dtype), bias.to(cuda),
+                          kh=1, kw=taps, pad=(0, 2 * (taps // 2)), dil=(1, 2), tile=tile)
+        check(y.float().cpu().permute(0, 3, 1, 2), ref64, acc64=acc64, k=cin * taps + 1, what=f"K-step sweep tile {tile} {dt} nsteps {n} taps {taps}")
+
+
+@pytest.mark.parametrize("i", range(len(ct.LATENCY_ROWS)), ids=lambda i: f"{i}-tile{ct.LATENCY_ROWS[i]['expect'][1]}")
+def test_conv_latency_tile_choice_on_device(cuda, i):
+    """the latency rows of the dispatch table (`conv_tiles.DISPATCH`, asserted through `mt4_conv_plan` on the CPU) on the probe's own shape with
+    random data: the launch inside `ops.latency_tiles()` is bit-identical to the explicit launch of the tile the row names.  Where that is a
+    K-split tile (37, 40, 41) it is also NOT bit-identical to the same call outside the context (another K order), which is what makes the first
+    assertion mean something.  Where it is a sequential-K tile (1, 4, 6, 10, 11) every such tile gives the same bits, so equality with tile=0
+    outside the context is all the device can show; the CPU test carries those rows."""
+    from computervision_codes_amd import ops
+    r = ct.LATENCY_ROWS[i]
+    dtype = torch.float32 if r["dt"] == "f32" else torch.bfloat16
+    g = torch.Generator(device=cuda).manual_seed(900 + i)
+    x = (torch.rand((r["B"], r["H"], r["W"], r["cin"]), device=cuda, generator=g) - 0.5).to(dtype)
+    kpad = ops.packed_k(r["cin"], r["kh"], r["kw"], dtype)      # (random values in the padding columns too: they meet zeros)
+    wp = ((torch.rand((r["cout"], kpad), device=cuda, generator=g) - 0.5) * (12.0 / kpad) ** 0.5).to(dtype)
+    bias = torch.rand((r["cout"],), device=cuda, generator=g)
+    kw = dict(kh=r["kh"], kw=r["kw"], stride=r["stride"], pad=r["pad"], dil=r["dil"])
+    with ops.latency_tiles():
+        lat = ops.conv_nhwc(x, wp, bias, tile=0, **kw)
+    named = ops.conv_nhwc(x, wp, bias, tile=r["expect"][1], **kw)
+    plain = ops.conv_nhwc(x, wp, bias, tile=0, **kw)
+    bits = torch.int32 if dtype == torch.float32 else torch.int16
+    assert float(lat.float().abs().max()) > 0.1
+    assert torch.equal(lat.view(bits), named.view(bits)), r["note"]
+    if r["expect"][1] in ct.KSPLIT_TILES:
+        assert not torch.equal(lat.view(bits), plain.view(bits)), r["note"]
+    else:
+        assert torch.equal(lat.view(bits), plain.view(bits)), r["note"]
+
+
+@pytest.mark.parametrize("dt,tile", [("f32", 40), ("bf16", 41)])
+def test_conv_whole_video_layer_on_its_latency_tile(cuda, dt, tile):
+    """the T = 2000 whole-video layer of the temporal heads (512 -> 512, 1x3) on the tile `latency_tiles()` gives it, every element against float64"""
+    _conv_case(cuda, 1, 1, 2000, 512, 512, 1, 3, (1, 1), (0, 1), (1, 1), torch.float32 if dt == "f32" else torch.bfloat16, relu=True, use_res=False,
+               tile=tile, seed=71)
 
 
 def test_conv_bf16_in_f32_out(cuda):

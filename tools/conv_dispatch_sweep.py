@@ -7,7 +7,9 @@ reproduce it line for line.
   python tools/conv_dispatch_sweep.py --list DIR/*/*_kernel_trace.csv >> DIR/calls.txt      (no GPU needed)
 The list: every explicit tile id on a bf16 3x3 layer and an fp32 1x3 TCN layer, then `tile=0` / `latency_tiles()` launches on both sides of
 every comparison of the tile choice that a descriptor can reach (the branch is named beside each; the sides nothing can reach are listed
-at the end), then the `stat_sums`, `second=` and `conv3x3_expand` routes."""
+at the end), then the `stat_sums`, `second=` and `conv3x3_expand` routes.
+The tile (or error) each plain probe must get is asserted without a GPU: `tests/conv_tiles.py` lists the same probes with the expectation derived
+by hand, `tests/test_conv_plan_cpu.py` checks them through `mt4_conv_plan`.  A probe added here belongs there too."""
 import os
 import sys
 
