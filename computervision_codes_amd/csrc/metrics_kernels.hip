@@ -186,6 +186,60 @@ __global__ __launch_bounds__(256) void component_max_kernel(const float* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------ top-K: rank histogram of the positives
+// hist[r] = number of (row, class) pairs with target != 0 whose score has STABLE RANK r in its row of k scores,
+//     rank(c) = #{ j : p[j] > p[c] } + #{ j < c : p[j] == p[c] }
+// -- the position of c in `np.argsort(-p, kind="stable")` (`Temporal_mstct/run.py:507-523`, `metrics.Recognition.topK`), so that
+// topK(k') = sum(hist[:k']) / sum(hist) for every k' at once.  The comparison runs on `score_image` words (numeric order, -0.0 == +0.0); a
+// NaN takes the word 0, below the image of -inf: last, and tied with the other NaNs, as numpy's sort leaves it.
+// A workgroup stages RH_ROWS rows (their score images and a label byte each) in LDS, a thread per (row, class) of a positive walks the row's k
+// words, the hits land in a k-bin LDS histogram; the workgroup walks row groups in a grid-stride loop and ends in at most k 64-bit integer
+// atomics on `hist`, which a kernel of the same call cleared (integers: any order gives the same counts).  A row's rank r occurs once, so a
+// workgroup's bin never exceeds the rows it walked: 32 bits are enough below RH_MAX_ROWS.
+constexpr int RH_ROWS = 16, RH_MAX_K = 128, RH_THREADS = 256, RH_MAX_GROUPS = 2048;
+constexpr long long RH_MAX_ROWS = 1LL << 40;
+
+__global__ __launch_bounds__(RH_MAX_K) void rank_hist_clear_kernel(unsigned long long* __restrict__ hist, int k) {
+    if ((int)threadIdx.x < k) hist[threadIdx.x] = 0ULL;
+}
+
+__global__ __launch_bounds__(RH_THREADS) void rank_hist_kernel(const float* __restrict__ scores, const float* __restrict__ targets, long long rows, int k,
+                                                               int ld, unsigned long long* __restrict__ hist) {
+    __shared__ unsigned ws[RH_ROWS * RH_MAX_K];
+    __shared__ unsigned char zs[RH_ROWS * RH_MAX_K];
+    __shared__ unsigned hs[RH_MAX_K];
+    const int tid = threadIdx.x;
+    if (tid < RH_MAX_K) hs[tid] = 0u;
+    const long long groups = (rows + RH_ROWS - 1) / RH_ROWS;
+    for (long long g = blockIdx.x; g < groups; g += gridDim.x) {       // (uniform over the workgroup)
+        const long long r0 = g * RH_ROWS;
+        const int nr = (int)min((long long)RH_ROWS, rows - r0);
+        __syncthreads();                                               // the previous group's walks are over (and hs is cleared)
+        for (int i = tid; i < nr * k; i += RH_THREADS) {
+            const int r = i / k, c = i - r * k;
+            const long long at = (r0 + r) * ld + c;
+            const float s = scores[at];
+            ws[i] = s != s ? 0u : score_image(s);
+            zs[i] = targets[at] != 0.f ? 1 : 0;
+        }
+        __syncthreads();
+        for (int i = tid; i < nr * k; i += RH_THREADS) {
+            if (!zs[i]) continue;
+            const int r = i / k, c = i - r * k;
+            const unsigned* row = ws + r * k;
+            const unsigned mine = row[c];
+            int rank = 0;
+            for (int j = 0; j < k; ++j) {
+                const unsigned w = row[j];
+                rank += (w > mine || (w == mine && j < c)) ? 1 : 0;
+            }
+            atomicAdd(&hs[rank], 1u);                                  // rank < k: at most k - 1 of the row's other words count
+        }
+    }
+    __syncthreads();
+    if (tid < k && hs[tid] != 0u) atomicAdd(hist + tid, (unsigned long long)hs[tid]);
+}
+
 }  // namespace
 
 extern "C" int mt4_video_ap_max_rows(void) { return AP_MAX_ROWS; }
@@ -232,5 +286,18 @@ extern "C" int mt4_component_max_f32(const float* x, const int32_t* col_of_tripl
     if ((rows + CM_ROWS - 1) / CM_ROWS > 0x7FFFFFFFLL) return MT4_EUNSUPPORTED;
     hipLaunchKernelGGL(component_max_kernel, dim3((unsigned)((rows + CM_ROWS - 1) / CM_ROWS)), dim3(256), 0, (hipStream_t)stream, x, tab, (int)kc, out,
                        (long long)rows);
+    return mt4_check_launch();
+}
+
+extern "C" int mt4_rank_hist_f32(const float* scores, const float* targets, int64_t rows, int32_t k, int32_t ld, int64_t* hist, void* stream) {
+    mt4_clear_error();
+    if (!scores || !targets || !hist || rows <= 0 || k <= 0 || ld < k) return MT4_EINVAL;
+    if (k > RH_MAX_K || rows > RH_MAX_ROWS) return MT4_EUNSUPPORTED;
+    hipLaunchKernelGGL(rank_hist_clear_kernel, dim3(1), dim3(RH_MAX_K), 0, (hipStream_t)stream, (unsigned long long*)hist, (int)k);
+    int rc = mt4_check_launch();
+    if (rc != MT4_OK) return rc;
+    const long long groups = (rows + RH_ROWS - 1) / RH_ROWS;
+    hipLaunchKernelGGL(rank_hist_kernel, dim3((unsigned)(groups < RH_MAX_GROUPS ? groups : RH_MAX_GROUPS)), dim3(RH_THREADS), 0, (hipStream_t)stream, scores,
+                       targets, (long long)rows, (int)k, (int)ld, (unsigned long long*)hist);
     return mt4_check_launch();
 }

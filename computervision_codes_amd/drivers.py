@@ -47,8 +47,10 @@ def _common(p: argparse.ArgumentParser):
     p.add_argument("--png_decode", type=str, default="host", choices=["host", "device"],
                    help="device: inflate + PNG unfiltering on the GPU (mt4_png_inflate / mt4_png_unfilter_rgb8), the host only reads the files")
     p.add_argument("--metrics", type=str, default="host", choices=["host", "device"],
-                   help="device: the video-wise AP of the trainers' validation and of the temporal closing reports on the GPU (mt4_video_ap_f32 / "
-                        "mt4_component_max_f32) from the fp32 scores where the model wrote them; top-K and the spatial -e / test.py passes stay on the host")
+                   help="device: the video-wise AP and top-K of the trainers' validation, of the temporal closing reports and of the spatial -e / test.py "
+                        "passes on the GPU (mt4_video_ap_f32 / mt4_component_max_f32 / mt4_rank_hist_f32) from the fp32 scores where the model wrote them; "
+                        "under torchrun the spatial passes exchange per-video AP rows and rank histograms instead of the rows.  The pickled metric "
+                        "objects and the temporal drivers' N-rank gather (rank 0 alone runs those) stay on the host")
 
 
 def _flag(*names, **kw):
@@ -165,6 +167,19 @@ def _label_rows(cache, v, lab, device: bool):
     return cache[v]
 
 
+def _spatial_recognition(F, scores_local, mine, order):
+    """{head -> metric object} over the videos of ALL ranks in `order`, identical on every rank, from this rank's `scores_local` (its videos
+    `mine`).  host: every video's (labels, scores) meet in `metrics.gather_recognition`.  --metrics device: the rows stay on the GPU; one
+    rank reports from `DeviceRecognition` objects, N ranks exchange their per-video AP rows and rank histograms
+    (`metrics_device.gather_device_recognition`) -- the same digits either way."""
+    if not _device_metrics(F):
+        return gather_recognition(scores_local, order)
+    from .metrics_device import device_recognition_from, gather_device_recognition, summarize
+    if _dist()[1] == 1:
+        return device_recognition_from(scores_local, order)
+    return gather_device_recognition(summarize(device_recognition_from(scores_local, mine), mine), order)
+
+
 def _recognition(scores, order, device: bool):
     if device:
         from .metrics_device import device_recognition_from
@@ -232,10 +247,12 @@ def _on_rank0(fn):
 # ------------------------------------------------------------------------------------------------ Spatial_cnn/test.py
 def _spatial_cnn_videos(F, model, vids, labels):
     """the per-video loop of `test_loop` (`Spatial_cnn/test.py:143-177`, `run.py:226-256`) over `vids`: -> ({video key -> feat [N,D]},
-    {video -> {head -> (labels [N,K], sigmoid scores [N,K])}})"""
+    {video -> {head -> (labels [N,K], sigmoid scores [N,K])}}); --metrics device: label rows and scores are fp32 tensors on the GPU, the
+    sigmoid of the logits where the extractor left them"""
     feats_local: Dict[str, np.ndarray] = {}
     scores_local = {}
     dev_dec = F.png_decode == "device"
+    dev_met, label_cache = _device_metrics(F), {}
 
     def loader(v):
         ids_all = labels[v]["ivt"][:, 0]                       # file order, no shuffle, drop_last False (`test.py:227-242`)
@@ -246,11 +263,16 @@ def _spatial_cnn_videos(F, model, vids, labels):
     # of 1024 frames, two in flight on streams of their own (sweep: profiles/r04_png_pipeline_sweep.txt -- 9.7-10.2 k frames/s from 480 x 854 files
     # through ResNet-50; the host reader alone delivers > 100 k files/s, what bounds the loop is inflate time + extractor time, which share the CUs).
     plan = [(v, len(labels[v]["ivt"]), loader(v)) for v in vids]
-    for v, feat, lgs in extract.extract_videos_device(model, plan, F.device_batch, prefetch=2 if dev_dec else 1,
-                                                          load_batch=(1023 // F.device_batch + 1) * F.device_batch if dev_dec else None):      # (>= 1024 frames per device decode)
+    for v, feat, lgs, *dev_lgs in extract.extract_videos_device(model, plan, F.device_batch, prefetch=2 if dev_dec else 1,
+                                                                    load_batch=(1023 // F.device_batch + 1) * F.device_batch if dev_dec else None,      # (>= 1024 frames per device decode)
+                                                                    keep_device=dev_met):
         lab = labels[v]
-        scores_local[v] = {key: (lab[key][:, 1:], torch.sigmoid(torch.from_numpy(lg)).numpy())       # `test.py:162-169`
-                           for key, lg in zip(("i", "v", "t", "ivt"), lgs)}
+        if dev_met:
+            rows = _label_rows(label_cache, v, lambda: lab, True)
+            scores_local[v] = {key: (rows[key], torch.sigmoid(lg)) for key, lg in zip(("i", "v", "t", "ivt"), dev_lgs[0])}
+        else:
+            scores_local[v] = {key: (lab[key][:, 1:], torch.sigmoid(torch.from_numpy(lg)).numpy())       # `test.py:162-169`
+                               for key, lg in zip(("i", "v", "t", "ivt"), lgs)}
         feats_local[featfile.video_key(v)] = np.array(feat)    # (own copy: the pinned staging buffer is released)
     return feats_local, scores_local
 
@@ -258,8 +280,8 @@ def _spatial_cnn_videos(F, model, vids, labels):
 def spatial_cnn_eval(argv=None) -> Dict[str, float]:
     """`Spatial_cnn/run.py -e` (:503-560): the TEST-split videos through the best checkpoint and the closing report -- per-category AP, the
     mean-AP row (I / V / T disentangled from the 100-way triplet head when --loss_type all, head-wise otherwise, `:518-525`), top-5 / 10 / 20
-    per component.  Under torchrun whole videos are sharded over the ranks and their (labels, scores) meet in one host-side gather, so N
-    ranks log exactly the single-rank report; rank 0 writes it."""
+    per component.  Under torchrun whole videos are sharded over the ranks and their (labels, scores) -- --metrics device: their AP rows and
+    rank histograms -- meet in one host-side gather, so N ranks log exactly the single-rank report; rank 0 writes it."""
     F = _parser("spatial_cnn", False).parse_known_args(argv)[0]
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold)
@@ -267,7 +289,7 @@ def spatial_cnn_eval(argv=None) -> Dict[str, float]:
     _, _, videos = cholect.split_videos(F.dataset_variant, kfold)
     labels, mine = _labelled_share(F, videos)
     _, scores_local = _spatial_cnn_videos(F, model, mine, labels)
-    m = gather_recognition(scores_local, videos)
+    m = _spatial_recognition(F, scores_local, mine, videos)
     return _on_rank0(lambda: _write_report(stem + ".log", m, F.loss_type, _chlg(F), "spatial_cnn"))
 
 
@@ -282,7 +304,7 @@ def spatial_cnn_test(argv=None) -> Dict[str, np.ndarray]:
     t0 = time.time()
     feats_local, scores_local = _spatial_cnn_videos(F, model, mine, labels)
     merged = extract.gather_feats(feats_local)
-    m = gather_recognition(scores_local, videos)               # the videos of ALL ranks in file order: N ranks log the 1-rank numbers
+    m = _spatial_recognition(F, scores_local, mine, videos)    # the videos of ALL ranks in file order: N ranks log the 1-rank numbers
     all_feats = {featfile.video_key(v): merged[featfile.video_key(v)] for v in videos}
     if rank == 0:
         featfile.write_feats(featfile.feats_path("..", F.version, F.kfold, F.loss_type), all_feats)
@@ -622,31 +644,38 @@ def spatial_transformer_test(argv=None) -> Dict[str, np.ndarray]:
 def _q2l_scores(F, model, vids, labels):
     """`test_loop` of `Spatial_transformer/run.py:231-262` over `vids`: device batches in file order (loads of one batch, one running ahead), the
     teacher features the loader hands a `loss_type all` model off the train split are zeros (`dataloader.py:240-246`) -> {video -> {head ->
-    (labels, sigmoid scores)}}; heads the model does not have score sigmoid(0) like the reference's zero logits (`network.py:84-89`)"""
+    (labels, sigmoid scores)}}; heads the model does not have score sigmoid(0) like the reference's zero logits (`network.py:84-89`).
+    --metrics device: label rows and scores are fp32 tensors on the GPU"""
     out_scores = {}
     single = F.loss_type != "all"
+    dev_met, label_cache = _device_metrics(F), {}
     for v in vids:
         acc = {k: [] for k in ("i", "v", "t", "ivt")}
         for fr in _q2l_chunks(F, v, labels[v]["ivt"][:, 0]):
             zt = [] if single else [torch.zeros((fr.shape[0], F.teacher_dim), device=fr.device)] * 3
             o = model(fr, *zt)
             for gi, key in enumerate(("i", "v", "t", "ivt")):
-                acc[key].append(_sigmoid(o[gi][1]))
-        out_scores[v] = {key: (labels[v][key][:, 1:], np.concatenate(acc[key])) for key in acc}
+                acc[key].append(_scores(o[gi][1], dev_met))
+        if dev_met:
+            rows = _label_rows(label_cache, v, lambda v=v: labels[v], True)
+            out_scores[v] = {key: (rows[key], torch.cat(acc[key])) for key in acc}
+        else:
+            out_scores[v] = {key: (labels[v][key][:, 1:], np.concatenate(acc[key])) for key in acc}
     return out_scores
 
 
 def spatial_transformer_eval(argv=None) -> Dict[str, float]:
     """`Spatial_transformer/run.py -e` (:482-527): the TEST-split videos through the best checkpoint of run_<version>[_<task>]/ and the closing
     report (per-category AP, mean-AP row; I / V / T from the component heads for a single-task teacher, disentangled from the triplet head for
-    --loss_type all).  Videos sharded over the ranks, (labels, scores) gathered on the host, rank 0 writes: N ranks log the 1-rank report."""
+    --loss_type all).  Videos sharded over the ranks, (labels, scores) gathered on the host (--metrics device: AP rows computed on the GPU),
+    rank 0 writes: N ranks log the 1-rank report."""
     F = _parser("spatial_transformer", False).parse_known_args(argv)[0]
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold, task_dir=True)
     model = _eval_model("spatial_transformer", F, [stem + ".pth"])
     _, _, videos = cholect.split_videos(F.dataset_variant, kfold)
     labels, mine = _labelled_share(F, videos)
-    m = gather_recognition(_q2l_scores(F, model, mine, labels), videos)
+    m = _spatial_recognition(F, _q2l_scores(F, model, mine, labels), mine, videos)
     return _on_rank0(lambda: _write_report(stem + ".log", m, F.loss_type, _chlg(F), "spatial_transformer"))
 
 

@@ -128,25 +128,28 @@ def iter_chunks(spans: Sequence[tuple], load_chunk: Callable[..., torch.Tensor],
                     pass
 
 
-def extract_videos_device(model, videos, device_batch: int = 512, streams: int = 1, prefetch=1, load_batch: int = None):
+def extract_videos_device(model, videos, device_batch: int = 512, streams: int = 1, prefetch=1, load_batch: int = None, keep_device: bool = False):
     """Several videos through the spatial extractor with ONE loader pipeline across them (`Spatial_cnn/test.py:266-268` loops over the videos;
     its DataLoader workers start each video cold): `videos` = sequence of (key, n_frames, load_chunk); the spans of all videos form one
     sequence for `iter_chunks`, so while video k's last passes run the first loads of video k + 1 are already being read and decoded -- the
     pipeline fills once per run, not once per video.  Yields (key, feat [N,D] float32 ndarray, logits (i, v, t, ivt) float32 ndarrays) per
-    video, in order; features and logits of a video stay on the device until it ends, then cross to the host ONCE through pinned memory."""
+    video, in order; features and logits of a video stay on the device until it ends, then cross to the host ONCE through pinned memory.
+    `keep_device` (--metrics device): a fourth item per video, the same four fp32 logit tensors as they lie on the device."""
     load_batch = max(device_batch, load_batch or device_batch) // device_batch * device_batch      # whole passes per load
     spans = [(vi, s, min(n, s + load_batch)) for vi, (_, n, _) in enumerate(videos) for s in range(0, n, load_batch)]
     last = {vi: e for vi, _, e in spans}
 
     def finish(feats, logits):
         if not feats:
-            return np.zeros((0, 0), np.float32), tuple(np.zeros((0, 0), np.float32) for _ in range(4))
+            none = (np.zeros((0, 0), np.float32), tuple(np.zeros((0, 0), np.float32) for _ in range(4)))
+            return none + (tuple(torch.zeros((0, 0), device="cuda") for _ in range(4)),) if keep_device else none
         dev_out = [torch.cat(feats).float()] + [torch.cat(l).float() for l in logits]
         host = [torch.empty(t.shape, dtype=torch.float32, pin_memory=True) for t in dev_out]
         for h, d in zip(host, dev_out):
             h.copy_(d, non_blocking=True)
         torch.cuda.current_stream().synchronize()
-        return host[0].numpy(), tuple(h.numpy() for h in host[1:])
+        out = (host[0].numpy(), tuple(h.numpy() for h in host[1:]))
+        return out + (tuple(dev_out[1:]),) if keep_device else out
     done = 0
     feats, logits = [], [[], [], [], []]
     chunks = iter_chunks(spans, lambda vi, s, e: videos[vi][2](s, e), prefetch)

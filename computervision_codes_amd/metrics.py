@@ -57,6 +57,27 @@ def component_table(component: str):
     return np.searchsorted(uniq, idx).astype(np.int32), int(len(uniq))
 
 
+def rank_hist(targets, predictions, k: int = None) -> np.ndarray:
+    """int64 [K]: hist[r] = number of (row, class) pairs with targets != 0 whose score has the STABLE RANK r among the first K = k (default:
+    all) columns of its row,  rank(c) = #{ j : p[j] > p[c] } + #{ j < c : p[j] == p[c] }  -- the place of c in `np.argsort(-p, kind="stable")`,
+    by that definition and not through a sort.  Numeric comparison (-0.0 == +0.0); a NaN ranks below every number and ties with the other
+    NaNs, as numpy's sort puts NaN last.  `Recognition.topK(k')` of the same rows is sum(hist[:k']) / max(sum(hist), 1) for every k';
+    what `ops.rank_hist` (`mt4_rank_hist_f32`) is tested against."""
+    t, p = np.asarray(targets), np.asarray(predictions)
+    k = p.shape[1] if k is None else int(k)
+    t, p = t[:, :k] != 0, p[:, :k]
+    hist = np.zeros(k, dtype=np.int64)
+    before = np.tri(k, k, -1, dtype=bool).T                           # [j, c]: j < c
+    for s in range(0, p.shape[0], 1024):                              # (rows x K x K booleans at a time)
+        pj, pc = p[s:s + 1024, :, None], p[s:s + 1024, None, :]
+        nj, nc = np.isnan(pj), np.isnan(pc)
+        above = (pj > pc) | (nc & ~nj)
+        tie = (pj == pc) | (nj & nc)
+        rank = (above | (tie & before)).sum(axis=1)                   # [rows, c]
+        hist += np.bincount(rank[t[s:s + 1024]], minlength=k)[:k]
+    return hist
+
+
 def video_mean(per_video, num_class: int):
     """per-video AP vectors ([K] each, NaN = class without positives in the video) -> {"AP": nan-mean over videos per class, "mAP": nan-mean
     over classes}; shared by `Recognition.compute_video_AP` and `metrics_device.DeviceRecognition.compute_video_AP`"""
@@ -102,11 +123,14 @@ class Recognition:
     def compute_video_AP(self, component: str = "ivt", ignore_null: bool = False):
         if component != "ivt" and self.num_class != 100:
             raise ValueError("component disentangling needs the 100-way triplet scores")
+        return video_mean(self.per_video_AP(component, ignore_null), self.num_class)
+
+    def per_video_AP(self, component: str = "ivt", ignore_null: bool = False) -> List[np.ndarray]:
+        """the rows `compute_video_AP` averages: per video the AP of every class of `component` (NaN: no positives in the video)"""
         drop = N_NULL_TRIPLETS if (ignore_null and component == "ivt" and self.num_class == 100) else 0
         cut = (lambda a: a[:, :a.shape[1] - drop]) if drop else (lambda a: a)
-        per_video = [self._ap_per_class(cut(disentangle(t, component)), cut(disentangle(p, component)))
-                     for t, p in zip(self.global_targets, self.global_predictions)]
-        return video_mean(per_video, self.num_class)
+        return [self._ap_per_class(cut(disentangle(t, component)), cut(disentangle(p, component)))
+                for t, p in zip(self.global_targets, self.global_predictions)]
 
     def topK(self, k: int = 5, component: str = "ivt") -> float:
         """`mAP.topK(k, component)` (`Spatial_cnn/run.py:543-548`) as the reference spells it out itself in `Temporal_mstct/run.py:507-523`

@@ -1318,6 +1318,21 @@ def component_max(x: torch.Tensor, col_of_triplet, kc: int) -> torch.Tensor:
     return out
 
 
+def rank_hist(scores: torch.Tensor, targets: torch.Tensor, k: Optional[int] = None) -> torch.Tensor:
+    """int64 [k] on the device: hist[r] = number of (row, class) pairs with targets != 0 whose score has stable rank r among the first k columns
+    of its row (`mt4_rank_hist_f32`; `metrics.rank_hist`) -- top-K for every K is sum(hist[:K]) / sum(hist).  scores / targets fp32 [N, ld]"""
+    _need_cuda(scores, targets)
+    assert scores.dtype == torch.float32 and targets.dtype == torch.float32 and scores.dim() == 2 and scores.shape == targets.shape
+    assert scores.is_contiguous() and targets.is_contiguous()
+    ld = scores.shape[1]
+    k = ld if k is None else int(k)
+    if scores.shape[0] == 0:
+        return torch.zeros(k, dtype=torch.int64, device=scores.device)
+    out = torch.empty(k, dtype=torch.int64, device=scores.device)
+    check(lib.mt4_rank_hist_f32(scores.data_ptr(), targets.data_ptr(), scores.shape[0], k, ld, out.data_ptr(), _stream()), "mt4_rank_hist_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- Swin / Q2L training pieces (fp32)
 def gather_rows(x: torch.Tensor, row_map: torch.Tensor, *, l_out: int, l_in: int, group: int = 1, m_out: Optional[int] = None) -> torch.Tensor:
     """y[m][g*C:(g+1)*C] = x[(m // l_out) * l_in + map[(m % l_out) * group + g]]  (`mt4_gather_rows_f32`)"""

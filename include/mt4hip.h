@@ -657,6 +657,17 @@ int mt4_video_ap_f32(const float* scores, const float* targets, const int64_t* r
  * col_of_triplet int32 [100] in HOST memory, every entry in [0, kc) (else MT4_EINVAL, before the launch); a column no triplet maps to
  * gets -inf. */
 int mt4_component_max_f32(const float* x, const int32_t* col_of_triplet, int32_t kc, float* out, int64_t rows, void* stream);
+/* hist[r] = number of (row, class) pairs with targets != 0 whose score has stable rank r among the row's first k scores,
+ *     rank(c) = #{ j : p[j] > p[c] } + #{ j < c : p[j] == p[c] },
+ * the place of class c in `np.argsort(-p, kind="stable")`: top-K as the reference spells it out (Temporal_mstct/run.py:507-523 `topk`;
+ * `mAP.topK(k, component)`, Spatial_cnn/run.py:543-548) is sum(hist[:K]) / sum(hist) over all frames, for every K from one call.
+ * Comparisons are numeric (-0.0 == +0.0); a NaN ranks below every number, -inf included, and ties with the other NaNs (numpy sorts NaN last).
+ *   scores, targets  float32 [rows][ld] on the device; the first k columns are read (ld > k: the ignore_null layout, 94 of 100)
+ *   hist             int64 [k] on the device; cleared by a kernel of this call (no memset node in a captured graph), then summed with
+ *                    64-bit integer atomics: exact and repeatable in any order.  Needs no scratch.
+ * Enqueue-only, capturable.  MT4_EINVAL: null pointer, rows <= 0, k <= 0, ld < k; MT4_EUNSUPPORTED: k > 128, rows > 2^40 (a workgroup's
+ * 32-bit bins; the grid itself is capped at 2048 workgroups that walk the row groups, so no grid limit applies) -- both before any launch. */
+int mt4_rank_hist_f32(const float* scores, const float* targets, int64_t rows, int32_t k, int32_t ld, int64_t* hist, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Backward pieces of the Swin + Query2Label teacher (what torch autograd derives inside Spatial_transformer/run.py:150-229 for
