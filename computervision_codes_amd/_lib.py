@@ -90,6 +90,7 @@ SIGNATURES = {
     "mt4_png_read_files": (C.c_int, [C.POINTER(C.c_char_p), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32]),
     "mt4_resize_pass_u8": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mt4_aug_channel_luts": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "mt4_aug_sharpen_u8": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "mt4_aug_flip_lut_rotate": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mt4_aug_resize_pass_u8": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mt4_take_rows_f32": (C.c_int, [C.POINTER(TakeSeg), _i32, _vp, C.c_int64, _vp]),

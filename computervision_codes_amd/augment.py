@@ -1,9 +1,9 @@
 """The train transform of the frame trainers (`Spatial_cnn/dataloader.py:89-100,153-162`: Resize -> vflip -> hflip -> autocontrast ->
-rotation by a random angle with expand -> Resize) as a function of (frames, random draws) that runs on the device and returns the bytes
+sharpening (the list's 'brightness') -> rotation by a random angle with expand -> Resize) as a function of (frames, random draws) that runs on the device and returns the bytes
 Pillow returns (`drivers.load_train_frames_u8`, the `--train_transform host` path).
 
 `draw_params` consumes the `random.Random` of the host path draw for draw and does the float64 matrix work of `Image.rotate`;
-`reference_u8` is the integer arithmetic in numpy (CPU tests, bug hunting); `train_transform_device` launches the three kernels of
+`reference_u8` is the integer arithmetic in numpy (CPU tests, bug hunting); `train_transform_device` launches the kernels of
 csrc/augment_kernels.hip; `load_train_batch_device` is the loader `drivers._frame_batch` routes to.  This module imports without
 libmt4hip.so: `ops` is imported where a launch happens."""
 from __future__ import annotations
@@ -14,15 +14,21 @@ from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
-NPARAMS = 12            # MT4_AUG_PARAMS (include/mt4hip.h): vflip, hflip, a0..a5, nw, nh, contrast, 0
+NPARAMS = 12            # MT4_AUG_PARAMS (include/mt4hip.h): vflip, hflip, a0..a5, nw, nh, contrast, sharpen
+# column 11, the draw of 'brightness': 0 = not drawn (always, for a list without the name); 1 = sharpen the frame as it stands -- its autocontrast,
+# if drawn, comes later and takes its range from the sharpened frame; 2 = the frame's autocontrast was drawn before it: the sharpening reads the
+# frame through its LUTs, and the gather kernel does not apply them again
+SHARP_ROWS, SHARP_COLS = 16, 64          # the tile of the sharpening kernel (AUG_SH_ROWS, AUG_SH_COLS of csrc/augment_kernels.hip)
 
 
 def supported(names: Sequence[str]) -> bool:
     """the lists the device form covers: at most one `rot90`, at most one `contrast`, and no `contrast` after the `rot90` (the black fill of
     the rotation would enter the histogram).  A second autocontrast is NOT the identity: `int(hi * scale + offset)` is 254 for about 15 % of
     the (lo, hi) pairs, so the second one stretches again; the kernels hold one LUT per channel, so such a list keeps the host path.  Flips may
-    stand anywhere; `original` and names `_augment` ignores are no-ops."""
-    seen_rot = seen_contrast = False
+    stand anywhere; `original` and names `_augment` ignores are no-ops.  At most one `brightness`, before the `rot90`: after it the sharpening
+    would act on the black fill and the rotated edge.  It may stand on either side of `contrast`, and anywhere among the flips: the stencil
+    and its border rule are symmetric and the result depends on the integers alone, so it commutes with both flips exactly."""
+    seen_rot = seen_contrast = seen_sharp = False
     for n in names:
         if n == "rot90":
             if seen_rot:
@@ -32,14 +38,20 @@ def supported(names: Sequence[str]) -> bool:
             if seen_rot or seen_contrast:
                 return False
             seen_contrast = True
+        elif n == "brightness":
+            if seen_rot or seen_sharp:
+                return False
+            seen_sharp = True
     return True
 
 
 class Params:
-    """table int32 [B, NPARAMS] (the rows the kernels read), the frame size (h, w) it was built for, rotated = the list has `rot90`"""
+    """table int32 [B, NPARAMS] (the rows the kernels read), the frame size (h, w) it was built for, rotated = the list has `rot90`,
+    sharpened = some frame drew the sharpening (column 11)"""
 
     def __init__(self, table: np.ndarray, h: int, w: int, rotated: bool):
         self.table, self.h, self.w, self.rotated = table, h, w, rotated
+        self.sharpened = bool(table[:, 11].any())
 
     def __len__(self):
         return len(self.table)
@@ -75,13 +87,14 @@ def rotation_row(angle: float, h: int, w: int) -> Tuple[List[int], int, int]:
 
 def draw_params(rng, names: Sequence[str], n: int, h: int, w: int) -> Params:
     """the draws of `drivers._augment` for n frames of h x w, frame by frame in list order (`random() < 0.4` per vflip, `random() < 0.4`
-    per hflip, `random() < 0.5` per contrast, `uniform(-90, 90)` per rot90): afterwards rng is in the state the host path leaves.  A flip
+    per hflip, `random() < 0.5` per contrast, `random() < 0.5` per brightness, `uniform(-90, 90)` per rot90): afterwards rng is in the state the host path leaves.  A flip
     listed after `rot90` acts on the rotated image; it is folded into the affine map (X -> nw-1-X, Y -> nh-1-Y), which is exact in integers."""
     if not supported(names):
-        raise ValueError(f"augmentation list {list(names)}: 'contrast' after 'rot90' (or 'contrast' / 'rot90' twice) has no device form")
+        raise ValueError(f"augmentation list {list(names)}: 'contrast' or 'brightness' after 'rot90' (or 'contrast' / 'brightness' / 'rot90' twice) "
+                         "has no device form")
     table = np.zeros((n, NPARAMS), np.int32)
     for i in range(n):
-        vflip = hflip = contrast = 0
+        vflip = hflip = contrast = sharpen = 0
         post_v = post_h = 0
         fx, nw, nh = [65536, 0, 32768, 0, 65536, 32768], w, h          # the identity map: (32768 + 65536 X) >> 16 = X
         rotated = False
@@ -98,6 +111,8 @@ def draw_params(rng, names: Sequence[str], n: int, h: int, w: int) -> Params:
                     hflip ^= 1
             elif name == "contrast" and rng.random() < 0.5:
                 contrast = 1                                             # (`supported`: the list names it once)
+            elif name == "brightness" and rng.random() < 0.5:
+                sharpen = 2 if contrast else 1                           # (column 11, see NPARAMS)
             elif name == "rot90":
                 fx, nw, nh = rotation_row(rng.uniform(-90.0, 90.0), h, w)
                 rotated = True
@@ -106,7 +121,7 @@ def draw_params(rng, names: Sequence[str], n: int, h: int, w: int) -> Params:
             a2, a5, a0, a3 = a2 + (nw - 1) * a0, a5 + (nw - 1) * a3, -a0, -a3
         if post_v:
             a2, a5, a1, a4 = a2 + (nh - 1) * a1, a5 + (nh - 1) * a4, -a1, -a4
-        table[i] = (vflip, hflip, a0, a1, a2, a3, a4, a5, nw, nh, contrast, 0)
+        table[i] = (vflip, hflip, a0, a1, a2, a3, a4, a5, nw, nh, contrast, sharpen)
     return Params(table, h, w, "rot90" in names)
 
 
@@ -185,6 +200,60 @@ def reference_luts(frames: np.ndarray, params: Params) -> np.ndarray:
     return luts
 
 
+def sharpen_u8(img: np.ndarray) -> np.ndarray:
+    """`ImageEnhance.Sharpness(im).enhance(1.6)` of one image uint8 [H,W,C] in integers: N = the 3 x 3 neighbourhood sum + 4 x centre (SMOOTH is
+    [1 1 1; 1 5 1; 1 1 1] / 13), deg = (2 N + 13) // 26 (Pillow's float32 `0.5 + N / 13` truncated: 13 is odd, so the sum is never within 1/26
+    of an integer), out = clamp(trunc((5 deg + 8 (p - deg)) / 5)) (the blend p + 0.6 (p - deg), truncated toward zero); the one-pixel border is
+    the source, an image with H < 3 or W < 3 comes back unchanged"""
+    h, w = img.shape[:2]
+    out = img.copy()
+    if h < 3 or w < 3:
+        return out
+    a = img.astype(np.int64)
+    n = 4 * a[1:-1, 1:-1]
+    for dy in range(3):
+        for dx in range(3):
+            n = n + a[dy:h - 2 + dy, dx:w - 2 + dx]
+    deg = (2 * n + 13) // 26
+    t = 5 * deg + 8 * (a[1:-1, 1:-1] - deg)
+    t = np.where(t >= 0, t // 5, -((-t) // 5))                              # toward zero
+    out[1:-1, 1:-1] = np.clip(t, 0, 255).astype(np.uint8)
+    return out
+
+
+def _lut_first(params: Params) -> bool:
+    """the call applies the autocontrast before the sharpening (some row has sharpen == 2).  A list has ONE order, so `draw_params` never puts
+    such a row beside a row whose autocontrast follows its sharpening (sharpen == 1 with the contrast flag)"""
+    t = params.table
+    first = bool((t[:, 11] == 2).any())
+    assert not (first and ((t[:, 11] == 1) & (t[:, 10] != 0)).any()), "rows of both autocontrast / sharpening orders in one table"
+    return first
+
+
+def reference_sharp(frames: np.ndarray, luts, params: Params) -> np.ndarray:
+    """uint8 [B,h,w,3], what `mt4_aug_sharpen_u8` writes: the sharpened image of every frame whose sharpen column is set (of the frame read
+    through its LUTs when the column is 2 and luts is given), a copy of the others"""
+    out = frames.copy()
+    for i in range(len(frames)):
+        mode = int(params.table[i, 11])
+        if mode:
+            src = frames[i]
+            if mode == 2 and luts is not None:
+                src = np.stack([luts[i, c][src[..., c]] for c in range(3)], -1)
+            out[i] = sharpen_u8(src)
+    return out
+
+
+def canvas_luts(luts: np.ndarray, params: Params) -> np.ndarray:
+    """the tables the gather applies: `luts`, the identity for the frames whose LUTs the sharpening already applied"""
+    done = params.table[:, 11] == 2
+    if not done.any():
+        return luts
+    luts = luts.copy()
+    luts[done] = np.arange(256, dtype=np.uint8)
+    return luts
+
+
 def canvas_dims(params: Params) -> Tuple[int, int]:
     """(Hc, Wc) of the padded canvas: the batch maxima of (nh, nw), the width rounded up to 4 pixels when a resize follows (its rows are then
     whole dwords)"""
@@ -230,19 +299,34 @@ def reference_resize_pass(img: np.ndarray, n_out: int, axis: int) -> np.ndarray:
 def reference_u8(frames: np.ndarray, params: Params, stages: bool = False):
     """the whole transform in numpy integers: uint8 [B,h,w,3] -> uint8 [B,h,w,3].  stages=True -> the dict of every stage: 'luts' [B,3,256],
     'canvas' [B,Hc,Wc,3], 'rotated' (the list of [nh,nw,3] images = what Pillow holds before the second Resize), 'hpass' (list of [nh,w,3]),
-    'out'"""
+    'out'; and, when a frame drew the sharpening, 'sharp' [B,h,w,3] = the frames after it (`reference_sharp`).  'luts' then holds the tables of
+    the frames as stored when the autocontrast comes first, of the sharpened frames when it comes second."""
     frames = np.ascontiguousarray(frames)
     b, h, w, _ = frames.shape
     assert (h, w) == (params.h, params.w) and b == len(params)
-    luts = reference_luts(frames, params)
-    canvas = reference_canvas(frames, luts, params)
+    sharp = None
+    if params.sharpened:
+        if _lut_first(params):
+            luts = reference_luts(frames, params)
+            frames = sharp = reference_sharp(frames, luts, params)
+        else:
+            frames = sharp = reference_sharp(frames, None, params)
+            luts = reference_luts(frames, params)
+    else:
+        luts = reference_luts(frames, params)
+    canvas = reference_canvas(frames, canvas_luts(luts, params), params)
     rotated = [canvas[i, :nh, :nw] for i, (nh, nw) in enumerate(params.sizes())]
     if params.rotated:
         hpass = [reference_resize_pass(im, w, 0) for im in rotated]
         out = np.stack([reference_resize_pass(im, h, 1) for im in hpass])
     else:
         hpass, out = rotated, canvas
-    return {"luts": luts, "canvas": canvas, "rotated": rotated, "hpass": hpass, "out": out} if stages else out
+    if not stages:
+        return out
+    st = {"luts": luts, "canvas": canvas, "rotated": rotated, "hpass": hpass, "out": out}
+    if sharp is not None:
+        st["sharp"] = sharp
+    return st
 
 
 # ------------------------------------------------------------------------------------------------ the device form
@@ -256,6 +340,17 @@ def channel_luts_device(frames, table_dev):
     ops.check(ops.lib.mt4_aug_channel_luts(frames.data_ptr(), table_dev.data_ptr(), minmax.data_ptr(), luts.data_ptr(), b, h, w, ops._stream()),
               "mt4_aug_channel_luts")
     return luts
+
+
+def sharpen_device(frames, luts, table_dev):
+    """`mt4_aug_sharpen_u8`: uint8 [B,H,W,3] on the GPU, the LUTs [B,3,256] or None -> a new uint8 [B,H,W,3] (a stencil cannot run in place)"""
+    import torch
+    from . import ops
+    b, h, w, _ = frames.shape
+    out = torch.empty_like(frames)
+    ops.check(ops.lib.mt4_aug_sharpen_u8(frames.data_ptr(), luts.data_ptr() if luts is not None else None, table_dev.data_ptr(), out.data_ptr(),
+                                         b, h, w, ops._stream()), "mt4_aug_sharpen_u8")
+    return out
 
 
 def flip_lut_rotate_device(frames, luts, table_dev, hc: int, wc: int):
@@ -299,7 +394,9 @@ def resize_pass_device(x, pool_buf, ft_dev, n_out: int, ksize_max: int, axis: in
 
 def train_transform_device(frames, params: Params, stages: bool = False):
     """uint8 [B,h,w,3] on the GPU -> uint8 [B,h,w,3]: the bytes of `reference_u8` (= Pillow's).  Nothing is read back from the device: the canvas size
-    and the tables come from `params`; the parameter rows and the frame-table rows go up as two small host-to-device copies per call.  stages=True -> the dict of 'luts', 'canvas', 'hpass', 'out' tensors."""
+    and the tables come from `params`; the parameter rows and the frame-table rows go up as two small host-to-device copies per call.  stages=True -> the dict of 'luts', 'canvas', 'hpass', 'out' tensors.
+    When a frame of the call drew the sharpening, one more launch and one more [B,h,w,3] buffer ('sharp' under stages=True): LUTs of the frames
+    as stored, then the sharpening through them, when the list has `contrast` first; the sharpening, then the LUTs of its output, otherwise."""
     import torch
     from . import ops
     ops._need_cuda(frames)
@@ -307,7 +404,16 @@ def train_transform_device(frames, params: Params, stages: bool = False):
     b, h, w, _ = frames.shape
     assert (h, w) == (params.h, params.w) and b == len(params) and b > 0
     table_dev = torch.from_numpy(params.table).to(frames.device)
-    luts = channel_luts_device(frames, table_dev)
+    sharp = None
+    if params.sharpened:
+        if _lut_first(params):
+            luts = channel_luts_device(frames, table_dev)
+            frames = sharp = sharpen_device(frames, luts, table_dev)
+        else:
+            frames = sharp = sharpen_device(frames, None, table_dev)
+            luts = channel_luts_device(frames, table_dev)
+    else:
+        luts = channel_luts_device(frames, table_dev)
     hc, wc = canvas_dims(params)
     canvas = flip_lut_rotate_device(frames, luts, table_dev, hc, wc)
     hpass = out = canvas
@@ -315,7 +421,12 @@ def train_transform_device(frames, params: Params, stages: bool = False):
         ft_dev, pool_buf, (kh, kv) = frame_tables(params, frames.device)
         hpass = resize_pass_device(canvas, pool_buf, ft_dev, w, kh, 0)
         out = resize_pass_device(hpass, pool_buf, ft_dev, h, kv, 1)
-    return {"luts": luts, "canvas": canvas, "hpass": hpass, "out": out} if stages else out
+    if not stages:
+        return out
+    st = {"luts": luts, "canvas": canvas, "hpass": hpass, "out": out}
+    if sharp is not None:
+        st["sharp"] = sharp
+    return st
 
 
 def load_train_batch_device(data_dir: str, samples: Sequence[Tuple[str, int]], height: int, width: int, rng, names: Sequence[str],

@@ -3,10 +3,13 @@
 // same random draws (augment.py draws them and builds the per-frame parameter table; its `reference_u8` is the same arithmetic in numpy).
 //
 //   mt4_aug_channel_luts      per frame and channel min / max -> the autocontrast lookup tables
+//   mt4_aug_sharpen_u8        RandomAdjustSharpness(1.6) (the list's 'brightness') of the frames that drew it, a copy of the others
 //   mt4_aug_flip_lut_rotate   flips + LUT + nearest-neighbour affine gather (16.16 fixed point) into a zero-filled padded canvas
 //   mt4_aug_resize_pass_u8    mt4_resize_pass_u8 with per-frame input extents and per-frame coefficient tables out of a device pool
 //
-// The per-frame parameter row (int32 x MT4_AUG_PARAMS): {vflip, hflip, a0, a1, a2, a3, a4, a5, nw, nh, contrast, 0}.
+// The per-frame parameter row (int32 x MT4_AUG_PARAMS): {vflip, hflip, a0, a1, a2, a3, a4, a5, nw, nh, contrast, sharpen}; sharpen = 0 (not
+// drawn), 1 (sharpen the frame as stored; an autocontrast, if drawn, follows and takes its range from the sharpened frame) or 2 (the frame's
+// autocontrast comes first: the sharpening reads through the LUTs and mt4_aug_flip_lut_rotate does not apply them again).
 #include "mt4_common.h"
 
 // the autocontrast LUT is `int(i * scale + offset)` with TWO float64 roundings (Python floats): a fused multiply-add would change bytes
@@ -122,10 +125,131 @@ extern "C" int mt4_aug_channel_luts(const uint8_t* frames, const int32_t* params
     return mt4_check_launch();
 }
 
+// ------------------------------------------------------------------------------------------------ sharpening ('brightness')
+// `ImageEnhance.Sharpness(im).enhance(1.6)` = blend(im.filter(SMOOTH), im, 1.6) in integers.  With N = the sum of the 3 x 3 neighbourhood plus
+// 4 x the centre (SMOOTH is [1 1 1; 1 5 1; 1 1 1] / 13), Pillow's float32 `0.5 + N / 13` truncated is deg = (2 N + 13) / 26: 13 is odd, so the
+// float sum is never within 1/26 of an integer.  The blend p + 0.6 (p - deg), truncated toward zero and clamped, is (5 deg + 8 (p - deg)) / 5
+// with C's division.  The one-pixel border of the image is the source, so an image with H < 3 or W < 3 is all border and comes back unchanged
+// (through its LUTs when they come first).  Nothing of this depends on the float unit.
+#define AUG_SH_ROWS 16                                         // a workgroup's tile: 16 rows x 64 pixels, a thread = 4 adjacent pixels of one row
+#define AUG_SH_COLS 64
+// LDS image of the tile: AUG_SH_ROWS + 2 rows of the bytes [3 X0 - 4, 3 X0 + 200) of the frame's row = 51 dwords, the dword that holds the left
+// halo pixel first.  A thread reads dwords 3 tx .. 3 tx + 4 of three rows; with a row stride of 16 mod 32 dwords the two rows of a 32-lane group
+// fall on disjoint banks ({3 t mod 32, t < 16} and the same set + 16).  Not measured against the dense stride.
+#define AUG_SH_STRIDE 80
+
+__device__ __forceinline__ uint32_t aug_sharpen_byte(int n, int p) {
+    const int deg = (2 * n + 13) / 26;
+    const int t = (5 * deg + 8 * (p - deg)) / 5;               // (truncation toward zero, as the float-to-int conversion of the blend)
+    return (uint32_t)(t < 0 ? 0 : (t > 255 ? 255 : t));
+}
+
+// grid (ceil(W / 64), ceil(H / 16), B).  mode = params[b][11]: 0 -> the tile is copied; 1, 2 -> sharpened, through the frame's LUTs when mode == 2
+// and luts != NULL.  Any other value sharpens like 1 (`augment.draw_params` writes 0, 1 or 2; the rows live on the device, so the entry point
+// cannot refuse them).  Rows are read and written as dwords when W % 4 == 0 (then every row of every frame starts on a dword), byte by byte
+// otherwise.
+__global__ void __launch_bounds__(256) aug_sharpen_kernel(const uint8_t* __restrict__ frames, const uint8_t* __restrict__ luts,
+                                                          const int* __restrict__ params, uint8_t* __restrict__ out, int H, int W) {
+    __shared__ uint32_t simg[(AUG_SH_ROWS + 2) * AUG_SH_STRIDE];
+    __shared__ uint32_t slut32[192];
+    const int b = blockIdx.z, tid = threadIdx.x;
+    const int mode = params[b * AUG_P + 11];
+    const int X0 = blockIdx.x * AUG_SH_COLS, Y0 = blockIdx.y * AUG_SH_ROWS;
+    const int tx = tid & 15, ty = tid >> 4;
+    const int X = X0 + tx * 4, Y = Y0 + ty;
+    const int rowb = W * 3;
+    const bool aligned = (W & 3) == 0;
+    const uint8_t* f = frames + (long long)b * H * rowb;
+    uint8_t* dst = out + ((long long)b * H + Y) * rowb + X * 3;
+    if (mode == 0) {                                           // (uniform over the workgroup: before any barrier)
+        if (Y >= H || X >= W) return;
+        const uint8_t* src = f + (long long)Y * rowb + X * 3;
+        if (aligned) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ((uint32_t*)dst)[k] = ((const uint32_t*)src)[k];
+        } else {
+            for (int k = 0; k < 12; ++k)
+                if (X + k / 3 < W) dst[k] = src[k];
+        }
+        return;
+    }
+    const bool use_lut = mode == 2 && luts != nullptr;
+    if (use_lut && tid < 192) slut32[tid] = ((const uint32_t*)(luts + (long long)b * 768))[tid];
+    if (use_lut) __syncthreads();
+    const uint8_t* slut = (const uint8_t*)slut32;
+    // stage: LDS byte j of LDS row r is byte 3 X0 - 4 + j of frame row Y0 - 1 + r.  Bytes outside the frame are staged as 0 (as lut[0] inside
+    // the frame's rows when the LUTs apply); their value is never used: only border pixels, which are copies, have such neighbours
+    for (int i = tid; i < (AUG_SH_ROWS + 2) * 51; i += 256) {
+        const int r = i / 51, k = i - r * 51;
+        const int y = Y0 - 1 + r, g0 = X0 * 3 - 4 + 4 * k;
+        uint32_t v = 0;
+        if (y >= 0 && y < H) {
+            const uint8_t* row = f + (long long)y * rowb;
+            if (aligned) {
+                if (g0 >= 0 && g0 < rowb) v = *(const uint32_t*)(row + g0);      // (rowb % 4 == 0: a dword is inside or outside as a whole)
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (g0 + e >= 0 && g0 + e < rowb) v |= (uint32_t)row[g0 + e] << (8 * e);
+            }
+            if (use_lut) {                                     // the channel of row byte g is g % 3, and 3 X0 - 4 = 2 (mod 3)
+                uint32_t t = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) t |= (uint32_t)slut[((4 * k + e + 2) % 3) * 256 + ((v >> (8 * e)) & 255u)] << (8 * e);
+                v = t;
+            }
+        }
+        simg[r * AUG_SH_STRIDE + k] = v;
+    }
+    __syncthreads();
+    if (Y >= H || X >= W) return;
+    // bytes 12 tx .. 12 tx + 19 of the rows above, at and below: output byte k of the thread is LDS byte 4 + k, its left and right neighbours
+    // (the same channel of the adjacent pixels) bytes 1 + k and 7 + k
+    uint32_t d[3][5];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int q = 0; q < 5; ++q) d[r][q] = simg[(ty + r) * AUG_SH_STRIDE + 3 * tx + q];
+    int mid[20], col[20];
+#pragma unroll
+    for (int j = 1; j < 19; ++j) {
+        const int sh = 8 * (j & 3);
+        mid[j] = (int)((d[1][j >> 2] >> sh) & 255u);
+        col[j] = (int)((d[0][j >> 2] >> sh) & 255u) + mid[j] + (int)((d[2][j >> 2] >> sh) & 255u);
+    }
+    const bool yedge = Y == 0 || Y == H - 1;
+    uint32_t px[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const int x = X + k / 3, p = mid[4 + k];
+        const bool edge = yedge || x == 0 || x >= W - 1;
+        px[k] = edge ? (uint32_t)p : aug_sharpen_byte(col[1 + k] + col[4 + k] + col[7 + k] + 4 * p, p);
+    }
+    if (aligned) {                                             // X % 4 == 0 and W % 4 == 0: all four pixels inside, 12-byte aligned
+        uint32_t* o = (uint32_t*)dst;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[k] = px[4 * k] | (px[4 * k + 1] << 8) | (px[4 * k + 2] << 16) | (px[4 * k + 3] << 24);
+    } else {
+        for (int k = 0; k < 12; ++k)
+            if (X + k / 3 < W) dst[k] = (uint8_t)px[k];
+    }
+}
+
+extern "C" int mt4_aug_sharpen_u8(const uint8_t* frames, const uint8_t* luts, const int32_t* params, uint8_t* out, int32_t B, int32_t H,
+                                  int32_t W, void* stream) {
+    mt4_clear_error();
+    if (!frames || !params || !out || frames == out || B <= 0 || H <= 0 || W <= 0) return MT4_EINVAL;
+    if (B > 65535 || H > 4096 || W > 4096) return MT4_EINVAL;
+    if (!aug_dword_aligned(frames) || !aug_dword_aligned(out) || !aug_dword_aligned(luts)) return MT4_EINVAL;
+    hipLaunchKernelGGL(aug_sharpen_kernel, dim3(cdiv(W, AUG_SH_COLS), cdiv(H, AUG_SH_ROWS), B), dim3(256), 0, (hipStream_t)stream, frames, luts,
+                       params, out, H, W);
+    return mt4_check_launch();
+}
+
 // ------------------------------------------------------------------------------------------------ flips + LUT + rotation gather
 // Output pixel (X, Y) of frame b, X < nw and Y < nh, reads source pixel xin = (a2 + X a0 + Y a1) >> 16, yin = (a5 + X a3 + Y a4) >> 16
 // (arithmetic shift; Pillow's affine transform with the NEAREST filter) of the flipped frame, i.e. (W-1-xin if hflip, H-1-yin if vflip) of the
-// frame as stored, through the channel's LUT; 0 outside the source, and 0 in the canvas outside nw x nh.  A workgroup writes a 64 x 16 pixel
+// frame as stored, through the channel's LUT (not for a frame whose row says that mt4_aug_sharpen_u8 applied it: sharpen == 2); 0 outside the source, and 0 in the canvas outside nw x nh.  A workgroup writes a 64 x 16 pixel
 // tile, so its source footprint is the rotated 64 x 16 rectangle; a thread writes 4 adjacent pixels = 12 bytes as three dwords when the canvas
 // rows are dword-aligned (Wc % 4 == 0).
 __global__ void __launch_bounds__(256) aug_flip_lut_rotate_kernel(const uint8_t* __restrict__ frames, const uint8_t* __restrict__ luts,
@@ -133,7 +257,11 @@ __global__ void __launch_bounds__(256) aug_flip_lut_rotate_kernel(const uint8_t*
                                                                   int Hc, int Wc) {
     __shared__ uint32_t slut32[192];
     const int b = blockIdx.z, tid = threadIdx.x;
-    if (tid < 192) slut32[tid] = ((const uint32_t*)(luts + (long long)b * 768))[tid];
+    if (tid < 192) {                                           // (the load does not wait for the row: sharpen == 2 replaces what it brought)
+        uint32_t v = ((const uint32_t*)(luts + (long long)b * 768))[tid];
+        if (params[b * AUG_P + 11] == 2) v = 0x03020100u + (uint32_t)(tid & 63) * 0x04040404u;      // the identity table: bytes 4 i .. 4 i + 3
+        slut32[tid] = v;
+    }
     __syncthreads();
     const uint8_t* slut = (const uint8_t*)slut32;
     const int X0 = blockIdx.x * 64 + (tid & 15) * 4, Y = blockIdx.y * 16 + (tid >> 4);

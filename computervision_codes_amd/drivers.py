@@ -316,8 +316,8 @@ def spatial_cnn_test(argv=None) -> Dict[str, np.ndarray]:
 # ------------------------------------------------------------------------------------------------ Spatial_cnn/run.py -t
 def _augment(im, rng, names):
     """the reference's PIL-side train augmentations (`Spatial_cnn/dataloader.py:89-100`; its dict lists 'contrast' twice, so the later
-    RandomAutocontrast is the one in effect), drawn from `rng` (python `random.Random`)"""
-    from PIL import Image, ImageOps
+    RandomAutocontrast is the one in effect; its 'brightness' is RandomAdjustSharpness(1.6, p=0.5)), drawn from `rng` (python `random.Random`)"""
+    from PIL import Image, ImageEnhance, ImageOps
     for n in names:
         if n == "vflip" and rng.random() < 0.4:
             im = ImageOps.flip(im)
@@ -325,6 +325,8 @@ def _augment(im, rng, names):
             im = ImageOps.mirror(im)
         elif n == "contrast" and rng.random() < 0.5:
             im = ImageOps.autocontrast(im)
+        elif n == "brightness" and rng.random() < 0.5:
+            im = ImageEnhance.Sharpness(im).enhance(1.6)
         elif n == "rot90":
             im = im.rotate(rng.uniform(-90.0, 90.0), resample=Image.NEAREST, expand=True)
     return im
@@ -358,8 +360,9 @@ _WARNED_TRANSFORM = False
 
 
 def _device_transform(F) -> bool:
-    """--train_transform device, unless the augmentation list has no device form ('contrast' after 'rot90': the black fill of the rotation
-    would enter the histogram; 'contrast' or 'rot90' named twice) -- such a run keeps the host transform; said once"""
+    """--train_transform device, unless the augmentation list has no device form ('contrast' or 'brightness' after 'rot90': the black fill of
+    the rotation would enter the histogram or be sharpened; 'contrast', 'brightness' or 'rot90' named twice) -- such a run keeps the host
+    transform; said once"""
     if getattr(F, "train_transform", "host") != "device":
         return False
     from . import augment
@@ -367,8 +370,8 @@ def _device_transform(F) -> bool:
         return True
     global _WARNED_TRANSFORM
     if not _WARNED_TRANSFORM:
-        print(f"[drivers] --train_transform device: the augmentation list {list(F.augmentation_list)} has no device form ('contrast' after "
-              "'rot90', or 'contrast' / 'rot90' twice); the train transform runs in Pillow on the host", flush=True)
+        print(f"[drivers] --train_transform device: the augmentation list {list(F.augmentation_list)} has no device form ('contrast' or "
+              "'brightness' after 'rot90', or 'contrast' / 'brightness' / 'rot90' twice); the train transform runs in Pillow on the host", flush=True)
         _WARNED_TRANSFORM = True
     return False
 

@@ -255,13 +255,23 @@ int mt4_resize_pass_u8(const void* in, void* out, const int32_t* bounds, const i
                        int32_t Win, int32_t Hout, int32_t Wout, int32_t C, int32_t axis, void* stream);
 /* The train transform of the frame trainers on the device (Spatial_cnn/dataloader.py:89-100,153-162: Resize -> vflip -> hflip -> autocontrast
  * -> rotation by a random angle with expand -> Resize), byte-identical to Pillow for the same draws.  Every frame has one parameter row of
- * MT4_AUG_PARAMS int32: {vflip, hflip, a0, a1, a2, a3, a4, a5, nw, nh, contrast, 0} -- a0..a5 the 16.16 fixed-point inverse affine map of the
- * rotation, nw x nh the size of the rotated image (augment.draw_params builds them on the host in float64).
+ * MT4_AUG_PARAMS int32: {vflip, hflip, a0, a1, a2, a3, a4, a5, nw, nh, contrast, sharpen} -- a0..a5 the 16.16 fixed-point inverse affine map of
+ * the rotation, nw x nh the size of the rotated image (augment.draw_params builds them on the host in float64).  sharpen is the draw of the
+ * list's 'brightness' (RandomAdjustSharpness(1.6) in the reference): 0 = not drawn (always, for a list without the name), 1 = sharpen the frame
+ * as stored -- an autocontrast, if drawn, comes after it and takes its range from the sharpened frame --, 2 = the frame's autocontrast was drawn
+ * and comes first: mt4_aug_sharpen_u8 reads the frame through its LUTs and mt4_aug_flip_lut_rotate does not apply them again -- so a row with
+ * sharpen == 2 that is passed to mt4_aug_flip_lut_rotate WITHOUT the mt4_aug_sharpen_u8 launch before it loses its autocontrast.  Any other
+ * nonzero value sharpens like 1.
  *   mt4_aug_channel_luts: frames uint8 [B][H][W][3] -> luts uint8 [B][3][256], the autocontrast table of every channel (smallest value -> 0,
  *     largest -> 255, int(i * scale + offset) in float64 with two roundings; identity when the channel is constant or the frame's contrast
  *     flag is 0).  minmax: int32 [B][3][2] scratch, left holding (min, max) of the frames whose flag is set.
+ *   mt4_aug_sharpen_u8: out uint8 [B][H][W][3], out != frames.  A frame with sharpen != 0 becomes ImageEnhance.Sharpness(im).enhance(1.6) of the
+ *     frame (of lut[frame] when sharpen == 2 and luts != NULL; luts may be NULL): with N = the 3 x 3 neighbourhood sum + 4 x centre,
+ *     deg = (2 N + 13) / 26 and out = clamp((5 deg + 8 (p - deg)) / 5, 0, 255), C division; the one-pixel border is the source (read through the LUTs like
+ *     the rest), so a frame with H < 3 or W < 3 is all border.  A frame with sharpen == 0 is copied.  H, W <= 4096.
  *   mt4_aug_flip_lut_rotate: canvas uint8 [B][Hc][Wc][3]; pixel (X, Y), X < nw and Y < nh, = lut[source pixel ((a2 + X a0 + Y a1) >> 16,
- *     (a5 + X a3 + Y a4) >> 16) of the flipped frame], 0 when that lies outside the frame; 0 outside nw x nh.  Hc >= max nh, Wc >= max nw.
+ *     (a5 + X a3 + Y a4) >> 16) of the flipped frame] (the pixel itself for a frame with sharpen == 2), 0 when that lies outside the frame; 0
+ *     outside nw x nh.  Hc >= max nh, Wc >= max nw.
  *   mt4_aug_resize_pass_u8: mt4_resize_pass_u8 (C = 3) where frame b's image is the top-left nh x nw corner of its canvas and its tables lie in
  *     the int32 `pool` at the offsets of frame_tab [B][8] = {h bounds, h coeffs, h ksize, nw, v bounds, v coeffs, v ksize, nh} (bounds
  *     [n_out][2], coeffs [n_out][ksize]; ksize_max sizes the LDS copy of a frame's horizontal table, a frame with a larger ksize reads the
@@ -272,6 +282,8 @@ int mt4_resize_pass_u8(const void* in, void* out, const int32_t* bounds, const i
 #define MT4_AUG_PARAMS 12
 int mt4_aug_channel_luts(const uint8_t* frames, const int32_t* params, int32_t* minmax, uint8_t* luts, int32_t B, int32_t H, int32_t W,
                          void* stream);
+int mt4_aug_sharpen_u8(const uint8_t* frames, const uint8_t* luts, const int32_t* params, uint8_t* out, int32_t B, int32_t H, int32_t W,
+                       void* stream);
 int mt4_aug_flip_lut_rotate(const uint8_t* frames, const uint8_t* luts, const int32_t* params, uint8_t* canvas, int32_t B, int32_t H, int32_t W,
                             int32_t Hc, int32_t Wc, void* stream);
 int mt4_aug_resize_pass_u8(const uint8_t* in, uint8_t* out, const int32_t* pool, const int32_t* frame_tab, int32_t B, int32_t Hc, int32_t Wc,

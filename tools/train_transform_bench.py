@@ -5,6 +5,8 @@
   make-data DIR [frames per video]        a CholecT45-shaped dataset of 480 x 854 PNGs under DIR (CPU only)
   kernels B H W                           the device transform and the bf16 ResNet-50 student step at the same batch: event-timed ms per call and
                                           the bytes each kernel must move; run it under `rocprofv3 --kernel-trace --stats` for the per-kernel table
+  transform B H W                         the device transform alone: event-timed ms per call, 7 repetitions of 24 calls and their median (cheap: for A/B
+                                          runs against another checkout, processes alternating)
   loader DIR [B H W]                      frames/s of `drivers._frame_batch` alone, --train_transform host against device (--png_decode device),
                                           median of 7 batches each, alternating
   loader DIR [B H W] --prefetch K,K,...   frames/s of a whole pass over the training batches, --train_transform device --png_decode device, for every K of
@@ -12,6 +14,9 @@
                                           fast as it delivers; median of 7 passes each, alternating; [--batches N] bounds the pass
   epoch DIR host|device [B]               frames/s of the second epoch of `Spatial_cnn/run.py -t` (ResNet-50, bf16 operands, --loss_type i);
                                           [--prefetch K] passes the flag on
+
+`kernels`, `transform`, `loader` and `epoch` take `--augmentation_list a,b,...` (comma-separated; default: the trainers' default list, so the commands
+without it measure what they always measured), e.g. `original,vflip,hflip,contrast,brightness,rot90` for the sharpening pass.
 
 Every step prints one JSON line."""
 import json
@@ -71,24 +76,26 @@ def _event_ms(fn, iters):
     return a.elapsed_time(b) / iters
 
 
-def kernels(B, H, W):
+def kernels(B, H, W, names=NAMES):
     import torch
     from computervision_codes_amd import augment, shapes, synth
     from computervision_codes_amd.spatial_cnn_train import SpatialCnnTrainer
     dev = torch.device("cuda:0")
     x = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (B, H, W, 3), dtype=np.uint8)).to(dev)
     rng = random.Random(47)
-    plist = [augment.draw_params(rng, NAMES, B, H, W) for _ in range(8)]
+    plist = [augment.draw_params(rng, names, B, H, W) for _ in range(8)]
     for p in plist:                                            # (fills the table pool)
         augment.train_transform_device(x, p)
     it = iter(range(10 ** 9))
     ms_t = _event_ms(lambda: augment.train_transform_device(x, plist[next(it) % 8]), 24)
     # the bytes every kernel MUST move, mean over the drawn batches: range = the frames with the contrast flag once; gather = the frames once in,
-    # the canvas once out; resize = canvas image in, h-pass image out and in again, frame out
+    # the canvas once out; resize = canvas image in, h-pass image out and in again, frame out; sharpen (calls in which a frame drew it) = every
+    # frame once in and once out
     fr = H * W * 3
-    nbytes = {"minmax": 0.0, "gather": 0.0, "resize_h": 0.0, "resize_v": 0.0}
+    nbytes = {"minmax": 0.0, "sharpen": 0.0, "gather": 0.0, "resize_h": 0.0, "resize_v": 0.0}
     for p in plist:
         hc, wc = augment.canvas_dims(p)
+        nbytes["sharpen"] += (2 * B * fr if p.table[:, 11].any() else 0) / 8
         nbytes["minmax"] += float(p.table[:, 10].sum()) * fr / 8
         nbytes["gather"] += (B * fr + B * hc * wc * 3) / 8
         nbytes["resize_h"] += sum(nh * nw * 3 + nh * W * 3 for nh, nw in p.sizes()) / 8
@@ -100,18 +107,33 @@ def kernels(B, H, W):
     tr = SpatialCnnTrainer("resnet50", lr=0.001, operand_dtype=torch.bfloat16).load_state_dict(sd)
     tr.exchange = False
     ms_s = _event_ms(lambda: tr.train_step(x, z, tp, tf), 5)
-    print(json.dumps({"step": "kernels", "batch": B, "size": [H, W], "transform_ms_per_call": round(ms_t, 4), "transform_us_per_frame": round(ms_t / B * 1e3, 3),
+    print(json.dumps({"step": "kernels", "augmentation_list": list(names), "batch": B, "size": [H, W], "transform_ms_per_call": round(ms_t, 4), "transform_us_per_frame": round(ms_t / B * 1e3, 3),
                       "student_bf16_step_ms": round(ms_s, 3), "transform_share_of_step": round(ms_t / ms_s, 5),
                       "must_move_bytes_per_call": {k: int(v) for k, v in nbytes.items()},
                       "us_per_call_at_%.1f_TBs" % HBM_TBS: {k: round(v / (HBM_TBS * 1e12) * 1e6, 3) for k, v in nbytes.items()}}))
 
 
-def _namespace(d, mode):
+def transform(B, H, W, names=NAMES, reps=7, iters=24):
+    import torch
+    from computervision_codes_amd import augment
+    dev = torch.device("cuda:0")
+    x = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (B, H, W, 3), dtype=np.uint8)).to(dev)
+    rng = random.Random(47)
+    plist = [augment.draw_params(rng, names, B, H, W) for _ in range(8)]
+    for p in plist:                                            # (fills the table pool)
+        augment.train_transform_device(x, p)
+    it = iter(range(10 ** 9))
+    ms = [_event_ms(lambda: augment.train_transform_device(x, plist[next(it) % 8]), iters) for _ in range(reps)]
+    print(json.dumps({"step": "transform", "package": os.path.dirname(os.path.abspath(augment.__file__)), "augmentation_list": list(names), "batch": B,
+                      "size": [H, W], "median_ms_per_call": round(statistics.median(ms), 4), "reps_ms_per_call": [round(v, 4) for v in ms]}))
+
+
+def _namespace(d, mode, names=NAMES):
     import argparse
-    return argparse.Namespace(data_dir=d, augmentation_list=NAMES, png_decode="device", decode_workers=8, train_transform=mode)
+    return argparse.Namespace(data_dir=d, augmentation_list=list(names), png_decode="device", decode_workers=8, train_transform=mode)
 
 
-def loader(d, B=64, H=256, W=448, reps=7):
+def loader(d, B=64, H=256, W=448, reps=7, names=NAMES):
     import torch
     from computervision_codes_amd import cholect, drivers
     vids, _, _ = cholect.split_videos("cholect45-crossval", 1)
@@ -123,7 +145,7 @@ def loader(d, B=64, H=256, W=448, reps=7):
     times = {"host": [], "device": []}
     for r in range(reps + 1):                                  # (round 0 warms both paths up: library load, table pool, file cache)
         for mode in ("host", "device"):
-            F, rng = _namespace(d, mode), random.Random(r)
+            F, rng = _namespace(d, mode, names), random.Random(r)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             fr = drivers._frame_batch(F, batches[r % len(batches)], labels, {}, {}, (H, W), rng)[0]
@@ -132,12 +154,12 @@ def loader(d, B=64, H=256, W=448, reps=7):
                 times[mode].append(time.perf_counter() - t0)
             assert tuple(fr.shape) == (B, H, W, 3)
     fps = {m: B / statistics.median(t) for m, t in times.items()}
-    print(json.dumps({"step": "loader", "batch": B, "size": [H, W], "png_decode": "device", "reps": reps,
+    print(json.dumps({"step": "loader", "augmentation_list": list(names), "batch": B, "size": [H, W], "png_decode": "device", "reps": reps,
                       "host_frames_per_s": round(fps["host"], 1), "device_frames_per_s": round(fps["device"], 1),
                       "host_s": [round(t, 4) for t in times["host"]], "device_s": [round(t, 4) for t in times["device"]]}))
 
 
-def loader_prefetch(d, ks, B=64, H=256, W=448, reps=7, max_batches=None):
+def loader_prefetch(d, ks, B=64, H=256, W=448, reps=7, max_batches=None, names=NAMES):
     import torch
     from computervision_codes_amd import cholect, drivers
     from computervision_codes_amd.loader import FrameLoader, SampleTables
@@ -148,7 +170,7 @@ def loader_prefetch(d, ks, B=64, H=256, W=448, reps=7, max_batches=None):
     batches = [samples[k:k + B] for k in range(0, len(samples), B)][:max_batches]
     frames = sum(len(b) for b in batches)
     tables = SampleTables(labels, videos=vids)
-    F = _namespace(d, "device")
+    F = _namespace(d, "device", names)
     times, stats = {k: [] for k in ks}, {}
     for r in range(reps + 1):                                  # (round 0 warms up: library load, table pools, file cache, pinned staging)
         for k in ks:
@@ -166,13 +188,13 @@ def loader_prefetch(d, ks, B=64, H=256, W=448, reps=7, max_batches=None):
             torch.cuda.synchronize()
             if r:
                 times[k].append(time.perf_counter() - t0)
-    print(json.dumps({"step": "loader-prefetch", "batch": B, "size": [H, W], "png_decode": "device", "train_transform": "device", "reps": reps,
+    print(json.dumps({"step": "loader-prefetch", "augmentation_list": list(names), "batch": B, "size": [H, W], "png_decode": "device", "train_transform": "device", "reps": reps,
                       "batches_per_pass": len(batches), "frames_per_pass": frames,
                       "frames_per_s": {str(k): round(frames / statistics.median(t), 1) for k, t in times.items()},
                       "pass_s": {str(k): [round(v, 4) for v in t] for k, t in times.items()}, "stats": {str(k): v for k, v in stats.items()}}))
 
 
-def epoch(d, mode, B=64, prefetch=0):
+def epoch(d, mode, B=64, prefetch=0, names=NAMES):
     from computervision_codes_amd import cholect, drivers
     vids, _, _ = cholect.split_videos("cholect45-crossval", 1)
     n = sum(len(cholect.load_labels(d, v)["ivt"]) for v in vids)
@@ -182,33 +204,36 @@ def epoch(d, mode, B=64, prefetch=0):
         try:
             drivers.spatial_cnn_train(["-t", "--network", "resnet50", "--student_dim", "2048", "--loss_type", "i", "--operand_dtype", "bf16", "--epochs", "2",
                                        "--val_interval", "2", "--batch", str(B), "--version", "B", "--data_dir", d, "--kfold", "1", "--png_decode", "device",
-                                       "--train_transform", mode, "--prefetch", str(prefetch)])
+                                       "--train_transform", mode, "--prefetch", str(prefetch), "--augmentation_list"] + list(names))
             log = open(os.path.join(work, "__checkpoint__", "run_B", "rendezvous_lcholect45-crossval_cholect1.log")).read()
         finally:
             os.chdir(cwd)
     secs = [float(ln.split("|")[-1].split()[0]) for ln in log.splitlines() if "Traning | lr:" in ln]
-    print(json.dumps({"step": "epoch", "train_transform": mode, "prefetch": prefetch, "batch": B, "frames_per_epoch": n, "epoch_s": secs,
+    print(json.dumps({"step": "epoch", "augmentation_list": list(names), "train_transform": mode, "prefetch": prefetch, "batch": B, "frames_per_epoch": n, "epoch_s": secs,
                       "second_epoch_frames_per_s": round(n / secs[1], 1)}))
 
 
 if __name__ == "__main__":
     cmd, a = sys.argv[1], sys.argv[2:]
     opts = {}
-    for flag in ("--prefetch", "--batches"):                   # (the two optional flags of `loader` / `epoch`)
+    for flag in ("--prefetch", "--batches", "--augmentation_list"):      # (the optional flags of `kernels` / `loader` / `epoch`)
         if flag in a:
             i = a.index(flag)
             opts[flag] = a[i + 1]
             del a[i:i + 2]
+    names = opts["--augmentation_list"].split(",") if "--augmentation_list" in opts else NAMES
     if cmd == "make-data":
         make_data(a[0], *[int(v) for v in a[1:2]])
     elif cmd == "kernels":
-        kernels(*[int(v) for v in a[:3]])
+        kernels(*[int(v) for v in a[:3]], names=names)
+    elif cmd == "transform":
+        transform(*[int(v) for v in a[:3]], names=names)
     elif cmd == "loader" and "--prefetch" in opts:
         loader_prefetch(a[0], [int(k) for k in opts["--prefetch"].split(",")], *[int(v) for v in a[1:4]],
-                        max_batches=int(opts["--batches"]) if "--batches" in opts else None)
+                        max_batches=int(opts["--batches"]) if "--batches" in opts else None, names=names)
     elif cmd == "loader":
-        loader(a[0], *[int(v) for v in a[1:4]])
+        loader(a[0], *[int(v) for v in a[1:4]], names=names)
     elif cmd == "epoch":
-        epoch(a[0], a[1], *[int(v) for v in a[2:3]], prefetch=int(opts.get("--prefetch", 0)))
+        epoch(a[0], a[1], *[int(v) for v in a[2:3]], prefetch=int(opts.get("--prefetch", 0)), names=names)
     else:
         sys.exit(__doc__)
