@@ -94,6 +94,8 @@ SIGNATURES = {
     "mt4_aug_flip_lut_rotate": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mt4_aug_resize_pass_u8": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mt4_take_rows_f32": (C.c_int, [C.POINTER(TakeSeg), _i32, _vp, C.c_int64, _vp]),
+    "mt4_put_frames_u8": (C.c_int, [_vp, _vp, _vp, _i32, C.c_int64, C.c_int64, _vp]),
+    "mt4_take_frames_u8": (C.c_int, [_vp, _vp, _vp, _i32, C.c_int64, C.c_int64, _vp]),
     "mt4_maxpool3x3s2_nhwc": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mt4_stem_maxpool_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mt4_global_avgpool_nhwc": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),

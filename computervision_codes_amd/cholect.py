@@ -152,3 +152,123 @@ def load_files_device(paths, height: int = 256, width: int = 448, device="cuda",
         y = x if (h0, w0) == (height, width) else ops.resize_bilinear_u8(x, height, width)
         out[torch.tensor(idx, device=device)] = y
     return out
+
+
+class FrameCache:
+    """The resized uint8 frames of a run kept in HBM across epochs (`--frame_cache GB`): what `load_files_device(paths, h, w)` returns is a pure
+    function of the file and the size, so epochs 2 ... N of a frame trainer -- and every validation after the first -- take their frames from a
+    pool on the device instead of reading, inflating, unfiltering and resizing every PNG again.  Only what FOLLOWS is random (the train
+    transform), so no byte of any batch changes.
+
+    The pool is one uint8 [slots, h, w, 3] tensor, slots = budget_bytes // (h * w * 3), allocated on the first `plan`, whose (h, w) fixes the
+    frame size; a request at another size bypasses the cache, and so does every request if the allocation ran out of memory (said once).  Keys
+    are the path strings.  A slot is free, ASSIGNED (handed to a path by `plan`, being written by that chunk's `fetch`) or READABLE; first come,
+    first served, nothing is ever evicted.
+
+    `plan(paths, h, w)` -> (take_slots, put_slots) int32 [n], on the CONSUMER thread only, in chunk order: it is the only place that touches
+    the table.  `fetch(paths, plan, load)` runs wherever the load runs (a helper thread and side stream of `extract.iter_chunks`), decodes the
+    misses with ONE `load(miss_paths)` call (none at all on a full hit), stores the rows that got a slot (`ops.put_frames`) and takes the hits
+    (`ops.take_frames`): exactly `load(paths)`.  `seal()` makes the assigned slots readable, after one device-wide synchronize that orders
+    every later stream behind the stores; the drivers call it after every training epoch and every validation.  Nothing becomes readable
+    between two `seal()` calls, so a chunk never reads a slot another chunk in flight on another side stream is still writing -- a path seen
+    again before `seal()` is decoded again and not stored.
+    `stats`: hits, misses, stored (frames), slots and bytes of the pool."""
+
+    def __init__(self, budget_bytes, device="cuda"):
+        self.budget, self.device = max(0, int(budget_bytes)), device
+        self.size = None                    # (h, w) of the pool, fixed by the first plan
+        self.pool = None
+        self.table: Dict[str, int] = {}     # path -> slot, assigned or readable
+        self.readable = 0                   # slots [0, readable) are readable, [readable, len(table)) assigned: slots are handed out in order
+        self.stats = {"hits": 0, "misses": 0, "stored": 0, "slots": 0, "bytes": 0}
+
+    # ------------------------------------------------------------------------------------------------ device side (replaced by numpy in the CPU tests)
+    def _alloc(self, slots, h, w):
+        import torch
+        return torch.empty((slots, h, w, 3), dtype=torch.uint8, device=self.device)
+
+    def _put(self, slots, frames):
+        from . import ops
+        ops.put_frames(self.pool, slots, frames)
+
+    def _take(self, slots, out):
+        from . import ops
+        ops.take_frames(self.pool, slots, out)
+
+    def _empty(self, n):
+        import torch
+        return torch.empty((n,) + tuple(self.pool.shape[1:]), dtype=torch.uint8, device=self.pool.device)
+
+    def _scatter(self, out, rows, frames):
+        import torch
+        out[torch.from_numpy(rows).to(out.device)] = frames
+
+    def _synchronize(self):
+        import torch
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+
+    # ------------------------------------------------------------------------------------------------ host logic
+    def _open(self, h, w):
+        """the first plan: the pool at this size, or an empty cache (a budget below one frame, or no memory for the pool)"""
+        self.size = (int(h), int(w))
+        slots = self.budget // (int(h) * int(w) * 3)
+        if slots > 0:
+            try:
+                self.pool = self._alloc(slots, int(h), int(w))
+            except (MemoryError, RuntimeError) as e:
+                if not isinstance(e, MemoryError) and "out of memory" not in str(e).lower():
+                    raise
+                print(f"[cholect] --frame_cache: no memory for a pool of {slots} frames of {h} x {w} ({slots * h * w * 3 / 2 ** 30:.1f} GiB); "
+                      "the run goes on without the cache", flush=True)
+                slots = 0
+        self.stats["slots"], self.stats["bytes"] = slots, slots * int(h) * int(w) * 3
+
+    def plan(self, paths, h, w):
+        n = len(paths)
+        take, put = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+        if self.size is None:
+            self._open(h, w)
+        if (int(h), int(w)) != self.size or not self.stats["slots"]:
+            self.stats["misses"] += n
+            return take, put
+        for i, p in enumerate(paths):
+            s = self.table.get(p)
+            if s is None:
+                if len(self.table) < self.stats["slots"]:
+                    s = self.table[p] = len(self.table)
+                    put[i] = s
+                    self.stats["stored"] += 1
+            elif s < self.readable:
+                take[i] = s
+        hits = int((take >= 0).sum())
+        self.stats["hits"] += hits
+        self.stats["misses"] += n - hits
+        return take, put
+
+    def seal(self):
+        if len(self.table) > self.readable:
+            self._synchronize()
+            self.readable = len(self.table)
+
+    def fetch(self, paths, plan, load):
+        take, put = plan
+        miss = np.flatnonzero(take < 0)
+        if len(miss) == len(paths):                          # nothing to take (the first epoch, a bypass, an empty cache)
+            out = load(list(paths))
+            if len(paths) and (put >= 0).any():
+                self._put(put, out)
+            return out
+        out = self._empty(len(paths))
+        if len(miss):
+            decoded = load([paths[i] for i in miss])
+            self._scatter(out, miss, decoded)
+            if (put[miss] >= 0).any():
+                self._put(np.ascontiguousarray(put[miss]), decoded)
+        self._take(take, out)
+        return out
+
+
+def fetch_files(cache, paths, plan, load):
+    """`load(paths)` through `cache` (a `FrameCache` with the `plan` of these paths), or directly without one"""
+    return load(list(paths)) if cache is None else cache.fetch(paths, plan, load)

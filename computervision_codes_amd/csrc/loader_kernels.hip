@@ -1,6 +1,8 @@
 // The sample rows of a training batch gathered on the device (loader.SampleTables): the label rows and the teacher prediction / feature rows
 // the reference's dataset assembles per sample on the host (Spatial_cnn/dataloader.py:216-261) live in fp32 tables that are uploaded once per
 // run; a batch (or a chunk of batches) is ONE launch over all tables.
+// The frame pool of cholect.FrameCache (--frame_cache): resized uint8 frames kept in HBM across epochs; a chunk's stores into the pool and its reads
+// from it are one launch each over (16-byte pieces, frame), rows picked by a slot list.
 #include <type_traits>
 
 #include "mt4_common.h"
@@ -43,7 +45,81 @@ __global__ __launch_bounds__(256) void take_rows_kernel(const TakeArgs a, const 
         take_rows_segment<false>(sg, rows, r0, nr);
 }
 
+// ------------------------------------------------------------------------------------------------ the frame pool
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+
+constexpr int FRAME_PIECES_PER_THREAD = 4;                                  // 4 x 16 bytes loaded before the first store: 16 KiB in flight per workgroup,
+constexpr int FRAME_PIECES_PER_BLOCK = 256 * FRAME_PIECES_PER_THREAD;       // 128 KiB per CU at 8 resident workgroups (a streaming CU needs ~32 KiB)
+
+// blockIdx.y = frame i, blockIdx.x = group of 1024 16-byte pieces of its row.  PUT: pool[slots[i]] = frames[i], else frames[i] = pool[slots[i]].
+// A row whose slot is negative or >= pool_slots is skipped by the whole workgroup (uniform): nothing of it is read or written.
+// VEC: frame_bytes % 16 == 0 and both bases 16-byte aligned -> every row of either side starts on a 16-byte boundary.  The pool side is touched once
+// per epoch (tens of GB between two uses): non-temporal on that side; the chunk side is written / read by the neighbouring kernels: cacheable.
+// Offsets are 64-bit: slot * frame_bytes passes 2^31 at slot 6242 of a 256 x 448 pool.
+template <bool PUT, bool VEC>
+__global__ __launch_bounds__(256) void frames_copy_kernel(unsigned char* __restrict__ pool, const int* __restrict__ slots, unsigned char* __restrict__ frames,
+                                                          long long frame_bytes, long long pool_slots) {
+    const long long s = slots[blockIdx.y];
+    if (s < 0 || s >= pool_slots) return;
+    unsigned char* prow = pool + s * frame_bytes;
+    unsigned char* frow = frames + (long long)blockIdx.y * frame_bytes;
+    const unsigned char* __restrict__ src = PUT ? frow : prow;
+    unsigned char* __restrict__ dst = PUT ? prow : frow;
+    const long long p0 = (long long)blockIdx.x * FRAME_PIECES_PER_BLOCK + threadIdx.x;
+    if constexpr (VEC) {
+        const long long pieces = frame_bytes >> 4;
+        u32x4_t v[FRAME_PIECES_PER_THREAD];
+#pragma unroll
+        for (int j = 0; j < FRAME_PIECES_PER_THREAD; ++j) {
+            const long long p = p0 + j * 256;
+            if (p < pieces) v[j] = PUT ? *((const u32x4_t*)src + p) : __builtin_nontemporal_load((const u32x4_t*)src + p);
+        }
+#pragma unroll
+        for (int j = 0; j < FRAME_PIECES_PER_THREAD; ++j) {
+            const long long p = p0 + j * 256;
+            if (p < pieces) {
+                if (PUT) __builtin_nontemporal_store(v[j], (u32x4_t*)dst + p);
+                else *((u32x4_t*)dst + p) = v[j];
+            }
+        }
+    } else {                                                                // any size, any alignment: byte by byte
+        for (int j = 0; j < FRAME_PIECES_PER_THREAD; ++j) {
+            const long long b0 = (p0 + j * 256) << 4;
+            const long long b1 = b0 + 16 < frame_bytes ? b0 + 16 : frame_bytes;
+            for (long long b = b0; b < b1; ++b) dst[b] = src[b];
+        }
+    }
+}
+
+template <bool PUT>
+int frames_copy(const void* pool, const int32_t* slots, const void* frames, int32_t n, int64_t frame_bytes, int64_t pool_slots, void* stream) {
+    mt4_clear_error();
+    if (n < 0 || frame_bytes <= 0 || pool_slots <= 0) return MT4_EINVAL;
+    if (n == 0) return MT4_OK;                       // nothing to move: no launch
+    if (!pool || !slots || !frames) return MT4_EINVAL;
+    if ((uintptr_t)slots & 3) return MT4_EALIGN;
+    const long long groups = ((frame_bytes + 15) / 16 + FRAME_PIECES_PER_BLOCK - 1) / FRAME_PIECES_PER_BLOCK;
+    if (n > 65535 || groups > 0x7fffffffLL) return MT4_EUNSUPPORTED;
+    const bool vec = !(frame_bytes & 15) && !(((uintptr_t)pool | (uintptr_t)frames) & 15);
+    const dim3 grid((unsigned)groups, (unsigned)n);
+    if (vec)
+        hipLaunchKernelGGL((frames_copy_kernel<PUT, true>), grid, dim3(256), 0, (hipStream_t)stream, (unsigned char*)pool, (const int*)slots,
+                           (unsigned char*)frames, (long long)frame_bytes, (long long)pool_slots);
+    else
+        hipLaunchKernelGGL((frames_copy_kernel<PUT, false>), grid, dim3(256), 0, (hipStream_t)stream, (unsigned char*)pool, (const int*)slots,
+                           (unsigned char*)frames, (long long)frame_bytes, (long long)pool_slots);
+    return mt4_check_launch();
+}
+
 }  // namespace
+
+extern "C" int mt4_put_frames_u8(void* pool, const int32_t* slots, const void* frames, int32_t n, int64_t frame_bytes, int64_t pool_slots, void* stream) {
+    return frames_copy<true>(pool, slots, frames, n, frame_bytes, pool_slots, stream);
+}
+
+extern "C" int mt4_take_frames_u8(const void* pool, const int32_t* slots, void* frames, int32_t n, int64_t frame_bytes, int64_t pool_slots, void* stream) {
+    return frames_copy<false>(pool, slots, frames, n, frame_bytes, pool_slots, stream);
+}
 
 extern "C" int mt4_take_rows_f32(const mt4_take_seg* segs, int32_t nseg, const int64_t* rows, int64_t n, void* stream) {
     mt4_clear_error();

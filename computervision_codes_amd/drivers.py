@@ -74,6 +74,10 @@ _FRAME_TRAIN = [
           help="K > 0: training batches come from `loader.FrameLoader` -- chunks of up to K batches (at most 1024 frames) decoded, transformed "
                "and gathered per call on helper threads and side streams while the step runs, labels and teacher rows resident on the device; "
                "the same batches as 0 (the synchronous loader), only faster"),
+    _flag("--frame_cache", type=float, default=0,
+          help="GB of HBM per rank for `cholect.FrameCache`: the decoded, resized uint8 frames stay on the device across epochs, so every epoch after "
+               "the first (and every validation after the first) takes its frames from the pool (mt4_take_frames_u8) instead of reading, inflating "
+               "and resizing the PNGs again; first come, first served, the same bytes; training frames are cached behind --train_transform device only; 0: off"),
     _flag("--rates", type=float, nargs="+", default=[1, 0, 0.1]),
     _flag("--temp", type=int, default=4),
     _flag("--pretrain_dir", type=str, default=""),
@@ -376,10 +380,42 @@ def _device_transform(F) -> bool:
     return False
 
 
-def _frame_batch(F, batch, labels, tpred, tfeat, size, rng):
+def _frame_cache(F):
+    """--frame_cache GB > 0: this rank's `cholect.FrameCache` (None for 0).  It sits behind the device transform only: with the host transform
+    (the flag, or an augmentation list without a device form) Pillow decodes and augments in one go, the training side runs uncached -- said
+    once -- and the cache serves the validation frames alone"""
+    gb = float(getattr(F, "frame_cache", 0) or 0)
+    if gb <= 0:
+        return None
+    if not _device_transform(F):
+        print("[drivers] --frame_cache: the train transform runs in Pillow on the host, which decodes its own frames; training frames are not cached "
+              "(validation frames are)", flush=True)
+    return cholect.FrameCache(int(gb * 1e9))
+
+
+def _cache_note(cache):
+    """-> (mark, note): `mark()` at the start of a training epoch, `note()` = ' | cache <hits>/<frames>' of the requests since, for its `Traning |` line"""
+    at = [0, 0]
+
+    def mark():
+        at[:] = [cache.stats["hits"], cache.stats["hits"] + cache.stats["misses"]]
+
+    def note():
+        return f" | cache {cache.stats['hits'] - at[0]}/{cache.stats['hits'] + cache.stats['misses'] - at[1]}"
+    return mark, note
+
+
+def _frame_batch(F, batch, labels, tpred, tfeat, size, rng, cache=None):
     """a training batch of (video, frame) samples -> (uint8 frames [B,H,W,3] on the GPU through the train transform at size = (H, W), the
-    labels of the i, v, t, ivt heads, the teacher predictions and features of i, v, t -- empty without teacher files)"""
-    if _device_transform(F):
+    labels of the i, v, t, ivt heads, the teacher predictions and features of i, v, t -- empty without teacher files).  `cache` (--frame_cache):
+    the frames ahead of the device transform go through `cholect.FrameCache.plan` + `fetch`"""
+    if _device_transform(F) and cache is not None:
+        from . import augment
+        paths = [os.path.join(F.data_dir, "data", v, "{}.png".format(str(int(labels[v]["ivt"][i, 0])).zfill(6))) for v, i in batch]
+        x = cache.fetch(paths, cache.plan(paths, size[0], size[1]),
+                        lambda ps: cholect.load_files_device(ps, size[0], size[1], workers=F.decode_workers, decode=F.png_decode))
+        frames = augment.train_transform_device(x, augment.draw_params(rng, F.augmentation_list, len(paths), size[0], size[1]))
+    elif _device_transform(F):
         from . import augment
         frames = augment.load_train_batch_device(F.data_dir, [(v, labels[v]["ivt"][i, 0]) for v, i in batch], size[0], size[1], rng,
                                                  F.augmentation_list, decode=F.png_decode, workers=F.decode_workers)
@@ -401,10 +437,11 @@ def _sample_tables(F, labels, tpred, tfeat, videos):
     return SampleTables(labels, tpred, tfeat, videos=videos)
 
 
-def _frame_validation(F, val_videos, labels, size, cap, forward, label_cache=None):
+def _frame_validation(F, val_videos, labels, size, cap, forward, label_cache=None, cache=None):
     """validation mAP of the task's head (`run.py:416-451`; ivt for --loss_type all) over the validation videos' frames in device batches of
     max(--batch, min(--device_batch, cap)) (results do not depend on it); forward(uint8 frames) -> the head's logits.  --metrics device: the
-    scores stay on the GPU, the label rows come from `label_cache` (the caller's, one per run)"""
+    scores stay on the GPU, the label rows come from `label_cache` (the caller's, one per run).  `cache` (--frame_cache): the spans' frames go
+    through the run's `cholect.FrameCache` (planned on this thread, span by span), which is sealed when the pass ends"""
     vt = F.loss_type if F.loss_type != "all" else "ivt"
     dev = _device_metrics(F)
     if dev:
@@ -416,10 +453,18 @@ def _frame_validation(F, val_videos, labels, size, cap, forward, label_cache=Non
         lv = labels[v][vt]
         zv = _label_rows(label_cache, v, lambda v=v: labels[v], dev)[vt]
         load = lambda s0, v=v, lv=lv: cholect.load_frames_device(F.data_dir, v, lv[s0:s0 + vb, 0], size[0], size[1], workers=F.decode_workers, decode=F.png_decode)
+        prepare = None
+        if cache is not None:
+            files = lambda s0, v=v, lv=lv: [os.path.join(F.data_dir, "data", v, "{}.png".format(str(int(fid)).zfill(6))) for fid in lv[s0:s0 + vb, 0]]
+            prepare = lambda s0, files=files: cache.plan(files(s0), size[0], size[1])
+            load = lambda s0, plan, files=files: cache.fetch(files(s0), plan, lambda ps: cholect.load_files_device(
+                ps, size[0], size[1], workers=F.decode_workers, decode=F.png_decode))
         spans = [(s0,) for s0 in range(0, len(lv), vb)]
-        for (s0,), fr in zip(spans, extract.iter_chunks(spans, load, 1 if getattr(F, "prefetch", 0) > 0 else 0)):      # --prefetch: the next span loads meanwhile
+        for (s0,), fr in zip(spans, extract.iter_chunks(spans, load, 1 if getattr(F, "prefetch", 0) > 0 else 0, prepare=prepare)):      # --prefetch: the next span loads meanwhile
             m.update(zv[s0:s0 + vb], _scores(forward(fr), dev))
         m.video_end()
+    if cache is not None:
+        cache.seal()
     score = float(m.compute_video_AP(ignore_null=_chlg(F))["mAP"]) if val_videos else 0.0
     return score, f"{vt}: [{score:.5f}]"
 
@@ -457,29 +502,36 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     order_rng, aug_rng = random.Random(F.seed), random.Random(F.seed * 1000003 + rank)
     size = (F.image_height, F.image_width)
     tables = _sample_tables(F, labels, tpred, tfeat, train_videos)
+    cache = _frame_cache(F)                                  # (--frame_cache: this rank's resized frames, resident from their first use on)
+    mark, note = _cache_note(cache) if cache is not None else (lambda: None, None)
 
     def train_epoch(epoch):
         order = list(samples)
         order_rng.shuffle(order)                             # the same permutation on every rank
         mine, tot = deal(order, F.batch, world, rank), 0.0
-        if tables is not None:                               # --prefetch K: the same batches, loaded ahead in chunks (`loader.FrameLoader`)
-            from .loader import FrameLoader
-            with FrameLoader(F, mine, labels, tables, size, aug_rng, prefetch=F.prefetch) as batches:
-                for fb in batches:
-                    tot += tr.train_step(*fb)["loss"]
+        mark()
+        try:
+            if tables is not None:                           # --prefetch K: the same batches, loaded ahead in chunks (`loader.FrameLoader`)
+                from .loader import FrameLoader
+                with FrameLoader(F, mine, labels, tables, size, aug_rng, prefetch=F.prefetch, cache=cache) as batches:
+                    for fb in batches:
+                        tot += tr.train_step(*fb)["loss"]
+                return tot, len(mine)
+            for batch in mine:
+                tot += tr.train_step(*_frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng, cache))["loss"]
             return tot, len(mine)
-        for batch in mine:
-            tot += tr.train_step(*_frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng))["loss"]
-        return tot, len(mine)
+        finally:
+            if cache is not None:
+                cache.seal()                                 # what this epoch stored is readable from the next one on
 
     val_labels = {}                                          # (--metrics device: the validation label rows on the GPU, uploaded once)
 
     def validate(state):
         model = _eval_model("spatial_cnn", F, state)
         gi = "ivt".index(F.loss_type) if single else 3
-        return _frame_validation(F, val_videos, labels, size, 256, lambda fr: model.extract_u8(fr)[gi][1], val_labels)
+        return _frame_validation(F, val_videos, labels, size, 256, lambda fr: model.extract_u8(fr)[gi][1], val_labels, cache)
 
-    return run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", latest, stem + ".pth", score_key="val_mAP_ivt")
+    return run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", latest, stem + ".pth", score_key="val_mAP_ivt", epoch_note=note)
 
 
 # ------------------------------------------------------------------------------------------------ Temporal_tenco/run.py -e
@@ -868,24 +920,31 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     order_rng, aug_rng = random.Random(F.seed), random.Random(F.seed * 1000003 + rank)
     size = (F.img_size, F.img_size)
     tables = _sample_tables(F, labels, tpred, tfeat, train_videos)
+    cache = _frame_cache(F)                                  # (--frame_cache: this rank's resized frames, resident from their first use on)
+    mark, note = _cache_note(cache) if cache is not None else (lambda: None, None)
 
     def train_epoch(epoch):
         from contextlib import nullcontext
         order = list(samples)
         order_rng.shuffle(order)                             # the same permutation on every rank
         mine, tot = deal(order, F.batch, world, rank), 0.0
+        mark()
         if tables is not None:                               # --prefetch K: the same batches, loaded ahead in chunks (`loader.FrameLoader`)
             from .loader import FrameLoader
-            source = FrameLoader(F, mine, labels, tables, size, aug_rng, prefetch=F.prefetch)
+            source = FrameLoader(F, mine, labels, tables, size, aug_rng, prefetch=F.prefetch, cache=cache)
         else:
-            source = nullcontext(_frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng) for batch in mine)
-        with source as loaded:
-            for s, (batch, (frames, lab, tp, tf)) in enumerate(zip(mine, loaded)):
-                masks = tr.draw_masks_device(len(batch), F.seed * 1000003 + rank, epoch * len(mine) + s)     # (a running step count)
-                if single:
-                    tot += tr.train_step(frames, lab["ivt".index(F.loss_type)], masks)
-                else:
-                    tot += tr.train_step(frames, lab, masks, teacher_pred=tp, teacher_feat=tf)["loss"]
+            source = nullcontext(_frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng, cache) for batch in mine)
+        try:
+            with source as loaded:
+                for s, (batch, (frames, lab, tp, tf)) in enumerate(zip(mine, loaded)):
+                    masks = tr.draw_masks_device(len(batch), F.seed * 1000003 + rank, epoch * len(mine) + s)     # (a running step count)
+                    if single:
+                        tot += tr.train_step(frames, lab["ivt".index(F.loss_type)], masks)
+                    else:
+                        tot += tr.train_step(frames, lab, masks, teacher_pred=tp, teacher_feat=tf)["loss"]
+        finally:
+            if cache is not None:
+                cache.seal()                                 # what this epoch stored is readable from the next one on
         return tot, len(mine)
 
     val_labels = {}                                          # (--metrics device: the validation label rows on the GPU, uploaded once)
@@ -894,9 +953,9 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
         model = _eval_model("spatial_transformer", F, state)
         gi = "ivt".index(F.loss_type) if single else 3
         zt = lambda fr: [] if single else [torch.zeros((fr.shape[0], F.teacher_dim), device=fr.device)] * 3   # (`dataloader.py:240-246`: zeros off the train split)
-        return _frame_validation(F, val_videos, labels, size, 128, lambda fr: model(fr, *zt(fr))[gi][1], val_labels)
+        return _frame_validation(F, val_videos, labels, size, 128, lambda fr: model(fr, *zt(fr))[gi][1], val_labels, cache)
 
-    return run_epochs(F, tr, rank, train_epoch, validate, logfile, latest, stem + ".pth")
+    return run_epochs(F, tr, rank, train_epoch, validate, logfile, latest, stem + ".pth", epoch_note=note)
 
 
 # ------------------------------------------------------------------------------------------------ run.py: -t, then -e

@@ -122,17 +122,22 @@ class FrameLoader:
     An exception of a load is raised in the consumer when it asks for the first batch of the failing chunk, after every batch of the chunks
     before it.  `close()` (or leaving the `with` block, or exhausting the iterator) lets the loads in flight finish; no helper is launching on
     the GPU afterwards.  A loop left early finds `aug_rng` advanced by the chunks already submitted.
-    `stats`: chunks loaded, `cholect.load_files_device` calls (`decode_calls`: one per chunk of the device transform, none in the host
-    transform, whose frames Pillow decodes one by one) and frames loaded."""
+    `cache` (a `cholect.FrameCache`, --frame_cache; device transform only): the consumer also makes the chunk's plan when it submits the chunk
+    (`cache.plan`, the only place that touches the cache's table) and the load goes through `cache.fetch` -- the frames the pool holds are taken
+    from it, the others decoded by one call and stored; the same bytes.
+    `stats`: chunks loaded, `cholect.load_files_device` calls that actually ran (`decode_calls`: at most one per chunk of the device transform
+    -- none for a chunk the cache holds entirely --, none in the host transform, whose frames Pillow decodes one by one), frames loaded, frames
+    those calls decoded (`frames_decoded`) and frames taken from the cache (`hits`)."""
 
-    def __init__(self, F, batches, labels, tables: SampleTables, size, aug_rng, prefetch: int = 2):
+    def __init__(self, F, batches, labels, tables: SampleTables, size, aug_rng, prefetch: int = 2, cache=None):
         from . import drivers
         if int(prefetch) < 1:
             raise ValueError("FrameLoader needs prefetch >= 1 (--prefetch 0 is the synchronous `_frame_batch` path)")
         self.F, self.batches, self.labels, self.tables, self.size, self.rng = F, list(batches), labels, tables, tuple(size), aug_rng
         self.device_transform = drivers._device_transform(F)
         self.chunks = plan_chunks(len(self.batches), max((len(b) for b in self.batches), default=1), int(prefetch))
-        self.stats = {"chunks": 0, "decode_calls": 0, "frames": 0}
+        self.cache = cache if self.device_transform else None
+        self.stats = {"chunks": 0, "decode_calls": 0, "frames": 0, "frames_decoded": 0, "hits": 0}
         self._lock = threading.Lock()
         self.in_flight = 0                       # loads running on a helper (or, for a single chunk, on the consumer) right now
         self._it = None
@@ -141,14 +146,20 @@ class FrameLoader:
     def _samples(self, b0, b1):
         return [s for b in self.batches[b0:b1] for s in b]
 
+    def _paths(self, samples):
+        return [os.path.join(self.F.data_dir, "data", v, "{}.png".format(str(int(self.labels[v]["ivt"][i, 0])).zfill(6))) for v, i in samples]
+
     def _draw(self, b0, b1):
-        """consumer thread, chunk order: the draws of every frame of the chunk (device transform); the host transform draws inside its load"""
+        """consumer thread, chunk order: the draws of every frame of the chunk and, with a cache, the chunk's plan (device transform); the host
+        transform draws inside its load"""
         if not self.device_transform:
             return None
         from . import augment
-        return augment.draw_params(self.rng, self.F.augmentation_list, sum(len(b) for b in self.batches[b0:b1]), self.size[0], self.size[1])
+        params = augment.draw_params(self.rng, self.F.augmentation_list, sum(len(b) for b in self.batches[b0:b1]), self.size[0], self.size[1])
+        plan = self.cache.plan(self._paths(self._samples(b0, b1)), self.size[0], self.size[1]) if self.cache is not None else None
+        return params, plan
 
-    def _load(self, b0, b1, params):
+    def _load(self, b0, b1, prepared):
         import torch
         with self._lock:
             self.in_flight += 1
@@ -156,20 +167,26 @@ class FrameLoader:
             F, (h, w), samples = self.F, self.size, self._samples(b0, b1)
             if self.device_transform:
                 from . import augment, cholect
-                paths = [os.path.join(F.data_dir, "data", v, "{}.png".format(str(int(self.labels[v]["ivt"][i, 0])).zfill(6))) for v, i in samples]
-                x = cholect.load_files_device(paths, h, w, workers=F.decode_workers, decode=F.png_decode)
+                params, plan = prepared
+                decoded = []                                 # frames of every `load_files_device` call that ran
+
+                def load(paths):
+                    decoded.append(len(paths))
+                    return cholect.load_files_device(paths, h, w, workers=F.decode_workers, decode=F.png_decode)
+                x = cholect.fetch_files(self.cache, self._paths(samples), plan, load)
                 frames = augment.train_transform_device(x, params)
-                decode_calls = 1
             else:
                 from .drivers import load_train_frames_u8
                 frames = torch.from_numpy(np.concatenate([load_train_frames_u8(F.data_dir, v, [self.labels[v]["ivt"][i, 0]], h, w, self.rng,
                                                                                F.augmentation_list) for v, i in samples])).cuda()
-                decode_calls = 0
+                decoded = []
             lab, tp, tf = self.tables.take(samples)
             with self._lock:
                 self.stats["chunks"] += 1
-                self.stats["decode_calls"] += decode_calls
+                self.stats["decode_calls"] += len(decoded)
                 self.stats["frames"] += len(samples)
+                self.stats["frames_decoded"] += sum(decoded)
+                self.stats["hits"] += len(samples) - sum(decoded) if self.device_transform else 0
             return frames, lab, tp, tf
         finally:
             with self._lock:

@@ -1362,6 +1362,38 @@ def take_rows(tables, rows: torch.Tensor):
     return outs
 
 
+def _frame_slots(what: str, pool: torch.Tensor, slots, frames: torch.Tensor):
+    """the checks `put_frames` and `take_frames` share -> (slots on the device, n, frame_bytes, pool_slots).  `slots` lives on the HOST (an int32
+    numpy array or CPU tensor): its bound is checked here, before anything is uploaded or launched"""
+    _need_cuda(pool, frames)
+    assert pool.dtype == torch.uint8 and frames.dtype == torch.uint8 and pool.is_contiguous() and frames.is_contiguous()
+    assert pool.dim() >= 2 and frames.dim() == pool.dim() and tuple(frames.shape[1:]) == tuple(pool.shape[1:]) and frames.device == pool.device
+    slots = torch.as_tensor(slots)
+    assert not slots.is_cuda and slots.dtype == torch.int32 and slots.dim() == 1 and slots.is_contiguous() and slots.numel() == frames.shape[0]
+    n, pool_slots = int(slots.numel()), int(pool.shape[0])
+    if n and int(slots.max()) >= pool_slots:
+        raise _lib.Mt4Error(f"{what}: slot {int(slots.max())} outside the {pool_slots} slots of the pool")
+    return slots.to(pool.device) if n else slots, n, pool[0].numel() if pool_slots else 0, pool_slots
+
+
+def put_frames(pool: torch.Tensor, slots, frames: torch.Tensor) -> None:
+    """pool[slots[i]] = frames[i] for every i with slots[i] >= 0 (`mt4_put_frames_u8`): pool uint8 [S, ...] and frames uint8 [n, ...] contiguous
+    device tensors of one row shape, slots int32 [n] on the host.  A negative slot leaves its row alone; a slot >= S raises before the launch;
+    n == 0 launches nothing."""
+    dev_slots, n, frame_bytes, pool_slots = _frame_slots("put_frames", pool, slots, frames)
+    check(lib.mt4_put_frames_u8(pool.data_ptr(), dev_slots.data_ptr() if n else None, frames.data_ptr(), n, frame_bytes, pool_slots, _stream()),
+          "mt4_put_frames_u8")
+
+
+def take_frames(pool: torch.Tensor, slots, out: torch.Tensor) -> torch.Tensor:
+    """out[i] = pool[slots[i]] for every i with slots[i] >= 0 (`mt4_take_frames_u8`), the other rows of `out` keep their bytes; arguments as
+    `put_frames`.  Returns `out`."""
+    dev_slots, n, frame_bytes, pool_slots = _frame_slots("take_frames", pool, slots, out)
+    check(lib.mt4_take_frames_u8(pool.data_ptr(), dev_slots.data_ptr() if n else None, out.data_ptr(), n, frame_bytes, pool_slots, _stream()),
+          "mt4_take_frames_u8")
+    return out
+
+
 def scatter_rows(y: torch.Tensor, row_map: torch.Tensor, *, l_out: int, l_in: int, group: int = 1, m_in: Optional[int] = None) -> torch.Tensor:
     """the inverse of `gather_rows` (the maps are bijections): x[(m // l_out) * l_in + map[...]] = y[m][g*C:(g+1)*C]"""
     _need_cuda(y, row_map)

@@ -306,6 +306,17 @@ typedef struct mt4_take_seg {
     int32_t nrows;
 } mt4_take_seg;
 int mt4_take_rows_f32(const mt4_take_seg* segs, int32_t nseg, const int64_t* rows, int64_t n, void* stream);
+/* The frame pool of `cholect.FrameCache` (--frame_cache; no reference counterpart: its DataLoader decodes and resizes every PNG again every epoch).
+ *   put:  pool[slots[i]] = frames[i]      take:  frames[i] = pool[slots[i]]      for every i < n with 0 <= slots[i] < pool_slots
+ * pool: DEVICE uint8 [pool_slots][frame_bytes]; frames: DEVICE uint8 [n][frame_bytes], contiguous; slots: DEVICE int32 [n].  A row with a negative
+ * slot is not touched in either direction (the caller has put a freshly decoded frame there); a slot >= pool_slots is the caller's error and the
+ * row is skipped the same way -- the bound is checked in the kernel, there is no out-of-range access (`ops.put_frames` / `take_frames` refuse it on
+ * the host before the launch).  Byte offsets are 64-bit (a pool is tens of GB).  frame_bytes % 16 == 0 with both bases 16-byte aligned moves 16
+ * bytes per lane, 64 bytes in flight per lane, non-temporal on the pool side; anything else goes byte by byte (correct, not fast).  One launch over
+ * (16-byte pieces, frame): n <= 65535 (MT4_EUNSUPPORTED beyond).  MT4_EINVAL for n < 0, frame_bytes <= 0, pool_slots <= 0 or a null pointer with
+ * n > 0; n == 0 launches nothing.  Two rows of one `put` naming the same slot race (the caller hands out every slot once).  Both only enqueue. */
+int mt4_put_frames_u8(void* pool, const int32_t* slots, const void* frames, int32_t n, int64_t frame_bytes, int64_t pool_slots, void* stream);
+int mt4_take_frames_u8(const void* pool, const int32_t* slots, void* frames, int32_t n, int64_t frame_bytes, int64_t pool_slots, void* stream);
 /* MaxPool2d(3, stride 2, pad 1) channels-last (resnet.py:149). C*esize % 16 == 0. */
 int mt4_maxpool3x3s2_nhwc(const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
                           void* stream);
