@@ -66,6 +66,7 @@ SELECT_SCRATCH_BYTES = 8448   # MT4_SELECT_SCRATCH_BYTES
 
 _vp, _i32 = C.c_void_p, C.c_int32
 _FLOAT3 = C.c_float * 3
+_PLAN_OUT = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]   # form, nparts, part_elems, ws_bytes of a `_det_plan`
 
 # name -> (restype, argtypes); must list every symbol of include/mt4hip.h
 SIGNATURES = {
@@ -113,6 +114,32 @@ SIGNATURES = {
     "mt4_wgrad_conv1d_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mt4_colsum_f32": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _vp]),
     "mt4_bce_logits_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i32, _i32, _i32, _vp]),
+    "mt4_fold_parts_f32": (C.c_int, [_vp, _i32, C.c_int64, C.c_int64, _vp, _i32, _vp]),
+    "mt4_fold_parts_f64": (C.c_int, [_vp, _i32, C.c_int64, C.c_int64, _vp, _i32, _vp]),
+    "mt4_fold_parts_chunked_f32": (C.c_int, [_vp, _i32, C.c_int64, C.c_int64, _vp, _i32, _vp]),
+    "mt4_fold_parts_chunked_f64": (C.c_int, [_vp, _i32, C.c_int64, C.c_int64, _vp, _i32, _vp]),
+    "mt4_wgrad_conv1d_det_plan": (C.c_int, [_i32] * 6 + [C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mt4_colsum_det_plan": (C.c_int, [C.c_int64, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mt4_bce_logits_det_plan": (C.c_int, [C.c_int64, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mt4_wgrad_conv1d_det_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
+    "mt4_colsum_det_f32": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _vp, C.c_int64, _vp]),
+    "mt4_bce_logits_det_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i32, _i32, _i32, _vp, C.c_int64, _vp]),
+    "mt4_bn_det_plan": (C.c_int, [C.c_int64, _i32] + _PLAN_OUT),
+    "mt4_bn_stats_det_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i32, C.c_float, C.c_float, _vp, C.c_int64, _vp]),
+    "mt4_bn_stats_det_t": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i32, C.c_float, C.c_float, _vp, C.c_int64, _vp]),
+    "mt4_bn_backward_det_f32": (C.c_int, [_vp] * 12 + [C.c_int64, _i32, _i32, _vp, C.c_int64, _vp]),
+    "mt4_bn_backward_det_t": (C.c_int, [_vp, _vp, _vp, _i32] + [_vp] * 9 + [C.c_int64, _i32, _i32, _vp, C.c_int64, _vp]),
+    "mt4_wgrad_conv2d_det_plan": (C.c_int, [_i32] * 7 + _PLAN_OUT),
+    "mt4_wgrad_conv2d_det_f32": (C.c_int, [_vp, _vp, _vp] + [_i32] * 16 + [_vp, C.c_int64, _vp]),
+    "mt4_wgrad_conv2d_bf16_det_plan": (C.c_int, [_i32] * 7 + _PLAN_OUT),
+    "mt4_wgrad_conv2d_det_bf16": (C.c_int, [_vp, _vp, _vp] + [_i32] * 10 + [_vp, C.c_int64, _vp]),
+    "mt4_maxpool3x3s2_bwd_gather_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mt4_bce_logits_pw_det_plan": (C.c_int, [_i32, _i32] + _PLAN_OUT),
+    "mt4_bce_logits_pw_det_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, C.c_int64, _vp]),
+    "mt4_distill_kl_det_plan": (C.c_int, [_i32, _i32] + _PLAN_OUT),
+    "mt4_distill_kl_det_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, C.c_float, _i32, _vp, C.c_int64, _vp]),
+    "mt4_mse_det_plan": (C.c_int, [C.c_int64] + _PLAN_OUT),
+    "mt4_mse_det_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_float, _vp, C.c_int64, _vp]),
     "mt4_sgd_step_f32": (C.c_int, [_vp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, _vp]),
     "mt4_mul_add_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "mt4_transpose_pack_conv1d_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),

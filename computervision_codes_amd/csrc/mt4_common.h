@@ -198,6 +198,9 @@ __host__ __device__ __forceinline__ unsigned long long splitmix64(unsigned long 
 // x 64 row phases), at most ~512 per launch: every workgroup ends in 128 float64 atomics on its slab's 128 addresses, and 2048 workgroups of
 // 256 threads on a 64-channel map made those same-address chains (~25 ns a link at the L2) longer than the stream itself -- 52-58 us for 59 MB
 // where the apply kernel moves twice the bytes in 20-29 us (profiles/r03_bn_training_kernels.txt)
+// DET (the `_det` entry points): `sums` is the workspace and row slab blockIdx.y STORES its 2 x C values into part blockIdx.y = sums + blockIdx.y * 2 C
+// -- every channel of both rows, no atomics; mt4_fold_parts_f64 adds the slabs in index order afterwards
+template <bool DET = false>
 __device__ __forceinline__ void bn_block_reduce(double (&acc)[8], double* __restrict__ sums, int C, int c0) {
     __shared__ double red[16][8][17];               // [wave][value][channel group], padded
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -217,7 +220,11 @@ __device__ __forceinline__ void bn_block_reduce(double (&acc)[8], double* __rest
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) t += red[rr][j][g];
         const int c = c0 + g * 4 + (j & 3);
-        if (c < C) atomicAdd(sums + (j >> 2) * C + c, t);
+        if constexpr (DET) {
+            if (c < C) sums[(long long)blockIdx.y * 2 * C + (j >> 2) * C + c] = t;
+        } else {
+            if (c < C) atomicAdd(sums + (j >> 2) * C + c, t);
+        }
     }
 }
 

@@ -13,7 +13,7 @@ namespace {
 // blocks (64 channels x 64 row phases) and at most ~512 of them: every block ends in 128 fp64 atomics on its slab's 128 addresses, and with 2048
 // blocks of 256 threads on a 64-channel tensor those 2048-deep same-address chains (~25 ns a link at the L2) took longer than the stream --
 // 52-58 us for 59 MB where the apply kernel moves twice the bytes in 20-29 us (profiles/r03_bn_training_kernels.txt)
-template <typename TZ>
+template <typename TZ, bool DET = false>
 __global__ __launch_bounds__(1024) void bn_stats_t_kernel(const TZ* __restrict__ x, double* __restrict__ sums, long long M, int C) {
     const int c0 = blockIdx.x * 64, c = c0 + (threadIdx.x & 15) * 4;
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(1024) void bn_stats_t_kernel(const TZ* __restrict__
         }
         for (; m < M; m += st) add(ld4<TZ>(x + m * C + c));
     }
-    bn_block_reduce(acc, sums, C, c0);
+    bn_block_reduce<DET>(acc, sums, C, c0);
 }
 
 __global__ void bn_finalize_t_kernel(const double* __restrict__ sums, float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ run_mean,
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void bn_apply_t_kernel(const TZ* __restrict__ 
 // relu: 0 none; 1 the ReLU gate is read from the stored output y; 2 it is recomputed from x -- (x - mean) * invstd * gamma + beta > 0, the
 // forward's own fp32 expression -- for units without a residual input: y need not be read (2 of the 6 / 8 bytes per element these HBM-bound
 // kernels move)
-template <typename TZ>
+template <typename TZ, bool DET = false>
 __global__ __launch_bounds__(1024) void bn_bwd_reduce_t_kernel(const u16* __restrict__ dy, const u16* __restrict__ y, const TZ* __restrict__ x,
                                                               const float* __restrict__ mean, const float* __restrict__ invstd,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta, double* __restrict__ sums,
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_reduce_t_kernel(const u16* __rest
             add(ld4<u16>(dy + i0), ld4<TZ>(x + i0), rd_y ? ld4<u16>(y + i0) : one);
         }
     }
-    bn_block_reduce(acc, sums, C, c0);
+    bn_block_reduce<DET>(acc, sums, C, c0);
 }
 
 // dx has the type of x (the convolution output: bf16, or fp32 for the stem); dres = the gated gradient, bf16.  Column slabs, parameters and the two
@@ -268,7 +268,11 @@ struct WgK {
     int tiles_h, tiles_w, ntiles, nsplit, cin_tiles;
 };
 
-template <int K, int S, int TH, int BMT, int BNT, int OCC = 2>
+// DET (mt4_wgrad_conv2d_det_bf16): `a.dw` is the workspace and the workgroups of split z STORE their blocks into part z = a.dw + z * Cout * kpad, an image of
+// the packed fp32 dW.  Within a split the (n-tile, c-tile, kh) regions are disjoint and together cover every (n, tap, c < Cin) -- the channel counts are
+// multiples of 8, so a tap has no padding columns -- and the workgroups of the last kernel row and last c-tile write the zeros of the row tail
+// [K K tapw, kpad); mt4_fold_parts_f32 adds the parts in z order afterwards.
+template <int K, int S, int TH, int BMT, int BNT, int OCC = 2, bool DET = false>
 __global__ __launch_bounds__(256, OCC) void wgrad_bf16_kernel(const WgK a) {
     constexpr bool PREFETCH = true;
     constexpr int PAD = K / 2;
@@ -398,6 +402,7 @@ __global__ __launch_bounds__(256, OCC) void wgrad_bf16_kernel(const WgK a) {
     }
     // ---- dW += the wave's block: lane (r16 = c, q4 = lane >> 4) holds output channels 4 q4 + e of input channel r16
     const int r16 = lane & 15, q4 = lane >> 4;
+    float* const dwp = DET ? a.dw + (long long)split * a.Cout * a.kpad : a.dw;
 #pragma unroll
     for (int kw = 0; kw < K; ++kw)
 #pragma unroll
@@ -408,12 +413,21 @@ __global__ __launch_bounds__(256, OCC) void wgrad_bf16_kernel(const WgK a) {
                 for (int e = 0; e < 4; ++e) {
                     const int n = n0 + wm * (32 * BMT) + mi * 16 + q4 * 4 + e;
                     const int c = c0 + wn * (32 * BNT) + ni * 16 + r16;
-                    if (n < a.Cout && c < a.Cin) atomicAdd(a.dw + (long long)n * a.kpad + (kh * K + kw) * a.tapw + c, acc[kw][mi][ni][e]);
+                    if constexpr (DET) {
+                        if (n < a.Cout && c < a.Cin) dwp[(long long)n * a.kpad + (kh * K + kw) * a.tapw + c] = acc[kw][mi][ni][e];
+                    } else {
+                        if (n < a.Cout && c < a.Cin) atomicAdd(dwp + (long long)n * a.kpad + (kh * K + kw) * a.tapw + c, acc[kw][mi][ni][e]);
+                    }
                 }
+    if constexpr (DET) {
+        if (kh == K - 1 && c0 + 64 * BNT >= a.Cin && tid < 64 * BMT && n0 + tid < a.Cout)
+            for (int k = K * K * a.tapw; k < a.kpad; ++k) dwp[(long long)(n0 + tid) * a.kpad + k] = 0.f;
+    }
 }
 
-template <int K, int S, int TH, int BMT, int BNT, int OCC = 2>
-int launch_wgrad(WgK a, hipStream_t stream) {
+// launch: false = plan only (fills *nsplit_out, launches nothing)
+template <int K, int S, int TH, int BMT, int BNT, int OCC = 2, bool DET = false>
+int launch_wgrad(WgK a, hipStream_t stream, bool launch = true, int* nsplit_out = nullptr) {
     constexpr int IW = S * 15 + K, PITCH = (IW + 15) / 16 * 16;
     constexpr int LDS = BMT * TH * 16 * WG_ROWB + BNT * TH * PITCH * WG_ROWB;
     static_assert(LDS * OCC <= 160 * 1024, "OCC workgroups per CU");
@@ -428,7 +442,9 @@ int launch_wgrad(WgK a, hipStream_t stream) {
     if (nsplit > a.ntiles) nsplit = a.ntiles;
     if (nsplit < 1) nsplit = 1;
     a.nsplit = nsplit;
-    return mt4_launch<wgrad_bf16_kernel<K, S, TH, BMT, BNT, OCC>>(dim3((unsigned)(pairs * nsplit)), dim3(256), LDS, stream, a);
+    if (nsplit_out) *nsplit_out = nsplit;
+    if (!launch) return MT4_OK;
+    return mt4_launch<wgrad_bf16_kernel<K, S, TH, BMT, BNT, OCC, DET>>(dim3((unsigned)(pairs * nsplit)), dim3(256), LDS, stream, a);
 }
 
 // ------------------------------------------------------------------------------------------------ pooling backward, packed-weight copy
@@ -649,19 +665,39 @@ extern "C" int mt4_refresh_weights(const mt4_refresh_entry* table_dev, int32_t n
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
+// det: the slabs' sums stored into their parts of `ws` and folded in fixed chunks of slabs (mt4_fold_parts_chunked_f64) INTO `sums` (mt4_bn_det_plan; no zeroing)
+static int bn_stats_t(const void* x, int32_t x_dtype, double* sums, float* mean, float* invstd, float* running_mean, float* running_var, int64_t M,
+                      int32_t C, float momentum, float eps, double* ws, int64_t ws_bytes, bool det, void* stream) {
+    mt4_clear_error();
+    if (!x || !sums || !mean || !invstd || M <= 0 || C <= 0 || (det && !ws)) return MT4_EINVAL;
+    if (C % 4 || (det && ((uintptr_t)ws & 15))) return MT4_EALIGN;
+    if (x_dtype != MT4_BF16 && x_dtype != MT4_F32) return MT4_EUNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const int slabs = bn_reduce_slabs(M, C);
+    if (det && ws_bytes < (long long)slabs * 2 * C * (long long)sizeof(double)) return MT4_EINVAL;
+    const dim3 grid(cdiv(C, 64), slabs);
+    if (det) {
+        if (x_dtype == MT4_BF16) hipLaunchKernelGGL((bn_stats_t_kernel<u16, true>), grid, dim3(1024), 0, s, (const u16*)x, ws, (long long)M, C);
+        else hipLaunchKernelGGL((bn_stats_t_kernel<float, true>), grid, dim3(1024), 0, s, (const float*)x, ws, (long long)M, C);
+        const int lc = mt4_check_launch();
+        if (lc != MT4_OK) return lc;
+        const int fc = mt4_fold_parts_chunked_f64(ws, slabs, 2LL * C, 2LL * C, sums, 0, stream);
+        if (fc != MT4_OK) return fc;
+    } else if (x_dtype == MT4_BF16) hipLaunchKernelGGL((bn_stats_t_kernel<u16, false>), grid, dim3(1024), 0, s, (const u16*)x, sums, (long long)M, C);
+    else hipLaunchKernelGGL((bn_stats_t_kernel<float, false>), grid, dim3(1024), 0, s, (const float*)x, sums, (long long)M, C);
+    hipLaunchKernelGGL(bn_finalize_t_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, sums, mean, invstd, running_mean, running_var, (long long)M, C, momentum,
+                       eps);
+    return mt4_check_launch();
+}
+
 extern "C" int mt4_bn_stats_t(const void* x, int32_t x_dtype, double* sums_zeroed, float* mean, float* invstd, float* running_mean, float* running_var,
                               int64_t M, int32_t C, float momentum, float eps, void* stream) {
-    mt4_clear_error();
-    if (!x || !sums_zeroed || !mean || !invstd || M <= 0 || C <= 0) return MT4_EINVAL;
-    if (C % 4) return MT4_EALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(cdiv(C, 64), bn_reduce_slabs(M, C));
-    if (x_dtype == MT4_BF16) hipLaunchKernelGGL(bn_stats_t_kernel<u16>, grid, dim3(1024), 0, s, (const u16*)x, sums_zeroed, (long long)M, C);
-    else if (x_dtype == MT4_F32) hipLaunchKernelGGL(bn_stats_t_kernel<float>, grid, dim3(1024), 0, s, (const float*)x, sums_zeroed, (long long)M, C);
-    else return MT4_EUNSUPPORTED;
-    hipLaunchKernelGGL(bn_finalize_t_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, sums_zeroed, mean, invstd, running_mean, running_var, (long long)M, C,
-                       momentum, eps);
-    return mt4_check_launch();
+    return bn_stats_t(x, x_dtype, sums_zeroed, mean, invstd, running_mean, running_var, M, C, momentum, eps, nullptr, 0, false, stream);
+}
+
+extern "C" int mt4_bn_stats_det_t(const void* x, int32_t x_dtype, double* sums, float* mean, float* invstd, float* running_mean, float* running_var,
+                                  int64_t M, int32_t C, float momentum, float eps, double* ws, int64_t ws_bytes, void* stream) {
+    return bn_stats_t(x, x_dtype, sums, mean, invstd, running_mean, running_var, M, C, momentum, eps, ws, ws_bytes, true, stream);
 }
 
 extern "C" int mt4_bn_apply_t(const void* x, int32_t x_dtype, const float* mean, const float* invstd, const float* gamma, const float* beta,
@@ -699,27 +735,80 @@ extern "C" int mt4_bn_apply_sums_t(const void* x, int32_t x_dtype, const double*
     return mt4_check_launch();
 }
 
+static int bn_backward_t(const void* dy_bf16, const void* y_post_bf16, const void* x, int32_t x_dtype, const float* mean, const float* invstd,
+                         const float* gamma, const float* beta, double* sums, void* dx, void* dres_bf16, float* dgamma, float* dbeta, int64_t M, int32_t C,
+                         int32_t relu, double* ws, int64_t ws_bytes, bool det, void* stream) {
+    mt4_clear_error();
+    if (!dy_bf16 || !x || !mean || !invstd || !gamma || !sums || !dx || !dgamma || !dbeta || M <= 0 || C <= 0 || (det && !ws)) return MT4_EINVAL;
+    if (relu < 0 || relu > 2 || (relu == 1 && !y_post_bf16) || (relu == 2 && !beta)) return MT4_EINVAL;
+    if (C % 4 || (det && ((uintptr_t)ws & 15))) return MT4_EALIGN;
+    if (x_dtype != MT4_BF16 && x_dtype != MT4_F32) return MT4_EUNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const int slabs = bn_reduce_slabs(M, C);
+    if (det && ws_bytes < (long long)slabs * 2 * C * (long long)sizeof(double)) return MT4_EINVAL;
+    const dim3 g1(cdiv(C, 64), slabs), g2(cdiv(C, 64), bn_row_slabs(M, C));
+    const u16 *dy = (const u16*)dy_bf16, *yp = (const u16*)y_post_bf16;
+    if (det) {
+        if (x_dtype == MT4_BF16)
+            hipLaunchKernelGGL((bn_bwd_reduce_t_kernel<u16, true>), g1, dim3(1024), 0, s, dy, yp, (const u16*)x, mean, invstd, gamma, beta, ws, (long long)M, C, relu);
+        else
+            hipLaunchKernelGGL((bn_bwd_reduce_t_kernel<float, true>), g1, dim3(1024), 0, s, dy, yp, (const float*)x, mean, invstd, gamma, beta, ws, (long long)M, C, relu);
+        const int lc = mt4_check_launch();
+        if (lc != MT4_OK) return lc;
+        const int fc = mt4_fold_parts_chunked_f64(ws, slabs, 2LL * C, 2LL * C, sums, 0, stream);
+        if (fc != MT4_OK) return fc;
+    } else if (x_dtype == MT4_BF16) {
+        hipLaunchKernelGGL((bn_bwd_reduce_t_kernel<u16, false>), g1, dim3(1024), 0, s, dy, yp, (const u16*)x, mean, invstd, gamma, beta, sums, (long long)M, C, relu);
+    } else {
+        hipLaunchKernelGGL((bn_bwd_reduce_t_kernel<float, false>), g1, dim3(1024), 0, s, dy, yp, (const float*)x, mean, invstd, gamma, beta, sums, (long long)M, C, relu);
+    }
+    if (x_dtype == MT4_BF16)
+        hipLaunchKernelGGL(bn_bwd_apply_t_kernel<u16>, g2, dim3(256), 0, s, dy, yp, (const u16*)x, mean, invstd, gamma, beta, sums, (u16*)dx, (u16*)dres_bf16, dgamma,
+                           dbeta, (long long)M, C, relu);
+    else
+        hipLaunchKernelGGL(bn_bwd_apply_t_kernel<float>, g2, dim3(256), 0, s, dy, yp, (const float*)x, mean, invstd, gamma, beta, sums, (float*)dx, (u16*)dres_bf16,
+                           dgamma, dbeta, (long long)M, C, relu);
+    return mt4_check_launch();
+}
+
 extern "C" int mt4_bn_backward_t(const void* dy_bf16, const void* y_post_bf16, const void* x, int32_t x_dtype, const float* mean, const float* invstd,
                                  const float* gamma, const float* beta, double* sums_zeroed, void* dx, void* dres_bf16, float* dgamma, float* dbeta,
                                  int64_t M, int32_t C, int32_t relu, void* stream) {
-    mt4_clear_error();
-    if (!dy_bf16 || !x || !mean || !invstd || !gamma || !sums_zeroed || !dx || !dgamma || !dbeta || M <= 0 || C <= 0) return MT4_EINVAL;
-    if (relu < 0 || relu > 2 || (relu == 1 && !y_post_bf16) || (relu == 2 && !beta)) return MT4_EINVAL;
-    if (C % 4) return MT4_EALIGN;
-    if (x_dtype != MT4_BF16 && x_dtype != MT4_F32) return MT4_EUNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 g1(cdiv(C, 64), bn_reduce_slabs(M, C)), g2(cdiv(C, 64), bn_row_slabs(M, C));
-    const u16 *dy = (const u16*)dy_bf16, *yp = (const u16*)y_post_bf16;
-    if (x_dtype == MT4_BF16) {
-        hipLaunchKernelGGL(bn_bwd_reduce_t_kernel<u16>, g1, dim3(1024), 0, s, dy, yp, (const u16*)x, mean, invstd, gamma, beta, sums_zeroed, (long long)M, C, relu);
-        hipLaunchKernelGGL(bn_bwd_apply_t_kernel<u16>, g2, dim3(256), 0, s, dy, yp, (const u16*)x, mean, invstd, gamma, beta, sums_zeroed, (u16*)dx,
-                           (u16*)dres_bf16, dgamma, dbeta, (long long)M, C, relu);
-    } else {
-        hipLaunchKernelGGL(bn_bwd_reduce_t_kernel<float>, g1, dim3(1024), 0, s, dy, yp, (const float*)x, mean, invstd, gamma, beta, sums_zeroed, (long long)M, C, relu);
-        hipLaunchKernelGGL(bn_bwd_apply_t_kernel<float>, g2, dim3(256), 0, s, dy, yp, (const float*)x, mean, invstd, gamma, beta, sums_zeroed, (float*)dx,
-                           (u16*)dres_bf16, dgamma, dbeta, (long long)M, C, relu);
+    return bn_backward_t(dy_bf16, y_post_bf16, x, x_dtype, mean, invstd, gamma, beta, sums_zeroed, dx, dres_bf16, dgamma, dbeta, M, C, relu, nullptr, 0, false,
+                         stream);
+}
+
+extern "C" int mt4_bn_backward_det_t(const void* dy_bf16, const void* y_post_bf16, const void* x, int32_t x_dtype, const float* mean, const float* invstd,
+                                     const float* gamma, const float* beta, double* sums, void* dx, void* dres_bf16, float* dgamma, float* dbeta, int64_t M,
+                                     int32_t C, int32_t relu, double* ws, int64_t ws_bytes, void* stream) {
+    return bn_backward_t(dy_bf16, y_post_bf16, x, x_dtype, mean, invstd, gamma, beta, sums, dx, dres_bf16, dgamma, dbeta, M, C, relu, ws, ws_bytes, true, stream);
+}
+
+// the eight launch forms (form = the index below) -- shared by the launch, the deterministic launch and its host-only plan query
+// wider (n, c) tiles where the channel counts allow: twice the FLOPs per staged byte
+// 3x3: 64 x 64 per kernel row (K x 16 accumulator registers per wave leave room for the one-tile-ahead staging registers), tiles of 4 rows
+// and THREE workgroups per CU: a workgroup waits out a load round trip per tile (request behind the barrier, needed at the next one), and
+// with two per CU the matrix cores idled through most of it -- same-box, ResNet-50 b64 shapes: layer2 117 -> 84 us, layer3 115 -> 71,
+// layer4 105 -> 69, the strided ones 142 -> 89 (profiles/r03_wgrad_experiments.txt).  The 1x1 forms spend ~45 % of their time in the
+// closing fp32 atomics (one dword per clock and L2 channel): more workgroups mean more of those, and they stay at two per CU.
+template <bool DET>
+static int wgrad_bf16_dispatch(WgK a, int K, int stride, hipStream_t s, bool launch, int* form, int* nsplit) {
+    const bool m2 = a.Cout > 64, n2 = a.Cin > 64;
+    int f;
+    if (K == 1 && stride == 1) f = (m2 && n2) ? 0 : m2 ? 1 : n2 ? 2 : 3;
+    else if (K == 1) f = m2 ? 4 : 5;
+    else f = stride == 1 ? 6 : 7;
+    if (form) *form = f;
+    switch (f) {
+        case 0: return launch_wgrad<1, 1, 8, 2, 2, 2, DET>(a, s, launch, nsplit);
+        case 1: return launch_wgrad<1, 1, 8, 2, 1, 2, DET>(a, s, launch, nsplit);
+        case 2: return launch_wgrad<1, 1, 8, 1, 2, 2, DET>(a, s, launch, nsplit);
+        case 3: return launch_wgrad<1, 1, 8, 1, 1, 2, DET>(a, s, launch, nsplit);
+        case 4: return launch_wgrad<1, 2, 8, 2, 1, 2, DET>(a, s, launch, nsplit);
+        case 5: return launch_wgrad<1, 2, 8, 1, 1, 2, DET>(a, s, launch, nsplit);
+        case 6: return launch_wgrad<3, 1, 4, 1, 1, 3, DET>(a, s, launch, nsplit);
+        default: return launch_wgrad<3, 2, 4, 1, 1, 3, DET>(a, s, launch, nsplit);
     }
-    return mt4_check_launch();
 }
 
 extern "C" int mt4_wgrad_conv2d_bf16(const void* dy, const void* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo,
@@ -735,26 +824,52 @@ extern "C" int mt4_wgrad_conv2d_bf16(const void* dy, const void* x, float* dw_pa
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
     a.kpad = (int)mt4_conv_packed_k(Cin, K, K, MT4_F32);
     a.tapw = (Cin + 3) / 4 * 4;
-    hipStream_t s = (hipStream_t)stream;
-    // wider (n, c) tiles where the channel counts allow: twice the FLOPs per staged byte
-    const bool m2 = Cout > 64, n2 = Cin > 64;
-    if (K == 1 && stride == 1) {
-        if (m2 && n2) return launch_wgrad<1, 1, 8, 2, 2>(a, s);
-        if (m2) return launch_wgrad<1, 1, 8, 2, 1>(a, s);
-        if (n2) return launch_wgrad<1, 1, 8, 1, 2>(a, s);
-        return launch_wgrad<1, 1, 8, 1, 1>(a, s);
-    }
-    if (K == 1) {
-        if (m2) return launch_wgrad<1, 2, 8, 2, 1>(a, s);
-        return launch_wgrad<1, 2, 8, 1, 1>(a, s);
-    }
-    // 3x3: 64 x 64 per kernel row (K x 16 accumulator registers per wave leave room for the one-tile-ahead staging registers), tiles of 4 rows
-    // and THREE workgroups per CU: a workgroup waits out a load round trip per tile (request behind the barrier, needed at the next one), and
-    // with two per CU the matrix cores idled through most of it -- same-box, ResNet-50 b64 shapes: layer2 117 -> 84 us, layer3 115 -> 71,
-    // layer4 105 -> 69, the strided ones 142 -> 89 (profiles/r03_wgrad_experiments.txt).  The 1x1 forms spend ~45 % of their time in the
-    // closing fp32 atomics (one dword per clock and L2 channel): more workgroups mean more of those, and they stay at two per CU.
-    if (stride == 1) return launch_wgrad<3, 1, 4, 1, 1, 3>(a, s);
-    return launch_wgrad<3, 2, 4, 1, 1, 3>(a, s);
+    return wgrad_bf16_dispatch<false>(a, K, stride, (hipStream_t)stream, true, nullptr, nullptr);
+}
+
+extern "C" int mt4_wgrad_conv2d_bf16_det_plan(int32_t B, int32_t Ho, int32_t Wo, int32_t Cout, int32_t Cin, int32_t K, int32_t stride, int32_t* form,
+                                              int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
+    if (B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0) return MT4_EINVAL;
+    if ((K != 1 && K != 3) || (stride != 1 && stride != 2)) return MT4_EUNSUPPORTED;
+    if ((Cin % 8) || (Cout % 8)) return MT4_EALIGN;
+    WgK a;
+    a.dy = nullptr; a.x = nullptr; a.dw = nullptr;
+    a.B = B; a.H = 0; a.W = 0; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;         // (the form and the split depend on the output pixels and the channels alone)
+    a.kpad = (int)mt4_conv_packed_k(Cin, K, K, MT4_F32);
+    a.tapw = (Cin + 3) / 4 * 4;
+    int f = 0, ns = 0;
+    const int rc = wgrad_bf16_dispatch<true>(a, K, stride, nullptr, false, &f, &ns);
+    if (rc != MT4_OK) return rc;
+    if (form) *form = f;
+    if (nparts) *nparts = ns;
+    if (part_elems) *part_elems = (long long)Cout * a.kpad;
+    if (ws_bytes) *ws_bytes = (long long)ns * Cout * a.kpad * (long long)sizeof(float);
+    return MT4_OK;
+}
+
+// fold order (the contract): parts z = 0 .. nparts-1 (split z holds the spatial tiles t of TH x 16 output pixels with t % nparts == z, added in ascending t)
+// front to back; the sum is then ADDED to dw_packed (accumulate != 0) or stored
+extern "C" int mt4_wgrad_conv2d_det_bf16(const void* dy, const void* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo,
+                                         int32_t Cout, int32_t K, int32_t stride, int32_t accumulate, float* ws, int64_t ws_bytes, void* stream) {
+    mt4_clear_error();
+    if (!dy || !x || !dw_packed || !ws || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) return MT4_EINVAL;
+    if ((K != 1 && K != 3) || (stride != 1 && stride != 2)) return MT4_EUNSUPPORTED;
+    if ((Cin % 8) || (Cout % 8)) return MT4_EALIGN;
+    if (Ho != (H + 2 * (K / 2) - K) / stride + 1 || Wo != (W + 2 * (K / 2) - K) / stride + 1) return MT4_EINVAL;
+    if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dw_packed | (uintptr_t)ws) & 15) return MT4_EALIGN;
+    WgK a;
+    a.dy = (const u16*)dy; a.x = (const u16*)x; a.dw = ws;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
+    a.kpad = (int)mt4_conv_packed_k(Cin, K, K, MT4_F32);
+    a.tapw = (Cin + 3) / 4 * 4;
+    int ns = 0;
+    int rc = wgrad_bf16_dispatch<true>(a, K, stride, nullptr, false, nullptr, &ns);
+    if (rc != MT4_OK) return rc;
+    const long long pe = (long long)Cout * a.kpad;
+    if (ws_bytes < ns * pe * (long long)sizeof(float)) return MT4_EINVAL;
+    rc = wgrad_bf16_dispatch<true>(a, K, stride, (hipStream_t)stream, true, nullptr, nullptr);
+    if (rc != MT4_OK) return rc;
+    return mt4_fold_parts_f32(ws, ns, pe, pe, dw_packed, accumulate, stream);
 }
 
 extern "C" int mt4_maxpool3x3s2_bwd_bf16(const void* x, const void* dy, void* dx, int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {

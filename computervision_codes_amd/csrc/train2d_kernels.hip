@@ -13,6 +13,7 @@
 // (64 channels x 64 row phases), at most ~512 per launch: every workgroup ends in 128 float64 atomics on its slab's 128 addresses, and 2048
 // workgroups of 256 threads on a 64-channel map made those same-address chains (~25 ns a link at the L2) longer than the stream itself
 // (profiles/r03_bn_training_kernels.txt; the bf16-tensor twins live in train2d_bf16.hip)
+template <bool DET = false>      // DET: the slab's sums stored into its part of the workspace `sums` (bn_block_reduce)
 __global__ __launch_bounds__(1024) void bn_stats_kernel(const float* __restrict__ x, double* __restrict__ sums, long long M, int C) {
     const int c0 = blockIdx.x * 64, c = c0 + (threadIdx.x & 15) * 4;
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -29,7 +30,7 @@ __global__ __launch_bounds__(1024) void bn_stats_kernel(const float* __restrict_
         }
         for (; m < M; m += st) add(*(const float4*)(x + m * C + c));
     }
-    bn_block_reduce(acc, sums, C, c0);
+    bn_block_reduce<DET>(acc, sums, C, c0);
 }
 
 // pass 2: batch mean / biased variance -> (mean, invstd); running stats with momentum and the UNBIASED variance (torch)
@@ -54,9 +55,42 @@ extern "C" int mt4_bn_stats_f32(const float* x, double* sums_zeroed, float* mean
     if (!x || !sums_zeroed || !mean || !invstd || M <= 0 || C <= 0) return MT4_EINVAL;
     if (C % 4) return MT4_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(cdiv(C, 64), bn_reduce_slabs(M, C)), dim3(1024), 0, s, x, sums_zeroed, (long long)M, C);
+    hipLaunchKernelGGL(bn_stats_kernel<false>, dim3(cdiv(C, 64), bn_reduce_slabs(M, C)), dim3(1024), 0, s, x, sums_zeroed, (long long)M, C);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, sums_zeroed, mean, invstd, running_mean, running_var,
                        (long long)M, C, momentum, eps);
+    return mt4_check_launch();
+}
+
+// ---- deterministic BatchNorm reductions (both tensor types; the bf16-tensor entry points are in train2d_bf16.hip)
+// parts [slabs][2][C] float64, one per row slab of the 1024-thread reduction; fold order: the fixed chunks of mt4_fold_parts_chunked_f64 over the slabs (up
+// to 512 of them, a few thousand elements each: the sequential fold was 15 us a launch, 106 launches a ResNet-50 step), INTO `sums` (stored: `sums` needs no
+// zeroing), which the unchanged finalize / apply kernels then read
+extern "C" int mt4_bn_det_plan(int64_t M, int32_t C, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
+    if (M <= 0 || C <= 0) return MT4_EINVAL;
+    if (C % 4) return MT4_EALIGN;
+    const int slabs = bn_reduce_slabs(M, C);
+    if (form) *form = 0;
+    if (nparts) *nparts = slabs;
+    if (part_elems) *part_elems = 2LL * C;
+    if (ws_bytes) *ws_bytes = (long long)slabs * 2 * C * (long long)sizeof(double);
+    return MT4_OK;
+}
+
+extern "C" int mt4_bn_stats_det_f32(const float* x, double* sums, float* mean, float* invstd, float* running_mean, float* running_var, int64_t M,
+                                    int32_t C, float momentum, float eps, double* ws, int64_t ws_bytes, void* stream) {
+    mt4_clear_error();
+    if (!x || !sums || !mean || !invstd || !ws || M <= 0 || C <= 0) return MT4_EINVAL;
+    if (C % 4 || ((uintptr_t)ws & 15)) return MT4_EALIGN;
+    const int slabs = bn_reduce_slabs(M, C);
+    if (ws_bytes < (long long)slabs * 2 * C * (long long)sizeof(double)) return MT4_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_stats_kernel<true>, dim3(cdiv(C, 64), slabs), dim3(1024), 0, s, x, ws, (long long)M, C);
+    const int lc = mt4_check_launch();
+    if (lc != MT4_OK) return lc;
+    const int fc = mt4_fold_parts_chunked_f64(ws, slabs, 2LL * C, 2LL * C, sums, 0, stream);
+    if (fc != MT4_OK) return fc;
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, sums, mean, invstd, running_mean, running_var, (long long)M, C, momentum,
+                       eps);
     return mt4_check_launch();
 }
 
@@ -149,6 +183,7 @@ extern "C" int mt4_bn_apply_sums_f32(const float* x, const double* stat_sums, fl
 }
 
 // backward pass 1: with dy' = relu ? (y > 0 ? dy : 0) : dy :  sums[0][c] += sum dy',  sums[1][c] += sum dy' * xhat
+template <bool DET = false>
 __global__ __launch_bounds__(1024) void bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                              const float* __restrict__ x, const float* __restrict__ mean,
                                                              const float* __restrict__ invstd, const float* __restrict__ gamma,
@@ -193,7 +228,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_reduce_kernel(const float* __rest
             add(*(const float4*)(dy + i0), *(const float4*)(x + i0), relu == 1 ? *(const float4*)(y + i0) : one);
         }
     }
-    bn_block_reduce(acc, sums, C, c0);
+    bn_block_reduce<DET>(acc, sums, C, c0);
 }
 
 // backward pass 2: dx = gamma * invstd * (dy' - sum(dy')/M - xhat * sum(dy' xhat)/M);  dres = dy' (gradient of the residual input);
@@ -262,10 +297,31 @@ extern "C" int mt4_bn_backward_f32(const float* dy, const float* y_post, const f
     if (relu < 0 || relu > 2 || (relu == 1 && !y_post) || (relu == 2 && !beta)) return MT4_EINVAL;
     if (C % 4) return MT4_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(cdiv(C, 64), bn_reduce_slabs(M, C)), dim3(1024), 0, s, dy, y_post, x, mean, invstd, gamma, beta, sums_zeroed,
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(cdiv(C, 64), bn_reduce_slabs(M, C)), dim3(1024), 0, s, dy, y_post, x, mean, invstd, gamma, beta, sums_zeroed,
                        (long long)M, C, relu);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(cdiv(C, 64), bn_row_slabs(M, C)), dim3(256), 0, s, dy, y_post, x, mean, invstd, gamma, beta, sums_zeroed, dx,
                        dres, dgamma, dbeta, (long long)M, C, relu);
+    return mt4_check_launch();
+}
+
+extern "C" int mt4_bn_backward_det_f32(const float* dy, const float* y_post, const float* x, const float* mean, const float* invstd, const float* gamma,
+                                       const float* beta, double* sums, float* dx, float* dres, float* dgamma, float* dbeta, int64_t M, int32_t C,
+                                       int32_t relu, double* ws, int64_t ws_bytes, void* stream) {
+    mt4_clear_error();
+    if (!dy || !x || !mean || !invstd || !gamma || !sums || !dx || !dgamma || !dbeta || !ws || M <= 0 || C <= 0) return MT4_EINVAL;
+    if (relu < 0 || relu > 2 || (relu == 1 && !y_post) || (relu == 2 && !beta)) return MT4_EINVAL;
+    if (C % 4 || ((uintptr_t)ws & 15)) return MT4_EALIGN;
+    const int slabs = bn_reduce_slabs(M, C);
+    if (ws_bytes < (long long)slabs * 2 * C * (long long)sizeof(double)) return MT4_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(cdiv(C, 64), slabs), dim3(1024), 0, s, dy, y_post, x, mean, invstd, gamma, beta, ws, (long long)M, C,
+                       relu);
+    const int lc = mt4_check_launch();
+    if (lc != MT4_OK) return lc;
+    const int fc = mt4_fold_parts_chunked_f64(ws, slabs, 2LL * C, 2LL * C, sums, 0, stream);
+    if (fc != MT4_OK) return fc;
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(cdiv(C, 64), bn_row_slabs(M, C)), dim3(256), 0, s, dy, y_post, x, mean, invstd, gamma, beta, sums, dx, dres,
+                       dgamma, dbeta, (long long)M, C, relu);
     return mt4_check_launch();
 }
 
@@ -278,6 +334,9 @@ struct Wg2 {
     long long M, rows_per_split;
 };
 
+// DET (mt4_wgrad_conv2d_det_f32, both kernels): `dwp` is the workspace and split z STORES its tile into part z = dwp + z * Cout * Kpad, an image of the
+// packed dW -- every column below Kpad, the padding columns as the zeros their operand columns are; mt4_fold_parts_f32 adds the parts in z order
+template <bool DET = false>
 __global__ __launch_bounds__(256) void wgrad_conv2d_f32_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                float* __restrict__ dwp, const Wg2 a) {
     constexpr int KT = 32, LDP = 68;
@@ -339,6 +398,7 @@ __global__ __launch_bounds__(256) void wgrad_conv2d_f32_kernel(const float* __re
         }
         __syncthreads();
     }
+    if constexpr (DET) dwp += (long long)blockIdx.z * a.Cout * a.Kpad;
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
         const int k = k0 + n * 16 + (lane & 15);
@@ -346,7 +406,11 @@ __global__ __launch_bounds__(256) void wgrad_conv2d_f32_kernel(const float* __re
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int co = co0 + wave * 16 + (lane >> 4) * 4 + e;
-            if (co < a.Cout) atomicAdd(dwp + (long long)co * a.Kpad + k, acc[n][e]);
+            if constexpr (DET) {
+                if (co < a.Cout) dwp[(long long)co * a.Kpad + k] = acc[n][e];
+            } else {
+                if (co < a.Cout) atomicAdd(dwp + (long long)co * a.Kpad + k, acc[n][e]);
+            }
         }
     }
 }
@@ -356,7 +420,7 @@ __global__ __launch_bounds__(256) void wgrad_conv2d_f32_kernel(const float* __re
 // bound by instruction issue, not by its matrix cores (profiles/r03_wgrad_experiments.txt) -- and the pixel coordinates of a thread's rows
 // advance incrementally instead of by a 64-bit division per row and chunk.  Same arithmetic: fp32 MFMA 16x16x4 over the pixels in order,
 // partial tiles added with fp32 atomics.
-template <int BMT, int BNT>      // tile = (64 BMT) output channels x (64 BNT) K columns; waves 2 x 2
+template <int BMT, int BNT, bool DET = false>      // tile = (64 BMT) output channels x (64 BNT) K columns; waves 2 x 2
 __global__ __launch_bounds__(256) void wgrad_conv2d_f32_wide_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                     float* __restrict__ dwp, const Wg2 a) {
     constexpr int KT = 32, BM = 64 * BMT, BN = 64 * BNT, LDY = BM + 4, LDX = BN + 4;
@@ -441,6 +505,7 @@ __global__ __launch_bounds__(256) void wgrad_conv2d_f32_wide_kernel(const float*
         }
         __syncthreads();
     }
+    if constexpr (DET) dwp += (long long)blockIdx.z * a.Cout * a.Kpad;
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -450,23 +515,56 @@ __global__ __launch_bounds__(256) void wgrad_conv2d_f32_wide_kernel(const float*
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int co = co0 + wm * (32 * BMT) + i * 16 + (lane >> 4) * 4 + e;
-                if (co < a.Cout) atomicAdd(dwp + (long long)co * a.Kpad + k, acc[i][j][e]);
+                if constexpr (DET) {
+                    if (co < a.Cout) dwp[(long long)co * a.Kpad + k] = acc[i][j][e];
+                } else {
+                    if (co < a.Cout) atomicAdd(dwp + (long long)co * a.Kpad + k, acc[i][j][e]);
+                }
             }
         }
 }
 
-template <int BMT, int BNT>
-static int launch_wgrad32_wide(const float* dy, const float* x, float* dw, Wg2 a, int Cout, hipStream_t s) {
-    const int tiles = cdiv(a.Kpad, 64 * BNT) * cdiv(Cout, 64 * BMT);
-    long long splits = (768 + tiles - 1) / tiles;
-    const long long max_splits = (a.M + 255) / 256;
+// The launch form of a shape and its pixel split -- shared by the launch, the deterministic launch and its host-only plan query.
+// form 0: 64 x 64 tiles; 1 / 2 / 3: the wide kernel <2,2> / <1,2> / <2,1>.  Wider tiles where the channel counts allow AND the launch still has >= 2
+// workgroups per CU (each pixel split covers >= 256 pixels: a small batch has few of them -- ResNet-50 at batch 8: 9.6 ms with the 64 x 64 kernel
+// everywhere, 10.2 with the wide tiles); the 64 x 64 kernel: the narrowest layers, small batches
+static int wgrad32_form(Wg2& a, int Cout, long long* splits_out) {
+    const long long max_splits = (a.M + 255) / 256;             // at least 256 rows per split
+    auto fills = [&](int bm, int bn) { return (long long)cdiv(a.Kpad, bn) * cdiv(Cout, bm) * max_splits >= 512; };
+    int form = 0, bm = 64, bn = 64;
+    if (Cout > 64 && a.Kpad > 64 && fills(128, 128)) { form = 1; bm = 128; bn = 128; }
+    else if (a.Kpad >= 128 && fills(64, 128)) { form = 2; bn = 128; }
+    else if (Cout > 64 && fills(128, 64)) { form = 3; bm = 128; }
+    const int tiles = cdiv(a.Kpad, bn) * cdiv(Cout, bm);
+    long long splits = ((form ? 768 : 1024) + tiles - 1) / tiles;   // 64 x 64: ~4 workgroups per CU in total
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     a.rows_per_split = ((a.M + splits - 1) / splits + 31) / 32 * 32;
-    splits = (a.M + a.rows_per_split - 1) / a.rows_per_split;
-    hipLaunchKernelGGL((wgrad_conv2d_f32_wide_kernel<BMT, BNT>), dim3(cdiv(a.Kpad, 64 * BNT), cdiv(Cout, 64 * BMT), (unsigned)splits), dim3(256), 0, s, dy, x,
-                       dw, a);
+    *splits_out = (a.M + a.rows_per_split - 1) / a.rows_per_split;
+    return form;
+}
+
+template <bool DET>
+static int launch_wgrad32(const float* dy, const float* x, float* dw, Wg2 a, int Cout, hipStream_t s) {
+    long long splits;
+    const int form = wgrad32_form(a, Cout, &splits);
+    const int bm = (form == 1 || form == 3) ? 128 : 64, bn = (form == 1 || form == 2) ? 128 : 64;
+    const dim3 grid(cdiv(a.Kpad, bn), cdiv(Cout, bm), (unsigned)splits);
+    if (form == 1) hipLaunchKernelGGL((wgrad_conv2d_f32_wide_kernel<2, 2, DET>), grid, dim3(256), 0, s, dy, x, dw, a);
+    else if (form == 2) hipLaunchKernelGGL((wgrad_conv2d_f32_wide_kernel<1, 2, DET>), grid, dim3(256), 0, s, dy, x, dw, a);
+    else if (form == 3) hipLaunchKernelGGL((wgrad_conv2d_f32_wide_kernel<2, 1, DET>), grid, dim3(256), 0, s, dy, x, dw, a);
+    else hipLaunchKernelGGL(wgrad_conv2d_f32_kernel<DET>, grid, dim3(256), 0, s, dy, x, dw, a);
     return mt4_check_launch();
+}
+
+static void wgrad32_args(Wg2& a, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo, int32_t Cout, int32_t KH, int32_t KW, int32_t stride_h,
+                         int32_t stride_w, int32_t pad_h, int32_t pad_w, int32_t dil_h, int32_t dil_w) {
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.KH = KH; a.KW = KW; a.sh = stride_h; a.sw = stride_w;
+    a.ph = pad_h; a.pw = pad_w; a.dh = dil_h; a.dw = dil_w;
+    a.Kpad = (int)mt4_conv_packed_k(Cin, KH, KW, MT4_F32);
+    a.tapw = ((Cin * 4 + 15) / 16) * 4;
+    a.M = (long long)B * Ho * Wo;
+    a.rows_per_split = 0;
 }
 
 extern "C" int mt4_wgrad_conv2d_f32(const float* dy, const float* x, float* dw_packed_zeroed, int32_t B, int32_t H, int32_t W, int32_t Cin,
@@ -477,32 +575,44 @@ extern "C" int mt4_wgrad_conv2d_f32(const float* dy, const float* x, float* dw_p
         return MT4_EINVAL;
     if (Cin % 4 || Cout % 4 || (((uintptr_t)dy | (uintptr_t)x) & 15)) return MT4_EALIGN;
     Wg2 a;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.KH = KH; a.KW = KW; a.sh = stride_h; a.sw = stride_w;
-    a.ph = pad_h; a.pw = pad_w; a.dh = dil_h; a.dw = dil_w;
-    a.Kpad = (int)mt4_conv_packed_k(Cin, KH, KW, MT4_F32);
-    a.tapw = ((Cin * 4 + 15) / 16) * 4;
-    a.M = (long long)B * Ho * Wo;
-    // wider tiles where the channel counts allow AND the launch still has >= 2 workgroups per CU (each pixel split covers >= 256 pixels: a small
-    // batch has few of them -- ResNet-50 at batch 8: 9.6 ms with the 64 x 64 kernel everywhere, 10.2 with the wide tiles);
-    // the 64 x 64 kernel below: the narrowest layers, small batches
-    {
-        hipStream_t s = (hipStream_t)stream;
-        const long long max_splits = (a.M + 255) / 256;
-        auto fills = [&](int bm, int bn) { return (long long)cdiv(a.Kpad, bn) * cdiv(Cout, bm) * max_splits >= 512; };
-        if (Cout > 64 && a.Kpad > 64 && fills(128, 128)) return launch_wgrad32_wide<2, 2>(dy, x, dw_packed_zeroed, a, Cout, s);
-        if (a.Kpad >= 128 && fills(64, 128)) return launch_wgrad32_wide<1, 2>(dy, x, dw_packed_zeroed, a, Cout, s);
-        if (Cout > 64 && fills(128, 64)) return launch_wgrad32_wide<2, 1>(dy, x, dw_packed_zeroed, a, Cout, s);
-    }
-    const int tiles = cdiv(a.Kpad, 64) * cdiv(Cout, 64);
-    long long splits = (1024 + tiles - 1) / tiles;             // ~4 workgroups per CU in total
-    const long long max_splits = (a.M + 255) / 256;             // at least 256 rows per split
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    a.rows_per_split = ((a.M + splits - 1) / splits + 31) / 32 * 32;
-    splits = (a.M + a.rows_per_split - 1) / a.rows_per_split;
-    hipLaunchKernelGGL(wgrad_conv2d_f32_kernel, dim3(cdiv(a.Kpad, 64), cdiv(Cout, 64), (unsigned)splits), dim3(256), 0, (hipStream_t)stream, dy, x,
-                       dw_packed_zeroed, a);
-    return mt4_check_launch();
+    wgrad32_args(a, B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+    return launch_wgrad32<false>(dy, x, dw_packed_zeroed, a, Cout, (hipStream_t)stream);
+}
+
+extern "C" int mt4_wgrad_conv2d_det_plan(int32_t B, int32_t Ho, int32_t Wo, int32_t Cout, int32_t Cin, int32_t KH, int32_t KW, int32_t* form, int32_t* nparts,
+                                         int64_t* part_elems, int64_t* ws_bytes) {
+    if (B <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || Cin <= 0 || KH <= 0 || KW <= 0) return MT4_EINVAL;
+    if (Cin % 4 || Cout % 4) return MT4_EALIGN;
+    Wg2 a;
+    wgrad32_args(a, B, 1, 1, Cin, Ho, Wo, Cout, KH, KW, 1, 1, 0, 0, 1, 1);      // (the form and the split depend on the output pixels and the channels alone)
+    long long splits;
+    const int f = wgrad32_form(a, Cout, &splits);
+    if (form) *form = f;
+    if (nparts) *nparts = (int32_t)splits;
+    if (part_elems) *part_elems = (long long)Cout * a.Kpad;
+    if (ws_bytes) *ws_bytes = splits * Cout * a.Kpad * (long long)sizeof(float);
+    return MT4_OK;
+}
+
+// fold order (the contract): parts z = 0 .. nparts-1 (ascending ranges of the B*Ho*Wo output pixels, rows_per_split each) front to back; the sum is then
+// ADDED to dw_packed (accumulate != 0) or stored
+extern "C" int mt4_wgrad_conv2d_det_f32(const float* dy, const float* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho,
+                                        int32_t Wo, int32_t Cout, int32_t KH, int32_t KW, int32_t stride_h, int32_t stride_w, int32_t pad_h,
+                                        int32_t pad_w, int32_t dil_h, int32_t dil_w, int32_t accumulate, float* ws, int64_t ws_bytes, void* stream) {
+    mt4_clear_error();
+    if (!dy || !x || !dw_packed || !ws || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || KH <= 0 || KW <= 0)
+        return MT4_EINVAL;
+    if (Cin % 4 || Cout % 4 || (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)ws) & 15)) return MT4_EALIGN;
+    Wg2 a;
+    wgrad32_args(a, B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+    long long splits;
+    Wg2 probe = a;
+    (void)wgrad32_form(probe, Cout, &splits);
+    const long long pe = (long long)Cout * a.Kpad;
+    if (ws_bytes < splits * pe * (long long)sizeof(float)) return MT4_EINVAL;
+    const int lc = launch_wgrad32<true>(dy, x, ws, a, Cout, (hipStream_t)stream);
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_f32(ws, (int32_t)splits, pe, pe, dw_packed, accumulate, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ pooling backward
@@ -543,6 +653,59 @@ extern "C" int mt4_maxpool3x3s2_bwd_f32(const float* x, const float* dy, float* 
     return mt4_check_launch();
 }
 
+// The same gradient in gather form, no atomics and no zeroing (modelled on maxpool3x3s2_bwd_bf16_kernel): a thread owns 4 channels of one INPUT pixel
+// and adds the gradients of the at most four windows whose first maximum it is, in ascending (ho, wo) order -- a fixed order, so the sum does not
+// depend on which workgroup runs first.  This pixel is a window's first maximum in a channel iff no EARLIER position of the window holds a value >= its
+// own and no LATER one a value > its own.
+__global__ void maxpool3x3s2_bwd_gather_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx, int B, int H, int W, int C,
+                                               int Ho, int Wo) {
+    const int CV = C >> 2;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)B * H * W * CV) return;
+    const int cv = (int)(i % CV);
+    long long r = i / CV;
+    const int w = (int)(r % W);
+    r /= W;
+    const int h = (int)(r % H), b = (int)(r / H);
+    const float4 o4 = *(const float4*)(x + (((long long)b * H + h) * W + w) * C + cv * 4);
+    const float own[4] = {o4.x, o4.y, o4.z, o4.w};
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int ho = h >> 1; ho <= ((h + 1) >> 1) && ho < Ho; ++ho)
+        for (int wo = w >> 1; wo <= ((w + 1) >> 1) && wo < Wo; ++wo) {
+            unsigned win = 0xfu;
+            for (int kh = 0; kh < 3; ++kh) {
+                const int hh = 2 * ho - 1 + kh;
+                if ((unsigned)hh >= (unsigned)H) continue;
+                for (int kw = 0; kw < 3; ++kw) {
+                    const int ww = 2 * wo - 1 + kw;
+                    if ((unsigned)ww >= (unsigned)W || (hh == h && ww == w)) continue;
+                    const float4 v4 = *(const float4*)(x + (((long long)b * H + hh) * W + ww) * C + cv * 4);
+                    const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+                    const bool before = hh < h || (hh == h && ww < w);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (before ? v[e] >= own[e] : v[e] > own[e]) win &= ~(1u << e);
+                }
+            }
+            const float4 g4 = *(const float4*)(dy + (((long long)b * Ho + ho) * Wo + wo) * C + cv * 4);
+            const float g[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (win & (1u << e)) acc[e] += g[e];
+        }
+    *(float4*)(dx + (((long long)b * H + h) * W + w) * C + cv * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+}
+
+extern "C" int mt4_maxpool3x3s2_bwd_gather_f32(const float* x, const float* dy, float* dx, int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
+    mt4_clear_error();
+    if (!x || !dy || !dx || B <= 0 || H <= 0 || W <= 0 || C <= 0) return MT4_EINVAL;
+    if (C % 4 || (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15)) return MT4_EALIGN;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const long long n = (long long)B * H * W * (C >> 2);
+    hipLaunchKernelGGL(maxpool3x3s2_bwd_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, B, H, W, C, Ho, Wo);
+    return mt4_check_launch();
+}
+
 // AdaptiveAvgPool2d(1) backward: dx[b][p][c] = dfeat[b][c] / HW
 __global__ void avgpool_bwd_kernel(const float* __restrict__ df, float* __restrict__ dx, int HW, int C, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -565,6 +728,8 @@ extern "C" int mt4_avgpool_bwd_f32(const float* dfeat, float* dx, int32_t B, int
 // dy = ((1-z) - lw + lw sigmoid(y)) * col_scale.  pos_weight NULL = 1.
 // 256 threads = 64 columns x 4 row groups over a slab of 64 rows; the column sums of a slab meet in LDS and leave as ONE atomic per
 // column (a step of the MS-TCT teacher has M = 31 x 256 rows: a thread per column looping over all rows took 4 ms there).
+// DET (mt4_bce_logits_pw_det_f32): `col_loss` is the workspace, row slab y STORES its N sums into part y = col_loss + y * N (folded in y order afterwards).
+template <bool DET = false>
 __global__ __launch_bounds__(256) void bce_pw_kernel(const float* __restrict__ y, const float* __restrict__ z, const float* __restrict__ pw,
                                                      const float* __restrict__ col_scale, float* __restrict__ dy, float* __restrict__ col_loss, int M,
                                                      int N, int ld_y, int ld_dy) {
@@ -584,7 +749,11 @@ __global__ __launch_bounds__(256) void bce_pw_kernel(const float* __restrict__ y
     }
     part[rg][c] = ls;
     __syncthreads();
-    if (rg == 0 && n < N) atomicAdd(col_loss + n, (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]));
+    if (rg == 0 && n < N) {
+        const float t = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
+        if constexpr (DET) col_loss[(long long)blockIdx.y * N + n] = t;
+        else atomicAdd(col_loss + n, t);
+    }
 }
 
 extern "C" int mt4_bce_logits_pw_f32(const float* y, const float* z, const float* pos_weight, const float* col_scale, float* dy, float* col_loss,
@@ -592,13 +761,40 @@ extern "C" int mt4_bce_logits_pw_f32(const float* y, const float* z, const float
     mt4_clear_error();
     if (!y || !z || !col_scale || !dy || !col_loss || M <= 0 || N <= 0 || ld_y < N || ld_dy < N) return MT4_EINVAL;
     if (cdiv(M, 64) > 65535) return MT4_EUNSUPPORTED;
-    hipLaunchKernelGGL(bce_pw_kernel, dim3(cdiv(N, 64), cdiv(M, 64)), dim3(256), 0, (hipStream_t)stream, y, z, pos_weight, col_scale, dy, col_loss, M, N,
+    hipLaunchKernelGGL(bce_pw_kernel<false>, dim3(cdiv(N, 64), cdiv(M, 64)), dim3(256), 0, (hipStream_t)stream, y, z, pos_weight, col_scale, dy, col_loss, M, N,
                        ld_y, ld_dy);
     return mt4_check_launch();
 }
 
+extern "C" int mt4_bce_logits_pw_det_plan(int32_t M, int32_t N, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
+    if (M <= 0 || N <= 0) return MT4_EINVAL;
+    if (cdiv(M, 64) > 65535) return MT4_EUNSUPPORTED;
+    if (form) *form = 0;
+    if (nparts) *nparts = cdiv(M, 64);
+    if (part_elems) *part_elems = N;
+    if (ws_bytes) *ws_bytes = (long long)cdiv(M, 64) * N * (long long)sizeof(float);
+    return MT4_OK;
+}
+
+// fold order (the contract): 64-row slabs y = 0 .. nparts-1 front to back (a slab's sum: four row groups r = m % 4 of ascending rows, (g0 + g1) + (g2 + g3)),
+// then ADDED to col_loss
+extern "C" int mt4_bce_logits_pw_det_f32(const float* y, const float* z, const float* pos_weight, const float* col_scale, float* dy, float* col_loss,
+                                         int32_t M, int32_t N, int32_t ld_y, int32_t ld_dy, float* ws, int64_t ws_bytes, void* stream) {
+    mt4_clear_error();
+    if (!y || !z || !col_scale || !dy || !col_loss || !ws || M <= 0 || N <= 0 || ld_y < N || ld_dy < N) return MT4_EINVAL;
+    if (cdiv(M, 64) > 65535) return MT4_EUNSUPPORTED;
+    if (ws_bytes < (long long)cdiv(M, 64) * N * (long long)sizeof(float)) return MT4_EINVAL;
+    hipLaunchKernelGGL(bce_pw_kernel<true>, dim3(cdiv(N, 64), cdiv(M, 64)), dim3(256), 0, (hipStream_t)stream, y, z, pos_weight, col_scale, dy, ws, M, N, ld_y,
+                       ld_dy);
+    const int lc = mt4_check_launch();
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_f32(ws, cdiv(M, 64), N, N, col_loss, 1, stream);
+}
+
 // DistillKL (run.py:284-295): loss += T^2/B * sum_k p_t (log p_t - log_softmax(y_s/T)),  p_t = softmax(sigmoid(t_pred)/T);
 // dy_s[b][k] (+)= scale * T/B * (softmax(y_s/T) - p_t).   One wave per row, K <= 128 (2 columns per lane).
+// DET (mt4_distill_kl_det_f32): `loss` is the workspace, row b STORES its term into part b = loss[b] (one element a part, folded in row order afterwards).
+template <bool DET = false>
 __global__ void distill_kl_kernel(const float* __restrict__ ys, const float* __restrict__ tp, float* __restrict__ dys, float* __restrict__ loss, int B,
                                   int K, int ld_y, int ld_dy, float temp, float scale, int accumulate) {
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -633,19 +829,47 @@ __global__ void distill_kl_kernel(const float* __restrict__ ys, const float* __r
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) l += __shfl_xor(l, o);
-    if (lane == 0) atomicAdd(loss, l * temp * temp / (float)B);
+    if (lane == 0) {
+        if constexpr (DET) loss[b] = l * temp * temp / (float)B;
+        else atomicAdd(loss, l * temp * temp / (float)B);
+    }
 }
 
 extern "C" int mt4_distill_kl_f32(const float* y_s, const float* t_pred, float* dy_s, float* loss, int32_t B, int32_t K, int32_t ld_y, int32_t ld_dy,
                                   float temp, float grad_scale, int32_t accumulate, void* stream) {
     mt4_clear_error();
     if (!y_s || !t_pred || !dy_s || !loss || B <= 0 || K <= 0 || K > 128 || ld_y < K || ld_dy < K) return MT4_EINVAL;
-    hipLaunchKernelGGL(distill_kl_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, y_s, t_pred, dy_s, loss, B, K, ld_y, ld_dy, temp, grad_scale,
+    hipLaunchKernelGGL(distill_kl_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, y_s, t_pred, dy_s, loss, B, K, ld_y, ld_dy, temp, grad_scale,
                        accumulate);
     return mt4_check_launch();
 }
 
+// the two scalar losses: one part element per workgroup (DistillKL: per batch row; MSE: per 256 elements), folded in the fixed chunks of mt4_fold_parts_chunked_f32 and ADDED
+// to *loss.  Tiny either way: a batch of 64 rows, 3 x 384 workgroups of the feature MSE.
+extern "C" int mt4_distill_kl_det_plan(int32_t B, int32_t K, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
+    if (B <= 0 || K <= 0 || K > 128) return MT4_EINVAL;
+    if (form) *form = 0;
+    if (nparts) *nparts = B;
+    if (part_elems) *part_elems = 1;
+    if (ws_bytes) *ws_bytes = (long long)B * (long long)sizeof(float);
+    return MT4_OK;
+}
+
+extern "C" int mt4_distill_kl_det_f32(const float* y_s, const float* t_pred, float* dy_s, float* loss, int32_t B, int32_t K, int32_t ld_y, int32_t ld_dy,
+                                      float temp, float grad_scale, int32_t accumulate, float* ws, int64_t ws_bytes, void* stream) {
+    mt4_clear_error();
+    if (!y_s || !t_pred || !dy_s || !loss || !ws || B <= 0 || K <= 0 || K > 128 || ld_y < K || ld_dy < K) return MT4_EINVAL;
+    if (ws_bytes < (long long)B * (long long)sizeof(float)) return MT4_EINVAL;
+    hipLaunchKernelGGL(distill_kl_kernel<true>, dim3(B), dim3(64), 0, (hipStream_t)stream, y_s, t_pred, dy_s, ws, B, K, ld_y, ld_dy, temp, grad_scale,
+                       accumulate);
+    const int lc = mt4_check_launch();
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_chunked_f32(ws, B, 1, 1, loss, 1, stream);
+}
+
 // MSELoss (mean): loss += sum (a-b)^2 / n ; da = scale * 2 (a-b) / n
+// DET (mt4_mse_det_f32): `loss` is the workspace, workgroup w STORES its sum into part w = loss[w].
+template <bool DET = false>
 __global__ void mse_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ da, float* __restrict__ loss, long long n,
                            float scale) {
     __shared__ float red[4];
@@ -660,14 +884,38 @@ __global__ void mse_kernel(const float* __restrict__ a, const float* __restrict_
     for (int o = 32; o > 0; o >>= 1) l += __shfl_xor(l, o);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = l;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss, red[0] + red[1] + red[2] + red[3]);
+    if (threadIdx.x == 0) {
+        if constexpr (DET) loss[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+        else atomicAdd(loss, red[0] + red[1] + red[2] + red[3]);
+    }
 }
 
 extern "C" int mt4_mse_f32(const float* a, const float* b, float* da, float* loss, int64_t n, float grad_scale, void* stream) {
     mt4_clear_error();
     if (!a || !b || !da || !loss || n <= 0) return MT4_EINVAL;
-    hipLaunchKernelGGL(mse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, da, loss, (long long)n, grad_scale);
+    hipLaunchKernelGGL(mse_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, da, loss, (long long)n, grad_scale);
     return mt4_check_launch();
+}
+
+extern "C" int mt4_mse_det_plan(int64_t n, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
+    if (n <= 0 || (n + 255) / 256 > 0x7fffffff) return MT4_EINVAL;
+    if (form) *form = 0;
+    if (nparts) *nparts = (int32_t)((n + 255) / 256);
+    if (part_elems) *part_elems = 1;
+    if (ws_bytes) *ws_bytes = (n + 255) / 256 * (long long)sizeof(float);
+    return MT4_OK;
+}
+
+extern "C" int mt4_mse_det_f32(const float* a, const float* b, float* da, float* loss, int64_t n, float grad_scale, float* ws, int64_t ws_bytes,
+                               void* stream) {
+    mt4_clear_error();
+    if (!a || !b || !da || !loss || !ws || n <= 0 || (n + 255) / 256 > 0x7fffffff) return MT4_EINVAL;
+    const long long wgs = (n + 255) / 256;
+    if (ws_bytes < wgs * (long long)sizeof(float)) return MT4_EINVAL;
+    hipLaunchKernelGGL(mse_kernel<true>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, a, b, da, ws, (long long)n, grad_scale);
+    const int lc = mt4_check_launch();
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_chunked_f32(ws, (int32_t)wgs, 1, 1, loss, 1, stream);
 }
 
 // KD mixing backward (forward: mt4_kd_mix).  u_n = s a_n, a = softmax_n(l), l_n = s tau_n / sqrt(C), tau_n = sum_d tea_n[b][d].

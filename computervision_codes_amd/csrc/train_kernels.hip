@@ -9,6 +9,10 @@
 // v_mfma_f32_16x16x4_f32 (lane l holds A[i = l&15][k = l>>4] / B[k = l>>4][j = l&15]): fragments are read straight
 // from row-major [time][channel] LDS tiles, no transpose.  One workgroup = a 64(co) x 64(k) tile of dW, looping over
 // time in chunks of 32 rows; wave w owns output rows [16w, 16w+16) x 64 columns.
+// DET (mt4_wgrad_conv1d_det_f32): `dw` is the workspace, split z STORES its tile into part z = dw + z * (Cout * Kpad (+ Cout with gb)) -- every element
+// of the part, the packed layout's padding columns as the zeros their operand columns are -- and the column sums of dY behind the part's weights; gb is
+// only a flag there.  mt4_fold_parts_f32 adds the parts in z order afterwards.
+template <bool DET>
 __global__ __launch_bounds__(256) void wgrad_conv1d_f32_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                float* __restrict__ dw, int B, int T, int Cout, int Cin, int taps,
                                                                int dil, int pad, int Kpad, int accumulate, long long rows_per_split,
@@ -76,6 +80,7 @@ __global__ __launch_bounds__(256) void wgrad_conv1d_f32_kernel(const float* __re
         }
         __syncthreads();
     }
+    if constexpr (DET) dw += (long long)blockIdx.z * ((long long)Cout * Kpad + (gb != nullptr ? Cout : 0));
     // D[i = co][j = k]: lane holds column j = lane&15, rows 4*(lane>>4) + e
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
@@ -86,7 +91,8 @@ __global__ __launch_bounds__(256) void wgrad_conv1d_f32_kernel(const float* __re
             const int co = co0 + wave * 16 + (lane >> 4) * 4 + e;
             if (co >= Cout) continue;
             float* p = dw + (long long)co * Kpad + k;
-            if (gridDim.z > 1) atomicAdd(p, acc[n][e]);
+            if constexpr (DET) *p = acc[n][e];
+            else if (gridDim.z > 1) atomicAdd(p, acc[n][e]);
             else *p = accumulate ? *p + acc[n][e] : acc[n][e];
         }
     }
@@ -98,7 +104,8 @@ __global__ __launch_bounds__(256) void wgrad_conv1d_f32_kernel(const float* __re
             float t = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) t += red[r * 64 + tid];
-            atomicAdd(gb + co0 + tid, t);
+            if constexpr (DET) dw[(long long)Cout * Kpad + co0 + tid] = t;
+            else atomicAdd(gb + co0 + tid, t);
         }
     }
 }
@@ -121,31 +128,81 @@ static inline void zero_f32(float* p, long long n, hipStream_t s) {
     hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, s, p, n);
 }
 
+// the time split of a conv1d weight gradient: `splits` workgroups per dW tile, each over `rps` rows (a multiple of the 32-row chunk)
+static void wgrad_conv1d_split(long long M, int Kpad, int Cout, long long* splits_out, long long* rps_out) {
+    const long long max_splits = (M + 255) / 256;              // at least 256 rows per split
+    const int tiles = cdiv(Kpad, 64) * cdiv(Cout, 64);
+    long long splits = (1024 + tiles - 1) / tiles;            // ~4 workgroups per CU in total
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    const long long rps = ((M + splits - 1) / splits + 31) / 32 * 32;
+    *splits_out = (M + rps - 1) / rps;
+    *rps_out = rps;
+}
+
 extern "C" int mt4_wgrad_conv1d_f32(const float* dy, const float* x, float* dw_packed, int32_t B, int32_t T, int32_t Cout, int32_t Cin,
                                     int32_t taps, int32_t dil, int32_t pad, int32_t accumulate, float* bias_grad, void* stream) {
     mt4_clear_error();
     if (!dy || !x || !dw_packed || B <= 0 || T <= 0 || Cout <= 0 || Cin <= 0 || taps <= 0 || dil <= 0 || pad < 0) return MT4_EINVAL;
     if (Cin % 4 || Cout % 4 || (((uintptr_t)dy | (uintptr_t)x) & 15)) return MT4_EALIGN;
     const int Kpad = (int)mt4_conv_packed_k(Cin, 1, taps, MT4_F32);
-    const long long M = (long long)B * T;
-    const long long max_splits = (M + 255) / 256;              // at least 256 rows per split
     hipStream_t s = (hipStream_t)stream;
-    const int tiles = cdiv(Kpad, 64) * cdiv(Cout, 64);
-    long long splits = (1024 + tiles - 1) / tiles;            // ~4 workgroups per CU in total
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    const long long rps = ((M + splits - 1) / splits + 31) / 32 * 32;
-    splits = (M + rps - 1) / rps;
+    long long splits, rps;
+    wgrad_conv1d_split((long long)B * T, Kpad, Cout, &splits, &rps);
     if (splits > 1 && !accumulate) zero_f32(dw_packed, (long long)Cout * Kpad, s);
     const dim3 grid(cdiv(Kpad, 64), cdiv(Cout, 64), (unsigned)splits);
-    hipLaunchKernelGGL(wgrad_conv1d_f32_kernel, grid, dim3(256), 0, s, dy, x, dw_packed, B, T, Cout, Cin, taps, dil, pad, Kpad, accumulate, rps, bias_grad);
+    hipLaunchKernelGGL(wgrad_conv1d_f32_kernel<false>, grid, dim3(256), 0, s, dy, x, dw_packed, B, T, Cout, Cin, taps, dil, pad, Kpad, accumulate, rps, bias_grad);
     return mt4_check_launch();
+}
+
+extern "C" int mt4_wgrad_conv1d_det_plan(int32_t B, int32_t T, int32_t Cout, int32_t Cin, int32_t taps, int32_t with_bias, int32_t* form, int32_t* nparts,
+                                         int64_t* part_elems, int64_t* ws_bytes) {
+    if (B <= 0 || T <= 0 || Cout <= 0 || Cin <= 0 || taps <= 0) return MT4_EINVAL;
+    if (Cin % 4 || Cout % 4) return MT4_EALIGN;
+    const int Kpad = (int)mt4_conv_packed_k(Cin, 1, taps, MT4_F32);
+    long long splits, rps;
+    wgrad_conv1d_split((long long)B * T, Kpad, Cout, &splits, &rps);
+    const long long pe = (long long)Cout * Kpad + (with_bias ? Cout : 0);
+    if (form) *form = 0;                                     // one launch form: 64 x 64 tiles of dW, the rows split over gridDim.z
+    if (nparts) *nparts = (int32_t)splits;
+    if (part_elems) *part_elems = pe;
+    if (ws_bytes) *ws_bytes = splits * pe * (long long)sizeof(float);
+    return MT4_OK;
+}
+
+extern "C" int mt4_wgrad_conv1d_det_f32(const float* dy, const float* x, float* dw_packed, int32_t B, int32_t T, int32_t Cout, int32_t Cin, int32_t taps,
+                                        int32_t dil, int32_t pad, int32_t accumulate, float* bias_grad, float* ws, int64_t ws_bytes, void* stream) {
+    mt4_clear_error();
+    if (!dy || !x || !dw_packed || !ws || B <= 0 || T <= 0 || Cout <= 0 || Cin <= 0 || taps <= 0 || dil <= 0 || pad < 0) return MT4_EINVAL;
+    if (Cin % 4 || Cout % 4 || (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)ws) & 15)) return MT4_EALIGN;
+    int32_t nparts;
+    int64_t pe, need;
+    const int rc = mt4_wgrad_conv1d_det_plan(B, T, Cout, Cin, taps, bias_grad != nullptr, nullptr, &nparts, &pe, &need);
+    if (rc != MT4_OK) return rc;
+    if (ws_bytes < need) return MT4_EINVAL;
+    const int Kpad = (int)mt4_conv_packed_k(Cin, 1, taps, MT4_F32);
+    hipStream_t s = (hipStream_t)stream;
+    long long splits, rps;
+    wgrad_conv1d_split((long long)B * T, Kpad, Cout, &splits, &rps);
+    const dim3 grid(cdiv(Kpad, 64), cdiv(Cout, 64), (unsigned)splits);
+    hipLaunchKernelGGL(wgrad_conv1d_f32_kernel<true>, grid, dim3(256), 0, s, dy, x, ws, B, T, Cout, Cin, taps, dil, pad, Kpad, 0, rps, bias_grad);
+    const int lc = mt4_check_launch();
+    if (lc != MT4_OK) return lc;
+    // fold order (the contract): parts z = 0 .. nparts-1 (ascending row ranges) summed front to back, then added to dW (accumulate) / stored, and
+    // ADDED to bias_grad -- one launch where the bias gradient lies right behind dW and both accumulate (the trainers' flat gradient buffer)
+    const long long nw = (long long)Cout * Kpad;
+    if (bias_grad && accumulate && bias_grad == dw_packed + nw) return mt4_fold_parts_f32(ws, nparts, pe, pe, dw_packed, 1, stream);
+    const int fc = mt4_fold_parts_f32(ws, nparts, nw, pe, dw_packed, accumulate, stream);
+    if (fc != MT4_OK || !bias_grad) return fc;
+    return mt4_fold_parts_f32(ws + nw, nparts, Cout, pe, bias_grad, 1, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ column sums (bias gradient)
 // out[c] (+)= sum_m x[m][c].  Workgroups = (64-column blocks) x (row slabs), a thread sums a strided set of rows, LDS combine, one
 // fp32 atomic per column and slab into `out` (zeroed first unless accumulating).  (One workgroup per 64 columns -- 8 workgroups for
 // the TCN's 512 channels -- was 21 % of the training step: 82 launches of ~50 us each.)
+// DET (mt4_colsum_det_f32): `out` is the workspace, slab y STORES its C sums into part y = out + y * C; mt4_fold_parts_f32 adds the slabs in y order.
+template <bool DET>
 __global__ __launch_bounds__(256) void colsum_f32_kernel(const float* __restrict__ x, float* __restrict__ out, long long M, int C, int ld) {
     __shared__ float red[4][64];
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), w = threadIdx.x >> 6;
@@ -154,7 +211,18 @@ __global__ __launch_bounds__(256) void colsum_f32_kernel(const float* __restrict
         for (long long m = (long long)blockIdx.y * 4 + w; m < M; m += (long long)gridDim.y * 4) s += x[m * ld + c];
     red[w][threadIdx.x & 63] = s;
     __syncthreads();
-    if (w == 0 && c < C) atomicAdd(out + c, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+    if (w == 0 && c < C) {
+        const float t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        if constexpr (DET) out[(long long)blockIdx.y * C + c] = t;
+        else atomicAdd(out + c, t);
+    }
+}
+
+static long long colsum_slabs(long long M, int C) {
+    long long slabs = (M + 63) / 64;                     // >= 16 rows per wave and slab
+    const long long cap = (1024 + cdiv(C, 64) - 1) / cdiv(C, 64);
+    if (slabs > cap) slabs = cap;
+    return slabs < 1 ? 1 : slabs;
 }
 
 extern "C" int mt4_colsum_f32(const float* x, float* out, int64_t M, int32_t C, int32_t ld, int32_t accumulate, void* stream) {
@@ -162,17 +230,39 @@ extern "C" int mt4_colsum_f32(const float* x, float* out, int64_t M, int32_t C, 
     if (!x || !out || M <= 0 || C <= 0 || ld < C) return MT4_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (!accumulate) zero_f32(out, C, s);      // (any float-aligned `out`: bias slices of a flat gradient buffer)
-    long long slabs = (M + 63) / 64;                     // >= 16 rows per wave and slab
-    const long long cap = (1024 + cdiv(C, 64) - 1) / cdiv(C, 64);
-    if (slabs > cap) slabs = cap;
-    if (slabs < 1) slabs = 1;
-    hipLaunchKernelGGL(colsum_f32_kernel, dim3(cdiv(C, 64), (unsigned)slabs), dim3(256), 0, s, x, out, (long long)M, C, ld);
+    const long long slabs = colsum_slabs(M, C);
+    hipLaunchKernelGGL(colsum_f32_kernel<false>, dim3(cdiv(C, 64), (unsigned)slabs), dim3(256), 0, s, x, out, (long long)M, C, ld);
     return mt4_check_launch();
+}
+
+extern "C" int mt4_colsum_det_plan(int64_t M, int32_t C, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
+    if (M <= 0 || C <= 0) return MT4_EINVAL;
+    const long long slabs = colsum_slabs(M, C);
+    if (form) *form = 0;
+    if (nparts) *nparts = (int32_t)slabs;
+    if (part_elems) *part_elems = C;
+    if (ws_bytes) *ws_bytes = slabs * C * (long long)sizeof(float);
+    return MT4_OK;
+}
+
+// fold order (the contract): row slabs y = 0 .. nparts-1 (slab y holds the rows m with (m / 4) % nparts == y) front to back, then added to / stored in `out`
+extern "C" int mt4_colsum_det_f32(const float* x, float* out, int64_t M, int32_t C, int32_t ld, int32_t accumulate, float* ws, int64_t ws_bytes,
+                                  void* stream) {
+    mt4_clear_error();
+    if (!x || !out || !ws || M <= 0 || C <= 0 || ld < C) return MT4_EINVAL;
+    const long long slabs = colsum_slabs(M, C);
+    if (ws_bytes < slabs * C * (long long)sizeof(float)) return MT4_EINVAL;
+    hipLaunchKernelGGL(colsum_f32_kernel<true>, dim3(cdiv(C, 64), (unsigned)slabs), dim3(256), 0, (hipStream_t)stream, x, ws, (long long)M, C, ld);
+    const int lc = mt4_check_launch();
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_f32(ws, (int32_t)slabs, C, C, out, accumulate, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ BCE with logits: loss + gradient
 // per element: l = max(y,0) - y z + log1p(exp(-|y|)) ; dy = (sigmoid(y) - z) * col_scale[n]
 // col_loss[n] += sum_m l   (the caller weights and normalises per head: mean over T*K_head, run.py:196-212)
+// DET (mt4_bce_logits_det_f32): `col_loss` is the workspace, slab y STORES its N sums into part y = col_loss + y * N (folded in y order afterwards).
+template <bool DET>
 __global__ __launch_bounds__(256) void bce_logits_kernel(const float* __restrict__ y, const float* __restrict__ z,
                                                          const float* __restrict__ col_scale, float* __restrict__ dy,
                                                          float* __restrict__ col_loss, long long M, int N, int ld_y, int ld_dy) {
@@ -190,18 +280,50 @@ __global__ __launch_bounds__(256) void bce_logits_kernel(const float* __restrict
     }
     red[w][threadIdx.x & 63] = ls;
     __syncthreads();
-    if (w == 0 && n < N) atomicAdd(col_loss + n, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+    if (w == 0 && n < N) {
+        const float t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        if constexpr (DET) col_loss[(long long)blockIdx.y * N + n] = t;
+        else atomicAdd(col_loss + n, t);
+    }
+}
+
+static int bce_logits_slabs(long long M) {
+    const long long gy = (M + 63) / 64;
+    return gy > 64 ? 64 : (int)gy;
 }
 
 extern "C" int mt4_bce_logits_f32(const float* y, const float* z, const float* col_scale, float* dy, float* col_loss, int64_t M, int32_t N,
                                   int32_t ld_y, int32_t ld_dy, void* stream) {
     mt4_clear_error();
     if (!y || !z || !col_scale || !dy || !col_loss || M <= 0 || N <= 0 || ld_y < N || ld_dy < N) return MT4_EINVAL;
-    int gy = (int)((M + 63) / 64);
-    if (gy > 64) gy = 64;
-    hipLaunchKernelGGL(bce_logits_kernel, dim3(cdiv(N, 64), gy), dim3(256), 0, (hipStream_t)stream, y, z, col_scale, dy, col_loss,
+    const int gy = bce_logits_slabs(M);
+    hipLaunchKernelGGL(bce_logits_kernel<false>, dim3(cdiv(N, 64), gy), dim3(256), 0, (hipStream_t)stream, y, z, col_scale, dy, col_loss,
                        (long long)M, N, ld_y, ld_dy);
     return mt4_check_launch();
+}
+
+extern "C" int mt4_bce_logits_det_plan(int64_t M, int32_t N, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
+    if (M <= 0 || N <= 0) return MT4_EINVAL;
+    const int gy = bce_logits_slabs(M);
+    if (form) *form = 0;
+    if (nparts) *nparts = gy;
+    if (part_elems) *part_elems = N;
+    if (ws_bytes) *ws_bytes = (long long)gy * N * (long long)sizeof(float);
+    return MT4_OK;
+}
+
+// fold order (the contract): row slabs y = 0 .. nparts-1 (slab y holds the rows m with (m / 4) % nparts == y) front to back, then ADDED to col_loss
+extern "C" int mt4_bce_logits_det_f32(const float* y, const float* z, const float* col_scale, float* dy, float* col_loss, int64_t M, int32_t N,
+                                      int32_t ld_y, int32_t ld_dy, float* ws, int64_t ws_bytes, void* stream) {
+    mt4_clear_error();
+    if (!y || !z || !col_scale || !dy || !col_loss || !ws || M <= 0 || N <= 0 || ld_y < N || ld_dy < N) return MT4_EINVAL;
+    const int gy = bce_logits_slabs(M);
+    if (ws_bytes < (long long)gy * N * (long long)sizeof(float)) return MT4_EINVAL;
+    hipLaunchKernelGGL(bce_logits_kernel<true>, dim3(cdiv(N, 64), gy), dim3(256), 0, (hipStream_t)stream, y, z, col_scale, dy, ws, (long long)M, N,
+                       ld_y, ld_dy);
+    const int lc = mt4_check_launch();
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_f32(ws, gy, N, N, col_loss, 1, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ SGD (no momentum) and element-wise pieces

@@ -63,6 +63,21 @@ def _flag(*names, **kw):
 _OPERAND_DTYPE = _flag("--operand_dtype", type=str, default="fp32", choices=["fp32", "bf16"],
                        help="bf16: the GEMM operands of the training step in bf16 (Spatial_cnn: the convolutions' activations, gradients and weight copies; "
                             "the transformer stages: operand copies of the nn.Linear GEMMs), master weights, accumulation and sums fp32")
+# --deterministic (not in the reference, which seeds torch and still sums with atomics): declared on EVERY trainer's parser -- the entry points read
+# their flags with parse_known_args, so an undeclared flag would be ignored in silence -- honoured by the trainers named in `_DETERMINISTIC_STAGES`
+# and refused by the others before any model is built (`_deterministic`)
+_DETERMINISTIC = _flag("--deterministic", action="store_true",
+                       help="reproducible training (Spatial_cnn, Temporal_tenco): every sum of the step that crosses workgroups (weight and bias gradients, "
+                            "BatchNorm sums, the max-pool backward, loss sums) is taken from per-workgroup partials folded in a fixed order (mt4_*_det_* + "
+                            "mt4_fold_parts_f32 / _f64) instead of float atomics -- the same seed and inputs give the same losses and the same checkpoint "
+                            "bytes; the BatchNorm statistics come from the separate pass instead of the convolution's epilogue")
+_DETERMINISTIC_STAGES = ("spatial_cnn", "tenco")
+_NOT_DETERMINISTIC = {
+    "spatial_transformer": "the sequence trainers' reductions are not covered yet (csrc/seq_train_kernels.hip: LayerNorm dgamma/dbeta, the "
+                           "relative-position table gradient, the depth-wise conv gradient)",
+    "mstct": "the sequence trainers' reductions are not covered yet (csrc/seq_train_kernels.hip: LayerNorm dgamma/dbeta, the "
+             "relative-position table gradient, the depth-wise conv gradient)",
+}
 _FRAME_TRAIN = [
     _flag("--teacher_feat_version", type=str, default="Q2L"),
     _flag("--teacher_pred_version", type=str, default="Q2LMSTCT"),
@@ -82,6 +97,7 @@ _FRAME_TRAIN = [
     _flag("--temp", type=int, default=4),
     _flag("--pretrain_dir", type=str, default=""),
     _OPERAND_DTYPE,
+    _DETERMINISTIC,
 ]
 # stage -> (the flags every entry point of the stage parses, the flags of its trainer alone), on top of `_common` and -- the trainer --
 # `add_schedule_flags`.  --teacher_dim: the student mixes in the 1536-wide Swin-L feature (`Spatial_cnn/run.py`), the transformer stage's
@@ -97,7 +113,8 @@ _FLAGS = {
                             _FRAME_TRAIN + [_flag("--drop_path_rate", type=float, default=0.1)]),          # `swin_transformer.py:488`
     "mstct": ([_flag("--input_dim", type=int, default=1536),
                _flag("--final_embedding_dim", type=int, default=512)],
-              [_flag("--num_clips", type=int, default=256, help="window length (the reference hard-codes 256, dataloader.py:237)"), _OPERAND_DTYPE]),
+              [_flag("--num_clips", type=int, default=256, help="window length (the reference hard-codes 256, dataloader.py:237)"), _OPERAND_DTYPE,
+               _DETERMINISTIC]),
     # --mask_draw / --subclip (not in the reference) device: the step's random pieces are drawn by HIP kernels from (seed, step) and whole-video
     # steps replay as hipGraphs; host: drawn with torch's generator and uploaded.  reference: `Temporal_tenco/dataloader.py:219-222` sub-clip sampling
     "tenco": ([_flag("--num_layers_PG", default=11, type=int),
@@ -109,7 +126,8 @@ _FLAGS = {
                _flag("--hier", default=False, type=bool),
                _flag("--input_dim", type=int, default=512)],
               [_flag("--mask_draw", choices=("host", "device"), default="host"),
-               _flag("--subclip", choices=("off", "reference"), default="off")]),
+               _flag("--subclip", choices=("off", "reference"), default="off"),
+               _DETERMINISTIC]),
 }
 _LATEST = {"spatial_cnn": "_latest.pth", "spatial_transformer": "_latest.pth", "tenco": "_latest.pth",
            "mstct": "latest.pth"}                            # <stem> + this = the trainer's newest checkpoint; MS-TCT: no underscore (`Temporal_mstct/run.py:268`)
@@ -126,6 +144,16 @@ def _parser(stage: str, train: bool) -> argparse.ArgumentParser:
     for names, kw in own + (train_only if train else []):
         p.add_argument(*names, **kw)
     return p
+
+
+def _deterministic(stage: str, F) -> bool:
+    """--deterministic of a trainer: said once at start where the stage's trainer has the mode, refused (before any model is built) where not"""
+    if not getattr(F, "deterministic", False):
+        return False
+    if stage not in _DETERMINISTIC_STAGES:
+        raise NotImplementedError(f"--deterministic: {_NOT_DETERMINISTIC[stage]}")
+    print("--deterministic: fixed-order sums (per-workgroup partials + mt4_fold_parts_f32 / _f64) in place of float atomics", flush=True)
+    return True
 
 
 def _dtype(name: str) -> torch.dtype:
@@ -488,7 +516,7 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     latest = stem + _LATEST["spatial_cnn"]
     tr = SpatialCnnTrainer(F.network, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay, rates=F.rates, temp=float(F.temp),
                            teacher_dim=F.teacher_dim, loss_type=F.loss_type,
-                           operand_dtype=_dtype(F.operand_dtype))
+                           operand_dtype=_dtype(F.operand_dtype), deterministic=_deterministic("spatial_cnn", F))
     table = shapes.spatial_cnn_shapes(F.network, F.student_dim, F.teacher_dim, F.loss_type)
     sd = synth.fill_from_shapes(table, seed=F.seed)          # no torch.nn init here: deterministic synthetic start
     for src in (F.pretrain_dir, latest):                     # `load_model` (:272-278): keys present in the model, strict=False
@@ -596,7 +624,8 @@ def _tenco_train(F):
         raise NotImplementedError("Temporal_tenco training needs --fpn (Scripts/train_fold1.sh:28): without it the reference's train loop itself fails "
                                   "in its first step (run.py:190,214: .item() on the int 0 that loss_i stays when the model returns no per-component logits)")
     tr = TencoTrainer(F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
-                      hier=bool(getattr(F, "hier", False)))      # --hier True: pooled refinement levels (`network.py:147,154-155`, `run.py:159-179`)
+                      hier=bool(getattr(F, "hier", False)),      # --hier True: pooled refinement levels (`network.py:147,154-155`, `run.py:159-179`)
+                      deterministic=_deterministic("tenco", F))
     from . import shapes, synth
     init = stem + _LATEST["tenco"]
     if os.path.exists(init):
@@ -819,6 +848,7 @@ def _mstct_train(F):
 
     from .mstct_train import NCLS, MstctTrainer, draw_windows
     from . import shapes, synth
+    _deterministic("mstct", F)
     rank, world = _dist()
     lt = F.loss_type
     if lt not in NCLS:
@@ -887,6 +917,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     from .q2l_train import Q2LTrainer
     from . import shapes, synth
     F = _parser("spatial_transformer", True).parse_known_args(argv)[0]
+    _deterministic("spatial_transformer", F)
     if F.loss_type not in ("i", "v", "t", "all"):
         raise ValueError("--loss_type i | v | t | all (`Spatial_transformer/run.py:168-197`)")
     single = F.loss_type != "all"

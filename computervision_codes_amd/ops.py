@@ -6,7 +6,7 @@ import contextvars
 import os
 import ctypes as C
 import functools
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -781,30 +781,148 @@ def kd_mix(s: torch.Tensor, ti: torch.Tensor, tv: torch.Tensor, tt: torch.Tensor
 
 
 # ----------------------------------------------------------------------------------------- training pieces (fp32)
+class DetPlan(NamedTuple):
+    """what a host-only plan query (`mt4_*_det_plan`) says about the deterministic launch of a shape: the launch form, the number of parts a
+    workgroup slot each, the elements of a part (its stride in the workspace) and the workspace bytes = nparts x part_elems x sizeof"""
+    form: int
+    nparts: int
+    part_elems: int
+    bytes: int
+
+
+def _det_plan(fn, what: str, *args) -> DetPlan:
+    form, nparts, pe, nbytes = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+    check(fn(*args, C.byref(form), C.byref(nparts), C.byref(pe), C.byref(nbytes)), what)
+    return DetPlan(form.value, nparts.value, pe.value, nbytes.value)
+
+
+def wgrad_conv1d_plan(batch: int, t: int, cout: int, cin: int, taps: int, bias: bool = False) -> DetPlan:
+    return _det_plan(lib.mt4_wgrad_conv1d_det_plan, "mt4_wgrad_conv1d_det_plan", batch, t, cout, cin, taps, 1 if bias else 0)
+
+
+def colsum_plan(m: int, c: int) -> DetPlan:
+    return _det_plan(lib.mt4_colsum_det_plan, "mt4_colsum_det_plan", m, c)
+
+
+def bce_logits_plan(m: int, n: int) -> DetPlan:
+    return _det_plan(lib.mt4_bce_logits_det_plan, "mt4_bce_logits_det_plan", m, n)
+
+
+def bn_plan(m: int, c: int) -> DetPlan:
+    """the BatchNorm reductions (statistics and backward, fp32 and bf16 tensors): float64 parts"""
+    return _det_plan(lib.mt4_bn_det_plan, "mt4_bn_det_plan", m, c)
+
+
+WGRAD2D_FORMS = ("64x64", "wide<2,2>", "wide<1,2>", "wide<2,1>")                 # DetPlan.form of `wgrad_conv2d_plan`
+WGRAD2D_BF16_FORMS = ("1x1s1<2,2>", "1x1s1<2,1>", "1x1s1<1,2>", "1x1s1<1,1>", "1x1s2<2,1>", "1x1s2<1,1>", "3x3s1", "3x3s2")   # of `wgrad_conv2d_bf16_plan`
+
+
+def wgrad_conv2d_plan(b: int, ho: int, wo: int, cout: int, cin: int, kh: int, kw: int) -> DetPlan:
+    return _det_plan(lib.mt4_wgrad_conv2d_det_plan, "mt4_wgrad_conv2d_det_plan", b, ho, wo, cout, cin, kh, kw)
+
+
+def wgrad_conv2d_bf16_plan(b: int, ho: int, wo: int, cout: int, cin: int, k: int, stride: int) -> DetPlan:
+    return _det_plan(lib.mt4_wgrad_conv2d_bf16_det_plan, "mt4_wgrad_conv2d_bf16_det_plan", b, ho, wo, cout, cin, k, stride)
+
+
+def bce_logits_pw_plan(m: int, n: int) -> DetPlan:
+    return _det_plan(lib.mt4_bce_logits_pw_det_plan, "mt4_bce_logits_pw_det_plan", m, n)
+
+
+def distill_kl_plan(b: int, k: int) -> DetPlan:
+    return _det_plan(lib.mt4_distill_kl_det_plan, "mt4_distill_kl_det_plan", b, k)
+
+
+def mse_plan(n: int) -> DetPlan:
+    return _det_plan(lib.mt4_mse_det_plan, "mt4_mse_det_plan", n)
+
+
+def check_workspace(ws: torch.Tensor, plan: DetPlan, what: str):
+    """(pointer, bytes) of a deterministic launch's workspace; refuses one that is not a contiguous 16-byte aligned device tensor of the plan's size
+    (the size first: nothing is launched into a workspace the plan does not fit)"""
+    nbytes = ws.numel() * ws.element_size()
+    if not ws.is_contiguous() or ws.data_ptr() % 16 or nbytes < plan.bytes:
+        raise ValueError(f"{what}: the workspace has {nbytes} bytes (contiguous {ws.is_contiguous()}, address % 16 = {ws.data_ptr() % 16}); the plan "
+                         f"needs {plan.bytes} contiguous 16-byte aligned bytes ({plan.nparts} parts x {plan.part_elems} elements)")
+    _need_cuda(ws)
+    return ws.data_ptr(), nbytes
+
+
+FOLD_CHUNKS = 16      # MT4_FOLD_CHUNKS
+
+
+def fold_parts_host(parts: torch.Tensor, accumulate_into: Optional[torch.Tensor] = None, chunked: bool = False) -> torch.Tensor:
+    """the fold-order contract of `mt4_fold_parts_f32` / `_f64` on the host: parts [nparts, ...] (fp32 or fp64) added front to back in their own
+    type, t = parts[0]; t += parts[p]; then accumulate_into + t when given.  One rounding per add: elementwise IEEE adds, no pairwise tree.
+    chunked: the order of `mt4_fold_parts_chunked_*` -- chunks of L = ceil(nparts / 16) consecutive parts folded so, then the chunks folded so."""
+    parts = parts.detach().cpu()
+    assert parts.dtype in (torch.float32, torch.float64) and parts.shape[0] >= 1
+    if chunked:
+        L = -(-parts.shape[0] // FOLD_CHUNKS)
+        parts = torch.stack([fold_parts_host(parts[k:k + L]) for k in range(0, parts.shape[0], L)])
+    t = parts[0].clone()
+    for p in range(1, parts.shape[0]):
+        t = t + parts[p]
+    return t if accumulate_into is None else accumulate_into.detach().cpu().to(parts.dtype) + t
+
+
+def fold_parts(parts: torch.Tensor, dst: torch.Tensor, accumulate: bool = False, n: Optional[int] = None, chunked: bool = False) -> torch.Tensor:
+    """dst[:n] (+)= parts[0][:n] + parts[1][:n] + ... in index order (`mt4_fold_parts_f32` / `_f64`), or in the fixed chunks of
+    `mt4_fold_parts_chunked_*` (many parts of few elements); parts [nparts, stride] with unit inner stride"""
+    _need_cuda(parts, dst)
+    assert parts.dim() == 2 and parts.stride(1) == 1 and dst.is_contiguous() and parts.dtype == dst.dtype
+    n = parts.shape[1] if n is None else n
+    assert 0 < n <= parts.shape[1] and dst.numel() >= n
+    what = "mt4_fold_parts_" + ("chunked_" if chunked else "") + {torch.float32: "f32", torch.float64: "f64"}[parts.dtype]
+    check(getattr(lib, what)(parts.data_ptr(), parts.shape[0], n, parts.stride(0) if parts.shape[0] > 1 else max(parts.stride(0), n), dst.data_ptr(),
+                             1 if accumulate else 0, _stream()), what)
+    return dst
+
+
 def wgrad_conv1d(dy: torch.Tensor, x: torch.Tensor, dw_packed: torch.Tensor, *, batch: int, t: int, taps: int, dil: int, pad: int,
-                 accumulate: bool = False, bias_grad: Optional[torch.Tensor] = None) -> None:
-    """bias_grad [cout] (optional, zeroed by the caller): += the column sums of dy in the same launch (instead of `colsum`)"""
+                 accumulate: bool = False, bias_grad: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> None:
+    """bias_grad [cout] (optional, zeroed by the caller): += the column sums of dy in the same launch (instead of `colsum`).
+    workspace (fp32, `wgrad_conv1d_plan(...).bytes`): the deterministic form -- partial tiles stored there and folded in index order, no atomics"""
     _need_cuda(dy, x, dw_packed, bias_grad)
     assert dy.dtype == x.dtype == dw_packed.dtype == torch.float32 and dy.is_contiguous() and x.is_contiguous() and dw_packed.is_contiguous()
     cout, cin = dy.shape[-1], x.shape[-1]
     assert dw_packed.shape == (cout, packed_k(cin, 1, taps, torch.float32)) and dy.numel() == batch * t * cout
     assert bias_grad is None or (bias_grad.dtype == torch.float32 and bias_grad.numel() >= cout)
+    gb = bias_grad.data_ptr() if bias_grad is not None else None
+    if workspace is not None:
+        ws, nbytes = check_workspace(workspace, wgrad_conv1d_plan(batch, t, cout, cin, taps, bias_grad is not None), "wgrad_conv1d")
+        check(lib.mt4_wgrad_conv1d_det_f32(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), batch, t, cout, cin, taps, dil, pad,
+                                           1 if accumulate else 0, gb, ws, nbytes, _stream()), "mt4_wgrad_conv1d_det_f32")
+        return
     check(lib.mt4_wgrad_conv1d_f32(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), batch, t, cout, cin, taps, dil, pad,
-                                   1 if accumulate else 0, bias_grad.data_ptr() if bias_grad is not None else None, _stream()), "mt4_wgrad_conv1d_f32")
+                                   1 if accumulate else 0, gb, _stream()), "mt4_wgrad_conv1d_f32")
 
 
-def colsum(x2d: torch.Tensor, out: torch.Tensor, accumulate: bool = False) -> None:
+def colsum(x2d: torch.Tensor, out: torch.Tensor, accumulate: bool = False, workspace: Optional[torch.Tensor] = None) -> None:
+    """workspace (fp32, `colsum_plan(m, c).bytes`): the deterministic form"""
     _need_cuda(x2d, out)
     assert x2d.dtype == out.dtype == torch.float32 and x2d.stride(-1) == 1
     m, c = x2d.shape
+    if workspace is not None:
+        ws, nbytes = check_workspace(workspace, colsum_plan(m, out.numel()), "colsum")
+        check(lib.mt4_colsum_det_f32(x2d.data_ptr(), out.data_ptr(), m, out.numel(), x2d.stride(0), 1 if accumulate else 0, ws, nbytes, _stream()),
+              "mt4_colsum_det_f32")
+        return
     check(lib.mt4_colsum_f32(x2d.data_ptr(), out.data_ptr(), m, out.numel(), x2d.stride(0), 1 if accumulate else 0, _stream()), "mt4_colsum_f32")
 
 
-def bce_logits(y: torch.Tensor, z: torch.Tensor, col_scale: torch.Tensor, dy: torch.Tensor, col_loss: torch.Tensor) -> None:
-    """y [M,N] (row pitch y.stride(0)), z [M,N] dense, dy [M,>=N] (row pitch dy.stride(0)); col_loss accumulates"""
+def bce_logits(y: torch.Tensor, z: torch.Tensor, col_scale: torch.Tensor, dy: torch.Tensor, col_loss: torch.Tensor,
+               workspace: Optional[torch.Tensor] = None) -> None:
+    """y [M,N] (row pitch y.stride(0)), z [M,N] dense, dy [M,>=N] (row pitch dy.stride(0)); col_loss accumulates.
+    workspace (fp32, `bce_logits_plan(m, n).bytes`): the deterministic form"""
     _need_cuda(y, z, col_scale, dy, col_loss)
     m, n = z.shape
     assert z.is_contiguous() and y.stride(-1) == 1 and dy.stride(-1) == 1
+    if workspace is not None:
+        ws, nbytes = check_workspace(workspace, bce_logits_plan(m, n), "bce_logits")
+        check(lib.mt4_bce_logits_det_f32(y.data_ptr(), z.data_ptr(), col_scale.data_ptr(), dy.data_ptr(), col_loss.data_ptr(), m, n, y.stride(0),
+                                         dy.stride(0), ws, nbytes, _stream()), "mt4_bce_logits_det_f32")
+        return
     check(lib.mt4_bce_logits_f32(y.data_ptr(), z.data_ptr(), col_scale.data_ptr(), dy.data_ptr(), col_loss.data_ptr(), m, n, y.stride(0),
                                  dy.stride(0), _stream()), "mt4_bce_logits_f32")
 
@@ -833,7 +951,7 @@ def transpose_pack_conv1d(w_packed: torch.Tensor, cout: int, cin: int, taps: int
 
 
 # ----------------------------------------------------------------------------------------- spatial training pieces (fp32)
-def bn_stats(x2d, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, sums=None):
+def bn_stats(x2d, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, sums=None, workspace=None):
     """`sums`: optional zeroed float64 scratch of 2*C (callers with many BatchNorms zero one arena per step)"""
     _need_cuda(x2d)
     m, c = x2d.shape
@@ -841,9 +959,14 @@ def bn_stats(x2d, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, s
         sums = torch.zeros(2 * c, dtype=torch.float64, device=x2d.device)   # scratch: float64 accumulators
     assert sums.dtype == torch.float64 and sums.numel() == 2 * c
     mean, invstd = torch.empty(c, device=x2d.device), torch.empty(c, device=x2d.device)
-    check(lib.mt4_bn_stats_f32(x2d.data_ptr(), sums.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                               running_mean.data_ptr() if running_mean is not None else None,
-                               running_var.data_ptr() if running_var is not None else None, m, c, momentum, eps, _stream()), "mt4_bn_stats_f32")
+    rm, rv = (running_mean.data_ptr() if running_mean is not None else None), (running_var.data_ptr() if running_var is not None else None)
+    if workspace is not None:      # the deterministic form (`bn_plan(m, c).bytes`): slab sums stored and folded in slab order into `sums`
+        ws, nbytes = check_workspace(workspace, bn_plan(m, c), "bn_stats")
+        check(lib.mt4_bn_stats_det_f32(x2d.data_ptr(), sums.data_ptr(), mean.data_ptr(), invstd.data_ptr(), rm, rv, m, c, momentum, eps, ws, nbytes,
+                                       _stream()), "mt4_bn_stats_det_f32")
+        return mean, invstd
+    check(lib.mt4_bn_stats_f32(x2d.data_ptr(), sums.data_ptr(), mean.data_ptr(), invstd.data_ptr(), rm, rv, m, c, momentum, eps, _stream()),
+          "mt4_bn_stats_f32")
     return mean, invstd
 
 
@@ -856,7 +979,7 @@ def bn_apply(x2d, mean, invstd, gamma, beta, residual=None, relu=True):
     return y
 
 
-def bn_backward(dy, y_post, x2d, mean, invstd, gamma, dgamma, dbeta, relu=True, want_dres=False, sums=None, beta=None):
+def bn_backward(dy, y_post, x2d, mean, invstd, gamma, dgamma, dbeta, relu=True, want_dres=False, sums=None, beta=None, workspace=None):
     """with `beta` and relu the ReLU gate is recomputed from x2d (the forward's fp32 expression: the stored output's sign bit for bit) instead
     of read from y_post -- units without a residual input"""
     m, c = x2d.shape
@@ -866,27 +989,45 @@ def bn_backward(dy, y_post, x2d, mean, invstd, gamma, dgamma, dbeta, relu=True, 
     dx = torch.empty_like(x2d)
     dres = torch.empty_like(x2d) if want_dres else None
     code = 0 if not relu else (2 if beta is not None else 1)
-    check(lib.mt4_bn_backward_f32(dy.data_ptr(), y_post.data_ptr() if (y_post is not None and code == 1) else None, x2d.data_ptr(), mean.data_ptr(),
-                                  invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr() if beta is not None else None, sums.data_ptr(), dx.data_ptr(),
-                                  dres.data_ptr() if want_dres else None, dgamma.data_ptr(), dbeta.data_ptr(), m, c, code, _stream()),
-          "mt4_bn_backward_f32")
+    args = (dy.data_ptr(), y_post.data_ptr() if (y_post is not None and code == 1) else None, x2d.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+            gamma.data_ptr(), beta.data_ptr() if beta is not None else None, sums.data_ptr(), dx.data_ptr(), dres.data_ptr() if want_dres else None,
+            dgamma.data_ptr(), dbeta.data_ptr(), m, c, code)
+    if workspace is not None:      # the deterministic form (`bn_plan(m, c).bytes`)
+        ws, nbytes = check_workspace(workspace, bn_plan(m, c), "bn_backward")
+        check(lib.mt4_bn_backward_det_f32(*args, ws, nbytes, _stream()), "mt4_bn_backward_det_f32")
+        return dx, dres
+    check(lib.mt4_bn_backward_f32(*args, _stream()), "mt4_bn_backward_f32")
     return dx, dres
 
 
-def wgrad_conv2d(dy, x, dw_packed, kh, kw, stride, pad, dil=(1, 1), zero=True):
-    """dy [B,Ho,Wo,Cout], x [B,H,W,Cin]; dw_packed is zeroed here (zero=False: the caller already did) and filled"""
+def wgrad_conv2d(dy, x, dw_packed, kh, kw, stride, pad, dil=(1, 1), zero=True, workspace=None):
+    """dy [B,Ho,Wo,Cout], x [B,H,W,Cin]; dw_packed is zeroed here (zero=False: the caller already did) and filled.
+    workspace (fp32, `wgrad_conv2d_plan(...).bytes`): the deterministic form -- partial tiles stored there, folded in index order and ADDED to dw_packed
+    (zero=False) or stored (zero=True: nothing is zeroed)"""
     _need_cuda(dy, x, dw_packed)
     b, ho, wo, cout = dy.shape
     _, h, w, cin = x.shape
     assert dw_packed.shape == (cout, packed_k(cin, kh, kw, torch.float32)) and dy.is_contiguous() and x.is_contiguous()
+    if workspace is not None:
+        ws, nbytes = check_workspace(workspace, wgrad_conv2d_plan(b, ho, wo, cout, cin, kh, kw), "wgrad_conv2d")
+        check(lib.mt4_wgrad_conv2d_det_f32(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), b, h, w, cin, ho, wo, cout, kh, kw, stride[0], stride[1],
+                                           pad[0], pad[1], dil[0], dil[1], 0 if zero else 1, ws, nbytes, _stream()), "mt4_wgrad_conv2d_det_f32")
+        return
     if zero:
         dw_packed.zero_()
     check(lib.mt4_wgrad_conv2d_f32(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), b, h, w, cin, ho, wo, cout, kh, kw, stride[0], stride[1],
                                    pad[0], pad[1], dil[0], dil[1], _stream()), "mt4_wgrad_conv2d_f32")
 
 
-def maxpool3x3s2_bwd(x, dy):
+def maxpool3x3s2_bwd(x, dy, gather=False):
+    """gather: the form without atomics (`mt4_maxpool3x3s2_bwd_gather_f32`: an input pixel adds its windows' gradients in a fixed order)"""
     b, h, w, c = x.shape
+    if gather:
+        _need_cuda(x, dy)
+        assert x.is_contiguous() and dy.is_contiguous() and x.dtype == dy.dtype == torch.float32
+        dx = torch.empty_like(x)
+        check(lib.mt4_maxpool3x3s2_bwd_gather_f32(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), b, h, w, c, _stream()), "mt4_maxpool3x3s2_bwd_gather_f32")
+        return dx
     dx = torch.zeros_like(x)
     check(lib.mt4_maxpool3x3s2_bwd_f32(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), b, h, w, c, _stream()), "mt4_maxpool3x3s2_bwd_f32")
     return dx
@@ -898,21 +1039,36 @@ def avgpool_bwd(dfeat, b, hw, c):
     return dx
 
 
-def bce_logits_pw(y, z, pos_weight, col_scale, dy, col_loss):
+def bce_logits_pw(y, z, pos_weight, col_scale, dy, col_loss, workspace=None):
     m, n = z.shape
+    if workspace is not None:      # the deterministic form (`bce_logits_pw_plan(m, n).bytes`)
+        ws, nbytes = check_workspace(workspace, bce_logits_pw_plan(m, n), "bce_logits_pw")
+        check(lib.mt4_bce_logits_pw_det_f32(y.data_ptr(), z.data_ptr(), pos_weight.data_ptr() if pos_weight is not None else None, col_scale.data_ptr(),
+                                            dy.data_ptr(), col_loss.data_ptr(), m, n, y.stride(0), dy.stride(0), ws, nbytes, _stream()),
+              "mt4_bce_logits_pw_det_f32")
+        return
     check(lib.mt4_bce_logits_pw_f32(y.data_ptr(), z.data_ptr(), pos_weight.data_ptr() if pos_weight is not None else None, col_scale.data_ptr(),
                                     dy.data_ptr(), col_loss.data_ptr(), m, n, y.stride(0), dy.stride(0), _stream()), "mt4_bce_logits_pw_f32")
 
 
-def distill_kl(y_s, t_pred, dy_s, loss, temp, grad_scale, accumulate=True):
+def distill_kl(y_s, t_pred, dy_s, loss, temp, grad_scale, accumulate=True, workspace=None):
     b, k = t_pred.shape
     assert t_pred.is_contiguous() and t_pred.shape == y_s.shape      # the kernel reads t_pred with pitch K; y_s / dy_s carry their own pitches
+    if workspace is not None:      # the deterministic form (`distill_kl_plan(b, k).bytes`)
+        ws, nbytes = check_workspace(workspace, distill_kl_plan(b, k), "distill_kl")
+        check(lib.mt4_distill_kl_det_f32(y_s.data_ptr(), t_pred.data_ptr(), dy_s.data_ptr(), loss.data_ptr(), b, k, y_s.stride(0), dy_s.stride(0), temp,
+                                         grad_scale, 1 if accumulate else 0, ws, nbytes, _stream()), "mt4_distill_kl_det_f32")
+        return
     check(lib.mt4_distill_kl_f32(y_s.data_ptr(), t_pred.data_ptr(), dy_s.data_ptr(), loss.data_ptr(), b, k, y_s.stride(0), dy_s.stride(0), temp,
                                  grad_scale, 1 if accumulate else 0, _stream()), "mt4_distill_kl_f32")
 
 
-def mse(a, b, loss, grad_scale):
+def mse(a, b, loss, grad_scale, workspace=None):
     da = torch.empty_like(a)
+    if workspace is not None:      # the deterministic form (`mse_plan(n).bytes`)
+        ws, nbytes = check_workspace(workspace, mse_plan(a.numel()), "mse")
+        check(lib.mt4_mse_det_f32(a.data_ptr(), b.data_ptr(), da.data_ptr(), loss.data_ptr(), a.numel(), grad_scale, ws, nbytes, _stream()), "mt4_mse_det_f32")
+        return da
     check(lib.mt4_mse_f32(a.data_ptr(), b.data_ptr(), da.data_ptr(), loss.data_ptr(), a.numel(), grad_scale, _stream()), "mt4_mse_f32")
     return da
 
@@ -985,15 +1141,19 @@ def interp_linear_rows(x: torch.Tensor, t_out: int) -> torch.Tensor:
     return y
 
 
-def bn_stats_t(x2d, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, sums=None):
+def bn_stats_t(x2d, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, sums=None, workspace=None):
     """`bn_stats` for a bf16 (or fp32) convolution output"""
     _need_cuda(x2d)
     m, c = x2d.shape
     assert sums is not None and sums.dtype == torch.float64 and sums.numel() == 2 * c and x2d.is_contiguous()
     mean, invstd = torch.empty(c, device=x2d.device), torch.empty(c, device=x2d.device)
-    check(lib.mt4_bn_stats_t(x2d.data_ptr(), dt_code(x2d.dtype), sums.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                             running_mean.data_ptr() if running_mean is not None else None,
-                             running_var.data_ptr() if running_var is not None else None, m, c, momentum, eps, _stream()), "mt4_bn_stats_t")
+    args = (x2d.data_ptr(), dt_code(x2d.dtype), sums.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+            running_mean.data_ptr() if running_mean is not None else None, running_var.data_ptr() if running_var is not None else None, m, c, momentum, eps)
+    if workspace is not None:      # the deterministic form (`bn_plan(m, c).bytes`)
+        ws, nbytes = check_workspace(workspace, bn_plan(m, c), "bn_stats_t")
+        check(lib.mt4_bn_stats_det_t(*args, ws, nbytes, _stream()), "mt4_bn_stats_det_t")
+        return mean, invstd
+    check(lib.mt4_bn_stats_t(*args, _stream()), "mt4_bn_stats_t")
     return mean, invstd
 
 
@@ -1041,7 +1201,7 @@ def bn_apply_t(x2d, mean, invstd, gamma, beta, residual=None, relu=True):
     return y
 
 
-def bn_backward_t(dy, y_post, x2d, mean, invstd, gamma, dgamma, dbeta, relu=True, want_dres=False, sums=None, beta=None):
+def bn_backward_t(dy, y_post, x2d, mean, invstd, gamma, dgamma, dbeta, relu=True, want_dres=False, sums=None, beta=None, workspace=None):
     """dy / y_post bf16; x2d (the convolution output) bf16 or fp32 -> dx of that type; dres bf16.  With `beta` and relu the ReLU gate is recomputed
     from x2d instead of read from y_post (units without a residual input)"""
     m, c = x2d.shape
@@ -1050,20 +1210,32 @@ def bn_backward_t(dy, y_post, x2d, mean, invstd, gamma, dgamma, dbeta, relu=True
     dx = torch.empty_like(x2d)
     dres = torch.empty((m, c), dtype=BF16, device=x2d.device) if want_dres else None
     code = 0 if not relu else (2 if beta is not None else 1)
-    check(lib.mt4_bn_backward_t(dy.data_ptr(), y_post.data_ptr() if (y_post is not None and code == 1) else None, x2d.data_ptr(), dt_code(x2d.dtype),
-                                mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr() if beta is not None else None, sums.data_ptr(),
-                                dx.data_ptr(), dres.data_ptr() if want_dres else None, dgamma.data_ptr(), dbeta.data_ptr(), m, c, code, _stream()),
-          "mt4_bn_backward_t")
+    args = (dy.data_ptr(), y_post.data_ptr() if (y_post is not None and code == 1) else None, x2d.data_ptr(), dt_code(x2d.dtype), mean.data_ptr(),
+            invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr() if beta is not None else None, sums.data_ptr(), dx.data_ptr(),
+            dres.data_ptr() if want_dres else None, dgamma.data_ptr(), dbeta.data_ptr(), m, c, code)
+    if workspace is not None:      # the deterministic form (`bn_plan(m, c).bytes`)
+        ws, nbytes = check_workspace(workspace, bn_plan(m, c), "bn_backward_t")
+        check(lib.mt4_bn_backward_det_t(*args, ws, nbytes, _stream()), "mt4_bn_backward_det_t")
+        return dx, dres
+    check(lib.mt4_bn_backward_t(*args, _stream()), "mt4_bn_backward_t")
     return dx, dres
 
 
-def wgrad_conv2d_bf16(dy, x, dw_packed, k, stride):
-    """dw_packed (fp32 packed, ADDED to) from dy [B,Ho,Wo,Cout] and x [B,H,W,Cin], both bf16"""
+def wgrad_conv2d_bf16(dy, x, dw_packed, k, stride, workspace=None, accumulate=True):
+    """dw_packed (fp32 packed, ADDED to) from dy [B,Ho,Wo,Cout] and x [B,H,W,Cin], both bf16.
+    workspace (fp32, `wgrad_conv2d_bf16_plan(...).bytes`): the deterministic form -- the splits' dW images stored there, folded in index order and added
+    to dw_packed (accumulate False: stored)"""
     _need_cuda(dy, x, dw_packed)
     b, ho, wo, cout = dy.shape
     _, h, w, cin = x.shape
     assert dy.dtype == x.dtype == BF16 and dy.is_contiguous() and x.is_contiguous() and dw_packed.dtype == torch.float32
     assert dw_packed.shape == (cout, packed_k(cin, k, k, torch.float32))
+    if workspace is not None:
+        ws, nbytes = check_workspace(workspace, wgrad_conv2d_bf16_plan(b, ho, wo, cout, cin, k, stride), "wgrad_conv2d_bf16")
+        check(lib.mt4_wgrad_conv2d_det_bf16(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), b, h, w, cin, ho, wo, cout, k, stride,
+                                            1 if accumulate else 0, ws, nbytes, _stream()), "mt4_wgrad_conv2d_det_bf16")
+        return
+    assert accumulate, "the atomic form always adds"
     check(lib.mt4_wgrad_conv2d_bf16(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), b, h, w, cin, ho, wo, cout, k, stride, _stream()),
           "mt4_wgrad_conv2d_bf16")
 

@@ -9,6 +9,8 @@
 * losses: `mt4_bce_logits_pw_f32`, `mt4_distill_kl_f32`, `mt4_mse_f32`; KD mixing `mt4_kd_mix` / `mt4_kd_mix_bwd_f32`;
 * one flat fp32 parameter buffer and one flat gradient buffer (packed layouts) -> ONE all-reduce per step for DDP, one
   `mt4_sgd_step_f32`.  BatchNorm statistics stay per GPU, like the reference's plain `BatchNorm2d`.
+* `deterministic=True`: every sum above that crosses workgroups goes through the `_det` entry points (per-workgroup partials in one workspace, folded in
+  index order; DESIGN.md, "Deterministic training") -- the same inputs give the same bits, eager or replayed.
 """
 from __future__ import annotations
 
@@ -43,7 +45,7 @@ class SpatialCnnTrainer(FlatTrainer):
     _refresh_table = None
     def __init__(self, network: str = "resnet50", lr: float = 0.01, weight_decay: float = 1e-5, rates: Sequence[float] = (1.0, 1.0, 1.0),
                  temp: float = 4.0, device: str = "cuda", process_group=None, overlap: bool = True, teacher_dim: int = 1536,
-                 loss_type: str = "all", operand_dtype: torch.dtype = torch.float32, epilogue_stats: bool = True):
+                 loss_type: str = "all", operand_dtype: torch.dtype = torch.float32, epilogue_stats: bool = True, deterministic: bool = False):
         """loss_type 'all': the distillation recipe (four heads, KD branch, hard + soft + feature losses: `run.py:180-192`);
         'i' | 'v' | 't': a single-task student -- only that classifier exists (`network.py:34-41`) and the loss is its BCE alone
         (`run.py:165-179`)"""
@@ -54,6 +56,15 @@ class SpatialCnnTrainer(FlatTrainer):
         self.op16 = operand_dtype == torch.bfloat16
         # BatchNorm statistics from the producing convolution's epilogue (False: the separate pass over the map -- same bits, tested)
         self.epilogue_stats = bool(epilogue_stats)
+        # deterministic: every sum of the step that crosses workgroups -- BatchNorm statistics and backward sums, conv and linear weight / bias gradients,
+        # the fp32 max-pool backward, the three losses -- comes from per-workgroup partials stored into ONE workspace and folded in index order (the
+        # `_det` entry points; the max-pool backward in gather form), in both operand modes; a step is then a pure function of its inputs, eager or
+        # replayed.  The statistics come from the separate pass (the convolution epilogue's sums are atomic: csrc/igemm_conv.hip is not covered).
+        # Up to two ranks the all-reduce is one commutative add; beyond, the step is as reproducible as the collective.
+        self.deterministic = bool(deterministic)
+        if self.deterministic:
+            self.epilogue_stats = False
+        self._ws = self._ws64 = None
         self.loss_type = loss_type
         self.heads = _ALL_HEADS if loss_type == "all" else tuple(h for h in _ALL_HEADS if h[0] == loss_type)
         self.NH = sum(k for _, k in self.heads)
@@ -176,6 +187,41 @@ class SpatialCnnTrainer(FlatTrainer):
 
     _refresh = _refresh_transposed      # (what `FlatTrainer.apply_update` runs after the update)
 
+    # ------------------------------------------------------------------ deterministic mode: the workspace
+    def workspace_bytes(self, b: int, h: int, w: int) -> int:
+        """the largest workspace over the launches of a step on b frames of h x w, from the plan queries (host only: needs no device, no weights)"""
+        C, TD = self.C, self.TD
+        need = [ops.bce_logits_pw_plan(b, self.NH).bytes, ops.wgrad_conv1d_plan(1, b, self.NHP, C, 1, True).bytes]
+        if self.loss_type == "all":
+            need += [ops.distill_kl_plan(b, k).bytes for _, k in self.heads[:3]] + [ops.mse_plan(b * TD).bytes]
+            need += [ops.wgrad_conv1d_plan(1, b, TD, C, 1, True).bytes, ops.wgrad_conv1d_plan(1, b, C, TD, 1, True).bytes]     # wi / wv / wt, mi / mv / mt
+        hp, wp = ops.stem_pad_dims(h, w)
+        ho, wo = ops.conv_out_size(hp, 7, 2, 0, 1), ops.conv_out_size(wp, 7, 2, 0, 1)
+        for conv, _, cin, cout, k, stride, _ in self._unit_specs():
+            if cin == 4:                                     # the stem; the trunk behind it starts from the max-pooled map
+                uh, uw = ho, wo
+                ho, wo = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
+            elif conv.endswith("downsample.0"):              # (declared behind its block's convolutions: the block's output size)
+                uh, uw = ho, wo
+            else:
+                uh, uw = ho, wo = (ho - 1) // stride + 1, (wo - 1) // stride + 1
+            need.append(ops.bn_plan(b * uh * uw, cout).bytes)
+            if self.op16 and cin != 4:
+                need.append(ops.wgrad_conv2d_bf16_plan(b, uh, uw, cout, cin, k, stride).bytes)
+            else:
+                need.append(ops.wgrad_conv2d_plan(b, uh, uw, cout, cin, k, k).bytes)
+        return max(need)
+
+    def _ensure_workspace(self, b: int, h: int, w: int):
+        """allocated before any capture of the shape, so that graphs keep its address; a larger shape later drops the graphs captured on the smaller one.
+        Reuse along the stream is ordered: a launch's fold has read the workspace before the next producer writes it, and every fold into a bucket's
+        region of G is on the stream ahead of `_reduce_bucket`."""
+        n = self.workspace_bytes(b, h, w)
+        if self._ws is None or self._ws.numel() * 4 < n:
+            self._graphs.clear()
+            self._ws = torch.empty((n + 15) // 16 * 4, dtype=F32, device=self.dev)
+            self._ws64 = self._ws.view(torch.float64)
+
     def running_stats(self) -> Dict[str, torch.Tensor]:
         """the BatchNorm buffers only (what a train-mode forward changes)"""
         out = {}
@@ -219,10 +265,10 @@ class SpatialCnnTrainer(FlatTrainer):
         b, ho, wo, c = z.shape
         z2 = z.view(-1, c)
         if self.op16:
-            mean, invstd = ops.bn_stats_t(z2, u.rmean, u.rvar, sums=u.sums_f)
+            mean, invstd = ops.bn_stats_t(z2, u.rmean, u.rvar, sums=u.sums_f, workspace=self._ws64)
             a = ops.bn_apply_t(z2, mean, invstd, u.gamma, u.beta, residual.view(-1, c) if residual is not None else None, relu).view(b, ho, wo, c)
         else:
-            mean, invstd = ops.bn_stats(z2, u.rmean, u.rvar, sums=u.sums_f)
+            mean, invstd = ops.bn_stats(z2, u.rmean, u.rvar, sums=u.sums_f, workspace=self._ws64)
             a = ops.bn_apply(z2, mean, invstd, u.gamma, u.beta, residual.view(-1, c) if residual is not None else None, relu).view(b, ho, wo, c)
         if saved is not None:
             saved.append((u, x, z, mean, invstd, a, relu, residual is not None))
@@ -261,15 +307,17 @@ class SpatialCnnTrainer(FlatTrainer):
         c = z.shape[-1]
         if self.op16:   # (units without a residual input recompute their ReLU gate from z: the stored activation is not read)
             dz, dres = ops.bn_backward_t(dy.reshape(-1, c), a.view(-1, c) if relu else None, z.view(-1, c), mean, invstd, u.gamma, u.ggamma, u.gbeta,
-                                         relu=relu, want_dres=want_dres, sums=u.sums_b, beta=u.beta if (relu and not has_res) else None)
+                                         relu=relu, want_dres=want_dres, sums=u.sums_b, beta=u.beta if (relu and not has_res) else None,
+                                         workspace=self._ws64)
         else:
             dz, dres = ops.bn_backward(dy.reshape(-1, c), a.view(-1, c) if relu else None, z.view(-1, c), mean, invstd, u.gamma, u.ggamma, u.gbeta,
-                                       relu=relu, want_dres=want_dres, sums=u.sums_b, beta=u.beta if (relu and not has_res) else None)
+                                       relu=relu, want_dres=want_dres, sums=u.sums_b, beta=u.beta if (relu and not has_res) else None,
+                                       workspace=self._ws64)
         dz = dz.view(z.shape)
         if self.op16 and u.cin != 4:
-            ops.wgrad_conv2d_bf16(dz, x, u.gw, u.k, u.stride)                                         # (adds to G, zeroed once per step)
+            ops.wgrad_conv2d_bf16(dz, x, u.gw, u.k, u.stride, workspace=self._ws)                     # (adds to G, zeroed once per step)
         else:
-            ops.wgrad_conv2d(dz, x, u.gw, u.k, u.k, (u.stride, u.stride), (u.pad, u.pad), zero=False)     # G is zeroed once per step
+            ops.wgrad_conv2d(dz, x, u.gw, u.k, u.k, (u.stride, u.stride), (u.pad, u.pad), zero=False, workspace=self._ws)   # G is zeroed once per step
         dx = self._dgrad(u, dz, x.shape, residual_for_dx) if need_dx else None
         return dx, (dres.view(z.shape) if dres is not None else None)
 
@@ -279,7 +327,8 @@ class SpatialCnnTrainer(FlatTrainer):
 
     def _linear_bwd(self, name, dy, x, need_dx=True):
         l = self.fp.L[name]
-        ops.wgrad_conv1d(dy, x, l.gw, batch=1, t=x.shape[0], taps=1, dil=1, pad=0, accumulate=True, bias_grad=l.gb)   # (G is zeroed once per step)
+        ops.wgrad_conv1d(dy, x, l.gw, batch=1, t=x.shape[0], taps=1, dil=1, pad=0, accumulate=True, bias_grad=l.gb,   # (G is zeroed once per step)
+                         workspace=self._ws)
         if not need_dx:
             return None
         wt = ops.transpose_pack_conv1d(l.w, l.cout, l.cin, 1)
@@ -299,6 +348,8 @@ class SpatialCnnTrainer(FlatTrainer):
         tf = [t.to(dev, F32).contiguous() for t in teacher_feat]
         B = frames.shape[0]
         assert frames.is_cuda and tuple(z.shape) == (B, self.NH)
+        if self.deterministic:
+            self._ensure_workspace(B, *(frames.shape[1:3] if frames.dtype == torch.uint8 else frames.shape[2:4]))
         self.bucket_order = []            # gradient buckets in the order their all-reduce was issued this step (DDP)
         if use_graph:
             col_loss, soft, kdl = self._graph_step((tuple(frames.shape), frames.dtype), lambda f, zz, *t: self._fwd_bwd(f, zz, t[:3], t[3:]),
@@ -332,6 +383,8 @@ class SpatialCnnTrainer(FlatTrainer):
         else:
             xp = ops.pad_nchw(frames, F32)
         B = frames.shape[0]
+        if self.deterministic:
+            self._ensure_workspace(B, *(frames.shape[1:3] if frames.dtype == torch.uint8 else frames.shape[2:4]))
         self._arena.zero_()
         pre, U = "basemodel.basemodel.", self.units
         x = ops.maxpool3x3s2(self._fwd_unit(U[pre + "conv1"], xp))
@@ -406,7 +459,7 @@ class SpatialCnnTrainer(FlatTrainer):
         col_scale = self._col_scale(B)
         col_loss = torch.zeros(NH, device=dev)
         dlog = torch.zeros((B, NHP), device=dev)
-        ops.bce_logits_pw(logits[:, :NH], z, self.pos_weight, col_scale, dlog, col_loss)
+        ops.bce_logits_pw(logits[:, :NH], z, self.pos_weight, col_scale, dlog, col_loss, workspace=self._ws)
         soft = torch.zeros(1, device=dev)
         kdl = torch.zeros(1, device=dev)
         if kd_on:
@@ -415,9 +468,9 @@ class SpatialCnnTrainer(FlatTrainer):
             cams = [self._linear_fwd(wn, mx) for wn, mx in zip(("wi", "wv", "wt"), mixed)]
             o = 0
             for (t, k), tpn in zip(self.heads[:3], tp):
-                ops.distill_kl(logits[:, o:o + k], tpn, dlog[:, o:o + k], soft, self.temp, r1 / 3.0, accumulate=True)
+                ops.distill_kl(logits[:, o:o + k], tpn, dlog[:, o:o + k], soft, self.temp, r1 / 3.0, accumulate=True, workspace=self._ws)
                 o += k
-            dcams = [ops.mse(c, t, kdl, r2 / 3.0) for c, t in zip(cams, tf)]
+            dcams = [ops.mse(c, t, kdl, r2 / 3.0, workspace=self._ws) for c, t in zip(cams, tf)]
         # ---- backward: heads + KD branch -> dfeat
         dfeat = self._linear_bwd("heads", dlog, feat)
         if kd_on:
@@ -443,7 +496,7 @@ class SpatialCnnTrainer(FlatTrainer):
                 dx, _ = self._bwd_unit(main[0], d, residual_for_dx=dres)
             if bi_ == 0 or blocks[bi_ - 1][3] != li:      # first block of the layer done: the layer's gradients are complete
                 self._reduce_bucket(f"layer{li}")
-        da0 = (ops.maxpool3x3s2_bwd_bf16 if self.op16 else ops.maxpool3x3s2_bwd)(a0, dx)
+        da0 = ops.maxpool3x3s2_bwd_bf16(a0, dx) if self.op16 else ops.maxpool3x3s2_bwd(a0, dx, gather=self.deterministic)   # (the bf16 form is a gather)
         self._bwd_unit(saved[0], da0, need_dx=False)
         self._reduce_bucket("stem")
         return col_loss, soft, kdl

@@ -34,12 +34,18 @@ NHP = 132  # padded to a multiple of 4 (16-byte rows for the gradient GEMMs)
 
 class TencoTrainer(FlatTrainer):
     def __init__(self, num_layers_PG=11, num_layers_R=10, num_R=3, num_f_maps=512, dim=512, num_classes=100, lr=0.1, weight_decay=1e-5,
-                 device: str = "cuda", process_group=None, overlap: bool = True, hier: bool = False, max_graphs: int = 64):
+                 device: str = "cuda", process_group=None, overlap: bool = True, hier: bool = False, max_graphs: int = 64,
+                 deterministic: bool = False):
         # overlap: a stage's gradients are all-reduced as soon as its backward has written them (DDP, `FlatTrainer`)
         super().__init__(lr, weight_decay, device, process_group, overlap)
         # hier = `args.hier` (`network.py:147,154-155`): AvgPool1d(7, 3) behind every refinement stage, so level l has its own length T_l, the FPN
         # resamples (`:96`) and `fusion` scores every level against the labels resized to it (`run.py:159-179,196-212`)
         self.hier = bool(hier)
+        # deterministic: every sum of the step that crosses workgroups (the weight and bias gradients, the BCE column sums) goes through the `_det`
+        # entry points -- partials stored into `_ws`, folded in index order -- so a step is a pure function of its inputs, eager or replayed, at any
+        # length.  Up to two ranks the all-reduce is one commutative add; beyond, the step is as reproducible as the collective.
+        self.deterministic = bool(deterministic)
+        self._ws: Optional[torch.Tensor] = None
         # max_graphs: how many captured steps (one per length and mode) are kept; a step whose graph would be one more runs eagerly
         self.max_graphs = int(max_graphs)
         assert num_classes == 100 and num_R == 3, "the FPN training recipe (Scripts/train_fold1.sh:28) has PG + 3 refinement stages"
@@ -76,8 +82,18 @@ class TencoTrainer(FlatTrainer):
         self.fp, self.convs = fp.build(sd), fp.L
         trained = fp.keys() | {f"conv_out{s}.{p}" for s, _, _ in HEADS for p in ("weight", "bias")}
         self._extra = {k: sd[k].detach().clone() for k in names if k not in trained}
+        if self.deterministic and self._ws is None:
+            self._ws = torch.empty(self.workspace_bytes() // 4, dtype=torch.float32, device=self.dev)
         self._refresh()
         return self
+
+    def workspace_bytes(self) -> int:
+        """the ONE workspace of the deterministic mode: the largest over the step's launches, from the plan queries.  A conv1d weight gradient has
+        at most ceil(1024 / tiles) parts however long the video (`mt4_wgrad_conv1d_det_plan`), which a plan at 2^24 frames reaches, and the BCE at
+        most 64 slabs -- so the size holds for every length and is allocated once, before any capture: graphs keep its address.  Reuse along the
+        stream is ordered: a launch's fold has read the workspace before the next producer writes it."""
+        big = 1 << 24
+        return max([ops.wgrad_conv1d_plan(1, big, l.cout, l.cin, l.taps, True).bytes for l in self.convs.values()] + [ops.bce_logits_plan(big, NH).bytes])
 
     def _export(self, which: str) -> Dict[str, torch.Tensor]:
         out = self.fp.export(which)
@@ -187,7 +203,7 @@ class TencoTrainer(FlatTrainer):
         state: {seed, step} on the device -- the draws are made by the kernels of csrc/tenco_draw_kernels.hip (the layer masks regenerated in
         the backward instead of stored) and `masks` is not looked at."""
         T, C, dev = x.shape[1], self.C, self.dev
-        cv = self.convs
+        cv, ws = self.convs, self._ws                      # ws: None (atomic sums) or the deterministic mode's workspace
         to_rows = lambda m: m[0].transpose(0, 1).contiguous().to(dev)        # [1,C,T] -> [T,C]
         h0 = x.contiguous().view(1, 1, T, self.D)
         sl = self._slots
@@ -245,20 +261,20 @@ class TencoTrainer(FlatTrainer):
         for li, lg in enumerate(logits):
             tl = lens[li]
             dy = torch.zeros((1, 1, tl, NHP), device=dev)
-            ops.bce_logits(lg.view(tl, NHP)[:, :NH], self._level_labels(z, T, tl), self._col_scale(tl), dy.view(tl, NHP), col_loss[li])
+            ops.bce_logits(lg.view(tl, NHP)[:, :NH], self._level_labels(z, T, tl), self._col_scale(tl), dy.view(tl, NHP), col_loss[li], workspace=ws)
             dys.append(dy)
         # ---- backward: heads and FPN (top-down adds fan the level gradients into each other)
         g = None
         dstage = [None, None, None, None]
         for li, (lv, dy) in enumerate(zip(levels, dys)):
             tl = lens[li]
-            ops.wgrad_conv1d(dy.view(tl, NHP), lv.view(tl, C), hd.gw, batch=1, t=tl, taps=1, dil=1, pad=0, accumulate=True, bias_grad=hd.gb)
+            ops.wgrad_conv1d(dy.view(tl, NHP), lv.view(tl, C), hd.gw, batch=1, t=tl, taps=1, dil=1, pad=0, accumulate=True, bias_grad=hd.gb, workspace=ws)
             if g is not None and self.hier:                                    # p_{li} = interp(p_{li+1}) + lateral: the adjoint of the resampling
                 g = ops.interp_linear_rows_bwd(g.view(1, lens[li - 1], C), tl).view(1, 1, tl, C)
             g = self._conv(dy, hd, transposed=True, residual=g)               # gradient w.r.t. p_{li+1}
             if li < 3:
                 cl_ = stage_out[li]                                            # lateral input c_{li+1}
-                ops.wgrad_conv1d(g.view(tl, C), cl_.view(tl, C), lat.gw, batch=1, t=tl, taps=1, dil=1, pad=0, accumulate=True, bias_grad=lat.gb)
+                ops.wgrad_conv1d(g.view(tl, C), cl_.view(tl, C), lat.gw, batch=1, t=tl, taps=1, dil=1, pad=0, accumulate=True, bias_grad=lat.gb, workspace=ws)
                 dstage[li] = self._conv(g, lat, transposed=True)
             else:
                 dstage[3] = g                                                  # p4 is the last stage's (pooled) output itself
@@ -276,15 +292,15 @@ class TencoTrainer(FlatTrainer):
                 p, d, zin, u, _ = saved[idx]
                 w1, wd = cv[p + ".conv_1x1"], cv[p + ".conv_dilated"]
                 do = ops.dropout_mul_add(df, state, sl[p], 0.5) if state is not None else ops.mul_add(df, lm[p]) if p in lm else df
-                ops.wgrad_conv1d(do.view(ts, C), u.view(ts, C), w1.gw, batch=1, t=ts, taps=1, dil=1, pad=0, accumulate=True, bias_grad=w1.gb)
+                ops.wgrad_conv1d(do.view(ts, C), u.view(ts, C), w1.gw, batch=1, t=ts, taps=1, dil=1, pad=0, accumulate=True, bias_grad=w1.gb, workspace=ws)
                 du = self._conv(do, w1, transposed=True, residual=u, act="relu_gate")
-                ops.wgrad_conv1d(du.view(ts, C), zin.view(ts, C), wd.gw, batch=1, t=ts, taps=3, dil=d, pad=d, accumulate=True, bias_grad=wd.gb)
+                ops.wgrad_conv1d(du.view(ts, C), zin.view(ts, C), wd.gw, batch=1, t=ts, taps=3, dil=d, pad=d, accumulate=True, bias_grad=wd.gb, workspace=ws)
                 df = self._conv(du, wd, dil=d, transposed=True, residual=df)
             if si > 0:
                 df = ops.mul_add(df, torch.ones_like(df), dstage[si - 1])      # + gradient of this stage's input as lateral c
                 self._reduce_bucket(prefix)                                    # this stage's gradients are complete: exchange them behind
         pin = cv["PG.conv_1x1"]                                                #   the backward of the earlier stages
-        ops.wgrad_conv1d(df.view(T, C), h0.view(T, self.D), pin.gw, batch=1, t=T, taps=1, dil=1, pad=0, accumulate=True, bias_grad=pin.gb)
+        ops.wgrad_conv1d(df.view(T, C), h0.view(T, self.D), pin.gw, batch=1, t=T, taps=1, dil=1, pad=0, accumulate=True, bias_grad=pin.gb, workspace=ws)
         self._reduce_bucket("PG")
         return col_loss
 

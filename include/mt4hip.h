@@ -421,6 +421,85 @@ int mt4_colsum_f32(const float* x, float* out, int64_t M, int32_t C, int32_t ld,
  * dy[m*ld_dy + n] = (sigmoid(y) - z) * col_scale[n].  z [M][N] dense. */
 int mt4_bce_logits_f32(const float* y, const float* z, const float* col_scale, float* dy, float* col_loss, int64_t M, int32_t N,
                        int32_t ld_y, int32_t ld_dy, void* stream);
+/* ---------------------------------------------------------------------------------------------
+ * Deterministic accumulation (no reference counterpart: torch's own deterministic mode is the nearest relative).  The three entry points above add
+ * the partial of every workgroup with fp32 atomics, so their sums depend on the order in which workgroups finish.  Their `_det` siblings STORE each
+ * partial into its own slot of a caller-provided workspace `ws` (16-byte aligned, at least `ws_bytes` of the plan, never read before it is written: no
+ * zeroing needed) and fold the slots in index order with mt4_fold_parts_f32 next on the stream.  Same inputs, same shape -> the same bits, whatever else
+ * runs on the device.  A short or NULL workspace is MT4_EINVAL before any launch.
+ *
+ * mt4_fold_parts_*: t = parts[0][i]; t += parts[p][i] for p = 1 .. nparts-1, sequentially in the element type (parts[p] = parts + p * part_stride);
+ * dst[i] = accumulate ? dst[i] + t : t, for i < n.  Reads exactly nparts x n elements; nparts = 1 is valid.  16-byte accesses when parts, dst,
+ * part_stride and n allow them, element accesses otherwise. */
+int mt4_fold_parts_f32(const float* parts, int32_t nparts, int64_t n, int64_t part_stride, float* dst, int32_t accumulate, void* stream);
+int mt4_fold_parts_f64(const double* parts, int32_t nparts, int64_t n, int64_t part_stride, double* dst, int32_t accumulate, void* stream);
+/* The fold of MANY parts of FEW elements (BatchNorm slabs, the scalar losses), in fixed chunks: with L = ceil(nparts / MT4_FOLD_CHUNKS), chunk k = the parts
+ * [k L, min((k + 1) L, nparts)) added front to back as above; then the chunks that hold parts added front to back, k = 0, 1, ...; then dst as above.  The order
+ * is a function of nparts alone; nparts <= MT4_FOLD_CHUNKS makes it the sequential fold.  Same arguments and refusals. */
+#define MT4_FOLD_CHUNKS 16
+int mt4_fold_parts_chunked_f32(const float* parts, int32_t nparts, int64_t n, int64_t part_stride, float* dst, int32_t accumulate, void* stream);
+int mt4_fold_parts_chunked_f64(const double* parts, int32_t nparts, int64_t n, int64_t part_stride, double* dst, int32_t accumulate, void* stream);
+/* Host-only plan queries (no device is touched): the launch form (0: each of these has one), the number of parts, the elements of a part (= its
+ * stride in the workspace) and the workspace bytes = nparts x part_elems x 4 of the `_det` call of the same shape.  Any output pointer may be NULL. */
+int mt4_wgrad_conv1d_det_plan(int32_t B, int32_t T, int32_t Cout, int32_t Cin, int32_t taps, int32_t with_bias, int32_t* form, int32_t* nparts,
+                              int64_t* part_elems, int64_t* ws_bytes);
+int mt4_colsum_det_plan(int64_t M, int32_t C, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes);
+int mt4_bce_logits_det_plan(int64_t M, int32_t N, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes);
+/* mt4_wgrad_conv1d_f32 without atomics.  Part z = [Cout][Kpad] of dW (padding columns written as zeros) followed, with bias_grad, by [Cout] column sums
+ * of dy, both over the rows [z * rps, (z + 1) * rps) of the B*T rows (rps = the plan's rows per part: ceil(B*T / nparts) rounded up to 32).  Fold order:
+ * parts z = 0 .. nparts-1 front to back; the sum is then added to dw_packed (accumulate) or stored, and ADDED to bias_grad. */
+int mt4_wgrad_conv1d_det_f32(const float* dy, const float* x, float* dw_packed, int32_t B, int32_t T, int32_t Cout, int32_t Cin, int32_t taps,
+                             int32_t dil, int32_t pad, int32_t accumulate, float* bias_grad, float* ws, int64_t ws_bytes, void* stream);
+/* mt4_colsum_f32 / mt4_bce_logits_f32 without atomics.  Part y = the [C] / [N] sums over the rows m with (m / 4) % nparts == y, each a sum of four
+ * per-wave sums (a wave adds its rows in ascending order).  Fold order: y = 0 .. nparts-1 front to back, then added to `out` (accumulate) or stored /
+ * ADDED to col_loss. */
+int mt4_colsum_det_f32(const float* x, float* out, int64_t M, int32_t C, int32_t ld, int32_t accumulate, float* ws, int64_t ws_bytes, void* stream);
+int mt4_bce_logits_det_f32(const float* y, const float* z, const float* col_scale, float* dy, float* col_loss, int64_t M, int32_t N, int32_t ld_y,
+                           int32_t ld_dy, float* ws, int64_t ws_bytes, void* stream);
+/* The same for the spatial stage's training step (declared here, beside the mechanism; the default entry points are further down).
+ * BatchNorm reductions, fp32 (`_f32`) and fp32 / bf16 (`_t`) tensors: parts [nparts][2][C] float64, one per 64-row-phase slab of the 1024-thread reduction
+ * (slab y holds the rows m with (m / 64) % nparts == y).  Fold order: that of mt4_fold_parts_chunked_f64 over the slabs, STORED into `sums` [2][C] (no zeroing of `sums`
+ * either), which the unchanged finalize / apply kernels read.  Arguments as mt4_bn_stats_f32 / _t and mt4_bn_backward_f32 / _t, then the workspace. */
+int mt4_bn_det_plan(int64_t M, int32_t C, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes);
+int mt4_bn_stats_det_f32(const float* x, double* sums, float* mean, float* invstd, float* running_mean, float* running_var, int64_t M, int32_t C,
+                         float momentum, float eps, double* ws, int64_t ws_bytes, void* stream);
+int mt4_bn_stats_det_t(const void* x, int32_t x_dtype, double* sums, float* mean, float* invstd, float* running_mean, float* running_var, int64_t M,
+                       int32_t C, float momentum, float eps, double* ws, int64_t ws_bytes, void* stream);
+int mt4_bn_backward_det_f32(const float* dy, const float* y_post, const float* x, const float* mean, const float* invstd, const float* gamma,
+                            const float* beta, double* sums, float* dx, float* dres, float* dgamma, float* dbeta, int64_t M, int32_t C, int32_t relu,
+                            double* ws, int64_t ws_bytes, void* stream);
+int mt4_bn_backward_det_t(const void* dy_bf16, const void* y_post_bf16, const void* x, int32_t x_dtype, const float* mean, const float* invstd,
+                          const float* gamma, const float* beta, double* sums, void* dx, void* dres_bf16, float* dgamma, float* dbeta, int64_t M,
+                          int32_t C, int32_t relu, double* ws, int64_t ws_bytes, void* stream);
+/* Conv2d weight gradients: parts [nparts] images of the packed fp32 dW [Cout][Kpad], padding columns written as zeros.  Fold order: parts 0 .. nparts-1
+ * front to back, then ADDED to dw_packed (accumulate != 0) or stored.
+ * fp32 operands: form 0 = 64 x 64 tiles, 1 / 2 / 3 = the wide kernel <2,2> / <1,2> / <2,1>; part z = the output pixels [z rps, (z + 1) rps), rps =
+ *   ceil(B Ho Wo / nparts) rounded up to 32.
+ * bf16 operands: form 0..7 = the launch forms in the order of mt4_wgrad_conv2d_bf16's dispatch (1x1 stride 1: <2,2> <2,1> <1,2> <1,1>; 1x1 stride 2:
+ *   <2,1> <1,1>; 3x3 stride 1; 3x3 stride 2); part z = the spatial tiles t (TH x 16 output pixels, TH = 8 for 1x1 and 4 for 3x3) with t % nparts == z,
+ *   added in ascending t. */
+int mt4_wgrad_conv2d_det_plan(int32_t B, int32_t Ho, int32_t Wo, int32_t Cout, int32_t Cin, int32_t KH, int32_t KW, int32_t* form, int32_t* nparts,
+                              int64_t* part_elems, int64_t* ws_bytes);
+int mt4_wgrad_conv2d_det_f32(const float* dy, const float* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo,
+                             int32_t Cout, int32_t KH, int32_t KW, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w, int32_t dil_h,
+                             int32_t dil_w, int32_t accumulate, float* ws, int64_t ws_bytes, void* stream);
+int mt4_wgrad_conv2d_bf16_det_plan(int32_t B, int32_t Ho, int32_t Wo, int32_t Cout, int32_t Cin, int32_t K, int32_t stride, int32_t* form,
+                                   int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes);
+int mt4_wgrad_conv2d_det_bf16(const void* dy, const void* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo,
+                              int32_t Cout, int32_t K, int32_t stride, int32_t accumulate, float* ws, int64_t ws_bytes, void* stream);
+/* mt4_maxpool3x3s2_bwd_f32 in gather form: no atomics, no workspace, dx need not be zeroed.  A thread owns 4 channels of one input pixel and adds the
+ * gradients of the at most four windows whose first maximum it is in ascending (ho, wo) order.  C % 4 == 0, 16-byte aligned pointers. */
+int mt4_maxpool3x3s2_bwd_gather_f32(const float* x, const float* dy, float* dx, int32_t B, int32_t H, int32_t W, int32_t C, void* stream);
+/* The three losses.  mt4_bce_logits_pw_f32: parts [ceil(M / 64)][N], one per 64-row slab, ADDED to col_loss after the fold.  mt4_distill_kl_f32 and
+ * mt4_mse_f32: one part ELEMENT per workgroup (a batch row; 256 elements), folded in the order of mt4_fold_parts_chunked_f32 and ADDED to *loss. */
+int mt4_bce_logits_pw_det_plan(int32_t M, int32_t N, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes);
+int mt4_bce_logits_pw_det_f32(const float* y, const float* z, const float* pos_weight, const float* col_scale, float* dy, float* col_loss, int32_t M,
+                              int32_t N, int32_t ld_y, int32_t ld_dy, float* ws, int64_t ws_bytes, void* stream);
+int mt4_distill_kl_det_plan(int32_t B, int32_t K, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes);
+int mt4_distill_kl_det_f32(const float* y_s, const float* t_pred, float* dy_s, float* loss, int32_t B, int32_t K, int32_t ld_y, int32_t ld_dy, float temp,
+                           float grad_scale, int32_t accumulate, float* ws, int64_t ws_bytes, void* stream);
+int mt4_mse_det_plan(int64_t n, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes);
+int mt4_mse_det_f32(const float* a, const float* b, float* da, float* loss, int64_t n, float grad_scale, float* ws, int64_t ws_bytes, void* stream);
 /* torch.optim.SGD without momentum (run.py:343): p -= lr * (grad_scale * g + weight_decay * p) */
 int mt4_sgd_step_f32(float* p, const float* g, int64_t n, float lr, float weight_decay, float grad_scale, void* stream);
 /* y = a * b (+ c): dropout masks (network.py:194-196) forward and backward */

@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""What --deterministic costs (GPU box): a trainer's whole step -- forward, losses, backward, SGD, replayed as one hipGraph -- with the default
+(atomic) sums and with the fixed-order sums.  Workloads: `tenco` = the temporal step with the draws made on the device, full-size head (11 + 3 x 10
+layers, 512 maps), at --lengths frames; `resnet50_bf16`, `resnet50_fp32`, `resnet18_bf16` = the student step on 64 uint8 frames of 256 x 448 (one
+"length": the batch).
+
+  python3 tools/deterministic_bench.py [--workload tenco] [--parent DIR] [--reps 7] [--steps 40] [--lengths 256,2000]
+        every repetition starts one fresh child process per variant, alternating: the default step of the checkout at DIR (a built parent
+        checkout carried in the tree, when given), the default step of this tree, the deterministic step of this tree.  A child times its steps
+        with device events after a warm-up that includes the graph capture and reports the median step; the table gives, per variant and
+        length, the median of the repetitions' medians and their spread (min .. max).  Each child runs under a time limit of its own and the
+        run stops at the first child that does not exit with status 0.
+  python3 tools/deterministic_bench.py --child default|det [--root DIR] ...
+        one such process: one JSON line (profile it with `rocprofv3 --kernel-trace --stats -- python3 tools/deterministic_bench.py --child det
+        --eager` in a run of its own for the per-kernel split; --eager launches the kernels one by one instead of replaying the graph)."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def student_child(workload: str, mode: str, root: str, steps: int, warmup: int, graph: bool = True, batch=64, h=256, w=448):
+    sys.path.insert(0, root)
+    import numpy as np
+    import torch
+    from computervision_codes_amd import shapes, synth
+    from computervision_codes_amd.spatial_cnn_train import SpatialCnnTrainer
+    net, op = workload.split("_")
+    kw = {"deterministic": True} if mode == "det" else {}            # (the parent checkout does not know the keyword: never passed there)
+    tr = SpatialCnnTrainer(net, lr=1e-3, weight_decay=1e-5, rates=(1.0, 0.0, 0.1), operand_dtype=torch.bfloat16 if op == "bf16" else torch.float32, **kw)
+    tr.load_state_dict(synth.fill_from_shapes(shapes.spatial_cnn_shapes(net), seed=1))
+    rng = np.random.default_rng(3)
+    frames = synth.synthetic_frames(batch, h, w, seed=2).cuda()
+    z = torch.from_numpy((rng.random((batch, 131)) < 0.1).astype(np.float32)).cuda()
+    tp = [torch.from_numpy(rng.standard_normal((batch, k)).astype(np.float32)).cuda() for k in (6, 10, 15)]
+    tf = [torch.from_numpy(rng.standard_normal((batch, 1536)).astype(np.float32)).cuda() for _ in range(3)]
+    out = {"workload": workload, "mode": mode, "root": os.path.relpath(root, HERE), "steps": steps, "ms": {}}
+    if mode == "det":
+        out["workspace_bytes"] = tr.workspace_bytes(batch, h, w)
+    ms = []
+    for i in range(warmup + steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        tr.train_step(frames, z, tp, tf, use_graph=graph)
+        b.record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            ms.append(a.elapsed_time(b))
+    out["ms"][str(batch)] = round(statistics.median(ms), 4)
+    print(json.dumps(out), flush=True)
+
+
+def child(mode: str, root: str, lengths, steps: int, warmup: int, graph: bool = True):
+    sys.path.insert(0, root)
+    import numpy as np
+    import torch
+    from computervision_codes_amd import shapes, synth
+    from computervision_codes_amd.tenco_train import TencoTrainer
+    kw = {"deterministic": True} if mode == "det" else {}            # (the parent checkout does not know the keyword: never passed there)
+    tr = TencoTrainer(11, 10, 3, 512, 512, lr=1e-3, weight_decay=1e-5, **kw)
+    tr.load_state_dict(synth.fill_from_shapes(shapes.tenco_shapes(11, 10, 3, 512, 512, 100, fpn=True), seed=1))
+    out = {"mode": mode, "root": os.path.relpath(root, HERE), "steps": steps, "ms": {}}
+    if mode == "det":
+        out["workspace_bytes"] = tr.workspace_bytes()
+    for T in lengths:
+        x = synth.synthetic_features(T, 512, seed=2).cuda()
+        rng = np.random.default_rng(3)
+        z = tr.prepare_labels({s: torch.from_numpy((rng.random((T, k)) < 0.1).astype(np.int64)) for s, k in (("", 100), ("_i", 6), ("_v", 10), ("_t", 15))})
+        ms = []
+        for i in range(warmup + steps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            tr.train_step(x, z, draws=(5, i), use_graph=graph)
+            b.record()
+            torch.cuda.synchronize()
+            if i >= warmup:
+                ms.append(a.elapsed_time(b))
+        out["ms"][str(T)] = round(statistics.median(ms), 4)
+    print(json.dumps(out), flush=True)
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--child", choices=["default", "det"])
+    p.add_argument("--workload", default="tenco", choices=["tenco", "resnet50_bf16", "resnet50_fp32", "resnet18_bf16"])
+    p.add_argument("--root", default=HERE)
+    p.add_argument("--parent", default=None)
+    p.add_argument("--reps", type=int, default=7)
+    p.add_argument("--steps", type=int, default=40)
+    p.add_argument("--warmup", type=int, default=8)
+    p.add_argument("--lengths", default="256,2000")
+    p.add_argument("--eager", action="store_true", help="(--child) launch the step's kernels one by one instead of replaying a graph: for a kernel trace")
+    a = p.parse_args()
+    lengths = [int(t) for t in a.lengths.split(",")] if a.workload == "tenco" else [64]
+    if a.child:
+        if a.workload != "tenco":
+            return student_child(a.workload, a.child, os.path.abspath(a.root), a.steps, a.warmup, not a.eager)
+        return child(a.child, os.path.abspath(a.root), lengths, a.steps, a.warmup, not a.eager)
+    variants = ([("parent default", "default", os.path.abspath(a.parent))] if a.parent else []) + [("default", "default", HERE), ("deterministic", "det", HERE)]
+    res = {name: {T: [] for T in lengths} for name, _, _ in variants}
+    for rep in range(a.reps):
+        for name, mode, root in variants:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode, "--workload", a.workload, "--root", root, "--steps", str(a.steps),
+                                "--warmup", str(a.warmup), "--lengths", a.lengths], capture_output=True, text=True, timeout=240)
+            if r.returncode != 0:
+                sys.exit(f"{name}: exit status {r.returncode}\n{r.stdout[-1000:]}{r.stderr[-2000:]}")
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+            print(f"rep {rep} {name}: {line}", flush=True)
+            for T, v in json.loads(line)["ms"].items():
+                res[name][int(T)].append(v)
+    what = "temporal step (device draws), T frames" if a.workload == "tenco" else f"{a.workload} student step, batch of 256 x 448 frames"
+    print(f"\n{what}; hipGraph replay, ms: median of {a.reps} process medians (min .. max)")
+    for T in lengths:
+        for name, _, _ in variants:
+            v = res[name][T]
+            print(f"  {T:5d}  {name:15s} {statistics.median(v):8.3f}  ({min(v):.3f} .. {max(v):.3f})")
+
+
+if __name__ == "__main__":
+    main()
