@@ -7,6 +7,8 @@ Swin pre-training files go into the MI355X modules unchanged.
 * `swin_pretrain_to_q2l` -- `build_backbone`'s Swin branch (`models/backbone.py:188-201`): an upstream Swin checkpoint
   (`{'model': state_dict}`, e.g. `swin_base_patch4_window12_384_22k.pth`) without its classification `head`, under the `backbone.0.`
   prefix the `Joiner` gives it inside `Qeruy2Label`.
+* `torchvision_resnet_to_student` -- `BaseModel`'s `resnet18/50(pretrained=True)` (`Spatial_cnn/network.py:100,105`): a torchvision ResNet
+  checkpoint under the student's `basemodel.basemodel.` prefix, shapes checked, `fc.*` left out.
 """
 from __future__ import annotations
 
@@ -44,6 +46,25 @@ def load_partial(model, source, strict_shapes: bool = True) -> Dict[str, list]:
             ignored.append(k)
     model.load_state_dict(cur, strict=False)
     return {"used": used, "ignored": ignored, "kept": [k for k in cur if k not in sd]}
+
+
+def torchvision_resnet_to_student(checkpoint, network: str, prefix: str = "basemodel.basemodel."):
+    """torchvision ResNet-18 / -50 checkpoint (`conv1.weight`, `layer1.0. ...`, `fc.*`; e.g. `resnet50-0676ba61.pth`) -> (the trunk entries of
+    the student's state dict under `basemodel.basemodel.`, the keys of the file that were ignored): what `BaseModel` starts from with
+    `resnet18/50(pretrained=True)` (`Spatial_cnn/network.py:100,105`).  `fc.*` is ignored (the student reads the pooled feature, its 1000-way
+    layer keeps the value it has); a `num_batches_tracked` the file lacks (files older than torch 0.4.1) is left out, so the table's zero stays.
+    Every entry is checked against `shapes.resnet_shapes(network)`: a tensor of another shape or a missing one -- a ResNet-18 file for a
+    ResNet-50 student -- is a ValueError naming the first of them, never a partial load."""
+    from . import shapes
+    sd = clean_state_dict(unwrap(checkpoint))
+    table = [(k, tuple(s)) for k, s in shapes.resnet_shapes(network) if not k.startswith("fc.")]
+    known = dict(table)
+    wrong = [f"{k}: {tuple(sd[k].shape)} in the file, {s} in {network}" for k, s in table if k in sd and tuple(sd[k].shape) != s]
+    missing = [k for k, _ in table if k not in sd and not k.endswith("num_batches_tracked")]
+    if wrong or missing:
+        raise ValueError(f"not a torchvision {network} state dict: " + "; ".join(wrong[:4] + [f"{k}: missing" for k in missing[:4]])
+                         + (f" (and {len(wrong) + len(missing) - len(wrong[:4]) - len(missing[:4])} more)" if len(wrong) > 4 or len(missing) > 4 else ""))
+    return OrderedDict((prefix + k, sd[k]) for k, _ in table if k in sd), [k for k in sd if k not in known]
 
 
 def swin_pretrain_to_q2l(checkpoint, prefix: str = "backbone.0.") -> "OrderedDict[str, torch.Tensor]":

@@ -17,7 +17,7 @@ import torch
 
 from . import cholect, extract, featfile
 from .metrics import Recognition, final_report, gather_recognition, recognition_from
-from .trainloop import _barrier, _dist, _log, add_schedule_flags, deal, run_epochs
+from .trainloop import _barrier, _dist, _log, add_schedule_flags, deal, load_resume, run_epochs
 
 
 def extraction_batch(img_size, device_batch):
@@ -71,6 +71,12 @@ _DETERMINISTIC = _flag("--deterministic", action="store_true",
                             "BatchNorm sums, the max-pool backward, loss sums) is taken from per-workgroup partials folded in a fixed order (mt4_*_det_* + "
                             "mt4_fold_parts_f32 / _f64) instead of float atomics -- the same seed and inputs give the same losses and the same checkpoint "
                             "bytes; the BatchNorm statistics come from the separate pass instead of the convolution's epilogue")
+# --resume (not in the reference, whose drivers load `_latest` and start again at epoch 0): every trainer, `trainloop.run_epochs`
+_RESUME = _flag("--resume", action="store_true",
+                help="write resume state beside the `_latest` checkpoint whenever that is written (`<latest>.resume`, ranks > 0 `<latest>.resume.rank<r>`: "
+                     "epoch, best score, world size, the digest of the `_latest` bytes, the host generators' states) and continue from it when it is there: "
+                     "the epoch after the recorded one, with its learning rate, draws and best score.  The same command line can be issued again "
+                     "after a kill; a `_latest` without matching resume state is refused.  `_latest.pth` itself stays the plain state dict")
 _DETERMINISTIC_STAGES = ("spatial_cnn", "tenco")
 _NOT_DETERMINISTIC = {
     "spatial_transformer": "the sequence trainers' reductions are not covered yet (csrc/seq_train_kernels.hip: LayerNorm dgamma/dbeta, the "
@@ -98,6 +104,7 @@ _FRAME_TRAIN = [
     _flag("--pretrain_dir", type=str, default=""),
     _OPERAND_DTYPE,
     _DETERMINISTIC,
+    _RESUME,
 ]
 # stage -> (the flags every entry point of the stage parses, the flags of its trainer alone), on top of `_common` and -- the trainer --
 # `add_schedule_flags`.  --teacher_dim: the student mixes in the 1536-wide Swin-L feature (`Spatial_cnn/run.py`), the transformer stage's
@@ -105,7 +112,11 @@ _FRAME_TRAIN = [
 _FLAGS = {
     "spatial_cnn": ([_flag("--network", type=str, default="resnet18"),
                      _flag("--student_dim", type=int, default=512),
-                     _flag("--teacher_dim", type=int, default=1536)], _FRAME_TRAIN),
+                     _flag("--teacher_dim", type=int, default=1536)],
+                    _FRAME_TRAIN + [_flag("--imagenet_trunk", type=str, default="",
+                                          help="a torchvision ResNet-18 / -50 checkpoint (e.g. resnet50-0676ba61.pth) for the trunk, the reference's "
+                                               "`pretrained=True` (`network.py:100,105`): loaded after the synthetic fill and before --pretrain_dir and "
+                                               "`_latest`; a file that is not there or is another architecture's is an error")]),
     "spatial_transformer": ([_flag("--backbone", type=str, default="swin_L_384_22k"),
                              _flag("--img_size", type=int, default=384),
                              _flag("--hidden_dim", type=int, default=1536),
@@ -114,7 +125,7 @@ _FLAGS = {
     "mstct": ([_flag("--input_dim", type=int, default=1536),
                _flag("--final_embedding_dim", type=int, default=512)],
               [_flag("--num_clips", type=int, default=256, help="window length (the reference hard-codes 256, dataloader.py:237)"), _OPERAND_DTYPE,
-               _DETERMINISTIC]),
+               _DETERMINISTIC, _RESUME]),
     # --mask_draw / --subclip (not in the reference) device: the step's random pieces are drawn by HIP kernels from (seed, step) and whole-video
     # steps replay as hipGraphs; host: drawn with torch's generator and uploaded.  reference: `Temporal_tenco/dataloader.py:219-222` sub-clip sampling
     "tenco": ([_flag("--num_layers_PG", default=11, type=int),
@@ -127,7 +138,7 @@ _FLAGS = {
                _flag("--input_dim", type=int, default=512)],
               [_flag("--mask_draw", choices=("host", "device"), default="host"),
                _flag("--subclip", choices=("off", "reference"), default="off"),
-               _DETERMINISTIC]),
+               _DETERMINISTIC, _RESUME]),
 }
 _LATEST = {"spatial_cnn": "_latest.pth", "spatial_transformer": "_latest.pth", "tenco": "_latest.pth",
            "mstct": "latest.pth"}                            # <stem> + this = the trainer's newest checkpoint; MS-TCT: no underscore (`Temporal_mstct/run.py:268`)
@@ -154,6 +165,20 @@ def _deterministic(stage: str, F) -> bool:
         raise NotImplementedError(f"--deterministic: {_NOT_DETERMINISTIC[stage]}")
     print("--deterministic: fixed-order sums (per-workgroup partials + mt4_fold_parts_f32 / _f64) in place of float atomics", flush=True)
     return True
+
+
+def _resume(F, latest: str):
+    """--resume of a trainer, read before any model is built: what `trainloop.load_resume` finds beside `latest` for this rank (a fresh run,
+    the state to continue from, or its ValueError); None without the flag"""
+    return load_resume(latest, *_dist()) if getattr(F, "resume", False) else None
+
+
+def _latest_state(latest: str, resume):
+    """the state dict a trainer starts from when its newest checkpoint is on disk (else None); under --resume the tensors of the very bytes
+    whose digest `load_resume` checked"""
+    if resume is not None:
+        return resume.state_dict()
+    return torch.load(latest, map_location="cpu") if os.path.exists(latest) else None
 
 
 def _dtype(name: str) -> torch.dtype:
@@ -497,6 +522,31 @@ def _frame_validation(F, val_videos, labels, size, cap, forward, label_cache=Non
     return score, f"{vt}: [{score:.5f}]"
 
 
+def student_start(F, latest: str, resume=None, say=None) -> Dict[str, torch.Tensor]:
+    """the state dict `Spatial_cnn/run.py -t` starts from, in the reference's order; host only.  The synthetic fill (no torch.nn init here:
+    deterministic synthetic start), then --imagenet_trunk (`BaseModel`'s `resnet18/50(pretrained=True)`, `network.py:100,105`: a torchvision
+    file through `checkpoint.torchvision_resnet_to_student`; given but not there, or another architecture's: an error), then --pretrain_dir
+    (`run.py:316-317`) and the newest checkpoint `latest` (`load_model`, `:272-278`: the keys present in the model, strict=False; a file that
+    is not there is skipped).  A later source wins key by key.  `resume`: --resume's `trainloop.Resume`, whose bytes stand for `latest`;
+    `say(line)` gets the one line about the trunk file"""
+    from . import checkpoint, shapes, synth
+    sd = synth.fill_from_shapes(shapes.spatial_cnn_shapes(F.network, F.student_dim, F.teacher_dim, F.loss_type), seed=F.seed)
+    trunk = getattr(F, "imagenet_trunk", "")
+    if trunk:
+        if not os.path.isfile(trunk):
+            raise FileNotFoundError(f"--imagenet_trunk {trunk}: no such file (leave the flag out for the synthetic start)")
+        hit, ignored = checkpoint.torchvision_resnet_to_student(torch.load(trunk, map_location="cpu"), F.network)
+        sd.update(hit)
+        if say:
+            say(f"--imagenet_trunk: {len(hit)} tensors from {trunk}, ignored {ignored}")
+    if F.pretrain_dir and os.path.exists(F.pretrain_dir):
+        sd.update({k: v for k, v in torch.load(F.pretrain_dir, map_location="cpu").items() if k in sd})
+    state = _latest_state(latest, resume)
+    if state is not None:
+        sd.update({k: v for k, v in state.items() if k in sd})
+    return sd
+
+
 def spatial_cnn_train(argv=None) -> Dict[str, float]:
     """`Spatial_cnn/run.py -t` (:296-470): student distillation.  Shuffled frames of all training videos in batches of --batch; with
     torchrun every rank takes its own batch of a step (frame-DDP: global batch = world x --batch), BatchNorm statistics stay per
@@ -505,7 +555,6 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     import random
 
     from .spatial_cnn_train import SpatialCnnTrainer
-    from . import shapes, synth
     F = _parser("spatial_cnn", True).parse_known_args(argv)[0]
     if F.loss_type not in ("all", "i", "v", "t"):
         raise ValueError("--loss_type all | i | v | t (`Spatial_cnn/run.py:165-192`)")
@@ -514,14 +563,11 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold)
     latest = stem + _LATEST["spatial_cnn"]
+    resume = _resume(F, latest)
+    sd = student_start(F, latest, resume, say=print if rank == 0 else None)
     tr = SpatialCnnTrainer(F.network, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay, rates=F.rates, temp=float(F.temp),
                            teacher_dim=F.teacher_dim, loss_type=F.loss_type,
                            operand_dtype=_dtype(F.operand_dtype), deterministic=_deterministic("spatial_cnn", F))
-    table = shapes.spatial_cnn_shapes(F.network, F.student_dim, F.teacher_dim, F.loss_type)
-    sd = synth.fill_from_shapes(table, seed=F.seed)          # no torch.nn init here: deterministic synthetic start
-    for src in (F.pretrain_dir, latest):                     # `load_model` (:272-278): keys present in the model, strict=False
-        if src and os.path.exists(src):
-            sd.update({k: v for k, v in torch.load(src, map_location="cpu").items() if k in sd})
     tr.load_state_dict(sd)
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, kfold)
     labels = {v: cholect.load_labels(F.data_dir, v) for v in train_videos + val_videos}
@@ -544,6 +590,7 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
                 with FrameLoader(F, mine, labels, tables, size, aug_rng, prefetch=F.prefetch, cache=cache) as batches:
                     for fb in batches:
                         tot += tr.train_step(*fb)["loss"]
+                batches.check_drained()                      # (--resume saves aug_rng's state behind this epoch: no chunk of it is still to draw)
                 return tot, len(mine)
             for batch in mine:
                 tot += tr.train_step(*_frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng, cache))["loss"]
@@ -559,7 +606,8 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
         gi = "ivt".index(F.loss_type) if single else 3
         return _frame_validation(F, val_videos, labels, size, 256, lambda fr: model.extract_u8(fr)[gi][1], val_labels, cache)
 
-    return run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", latest, stem + ".pth", score_key="val_mAP_ivt", epoch_note=note)
+    return run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", latest, stem + ".pth", score_key="val_mAP_ivt", epoch_note=note,
+                      generators={"order_rng": order_rng, "aug_rng": aug_rng}, resume=resume)
 
 
 # ------------------------------------------------------------------------------------------------ Temporal_tenco/run.py -e
@@ -623,13 +671,15 @@ def _tenco_train(F):
         # `loss_v`, `loss_t` stay the int 0 they start as (`run.py:190`) and `loss_i.item()` raises AttributeError at `run.py:214` in the first step
         raise NotImplementedError("Temporal_tenco training needs --fpn (Scripts/train_fold1.sh:28): without it the reference's train loop itself fails "
                                   "in its first step (run.py:190,214: .item() on the int 0 that loss_i stays when the model returns no per-component logits)")
+    init = stem + _LATEST["tenco"]
+    resume = _resume(F, init)
     tr = TencoTrainer(F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                       hier=bool(getattr(F, "hier", False)),      # --hier True: pooled refinement levels (`network.py:147,154-155`, `run.py:159-179`)
                       deterministic=_deterministic("tenco", F))
     from . import shapes, synth
-    init = stem + _LATEST["tenco"]
-    if os.path.exists(init):
-        tr.load_state_dict(torch.load(init, map_location="cpu"))
+    state = _latest_state(init, resume)
+    if state is not None:
+        tr.load_state_dict(state)
     else:   # no torch.nn init here: deterministic synthetic start (the reference starts from torch's default init)
         tr.load_state_dict(synth.fill_from_shapes(shapes.tenco_shapes(F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100, fpn=True),
                                                   seed=F.seed))
@@ -689,7 +739,8 @@ def _tenco_train(F):
         return score, f"ivt: [{ivt:.5f}]"
 
     run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", init, stem + ".pth", latest_every_epoch=True,
-               epoch_note=(lambda: f" | clips {clipped[0]}/{clipped[1]}") if subclip else None)
+               epoch_note=(lambda: f" | clips {clipped[0]}/{clipped[1]}") if subclip else None,
+               generators={"rng": rng, "clip_rng": clip_rng, "gen": gen}, resume=resume)
     if rank == 0 and device_draw:
         _log(stem + ".log", f"mask_draw device | subclip {F.subclip} | cached graphs {len(tr._graphs)} | reserved bytes added {tr.graph_reserved_bytes}")
 
@@ -855,10 +906,12 @@ def _mstct_train(F):
         raise ValueError("Temporal_mstct trains one task at a time: --loss_type i | v | t | ivt (Scripts/train_fold1.sh:16)")
     stem = _stem(F, task_dir=True)
     latest = stem + _LATEST["mstct"]
+    resume = _resume(F, latest)
     tr = MstctTrainer(*_MSTCT_ARCH, F.input_dim, F.final_embedding_dim, lt, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                       operand_dtype=_dtype(F.operand_dtype))
-    if os.path.exists(latest):
-        tr.load_state_dict(torch.load(latest, map_location="cpu"))
+    state = _latest_state(latest, resume)
+    if state is not None:
+        tr.load_state_dict(state)
     else:   # no torch.nn init here: deterministic synthetic start (the reference starts from its trunc_normal_ init)
         tr.load_state_dict(synth.fill_from_shapes(shapes.mstct_shapes(F.input_dim, _MSTCT_ARCH[0], _MSTCT_ARCH[1], _MSTCT_ARCH[3], F.final_embedding_dim, lt), seed=F.seed))
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, F.kfold)
@@ -895,7 +948,8 @@ def _mstct_train(F):
         score = float(vm[lt].compute_video_AP(ignore_null=_chlg(F))["mAP"]) if vm else 0.0
         return score, f"{lt}: [{score:.5f}]"
 
-    run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", latest, stem + ".pth", latest_every_epoch=True)
+    run_epochs(F, tr, rank, train_epoch, validate, stem + ".log", latest, stem + ".pth", latest_every_epoch=True,
+               generators={"order_rng": order_rng, "win_rng": win_rng}, resume=resume)
 
 
 # ------------------------------------------------------------------------------------------------ Spatial_transformer/run.py -t
@@ -926,6 +980,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold, task_dir=True)
     logfile, latest = stem + ".log", stem + _LATEST["spatial_transformer"]
+    resume = _resume(F, latest)
     tr = Q2LTrainer(F.backbone, F.img_size, F.hidden_dim, F.loss_type, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                     drop_path_rate=F.drop_path_rate, operand_dtype=_dtype(F.operand_dtype),
                     teacher_dim=F.teacher_dim, rates=F.rates, temp=float(F.temp))
@@ -940,9 +995,11 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
         sd.update(hit)
         if rank == 0:
             _log(logfile, f"backbone: {len(hit)} tensors from {swin_file}")
-    for src in (F.pretrain_dir, latest):                     # `load_model` (:280-287): keys present in the model, strict=False
-        if src and os.path.exists(src):
-            sd.update({k: v for k, v in torch.load(src, map_location="cpu").items() if k in sd})
+    if F.pretrain_dir and os.path.exists(F.pretrain_dir):    # `load_model` (:280-287): keys present in the model, strict=False
+        sd.update({k: v for k, v in torch.load(F.pretrain_dir, map_location="cpu").items() if k in sd})
+    state = _latest_state(latest, resume)
+    if state is not None:
+        sd.update({k: v for k, v in state.items() if k in sd})
     tr.load_state_dict(sd)
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, kfold)
     labels = {v: cholect.load_labels(F.data_dir, v) for v in train_videos + val_videos}
@@ -973,6 +1030,8 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
                         tot += tr.train_step(frames, lab["ivt".index(F.loss_type)], masks)
                     else:
                         tot += tr.train_step(frames, lab, masks, teacher_pred=tp, teacher_feat=tf)["loss"]
+            if tables is not None:
+                source.check_drained()                       # (--resume saves aug_rng's state behind this epoch: no chunk of it is still to draw)
         finally:
             if cache is not None:
                 cache.seal()                                 # what this epoch stored is readable from the next one on
@@ -986,7 +1045,8 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
         zt = lambda fr: [] if single else [torch.zeros((fr.shape[0], F.teacher_dim), device=fr.device)] * 3   # (`dataloader.py:240-246`: zeros off the train split)
         return _frame_validation(F, val_videos, labels, size, 128, lambda fr: model(fr, *zt(fr))[gi][1], val_labels, cache)
 
-    return run_epochs(F, tr, rank, train_epoch, validate, logfile, latest, stem + ".pth", epoch_note=note)
+    return run_epochs(F, tr, rank, train_epoch, validate, logfile, latest, stem + ".pth", epoch_note=note,
+                      generators={"order_rng": order_rng, "aug_rng": aug_rng}, resume=resume)
 
 
 # ------------------------------------------------------------------------------------------------ run.py: -t, then -e

@@ -141,6 +141,15 @@ class FrameLoader:
         self._lock = threading.Lock()
         self.in_flight = 0                       # loads running on a helper (or, for a single chunk, on the consumer) right now
         self._it = None
+        self._handed = 0                         # batches handed out
+
+    def check_drained(self):
+        """after the `with` block: the epoch boundary --resume saves `aug_rng` at.  Every batch was handed out -- so every chunk was drawn and
+        loaded -- and no helper is still running: the generator is in the state the epoch's `_frame_batch` calls leave.  RuntimeError
+        otherwise (a loop left early)"""
+        if self._handed != len(self.batches) or self.in_flight:
+            raise RuntimeError(f"FrameLoader: {self._handed} of {len(self.batches)} batches handed out, {self.in_flight} loads in flight: aug_rng "
+                               "is not at the epoch's end")
 
     # ------------------------------------------------------------------------------------------------ one chunk
     def _samples(self, b0, b1):
@@ -202,6 +211,7 @@ class FrameLoader:
                 o = 0
                 for b in self.batches[b0:b1]:              # batches are views into the chunk's tensors
                     e = o + len(b)
+                    self._handed += 1
                     yield frames[o:e], [t[o:e] for t in lab], [t[o:e] for t in tp], [t[o:e] for t in tf]
                     o = e
         finally:

@@ -1,9 +1,12 @@
 """The epoch and checkpoint loop the four training drivers share (`Spatial_cnn`, `Spatial_transformer`, `Temporal_tenco`, `Temporal_mstct`
-`run.py -t`): the schedule flags, `lr_at_epoch`, the round-robin dealing of batches to ranks, the `Traning | lr:` line and one `weight_mgt`.
-Host code only: it imports without the HIP library."""
+`run.py -t`): the schedule flags, `lr_at_epoch`, the round-robin dealing of batches to ranks, the `Traning | lr:` line, one `weight_mgt`, and
+the resume state of --resume (`load_resume`, `resume_file`).  Host code only: it imports without the HIP library."""
 from __future__ import annotations
 
 import argparse
+import hashlib
+import io
+import json
 import os
 import time
 from typing import Callable, Dict, List, Tuple
@@ -71,27 +74,186 @@ def save_atomic(state: Dict[str, torch.Tensor], path: str):
             os.remove(tmp)
 
 
+# ------------------------------------------------------------------------------------------------ --resume
+# The resume state of a run lives beside its newest checkpoint `<latest>` (which stays the plain state dict it always was):
+#   <latest>.resume          rank 0: {"format", "world", "records": [newest, the one before]}, a record = {"epoch": the last completed epoch,
+#                            "top": the best score so far, "digest": "sha256:<hex of the <latest> bytes it belongs to>", "generators": {name: state}}
+#   <latest>.resume.rank<r>  rank r > 0: {"format", "world", "rank", "records": [...]}, a record = {"epoch", "generators"} -- that rank's own draws
+# JSON, readable with any editor.  TWO records are kept because the pair cannot be replaced in one step: the sidecar is replaced first, then
+# `<latest>`; a run killed in between leaves the new sidecar beside the old `<latest>`, whose digest the older record still names.
+RESUME_SUFFIX = ".resume"
+_RESUME_FORMAT = 1
+
+
+def resume_file(latest: str, rank: int = 0) -> str:
+    """the file rank `rank` keeps its resume state in, beside the checkpoint `latest`"""
+    return latest + RESUME_SUFFIX + (f".rank{rank}" if rank else "")
+
+
+def _digest(data) -> str:
+    return "sha256:" + hashlib.sha256(data).hexdigest()
+
+
+def _file_digest(path: str) -> str:
+    h = hashlib.sha256()
+    with open(path, "rb") as f:
+        for block in iter(lambda: f.read(1 << 24), b""):
+            h.update(block)
+    return "sha256:" + h.hexdigest()
+
+
+def _generator_state(g):
+    """a host generator's state as JSON: `random.Random`-like objects (getstate / setstate), `torch.Generator`-like ones (get_state / set_state)"""
+    if hasattr(g, "getstate"):
+        version, words, gauss = g.getstate()
+        return {"py": [version, list(words), gauss]}
+    if hasattr(g, "get_state"):
+        return {"torch": bytes(g.get_state().tolist()).hex()}
+    raise TypeError(f"a generator handed to run_epochs needs getstate/setstate or get_state/set_state: {type(g).__name__}")
+
+
+def _set_generator_state(g, s):
+    if "py" in s:
+        version, words, gauss = s["py"]
+        g.setstate((version, tuple(words), gauss))
+    else:
+        g.set_state(torch.tensor(list(bytes.fromhex(s["torch"])), dtype=torch.uint8))
+
+
+def _write_json_atomic(obj, path: str):
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    tmp = path + ".tmp"
+    try:
+        with open(tmp, "w") as f:
+            json.dump(obj, f)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def _read_json(path: str) -> dict:
+    try:
+        with open(path) as f:
+            obj = json.load(f)
+        if obj.get("format") != _RESUME_FORMAT or not isinstance(obj.get("records"), list):
+            raise ValueError("not a resume state of this format")
+        return obj
+    except (OSError, ValueError, AttributeError) as e:
+        raise ValueError(f"--resume: {path} cannot be read as resume state ({e}); move it and the checkpoint beside it away to start a fresh run, "
+                         "or drop --resume to start again at epoch 0 from the checkpoint's weights") from None
+
+
+class Resume:
+    """what `load_resume` found: `epoch` = the last completed epoch (-1: a fresh run), `top`, this rank's generator states by name, and
+    `state_dict()` = the tensors of exactly the `<latest>` bytes the digest was checked on (None for a fresh run)"""
+
+    def __init__(self, epoch: int = -1, top: float = 0.0, generators: dict = None, data: bytes = None, record: dict = None):
+        self.epoch, self.top, self.generators, self._data, self.record = epoch, top, generators or {}, data, record
+
+    def state_dict(self):
+        return None if self._data is None else torch.load(io.BytesIO(self._data), map_location="cpu")
+
+
+def load_resume(latest: str, rank: int = 0, world: int = 1) -> Resume:
+    """--resume at the start of a run, before any model is built and without touching a file: a fresh `Resume` when there is no `latest`, the
+    state to continue from when its sidecar names the bytes of `latest`, ValueError otherwise (no sidecar: the checkpoint was written without
+    --resume; another `world`; no record with the digest of `latest`; rank > 0: no record of that epoch in its own file)"""
+    if not os.path.exists(latest):
+        return Resume()                                            # (a sidecar alone: the run died before its first checkpoint; it is overwritten)
+    side = resume_file(latest)
+    if not os.path.exists(side):
+        raise ValueError(f"--resume: {latest} has no resume state beside it ({side} is missing): it was written by a run without --resume.  "
+                         "Drop --resume to start again at epoch 0 from its weights, or move the checkpoint away to start a fresh run")
+    obj = _read_json(side)
+    if obj.get("world") != world:
+        raise ValueError(f"--resume: {side} was written by a run of {obj.get('world')} rank(s) and this one has {world}; the ranks' draws do not "
+                         "carry over.  Start it with the same number of ranks, or drop --resume to start again at epoch 0 from the weights")
+    with open(latest, "rb") as f:
+        data = f.read()
+    digest = _digest(data)
+    rec = next((r for r in obj["records"] if r.get("digest") == digest), None)
+    if rec is None:
+        raise ValueError(f"--resume: {latest} ({digest[:19]}...) is not the checkpoint {side} was written for (epochs "
+                         f"{[r.get('epoch') for r in obj['records']]}): it was replaced or its write was torn.  Put the matching file back, or move "
+                         "both away to start a fresh run, or drop --resume to start again at epoch 0 from these weights")
+    gens = rec["generators"]
+    if rank:
+        mine = resume_file(latest, rank)
+        if not os.path.exists(mine):
+            raise ValueError(f"--resume: rank {rank} has no resume state ({mine} is missing) for {latest}; restore it or start a fresh run")
+        own = _read_json(mine)
+        own_rec = next((r for r in own["records"] if r.get("epoch") == rec["epoch"]), None)
+        if own.get("world") != world or own_rec is None:
+            raise ValueError(f"--resume: {mine} (world {own.get('world')}, epochs {[r.get('epoch') for r in own['records']]}) does not belong to "
+                             f"epoch {rec['epoch']} of {side} (world {world}); restore the matching file or start a fresh run")
+        gens = own_rec["generators"]
+    return Resume(int(rec["epoch"]), float(rec["top"]), gens, data, rec)
+
+
+def _save_pair(state, latest: str, record: dict, older: list, world: int):
+    """`latest` and its sidecar: the checkpoint is written to its temporary file and digested there, the sidecar (the new record in front of
+    the one before) is replaced, then `latest` is.  Killed before the first replace: the old pair; between the two: the new sidecar, whose
+    older record names the old `latest`; after: the new pair"""
+    os.makedirs(os.path.dirname(latest) or ".", exist_ok=True)
+    tmp = latest + ".tmp"
+    try:
+        torch.save(state, tmp)
+        record["digest"] = _file_digest(tmp)
+        _write_json_atomic({"format": _RESUME_FORMAT, "world": world, "records": [record] + older[:1]}, resume_file(latest))
+        os.replace(tmp, latest)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
 def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]], validate: Callable[[dict], Tuple[float, str]],
                logfile: str, latest: str, best: str, latest_every_epoch: bool = False, score_key: str = "val_mAP",
-               epoch_note: Callable[[], str] = None) -> Dict[str, float]:
+               epoch_note: Callable[[], str] = None, generators: Dict[str, object] = None, resume: Resume = None,
+               world: int = None) -> Dict[str, float]:
     """--epochs epochs: `tr.lr` from the schedule, `train_epoch(epoch) -> (loss sum, steps)` runs the epoch's steps (it owns the data and
     every random draw), then rank 0 logs and runs `weight_mgt`, and all ranks meet at a barrier.  `weight_mgt` (`Spatial_cnn/run.py:258-269`,
     `Temporal_tenco/run.py:270-282`): every --val_interval epochs `validate(state) -> (score, "<head>: [<mAP>]")`, the best `.pth` by that
     score; `_latest` at validation epochs, or after every epoch with `latest_every_epoch`.  Returns the last epoch's loss and lr (+ its
-    validation score under `score_key`).  `epoch_note()`, if given, is appended to the epoch's `Traning |` line."""
+    validation score under `score_key`).  `epoch_note()`, if given, is appended to the epoch's `Traning |` line.
+
+    --resume (`F.resume`; off: every byte and line as above): `generators` = {name: the host generators `train_epoch` draws from}.  Whenever
+    `latest` is written its sidecar is too (`resume_file`: epoch, best score, world, the digest of the `latest` bytes, the generators' states;
+    ranks > 0 write their own generators' states), AFTER the epoch's validation and best `.pth`, so the record holds the score of its own
+    epoch.  `resume` = what `load_resume(latest, rank, world)` returned at the start of the run (loaded here when not given; the driver has
+    loaded `resume.state_dict()` into `tr`): the loop starts at the epoch after the recorded one with that `top` and those generator states.
+    {} when nothing is left to train."""
     val_interval = max(1, F.epochs - 1 if F.val_interval == -1 else F.val_interval)
-    top, last = 0.0, {}
-    for epoch in range(F.epochs):
+    top, last, first = 0.0, {}, 0
+    resuming = bool(getattr(F, "resume", False))
+    if resuming:
+        world = _dist()[1] if world is None else world
+        generators = generators or {}
+        resume = load_resume(latest, rank, world) if resume is None else resume
+        older = [resume.record] if resume.record else []           # rank 0: the record on disk that names the `latest` on disk
+        own_older = [{"epoch": resume.epoch, "generators": resume.generators}] if resume.epoch >= 0 else []
+        if resume.epoch >= 0:
+            if set(resume.generators) != set(generators):
+                raise ValueError(f"--resume: {resume_file(latest, rank)} holds the generators {sorted(resume.generators)} and this trainer draws "
+                                 f"from {sorted(generators)}; it belongs to another trainer or version: start a fresh run")
+            for name, g in generators.items():
+                _set_generator_state(g, resume.generators[name])
+            top, first = resume.top, resume.epoch + 1
+            if rank == 0:
+                _log(logfile, f"Resuming at epoch {first} (best so far {top:.5f})" if first < F.epochs else
+                     f"Resuming: epoch {resume.epoch} was the last of --epochs {F.epochs} (best so far {top:.5f}); nothing left to train")
+    for epoch in range(first, F.epochs):
         tr.lr = lr_at_epoch(epoch, F.initial_learning_rates[2], F.power, F.warmups[2], F.decay_rate)
         t0 = time.time()
         tot, steps = train_epoch(epoch)
         last = {"loss": tot / steps, "lr": tr.lr}
+        val = epoch % val_interval == 0
         if rank == 0:
             _log(logfile, f"Traning | lr: {tr.lr:.6f} | epoch {epoch} | loss {tot / steps:.4f} | {time.time() - t0:.2f} secs" + (epoch_note() if epoch_note else ""))
-            val = epoch % val_interval == 0
             if val or latest_every_epoch:
                 state = tr.state_dict()
-                save_atomic(state, latest)
+                if not resuming:
+                    save_atomic(state, latest)
             if val:
                 t1 = time.time()
                 score, shown = validate(state)
@@ -101,6 +263,17 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
                     save_atomic(state, best)
                     _log(logfile, f">>> Saving checkpoint for epoch {epoch + 1} at {best}, time {time.ctime()} ")
                 _log(logfile, f"\t\t\t\t\t\t\t video-wise | eta {time.time() - t1:.2f} secs | mAP => {shown} ")
+        if resuming and (val or latest_every_epoch):
+            gens = {name: _generator_state(g) for name, g in generators.items()}
+            if rank:
+                rec = {"epoch": epoch, "generators": gens}
+                _write_json_atomic({"format": _RESUME_FORMAT, "world": world, "rank": rank, "records": [rec] + own_older[:1]}, resume_file(latest, rank))
+                own_older = [rec]
+            _barrier()                                             # every other rank's record of this epoch is on disk before rank 0's names it
+            if rank == 0:
+                rec = {"epoch": epoch, "top": top, "generators": gens}
+                _save_pair(state, latest, rec, older, world)
+                older = [rec]
         _barrier()
     _barrier()                                                     # the last checkpoint is on disk before any rank goes on to -e
     return last
