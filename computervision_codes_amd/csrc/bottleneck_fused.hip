@@ -15,7 +15,7 @@
 // fragment is 1 KB contiguous = 8 full cache lines; read from the row-major packed layout it was 16 half lines, and with 136 KB of weights
 // per tile those were most of the kernel's L2 requests); pixel fragments from LDS rows of 64 channels (128 B, 16-byte chunks XOR-swizzled with row & 7).
 //   phase 1: x halo tile in K-chunks of 64 channels, global -> registers -> LDS, two chunks in flight; wave w computes channels 16w..16w+15
-//            of t1 for all 160 halo pixels; out-of-image halo pixels are written as zeros.
+//            of t1 for all 160 halo pixels; out-of-image halo pixels are loaded from the nearest pixel of the image and written as zeros.
 //   phase 2: conv2 from t1 (tap (kh, kw) of pixel (ty, tx) = t1 row (ty + kh) * 16 + tx + kw); wave w: 16 channels x 7 pixel tiles.
 //   phase 3: conv3 in two passes of 128 output channels; wave w owns channel tiles w, w + 4, w + 8, w + 12; residual added in the
 //            accumulator layout (identity blocks: picked out of the LDS copy of x chunk i during phase 1 -- no second read), result staged in
@@ -25,9 +25,24 @@
 // K order and MFMA chain (bias-initialised fp32 accumulator; K-steps of 64 channels ascending, 3x3: tap-major; two 32-wide MFMAs per step;
 // t1 / t2 / the downsample branch rounded to bf16 exactly where the layer-by-layer path stores them) are those of the stand-alone launches:
 // the result is bit-identical to conv1 -> conv2 -> conv3 through mt4_conv_nhwc.
+//
+// Waits.  hipcc counts vector-memory operations in issue order and waits with s_waitcnt vmcnt(N) for "all but the N youngest"; an operation
+// behind a per-lane condition sits behind an execz branch and cannot be counted, so a wait for anything older than it becomes vmcnt(0).  What
+// this kernel does about it (tools/kernel_wait_map.py prints the order the compiled kernel issues loads, stores, waits, barriers and MFMAs in;
+// profiles/bottleneck_fused_wait_map.txt holds it before and after):
+//   - no load is conditional: halo pixels outside the image are clamped loads (phase 1), the biases are copied to LDS once per tile by an
+//     unconditional load + write and read from there, and whatever selects a load is a template parameter.  The x chunks kc + 1 and kc + 2 are
+//     then still outstanding across the MFMAs of chunk kc (vmcnt(15) / (14) in front of them; it was vmcnt(0), twice per tile).
+//   - the output stores stay behind their ragged-edge branches, so nothing is waited for behind them: pass 1's conv3 fragments are made to land
+//     before pass 0's stores, NEXT requests the following conv's fragments behind pass 0's stores and waits for them before pass 1's, and no
+//     bias load stands between the passes (each was an L2 round trip that also waited out the previous pass's stores).
+//   - the stores are non-temporal unconditionally (a runtime flag put a second branch in front of every one).
+// Loads into a struct (uint4, float4) that is only copied on stay in scratch in this form of the kernel: the staging uses native vectors.
 #include "mt4_common.h"
 
 namespace {
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TH = 8, TW = 14, NHALO = 160, NPX = 128;   // NPX: the 8 x 16 grid of phases 2 and 3 (14 of 16 columns are stored)
 constexpr int ROW_B = 128;                   // 64 bf16 channels
@@ -35,6 +50,10 @@ constexpr int XS_BYTES = NHALO * ROW_B;      // one K-chunk of the halo tile (al
 constexpr int T2_BYTES = NPX * ROW_B;
 constexpr int T1_BYTES = XS_BYTES + 2 * ROW_B;   // + the two slack rows the junk columns read
 constexpr int YS_BYTES = NPX * 256;          // one pass of the output staging: 128 channels per pixel
+// the biases live in LDS behind everything else, as floats: b1 | b2 | b3 | bds (downsample) or bn (NEXT)
+constexpr int BS_B1 = 0, BS_B2 = 64, BS_B3 = 128, BS_X = 384;
+constexpr int bias_floats(bool ds, bool next) { return BS_X + (ds ? 256 : next ? 128 : 0); }
+constexpr int main_lds_bytes(int cin, bool ds) { return (cin > 64 ? 2 : 1) * XS_BYTES + T2_BYTES + (ds ? YS_BYTES : T1_BYTES); }
 
 struct BneckK {
     const char* x;
@@ -42,7 +61,6 @@ struct BneckK {
     const char *w1, *w2, *w3, *wds;             // fragment-ordered weights (mt4_bottleneck_pack_bf16): [channel tile][K step of 32][lane] x 16 B
     const float *b1, *b2, *b3, *bds;
     int B, H, W, tiles_h, tiles_w;
-    int nt;                                  // non-temporal output stores
     // NEXT: the 1x1 conv that follows the block (conv1 + bn1 + relu of the strided Bottleneck behind it, 256 -> 128 channels) runs on the tile's
     // result while it is in LDS: y2 [B][H][W][128]; y itself is then stored at the even pixels only, [B][H2][W2][256] (all its other reader,
     // the stride-2 downsample branch, takes)
@@ -70,6 +88,13 @@ __device__ __forceinline__ f32x4 mfma_bf16(uint4 wfrag, uint4 xfrag, f32x4 acc) 
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wfrag), __builtin_bit_cast(bf16x8_t, xfrag), acc, 0, 0, 0);
 }
 
+// an explicit wait for a load: as an operand of the (empty) asm the value has to be in its registers, so hipcc puts the counted wait here
+__device__ __forceinline__ void landed(uint4& v) {
+    u32x4 t = {v.x, v.y, v.z, v.w};
+    asm volatile("" : "+v"(t));
+    v = make_uint4(t.x, t.y, t.z, t.w);
+}
+
 template <int CIN, bool DS, bool NEXT = false>
 __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK a) {
     static_assert(!NEXT || !DS, "the following conv rides behind an identity block");
@@ -83,6 +108,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
     char* const t2 = smem + NXS * XS_BYTES;
     char* const t1 = t2 + T2_BYTES;
     char* const ys = DS ? t1 : xs;
+    const float* const bs = (const float*)(smem + main_lds_bytes(CIN, DS));
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -106,44 +132,67 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
     // ---------------------------------------------------------------- phase 1: t1 = relu(W1 . x + b1) on the halo tile
     // staging: thread (row tid >> 3, chunk tid & 7) moves 16 bytes of halo pixels row, row + 32, ... (5 passes per K-chunk)
     const int ld_row = tid >> 3, ld_chunk = tid & 7;
-    int xoff[5];          // byte offset of the halo pixel in the image, -1 outside
+    // Every halo load is UNCONDITIONAL: a halo pixel outside the image reads the nearest pixel inside it (h clamped to [0, H - 1], w to
+    // [0, W - 1]) instead of being a "zero or load".  hipcc puts a load behind a per-lane condition behind its own execz branch and cannot
+    // count a load that may be skipped, so every wait for older data with such a load behind it became vmcnt(0): the prefetch of chunk
+    // kc + 2 was waited out in full in front of the MFMAs of chunk kc (tools/kernel_wait_map.py shows the order).  No select is needed
+    // afterwards.  The pixel tile is the MFMA B operand, so a halo pixel feeds its own column of conv1 only, and the t1 row of a pixel
+    // outside the image is written as zeros below whatever was computed for it (conv2's padding); the residual pick and the downsample GEMM
+    // read the x tile at the tile's own pixels only, which are in the image or (ragged tiles, the junk columns 14 / 15) never stored.
+    // Every address lies inside image `img`: h0 < H and w0 < W for every tile that exists (tiles_h = cdiv(H, TH), tiles_w = cdiv(W, TW)),
+    // so both clamps are onto a non-empty range and the offset is below H * W * CIN * 2 -- for the first and the last image of the batch, a
+    // 1 x 1 image (every halo pixel reads pixel (0, 0)) and ragged tiles (rows past H - 1 read row H - 1) alike.
+    int xoff[5];          // byte offset in the image of the halo pixel, clamped into it
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
         const int hp = ld_row + 32 * i;
-        const int h = h0 - 1 + (hp >> 4), w = w0 - 1 + (hp & 15);
-        xoff[i] = ((unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W) ? (h * a.W + w) * (CIN * 2) + ld_chunk * 16 : -1;
+        const int h = min(max(h0 - 1 + (hp >> 4), 0), a.H - 1), w = min(max(w0 - 1 + (hp & 15), 0), a.W - 1);
+        xoff[i] = (h * a.W + w) * (CIN * 2) + ld_chunk * 16;
     }
-    auto load_chunk = [&](int kc, uint4 (&stg)[5]) {
+    // (staging in a native vector: as uint4, a struct, the plain copy global -> stg -> LDS stayed in scratch)
+    auto load_chunk = [&](int kc, u32x4 (&stg)[5]) {
 #pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            stg[i] = make_uint4(0, 0, 0, 0);
-            if (xoff[i] >= 0) stg[i] = *(const uint4*)(ximg + xoff[i] + kc * 128);
-        }
+        for (int i = 0; i < 5; ++i) stg[i] = *(const u32x4*)(ximg + xoff[i] + kc * 128);
     };
-    auto store_chunk = [&](int buf, const uint4 (&stg)[5]) {
+    auto store_chunk = [&](int buf, const u32x4 (&stg)[5]) {
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
             const int hp = ld_row + 32 * i;
-            *(uint4*)(xs + buf * XS_BYTES + hp * ROW_B + ((ld_chunk ^ (hp & 7)) << 4)) = stg[i];
+            *(u32x4*)(xs + buf * XS_BYTES + hp * ROW_B + ((ld_chunk ^ (hp & 7)) << 4)) = stg[i];
         }
     };
-    uint4 stg0[5], stg1[5];
-    load_chunk(0, stg0);
-    if constexpr (KC > 1) load_chunk(1, stg1);
-
+    // The biases go to LDS once per tile (chain_gemm.hip does the same with B1s): a bias load in front of its first MFMA is an L2 round trip
+    // waited for with vmcnt(0), and in phase 3 that wait also drained the previous pass's output stores.  Thread f moves float4 f of
+    // b1 | b2 | b3 | bds or bn.  The load is the oldest of the tile, and load and LDS write are both unconditional (a write behind a condition
+    // takes its load with it): the threads past the end repeat what threads 0 .. 15 do, the same value to the same place.
+    constexpr int NB4 = bias_floats(DS, NEXT) / 4;
+    f32x4 bstg;
+    const int bslot = tid < NB4 ? tid : tid & 15;
+    {
+        const float* const bx = DS ? a.bds : NEXT ? a.bn : a.b1;
+        const float* const src = bslot < 16 ? a.b1 : bslot < 32 ? a.b2 : bslot < 96 ? a.b3 : bx;
+        const int idx = bslot < 16 ? bslot : bslot < 32 ? bslot - 16 : bslot < 96 ? bslot - 32 : bslot - 96;
+        bstg = *(const f32x4*)(src + idx * 4);
+    }
     const int ch1 = wave * 16;                       // this wave's 16 channels of t1 / t2
+    // conv1's fragments travel with the x chunk they multiply, in front of it: the MFMAs of chunk kc wait for nothing behind x chunk kc, and
+    // at most three chunks' fragments are held at a time instead of all KC * 2 from the start (beside two x chunks in flight, the 20 pixel
+    // fragments and the residual, phase 1 is where the register count peaks)
     uint4 wf1[KC * 2];
-    {
-        const char* wr = a.w1 + (wave * (KC * 2) * 64 + lane) * 16;       // channel tile `wave`, K step s: 64 lanes x 16 B contiguous
-#pragma unroll
-        for (int s = 0; s < KC * 2; ++s) wf1[s] = *(const uint4*)(wr + s * 1024);
+    const char* const wr1 = a.w1 + (wave * (KC * 2) * 64 + lane) * 16;    // channel tile `wave`, K step s: 64 lanes x 16 B contiguous
+    auto load_wf1 = [&](int kc) {
+        wf1[kc * 2] = *(const uint4*)(wr1 + kc * 2048);
+        wf1[kc * 2 + 1] = *(const uint4*)(wr1 + kc * 2048 + 1024);
+    };
+    u32x4 stg0[5], stg1[5];
+    load_wf1(0);
+    load_chunk(0, stg0);
+    if constexpr (KC > 1) {
+        load_wf1(1);
+        load_chunk(1, stg1);
     }
+    *(f32x4*)(smem + main_lds_bytes(CIN, DS) + bslot * 16) = bstg;      // visible behind the first barrier of phase 1
     f32x4 acc1[10];
-    {
-        const f32x4 b4 = bias4(a.b1, ch1 + q * 4);
-#pragma unroll
-        for (int i = 0; i < 10; ++i) acc1[i] = b4;
-    }
     const int sw0 = (q ^ (r16 & 7)) << 4, sw1 = ((4 + q) ^ (r16 & 7)) << 4;   // fragment chunk of kk = 0 / 1 in rows 16 i + r16
     // identity blocks: the residual of output channels 64 i + 16 wave + 4 q .. + 3 (channel tile 4 i + wave of pass i / 2) IS x chunk i at the
     // tile's own pixels -- picked out of the LDS copy of the chunk while it is there (row (j + 1) * 16 + r16 + 1 of the halo tile) instead of
@@ -154,8 +203,16 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
         if (kc & 1) store_chunk(1, stg1); else store_chunk(0, stg0);
-        if (kc + 2 < KC) { if (kc & 1) load_chunk(kc + 2, stg1); else load_chunk(kc + 2, stg0); }
+        if (kc + 2 < KC) {
+            load_wf1(kc + 2);
+            if (kc & 1) load_chunk(kc + 2, stg1); else load_chunk(kc + 2, stg0);
+        }
         __syncthreads();
+        if (kc == 0) {
+            const f32x4 b4 = bias4(bs + BS_B1, ch1 + q * 4);
+#pragma unroll
+            for (int i = 0; i < 10; ++i) acc1[i] = b4;
+        }
         const char* sb = xs + (kc & 1) * XS_BYTES + r16 * ROW_B;
         // all 20 fragments of the chunk go in flight before the first MFMA (left alone, hipcc pairs each read with its MFMA and every MFMA
         // waits out an LDS round trip); the empty asm keeps the reads above it
@@ -192,9 +249,8 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
         for (int i = 0; i < 10; ++i) {
             const int h = h0 - 1 + i;
             const bool in = (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W;
-            uint2 o = make_uint2(0, 0);
-            if (in) o = relu_pack4(acc1[i]);
-            *(uint2*)(t1 + i * (16 * ROW_B) + wr_off) = o;
+            const uint2 o = relu_pack4(acc1[i]);       // of a clamped pixel where !in: dropped here
+            *(uint2*)(t1 + i * (16 * ROW_B) + wr_off) = in ? o : make_uint2(0, 0);
         }
     }
     __syncthreads();
@@ -204,7 +260,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
     // Per accumulator the K order stays (kh, kw) ascending, kk inner.
     f32x4 acc2[8];
     {
-        const f32x4 b4 = bias4(a.b2, ch1 + q * 4);
+        const f32x4 b4 = bias4(bs + BS_B2, ch1 + q * 4);
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc2[j] = b4;
     }
@@ -269,13 +325,24 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
     for (int pass = 0; pass < 2; ++pass) {
         char* const ysp = NEXT ? xs + pass * YS_BYTES : ys;   // NEXT keeps both passes (the whole 256-channel tile) for phase 4
         if (pass && !NEXT) __syncthreads();              // the previous pass has been read back
+        if constexpr (NEXT) {
+            // the following conv's fragments: requested behind pass 0's stores and waited for (below) before pass 1's go out, with this
+            // pass's MFMAs in between -- no load is younger than a store when it is waited for, so phase 4 starts without touching the
+            // store queue (requested after pass 1's MFMAs and first used in phase 4, their wait drained pass 1's stores)
+            if (pass == 1) {
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+#pragma unroll
+                    for (int ks = 0; ks < 8; ++ks) wfn[c][ks] = *(const uint4*)(a.wn + (((2 * wave + c) * 8 + ks) * 64 + lane) * 16);
+            }
+        }
 #pragma unroll
         for (int ii = 0; ii < 2; ++ii) {
             const int i = pass * 2 + ii;
             const int ct = 4 * i + wave;                  // channel tile of y (16 channels)
             f32x4 acc3[8];
             {
-                const f32x4 b4 = bias4(a.b3, ct * 16 + q * 4);
+                const f32x4 b4 = bias4(bs + BS_B3, ct * 16 + q * 4);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc3[j] = b4;
             }
@@ -284,7 +351,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc3[j] = mfma_bf16(wf3[i][kk], fx3[j][kk], acc3[j]);
             if constexpr (DS) {
-                const f32x4 bd4 = bias4(a.bds, ct * 16 + q * 4);
+                const f32x4 bd4 = bias4(bs + BS_X, ct * 16 + q * 4);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {              // the pixel itself in the halo tile: row ty + 1, column shift 1
                     f32x4 accd = bd4;
@@ -310,12 +377,24 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
                 *(uint2*)(ysp + j * (16 * 256) + wr_off) = o;
             }
         }
+        if (pass == 0) {
+            // pass 1's fragments were requested in phase 2: have them landed before the first store goes out.  Left to their first use in
+            // pass 1, their counted wait stands behind pass 0's stores, which hipcc cannot count (each is behind a ragged-edge branch) --
+            // an older load waited for behind uncounted stores drains those stores just as a younger one does.
+#pragma unroll
+            for (int i = 2; i < 4; ++i)
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+                    landed(wf3[i][kk]);
+                    if constexpr (DS) landed(wfd[i][kk]);
+                }
+        }
         if constexpr (NEXT) {
-            if (pass == 1) {     // in flight across the barrier and the read-back
+            if (pass == 1) {     // the explicit wait: as an operand of the (empty) asm a fragment has to have landed
 #pragma unroll
                 for (int c = 0; c < 2; ++c)
 #pragma unroll
-                    for (int ks = 0; ks < 8; ++ks) wfn[c][ks] = *(const uint4*)(a.wn + (((2 * wave + c) * 8 + ks) * 64 + lane) * 16);
+                    for (int ks = 0; ks < 8; ++ks) landed(wfn[c][ks]);
             }
         }
         __syncthreads();
@@ -341,10 +420,8 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
 #pragma unroll
                 for (int ty = 0; ty < 8; ++ty) {
                     if (h0 + ty < a.H) {
-                        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                         char* yp = yimg + (unsigned)((h0 + ty) * a.W * 512) + (unsigned)(w * 512 + pass * 256 + st_chunk * 16);
-                        if (a.nt) __builtin_nontemporal_store((u32x4){v[ty].x, v[ty].y, v[ty].z, v[ty].w}, (u32x4*)yp);
-                        else *(uint4*)yp = v[ty];
+                        __builtin_nontemporal_store((u32x4){v[ty].x, v[ty].y, v[ty].z, v[ty].w}, (u32x4*)yp);
                     }
                 }
             }
@@ -356,7 +433,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
         f32x4 acc4[2][8];
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-            const f32x4 b4 = bias4(a.bn, (2 * wave + c) * 16 + q * 4);
+            const f32x4 b4 = bias4(bs + BS_X, (2 * wave + c) * 16 + q * 4);
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc4[c][j] = b4;
         }
@@ -392,10 +469,8 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
 #pragma unroll
             for (int ty = 0; ty < 8; ++ty) {
                 if (h0 + ty < a.H) {
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                     char* yp = y2img + (unsigned)(((h0 + ty) * a.W + w) * 256 + st_chunk * 16);
-                    if (a.nt) __builtin_nontemporal_store((u32x4){v[ty].x, v[ty].y, v[ty].z, v[ty].w}, (u32x4*)yp);
-                    else *(uint4*)yp = v[ty];
+                    __builtin_nontemporal_store((u32x4){v[ty].x, v[ty].y, v[ty].z, v[ty].w}, (u32x4*)yp);
                 }
             }
         }
@@ -411,10 +486,9 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused_kernel(const BneckK
 // fragments' 64-byte pieces, see the header), not occupancy.
 template <int CIN, bool DS, bool NEXT = false>
 int launch(const BneckK& a, hipStream_t stream) {
-    constexpr int NXS = CIN > 64 ? 2 : 1;
-    constexpr int LDS = NXS * XS_BYTES + T2_BYTES + (DS ? YS_BYTES : T1_BYTES);
+    constexpr int LDS = main_lds_bytes(CIN, DS) + bias_floats(DS, NEXT) * 4;
     static_assert(LDS <= 80 * 1024, "two workgroups per CU");
-    static_assert(!NEXT || LDS >= 2 * YS_BYTES, "both output passes stay in LDS");
+    static_assert(!NEXT || main_lds_bytes(CIN, DS) >= 2 * YS_BYTES, "both output passes stay in LDS");
     const long long nblk = (long long)a.B * a.tiles_h * a.tiles_w;
     return mt4_launch<bottleneck64_fused_kernel<CIN, DS, NEXT>>(dim3((unsigned)nblk), dim3(256), LDS, stream, a);
 }
@@ -477,7 +551,6 @@ extern "C" int mt4_bottleneck_fused_bf16(const void* x, void* y, const void* w_f
     a.b1 = b1; a.b2 = b2; a.b3 = b3; a.bds = bds;
     a.B = B; a.H = H; a.W = W;
     a.tiles_h = cdiv(H, TH); a.tiles_w = cdiv(W, TW);
-    a.nt = 1;
     if ((long long)B * a.tiles_h * a.tiles_w > 0x7fffffffLL) return MT4_EUNSUPPORTED;
     return ds ? launch<64, true>(a, (hipStream_t)stream) : launch<256, false>(a, (hipStream_t)stream);
 }
@@ -517,7 +590,6 @@ extern "C" int mt4_bottleneck_fused_next_bf16(const void* x, void* y_even, void*
     a.wn = (const char*)w_next; a.bn = b_next;
     a.B = B; a.H = H; a.W = W; a.H2 = (H + 1) / 2; a.W2 = (W + 1) / 2;
     a.tiles_h = cdiv(H, TH); a.tiles_w = cdiv(W, TW);
-    a.nt = 1;
     if ((long long)B * a.tiles_h * a.tiles_w > 0x7fffffffLL) return MT4_EUNSUPPORTED;
     return launch<256, false, true>(a, (hipStream_t)stream);
 }
