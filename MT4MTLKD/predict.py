@@ -1,0 +1,11 @@
+#!/usr/bin/env python3
+"""MI355X entry point without a reference counterpart: frames of a video -> per-frame top-K triplet predictions in one pass
+(student -> temporal head -> `mt4_topk_rows_f32`; see computervision_codes_amd/drivers.py `predict`).  One process; no label files."""
+import os
+import sys
+
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+from computervision_codes_amd.drivers import predict  # noqa: E402
+
+if __name__ == "__main__":
+    predict(sys.argv[1:])

@@ -1049,6 +1049,92 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
                       generators={"order_rng": order_rng, "aug_rng": aug_rng}, resume=resume)
 
 
+# ------------------------------------------------------------------------------------------------ predict.py (no reference counterpart)
+def _predict_parser() -> argparse.ArgumentParser:
+    """the shared flags, the stage flags of the student (`spatial_cnn`) and of the temporal head (`tenco`), and predict.py's own"""
+    p = argparse.ArgumentParser()
+    _common(p)
+    for stage in ("spatial_cnn", "tenco"):
+        for names, kw in _FLAGS[stage][0]:
+            p.add_argument(*names, **kw)
+    p.add_argument("--student_ckpt", type=str, default="", help="the student's checkpoint (required)")
+    p.add_argument("--temporal_ckpt", type=str, default="", help="a Temporal_tenco checkpoint; empty: the student's own heads are decoded")
+    p.add_argument("--frames_dir", type=str, action="append", default=[], help="a directory of *.png, one video, frames in sorted name order; may be repeated")
+    p.add_argument("--videos", type=str, nargs="*", default=[], help="videos read from <data_dir>/data/<video>")
+    p.add_argument("--out", type=str, default="./predictions")
+    p.add_argument("--topk", type=int, default=5)
+    p.add_argument("--threshold", type=float, default=0.5)
+    p.add_argument("--names", type=str, default="", help="one line per triplet id, with an optional `id:` prefix")
+    p.add_argument("--save_scores", action="store_true", help="the four heads' full sigmoid score matrices into the .npz")
+    p.add_argument("--segments", action="store_true", help="also <video>.segments.csv: runs of frames in which a triplet is above --threshold")
+    return p
+
+
+def _predict_inputs(F):
+    """everything of predict.py's command line that can be wrong, looked at BEFORE any model is built -> ([(video name, frame paths)], triplet
+    names or None); every message names its flag"""
+    from . import ops, predict as P
+    if not F.student_ckpt:
+        raise ValueError("--student_ckpt FILE is required")
+    for flag, path in (("--student_ckpt", F.student_ckpt), ("--temporal_ckpt", F.temporal_ckpt), ("--names", F.names)):
+        if path and not os.path.isfile(path):
+            raise FileNotFoundError(f"{flag} {path}: no such file")
+    if not 1 <= F.topk <= ops.TOPK_MAX_K:
+        raise ValueError(f"--topk {F.topk}: 1..{ops.TOPK_MAX_K}")
+    if not 0.0 < F.threshold < 1.0:
+        raise ValueError(f"--threshold {F.threshold}: a score strictly between 0 and 1")
+    dirs = [("--frames_dir", os.path.basename(os.path.normpath(d)) or "video", d) for d in F.frames_dir]
+    dirs += [("--videos", v, os.path.join(F.data_dir, "data", v)) for v in F.videos]
+    if not dirs:
+        raise ValueError("nothing to predict: give --frames_dir DIR (may be repeated) or --videos VID ...")
+    videos = []
+    for flag, name, d in dirs:
+        if not os.path.isdir(d):
+            raise FileNotFoundError(f"{flag} {name}: {d} is not a directory")
+        frames = sorted(f for f in os.listdir(d) if f.lower().endswith(".png"))
+        if not frames:
+            raise ValueError(f"{flag} {name}: no *.png in {d}")
+        if name in [n for n, _ in videos]:
+            raise ValueError(f"{flag} {name}: two videos of this name would write the same files in --out")
+        videos.append((name, [os.path.join(d, f) for f in frames]))
+    return videos, P.parse_names(F.names) if F.names else None
+
+
+def predict(argv=None):
+    """`MT4MTLKD/predict.py`: frames -> per-frame top-K triplets in one pass and one process.  Every video (a --frames_dir directory, or
+    --videos under --data_dir/data) goes through `predict.Predictor`: PNG decode + Resize, the student in passes of --device_batch, the
+    whole-video TCN of --temporal_ckpt on the features left on the device (without it: the student's own heads), `mt4_topk_rows_f32`, one D2H
+    copy; --out/<video>.npz and .csv (`Prediction.save`), with --segments also <video>.segments.csv.  No label file is opened.
+    -> {video -> Prediction}"""
+    from . import predict as P
+    F = _predict_parser().parse_known_args(argv)[0]
+    videos, names = _predict_inputs(F)
+    F.test_ckpt = None                                               # (the files are --student_ckpt / --temporal_ckpt, whatever --test_ckpt says)
+    student = _eval_model("spatial_cnn", F, [F.student_ckpt])
+    temporal = _eval_model("tenco", F, [F.temporal_ckpt]) if F.temporal_ckpt else None
+    if temporal is None:
+        print("no --temporal_ckpt: the student's own i / v / t / ivt heads are decoded, frame by frame", flush=True)
+    pr = P.Predictor(student, temporal, height=F.image_height, width=F.image_width, device_batch=F.device_batch, png_decode=F.png_decode,
+                     decode_workers=F.decode_workers, topk=F.topk, threshold=F.threshold)
+    os.makedirs(F.out, exist_ok=True)
+    out = {}
+    for name, paths in videos:
+        t0 = time.time()
+        try:
+            pred = pr.predict_paths(paths, keep_scores=F.save_scores)
+        except ValueError as e:                                      # (--hier on a video too short for the pooled levels: the model's own words)
+            raise ValueError(f"{name} ({len(paths)} frames): {e}") from e
+        pred.save(os.path.join(F.out, name), names)
+        note = ""
+        if F.segments:
+            segs = P.segments(pred)
+            P.save_segments(os.path.join(F.out, name + ".segments.csv"), segs, pred.frames, names)
+            note = f" | {len(segs)} segments"
+        print(f"{name}: {len(paths)} frames | {float(pred.n_active.mean()):.2f} triplets above {F.threshold:g} per frame{note} | {time.time() - t0:.3f} s", flush=True)
+        out[name] = pred
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ run.py: -t, then -e
 def _run(argv, train, evaluate):
     """a stage's `run.py`: -t trains, -e evaluates the test split and writes the closing report; -> the evaluation's result, else the training's"""

@@ -1505,6 +1505,56 @@ def rank_hist(scores: torch.Tensor, targets: torch.Tensor, k: Optional[int] = No
     return out
 
 
+# ----------------------------------------------------------------------------------------- decoding logits (predict.py)
+TOPK_MAX_COLS, TOPK_MAX_K = 256, 32     # the limits of `mt4_topk_rows_f32`
+
+
+def _topk_layout(x: torch.Tensor):
+    """(row_stride, col_stride) of a 2-D view as `mt4_topk_rows_f32` takes them -- row-major with a row pitch >= cols, or [K, T] with the unit
+    stride along the rows and a column pitch >= rows -- or ValueError; the stride of a dimension of size 1 says nothing and is made to fit"""
+    rows, cols = x.shape
+    rs, cs = x.stride()
+    if cols == 1:
+        cs = 1
+    if rows == 1:
+        rs = cols if cs == 1 else 1
+    if (cs == 1 and rs >= cols) or (rs == 1 and cs >= rows):
+        return int(rs), int(cs)
+    raise ValueError(f"topk_rows: strides {tuple(x.stride())} of a {tuple(x.shape)} view are neither row-major with a row pitch >= {cols} nor "
+                     f"[K, T] with a column pitch >= {rows}")
+
+
+def topk_rows(x: torch.Tensor, k: int, count_above: Optional[float] = None):
+    """(ids int32 [rows, k], vals fp32 [rows, k], n_above int32 [rows] | None) of a 2-D fp32 device view: column and value of the k largest
+    elements of every row, descending as floats compare, equal values lower column first -- the first k entries of `torch.sort(x, dim=1,
+    descending=True, stable=True)` --, and the number of columns > count_above (`mt4_topk_rows_f32`).  The view's strides are passed through
+    (row-major with a pitch, or the temporal head's [K, T] seen as [T, K]): no `.contiguous()` copy.  NaN input is outside the contract."""
+    _need_cuda(x)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"topk_rows: a 2-D float32 view, got {tuple(x.shape)} {x.dtype}")
+    rows, cols = x.shape
+    k = int(k)
+    if rows < 1 or cols < 1 or cols > TOPK_MAX_COLS or not 1 <= k <= min(cols, TOPK_MAX_K):
+        raise ValueError(f"topk_rows: rows >= 1, 1 <= cols <= {TOPK_MAX_COLS}, 1 <= k <= min(cols, {TOPK_MAX_K}); got {tuple(x.shape)}, k = {k}")
+    rs, cs = _topk_layout(x)
+    ids = torch.empty((rows, k), dtype=torch.int32, device=x.device)
+    vals = torch.empty((rows, k), dtype=torch.float32, device=x.device)
+    n_above = torch.empty(rows, dtype=torch.int32, device=x.device) if count_above is not None else None
+    check(lib.mt4_topk_rows_f32(x.data_ptr(), rows, cols, rs, cs, k, float(count_above) if count_above is not None else 0.0, ids.data_ptr(),
+                                vals.data_ptr(), n_above.data_ptr() if n_above is not None else None, _stream()), "mt4_topk_rows_f32")
+    return ids, vals, n_above
+
+
+def topk_rows_host(x, k: int, count_above: Optional[float] = None):
+    """the contract of `topk_rows` on the CPU, by `torch.sort(stable=True)`: what the kernel is tested against"""
+    x = torch.as_tensor(x).detach().to("cpu", torch.float32)
+    if x.dim() != 2 or not 1 <= int(k) <= x.shape[1]:
+        raise ValueError(f"topk_rows_host: a 2-D array and 1 <= k <= cols; got {tuple(x.shape)}, k = {k}")
+    vals, ids = torch.sort(x, dim=1, descending=True, stable=True)
+    n_above = (x > float(count_above)).sum(dim=1).to(torch.int32) if count_above is not None else None
+    return ids[:, :int(k)].to(torch.int32).contiguous(), vals[:, :int(k)].contiguous(), n_above
+
+
 # ----------------------------------------------------------------------------------------- Swin / Q2L training pieces (fp32)
 def gather_rows(x: torch.Tensor, row_map: torch.Tensor, *, l_out: int, l_in: int, group: int = 1, m_out: Optional[int] = None) -> torch.Tensor:
     """y[m][g*C:(g+1)*C] = x[(m // l_out) * l_in + map[(m % l_out) * group + g]]  (`mt4_gather_rows_f32`)"""

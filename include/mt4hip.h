@@ -772,6 +772,26 @@ int mt4_component_max_f32(const float* x, const int32_t* col_of_triplet, int32_t
 int mt4_rank_hist_f32(const float* scores, const float* targets, int64_t rows, int32_t k, int32_t ld, int64_t* hist, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Decoding logits into an answer (computervision_codes_amd/predict.py; no reference counterpart: its drivers rank scores against labels only).
+ */
+/* Per row the k largest of `cols` columns.  Element (r, c) is x[r * row_stride + c * col_stride] (strides in elements), float32 on the device.
+ * Two layouts, both read with unit stride:
+ *   row-major   col_stride == 1, row_stride >= cols   ([T, K] with a row pitch: the student's heads)
+ *   [K, T]      row_stride == 1, col_stride >= rows   (the temporal head as the reference lays it out; staged through LDS in 16-row tiles)
+ * (rows == 1 / cols == 1: the stride of that dimension is not looked at beyond being positive.)
+ *   ids, vals   int32 / float32 [rows][k], dense: column and value of the j-th largest element of row r.  Descending AS FLOATS COMPARE, equal
+ *               values (+0.0 == -0.0) lower column first, +-inf ordinary values: the first k entries of
+ *               torch.sort(x, dim=1, descending=True, stable=True).  vals are copies of the input's bits (no sigmoid: the caller applies it to
+ *               [rows][k], so the ranking never sees saturated, tied scores).  NaN input is OUTSIDE the contract: the order among and around
+ *               NaNs is unspecified (nothing is read or written out of bounds).
+ *   n_above     int32 [rows] or NULL: the number of columns with x > count_above (strict)
+ * One wave per row, k rounds of a wave-wide maximum over (value, column) pairs; no atomics: a repeated call gives the same bits.
+ * Enqueue-only, capturable.  MT4_EINVAL: x / ids / vals NULL, rows, cols, k or a stride <= 0; MT4_EUNSUPPORTED: cols > 256, k > 32, k > cols,
+ * strides of neither layout, more than 2^33 rows -- all before any launch: nothing is written. */
+int mt4_topk_rows_f32(const float* x, int64_t rows, int32_t cols, int64_t row_stride, int64_t col_stride, int32_t k, float count_above,
+                      int32_t* ids, float* vals, int32_t* n_above, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Backward pieces of the Swin + Query2Label teacher (what torch autograd derives inside Spatial_transformer/run.py:150-229 for
  * Spatial_transformer/models/swin_transformer.py and models/transformer.py).  float32.  LayerNorm / GELU / softmax / batched-GEMM
  * backward are the entry points above.
