@@ -141,6 +141,11 @@ SIGNATURES = {
     "mt4_mse_det_plan": (C.c_int, [C.c_int64] + _PLAN_OUT),
     "mt4_mse_det_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_float, _vp, C.c_int64, _vp]),
     "mt4_sgd_step_f32": (C.c_int, [_vp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, _vp]),
+    "mt4_grad_norm_plan": (C.c_int, [C.c_int64, C.POINTER(_i32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mt4_grad_norm_parts_f32": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "mt4_grad_guard_finalize": (C.c_int, [_vp, _i32, C.c_float, C.c_double, _i32, _vp, _vp, _vp]),
+    "mt4_sgd_step_guarded_f32": (C.c_int, [_vp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, _vp, _vp]),
+    "mt4_restore_if_skipped_f32": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
     "mt4_mul_add_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "mt4_transpose_pack_conv1d_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mt4_bn_stats_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i32, C.c_float, C.c_float, _vp]),

@@ -17,7 +17,7 @@ import torch
 
 from . import cholect, extract, featfile
 from .metrics import Recognition, final_report, gather_recognition, recognition_from
-from .trainloop import _barrier, _dist, _log, add_schedule_flags, deal, load_resume, run_epochs
+from .trainloop import LossMean, _barrier, _dist, _log, add_schedule_flags, deal, guard_flags, load_resume, run_epochs
 
 
 def extraction_batch(img_size, device_batch):
@@ -77,6 +77,17 @@ _RESUME = _flag("--resume", action="store_true",
                      "epoch, best score, world size, the digest of the `_latest` bytes, the host generators' states) and continue from it when it is there: "
                      "the epoch after the recorded one, with its learning rate, draws and best score.  The same command line can be issued again "
                      "after a kill; a `_latest` without matching resume state is refused.  `_latest.pth` itself stays the plain state dict")
+# --clip_grad_norm / --skip_nonfinite (not in the reference, which applies whatever gradient it gets): every trainer, `FlatTrainer.apply_update`
+_GUARD = [
+    _flag("--clip_grad_norm", type=float, default=0.0,
+          help="X > 0: the step's gradient (after the data-parallel exchange, weight decay not included) is scaled to the global L2 norm X when its "
+               "norm is larger -- torch.nn.utils.clip_grad_norm_'s coefficient min(1, X / (norm + 1e-6)), the norm taken in float64 on the device "
+               "(mt4_grad_norm_parts_f32 + mt4_grad_guard_finalize), no copy to the host; 0: off; negative: refused"),
+    _flag("--skip_nonfinite", action="store_true",
+          help="a step whose gradient holds a NaN or an Inf changes nothing: parameters and BatchNorm running statistics stay as they were "
+               "(mt4_sgd_step_guarded_f32, mt4_restore_if_skipped_f32; num_batches_tracked still advances), the epoch's loss is the mean over the "
+               "steps with a finite loss, and an epoch in which every step was skipped ends the run before a checkpoint is written"),
+]
 _DETERMINISTIC_STAGES = ("spatial_cnn", "tenco")
 _NOT_DETERMINISTIC = {
     "spatial_transformer": "the sequence trainers' reductions are not covered yet (csrc/seq_train_kernels.hip: LayerNorm dgamma/dbeta, the "
@@ -105,7 +116,7 @@ _FRAME_TRAIN = [
     _OPERAND_DTYPE,
     _DETERMINISTIC,
     _RESUME,
-]
+] + _GUARD
 # stage -> (the flags every entry point of the stage parses, the flags of its trainer alone), on top of `_common` and -- the trainer --
 # `add_schedule_flags`.  --teacher_dim: the student mixes in the 1536-wide Swin-L feature (`Spatial_cnn/run.py`), the transformer stage's
 # `loss_type all` variant the 512-wide ResNet-18 one (`Spatial_transformer/run.py:82`, `test.py:82`)
@@ -125,7 +136,7 @@ _FLAGS = {
     "mstct": ([_flag("--input_dim", type=int, default=1536),
                _flag("--final_embedding_dim", type=int, default=512)],
               [_flag("--num_clips", type=int, default=256, help="window length (the reference hard-codes 256, dataloader.py:237)"), _OPERAND_DTYPE,
-               _DETERMINISTIC, _RESUME]),
+               _DETERMINISTIC, _RESUME] + _GUARD),
     # --mask_draw / --subclip (not in the reference) device: the step's random pieces are drawn by HIP kernels from (seed, step) and whole-video
     # steps replay as hipGraphs; host: drawn with torch's generator and uploaded.  reference: `Temporal_tenco/dataloader.py:219-222` sub-clip sampling
     "tenco": ([_flag("--num_layers_PG", default=11, type=int),
@@ -138,7 +149,7 @@ _FLAGS = {
                _flag("--input_dim", type=int, default=512)],
               [_flag("--mask_draw", choices=("host", "device"), default="host"),
                _flag("--subclip", choices=("off", "reference"), default="off"),
-               _DETERMINISTIC, _RESUME]),
+               _DETERMINISTIC, _RESUME] + _GUARD),
 }
 _LATEST = {"spatial_cnn": "_latest.pth", "spatial_transformer": "_latest.pth", "tenco": "_latest.pth",
            "mstct": "latest.pth"}                            # <stem> + this = the trainer's newest checkpoint; MS-TCT: no underscore (`Temporal_mstct/run.py:268`)
@@ -165,6 +176,18 @@ def _deterministic(stage: str, F) -> bool:
         raise NotImplementedError(f"--deterministic: {_NOT_DETERMINISTIC[stage]}")
     print("--deterministic: fixed-order sums (per-workgroup partials + mt4_fold_parts_f32 / _f64) in place of float atomics", flush=True)
     return True
+
+
+def _guard(F) -> dict:
+    """--clip_grad_norm / --skip_nonfinite of a trainer, read before any model is built: a negative norm is refused, the mode is said once at
+    start; -> the trainer's keyword arguments"""
+    clip, skip = guard_flags(F)
+    if not clip >= 0:
+        raise ValueError(f"--clip_grad_norm {clip}: 0 (off) or a positive global L2 norm")
+    if clip > 0 or skip:
+        print("guarded update:" + (f" --clip_grad_norm {clip:g} (global L2 norm of the exchanged gradient, float64, on the device)" if clip > 0 else "")
+              + (" --skip_nonfinite (a step with a NaN / Inf gradient changes nothing)" if skip else ""), flush=True)
+    return {"clip_grad_norm": clip, "skip_nonfinite": skip}
 
 
 def _resume(F, latest: str):
@@ -559,6 +582,7 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     if F.loss_type not in ("all", "i", "v", "t"):
         raise ValueError("--loss_type all | i | v | t (`Spatial_cnn/run.py:165-192`)")
     single = F.loss_type != "all"
+    guard = _guard(F)
     rank, world = _dist()
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold)
@@ -567,7 +591,7 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     sd = student_start(F, latest, resume, say=print if rank == 0 else None)
     tr = SpatialCnnTrainer(F.network, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay, rates=F.rates, temp=float(F.temp),
                            teacher_dim=F.teacher_dim, loss_type=F.loss_type,
-                           operand_dtype=_dtype(F.operand_dtype), deterministic=_deterministic("spatial_cnn", F))
+                           operand_dtype=_dtype(F.operand_dtype), deterministic=_deterministic("spatial_cnn", F), **guard)
     tr.load_state_dict(sd)
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, kfold)
     labels = {v: cholect.load_labels(F.data_dir, v) for v in train_videos + val_videos}
@@ -582,19 +606,19 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     def train_epoch(epoch):
         order = list(samples)
         order_rng.shuffle(order)                             # the same permutation on every rank
-        mine, tot = deal(order, F.batch, world, rank), 0.0
+        mine, tot = deal(order, F.batch, world, rank), LossMean(guard["skip_nonfinite"])
         mark()
         try:
             if tables is not None:                           # --prefetch K: the same batches, loaded ahead in chunks (`loader.FrameLoader`)
                 from .loader import FrameLoader
                 with FrameLoader(F, mine, labels, tables, size, aug_rng, prefetch=F.prefetch, cache=cache) as batches:
                     for fb in batches:
-                        tot += tr.train_step(*fb)["loss"]
+                        tot.add(tr.train_step(*fb)["loss"])
                 batches.check_drained()                      # (--resume saves aug_rng's state behind this epoch: no chunk of it is still to draw)
-                return tot, len(mine)
+                return tot.total, tot.steps
             for batch in mine:
-                tot += tr.train_step(*_frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng, cache))["loss"]
-            return tot, len(mine)
+                tot.add(tr.train_step(*_frame_batch(F, batch, labels, tpred, tfeat, size, aug_rng, cache))["loss"])
+            return tot.total, tot.steps
         finally:
             if cache is not None:
                 cache.seal()                                 # what this epoch stored is readable from the next one on
@@ -671,11 +695,12 @@ def _tenco_train(F):
         # `loss_v`, `loss_t` stay the int 0 they start as (`run.py:190`) and `loss_i.item()` raises AttributeError at `run.py:214` in the first step
         raise NotImplementedError("Temporal_tenco training needs --fpn (Scripts/train_fold1.sh:28): without it the reference's train loop itself fails "
                                   "in its first step (run.py:190,214: .item() on the int 0 that loss_i stays when the model returns no per-component logits)")
+    guard = _guard(F)
     init = stem + _LATEST["tenco"]
     resume = _resume(F, init)
     tr = TencoTrainer(F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                       hier=bool(getattr(F, "hier", False)),      # --hier True: pooled refinement levels (`network.py:147,154-155`, `run.py:159-179`)
-                      deterministic=_deterministic("tenco", F))
+                      deterministic=_deterministic("tenco", F), **guard)
     from . import shapes, synth
     state = _latest_state(init, resume)
     if state is not None:
@@ -709,7 +734,7 @@ def _tenco_train(F):
     def train_epoch(epoch):
         order = list(train_videos)
         rng.shuffle(order)                                         # same permutation on every rank
-        mine, tot = deal(order, 1, world, rank), 0.0
+        mine, tot = deal(order, 1, world, rank), LossMean(guard["skip_nonfinite"])
         clips = {v: clip(xs[v].shape[1]) for v in order} if subclip else {}
         clipped[:] = [0, len(mine)]
         for i, (v,) in enumerate(mine):
@@ -720,13 +745,13 @@ def _tenco_train(F):
                 clipped[0] += not whole
                 x, z = x[:, s:s + n], z[s:s + n]
             if device_draw:                                        # Dropout2d + per-layer Dropout are always on in train mode
-                tot += tr.train_step(x, z, draws=(F.seed + rank, epoch * len(mine) + i), input_mask=bool(F.mask), use_graph=whole)[0]
+                tot.add(tr.train_step(x, z, draws=(F.seed + rank, epoch * len(mine) + i), input_mask=bool(F.mask), use_graph=whole)[0])
                 continue
             masks = tr.draw_masks(x.shape[1], gen)
             if not F.mask:                                         # (`network.py:123-127,194-196`); --mask gates the 75 % input mask only
                 masks["input_mask"] = None                         # (`network.py:43-48`)
-            tot += tr.train_step(x, z, masks=masks)[0]
-        return tot, len(mine)
+            tot.add(tr.train_step(x, z, masks=masks)[0])
+        return tot.total, tot.steps
 
     dev_metrics, val_labels = _device_metrics(F), {}
 
@@ -900,6 +925,7 @@ def _mstct_train(F):
     from .mstct_train import NCLS, MstctTrainer, draw_windows
     from . import shapes, synth
     _deterministic("mstct", F)
+    guard = _guard(F)
     rank, world = _dist()
     lt = F.loss_type
     if lt not in NCLS:
@@ -908,7 +934,7 @@ def _mstct_train(F):
     latest = stem + _LATEST["mstct"]
     resume = _resume(F, latest)
     tr = MstctTrainer(*_MSTCT_ARCH, F.input_dim, F.final_embedding_dim, lt, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
-                      operand_dtype=_dtype(F.operand_dtype))
+                      operand_dtype=_dtype(F.operand_dtype), **guard)
     state = _latest_state(latest, resume)
     if state is not None:
         tr.load_state_dict(state)
@@ -933,12 +959,12 @@ def _mstct_train(F):
         starts = draw_windows(lengths, win_rng, F.num_clips)                                       # same draw on every rank, before the shuffle
         order = list(train_videos)
         order_rng.shuffle(order)
-        mine, tot = deal(order, F.batch, world, rank), 0.0
+        mine, tot = deal(order, F.batch, world, rank), LossMean(guard["skip_nonfinite"])
         for s, vids in enumerate(mine):
             x = torch.stack([xs[v][starts[v]:starts[v] + F.num_clips] for v in vids])             # [B,T,D] frame-major
             z = torch.cat([zs[v][starts[v]:starts[v] + F.num_clips] for v in vids])               # [B*T,K]
-            tot += tr.train_step_btd(x, z, masks=tr.draw_masks_device(len(vids), F.num_clips, F.seed + rank, epoch * len(mine) + s))
-        return tot, len(mine)
+            tot.add(tr.train_step_btd(x, z, masks=tr.draw_masks_device(len(vids), F.num_clips, F.seed + rank, epoch * len(mine) + s)))
+        return tot.total, tot.steps
 
     dev_metrics, val_labels = _device_metrics(F), {}
 
@@ -972,6 +998,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     from . import shapes, synth
     F = _parser("spatial_transformer", True).parse_known_args(argv)[0]
     _deterministic("spatial_transformer", F)
+    guard = _guard(F)
     if F.loss_type not in ("i", "v", "t", "all"):
         raise ValueError("--loss_type i | v | t | all (`Spatial_transformer/run.py:168-197`)")
     single = F.loss_type != "all"
@@ -983,7 +1010,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     resume = _resume(F, latest)
     tr = Q2LTrainer(F.backbone, F.img_size, F.hidden_dim, F.loss_type, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                     drop_path_rate=F.drop_path_rate, operand_dtype=_dtype(F.operand_dtype),
-                    teacher_dim=F.teacher_dim, rates=F.rates, temp=float(F.temp))
+                    teacher_dim=F.teacher_dim, rates=F.rates, temp=float(F.temp), **guard)
     table = shapes.q2l_param_shapes(F.backbone, F.img_size, F.hidden_dim, F.loss_type, teacher_dim=F.teacher_dim)
     sd = synth.fill_from_shapes(table, seed=F.seed)          # deterministic synthetic start when no pretrained file is on disk
     # `build_backbone` (`backbone.py:188-196`): the upstream Swin checkpoint ../Pretrain/<file> ('model' entry, `head.*` dropped) into the backbone
@@ -1015,7 +1042,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
         from contextlib import nullcontext
         order = list(samples)
         order_rng.shuffle(order)                             # the same permutation on every rank
-        mine, tot = deal(order, F.batch, world, rank), 0.0
+        mine, tot = deal(order, F.batch, world, rank), LossMean(guard["skip_nonfinite"])
         mark()
         if tables is not None:                               # --prefetch K: the same batches, loaded ahead in chunks (`loader.FrameLoader`)
             from .loader import FrameLoader
@@ -1027,15 +1054,15 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
                 for s, (batch, (frames, lab, tp, tf)) in enumerate(zip(mine, loaded)):
                     masks = tr.draw_masks_device(len(batch), F.seed * 1000003 + rank, epoch * len(mine) + s)     # (a running step count)
                     if single:
-                        tot += tr.train_step(frames, lab["ivt".index(F.loss_type)], masks)
+                        tot.add(tr.train_step(frames, lab["ivt".index(F.loss_type)], masks))
                     else:
-                        tot += tr.train_step(frames, lab, masks, teacher_pred=tp, teacher_feat=tf)["loss"]
+                        tot.add(tr.train_step(frames, lab, masks, teacher_pred=tp, teacher_feat=tf)["loss"])
             if tables is not None:
                 source.check_drained()                       # (--resume saves aug_rng's state behind this epoch: no chunk of it is still to draw)
         finally:
             if cache is not None:
                 cache.seal()                                 # what this epoch stored is readable from the next one on
-        return tot, len(mine)
+        return tot.total, tot.steps
 
     val_labels = {}                                          # (--metrics device: the validation label rows on the GPU, uploaded once)
 

@@ -1,6 +1,8 @@
 """The host-side core of the four trainers: every trained tensor in ONE flat fp32 parameter buffer P and ONE flat gradient buffer G (packed
 GEMM layouts, every slot padded to 4 floats), the weight copies derived from the masters by one launch, and the data-parallel exchange of G
--- per-bucket all-reduces behind the backward or one flat all-reduce after it -- ahead of one `mt4_sgd_step_f32`.
+-- per-bucket all-reduces behind the backward or one flat all-reduce after it -- ahead of one `mt4_sgd_step_f32`, or, with a gradient-norm clip or
+the non-finite guard on, of the guarded update (norm and decisions taken on the device: `mt4_grad_norm_parts_f32`, `mt4_grad_guard_finalize`,
+`mt4_sgd_step_guarded_f32`).
 
 * `FlatParams` lays the slots out in the order they are declared, loads them from the reference state dict and exports P or G back in the
   reference's key names and shapes;
@@ -169,8 +171,15 @@ class FlatTrainer:
     bucket is complete and the bucket's all-reduce runs behind the backward of the earlier layers; otherwise `apply_update`
     all-reduces the whole of G once."""
 
-    def __init__(self, lr: float, weight_decay: float, device, process_group, overlap: bool = False):
+    def __init__(self, lr: float, weight_decay: float, device, process_group, overlap: bool = False, clip_grad_norm: float = 0.0,
+                 skip_nonfinite: bool = False):
+        """clip_grad_norm > 0: the exchanged gradient is scaled to that global L2 norm when it is longer; skip_nonfinite: a step whose exchanged
+        gradient holds a NaN or an Inf changes nothing (`apply_update`, the guarded update).  Both off: the plain `mt4_sgd_step_f32`."""
+        if not clip_grad_norm >= 0:
+            raise ValueError(f"clip_grad_norm {clip_grad_norm}: 0 (off) or a positive norm")
         self.lr, self.wd = lr, weight_decay
+        self.clip_grad_norm, self.skip_nonfinite = float(clip_grad_norm), bool(skip_nonfinite)
+        self._guard = None                          # (workspace, state, stats) of the guarded update, allocated at its first use
         self.dev, self.pg = torch.device(device), process_group
         self.exchange = True
         self.overlap = overlap
@@ -255,8 +264,44 @@ class FlatTrainer:
             scale = 1.0 / self._ddp_world()
         else:
             scale = allreduce_sum_flat(self.G, self.pg) if self.exchange else 1.0
-        ops.sgd_step(self.P, self.G, self.lr, self.wd, scale)
+        if not self.guarded:
+            ops.sgd_step(self.P, self.G, self.lr, self.wd, scale)
+            self._refresh()
+            return
+        # the guarded update: norm and decisions from the fully exchanged G -- the same on every rank (NaN and Inf survive a sum), so all ranks clip
+        # and skip alike without another collective -- taken on the device and read there by the update; no copy to the host
+        ws, state, stats = self._guard_buffers()
+        ops.grad_guard(self.G, scale, self.clip_grad_norm, self.skip_nonfinite, ws, state, stats)
+        ops.sgd_step_guarded(self.P, self.G, self.lr, self.wd, scale, state)
+        self._restore_skipped(state)
         self._refresh()
+
+    @property
+    def guarded(self) -> bool:
+        return self.clip_grad_norm > 0 or self.skip_nonfinite
+
+    def _guard_buffers(self):
+        if self._guard is None or self._guard[0].shape[0] != ops.grad_norm_plan(self.G.numel()).nparts or self._guard[0].device != self.G.device:
+            self._guard = ops.guard_buffers(self.G.numel(), self.G.device)
+        return self._guard
+
+    def _restore_skipped(self, state: torch.Tensor):
+        """buffers besides P that a skipped step must leave as they were (the student's BatchNorm running statistics)"""
+
+    def guard_state(self) -> dict:
+        """what the last guarded update decided: sumsq, norm, coef, skip, nonfinite (one device-to-host copy)"""
+        return ops.read_guard_state(self._guard_buffers()[1])
+
+    def guard_stats(self, reset: bool = False) -> dict:
+        """the guarded updates since the last reset: steps, skipped, clipped, norm_sum / norm_max / norm_mean over the steps not skipped (one
+        device-to-host copy)"""
+        stats = self._guard_buffers()[2]
+        out = ops.read_guard_stats(stats)
+        applied = out["steps"] - out["skipped"]
+        out["norm_mean"] = out["norm_sum"] / applied if applied else 0.0
+        if reset:
+            stats.zero_()
+        return out
 
 
 class GemmTrainer(FlatTrainer):

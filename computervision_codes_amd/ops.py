@@ -933,6 +933,113 @@ def sgd_step(p: torch.Tensor, g: torch.Tensor, lr: float, weight_decay: float, g
     check(lib.mt4_sgd_step_f32(p.data_ptr(), g.data_ptr(), p.numel(), lr, weight_decay, grad_scale, _stream()), "mt4_sgd_step_f32")
 
 
+# ----------------------------------------------------------------------------------------- guarded update (--clip_grad_norm, --skip_nonfinite)
+class GradNormPlan(NamedTuple):
+    """`mt4_grad_norm_plan`: the parts (a workgroup slot each) of the pass over a flat gradient of n elements, the elements of the gradient a part
+    covers and the workspace bytes = nparts x 16 (a part = float64 sum of squares, int64 count of non-finite elements); functions of n alone"""
+    nparts: int
+    part_elems: int
+    bytes: int
+
+
+GUARD_STATE_BYTES = 32        # mt4_guard_state: double sumsq, double norm, float coef, int32 skip, int64 nonfinite
+GUARD_STATS_BYTES = 40        # mt4_guard_stats: int64 steps, skipped, clipped; double norm_sum, norm_max
+
+
+def grad_norm_plan(n: int) -> GradNormPlan:
+    nparts, pe, nbytes = C.c_int32(), C.c_int64(), C.c_int64()
+    check(lib.mt4_grad_norm_plan(n, C.byref(nparts), C.byref(pe), C.byref(nbytes)), "mt4_grad_norm_plan")
+    return GradNormPlan(nparts.value, pe.value, nbytes.value)
+
+
+def guard_buffers(n: int, device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(workspace, state, stats) of the guarded update of n parameters: float64 tensors (8-byte words; the workspace [nparts, 2]), the stats zeroed"""
+    plan = grad_norm_plan(n)
+    return (torch.empty((plan.nparts, 2), dtype=torch.float64, device=device), torch.zeros(GUARD_STATE_BYTES // 8, dtype=torch.float64, device=device),
+            torch.zeros(GUARD_STATS_BYTES // 8, dtype=torch.float64, device=device))
+
+
+def _guard_record(t: torch.Tensor, nbytes: int, what: str) -> int:
+    _need_cuda(t)
+    if not t.is_contiguous() or t.numel() * t.element_size() < nbytes or t.data_ptr() % 8:
+        raise ValueError(f"{what}: needs a contiguous 8-byte aligned device tensor of at least {nbytes} bytes")
+    return t.data_ptr()
+
+
+def grad_guard(g: torch.Tensor, grad_scale: float, max_norm: float, skip_nonfinite: bool, workspace: torch.Tensor, state: torch.Tensor,
+               stats: torch.Tensor) -> None:
+    """the pass over the flat gradient g (`mt4_grad_norm_parts_f32`: per-workgroup float64 sums of squares and non-finite counts stored into
+    `workspace`) and the one-workgroup finalize behind it (`mt4_grad_guard_finalize`): `state` <- sumsq, norm = |grad_scale| sqrt(sumsq), the clip
+    coefficient min(1, max_norm / (norm + 1e-6)) (1 for max_norm 0 or a non-finite gradient), skip = skip_nonfinite and any non-finite element;
+    `stats` advances.  Everything stays on the device; read with `read_guard_state` / `read_guard_stats`"""
+    _need_cuda(g)
+    assert g.dtype == torch.float32 and g.is_contiguous()
+    if not max_norm >= 0:
+        raise ValueError(f"max_norm {max_norm}: 0 (no clip) or a positive norm")
+    plan = grad_norm_plan(g.numel())
+    ws, nbytes = check_workspace(workspace, DetPlan(0, plan.nparts, 2, plan.bytes), "grad_guard")
+    st, sa = _guard_record(state, GUARD_STATE_BYTES, "grad_guard state"), _guard_record(stats, GUARD_STATS_BYTES, "grad_guard stats")
+    check(lib.mt4_grad_norm_parts_f32(g.data_ptr(), g.numel(), ws, nbytes, _stream()), "mt4_grad_norm_parts_f32")
+    check(lib.mt4_grad_guard_finalize(ws, plan.nparts, grad_scale, float(max_norm), 1 if skip_nonfinite else 0, st, sa, _stream()),
+          "mt4_grad_guard_finalize")
+
+
+def sgd_step_guarded(p: torch.Tensor, g: torch.Tensor, lr: float, weight_decay: float, grad_scale: float, state: torch.Tensor) -> None:
+    """`sgd_step` with grad_scale x the state's clip coefficient; leaves p untouched when the state says skip (`mt4_sgd_step_guarded_f32`)"""
+    _need_cuda(p, g)
+    assert p.dtype == g.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous() and p.numel() == g.numel()
+    check(lib.mt4_sgd_step_guarded_f32(p.data_ptr(), g.data_ptr(), p.numel(), lr, weight_decay, grad_scale,
+                                       _guard_record(state, GUARD_STATE_BYTES, "sgd_step_guarded state"), _stream()), "mt4_sgd_step_guarded_f32")
+
+
+def restore_if_skipped(dst: torch.Tensor, src: torch.Tensor, state: torch.Tensor) -> None:
+    """dst <- src when the state says skip, nothing otherwise (`mt4_restore_if_skipped_f32`)"""
+    _need_cuda(dst, src)
+    assert dst.dtype == src.dtype == torch.float32 and dst.is_contiguous() and src.is_contiguous() and dst.numel() == src.numel()
+    check(lib.mt4_restore_if_skipped_f32(dst.data_ptr(), src.data_ptr(), dst.numel(), _guard_record(state, GUARD_STATE_BYTES, "restore_if_skipped state"),
+                                         _stream()), "mt4_restore_if_skipped_f32")
+
+
+def read_guard_state(state: torch.Tensor) -> dict:
+    """mt4_guard_state on the host (one device-to-host copy): sumsq, norm, coef, skip, nonfinite"""
+    import struct
+    sumsq, norm, coef, skip, bad = struct.unpack("<ddfiq", state.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()[:GUARD_STATE_BYTES])
+    return {"sumsq": sumsq, "norm": norm, "coef": coef, "skip": skip, "nonfinite": bad}
+
+
+def read_guard_stats(stats: torch.Tensor) -> dict:
+    """mt4_guard_stats on the host (one device-to-host copy): steps, skipped, clipped, norm_sum and norm_max over the steps not skipped"""
+    import struct
+    steps, skipped, clipped, nsum, nmax = struct.unpack("<qqqdd", stats.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()[:GUARD_STATS_BYTES])
+    return {"steps": steps, "skipped": skipped, "clipped": clipped, "norm_sum": nsum, "norm_max": nmax}
+
+
+def guarded_sgd_host(p: torch.Tensor, g: torch.Tensor, lr: float, weight_decay: float, grad_scale: float = 1.0, max_norm: float = 0.0,
+                     skip_nonfinite: bool = False):
+    """the guarded update restated on the host: the decisions of `mt4_grad_guard_finalize` in float64 (sumsq of the exact squares, norm =
+    |grad_scale| sqrt(sumsq), coef = float32(min(1, max_norm / (norm + 1e-6))) when max_norm > 0 and every element is finite, else 1; skip =
+    skip_nonfinite and any non-finite element) and the float32 expression of `mt4_sgd_step_guarded_f32`, p - lr (g (grad_scale coef) + wd p), every
+    scalar a float32.  -> (the new p, float32 on the CPU -- p's own values when skipped; {"sumsq", "norm", "coef", "skip", "nonfinite"})"""
+    import numpy as np
+    pn, gn = p.detach().cpu().numpy().astype(np.float32, copy=True), g.detach().cpu().numpy().astype(np.float32)
+    f32 = np.float32
+    with np.errstate(all="ignore"):
+        bad = int(np.count_nonzero(~np.isfinite(gn)))
+        g64 = gn.astype(np.float64).ravel()
+        sumsq = float(np.sum(g64 * g64))
+        norm = abs(float(f32(grad_scale))) * float(np.sqrt(sumsq))
+        coef = f32(1.0)
+        if max_norm > 0 and bad == 0:
+            r = float(max_norm) / (norm + 1e-6)
+            if r < 1.0:
+                coef = f32(r)
+        skip = bool(skip_nonfinite and bad > 0)
+        if not skip:
+            s = f32(grad_scale) * coef
+            pn = pn - f32(lr) * (gn * s + f32(weight_decay) * pn)
+    return torch.from_numpy(np.ascontiguousarray(pn, dtype=np.float32)), {"sumsq": sumsq, "norm": norm, "coef": float(coef), "skip": int(skip), "nonfinite": bad}
+
+
 def mul_add(a: torch.Tensor, b: torch.Tensor, c: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _need_cuda(a, b, c)
     assert a.is_contiguous() and b.is_contiguous() and a.dtype == torch.float32 and a.numel() == b.numel()

@@ -20,7 +20,7 @@ from typing import Dict, List, Sequence
 import torch
 
 from . import ops
-from .flatparams import FlatParams, FlatTrainer
+from .flatparams import FlatParams, FlatTrainer, _r4
 from .shapes import resnet_feat_dim, spatial_cnn_shapes
 
 _DEPTHS = {"resnet18": (2, 2, 2, 2), "resnet50": (3, 4, 6, 3)}
@@ -45,7 +45,8 @@ class SpatialCnnTrainer(FlatTrainer):
     _refresh_table = None
     def __init__(self, network: str = "resnet50", lr: float = 0.01, weight_decay: float = 1e-5, rates: Sequence[float] = (1.0, 1.0, 1.0),
                  temp: float = 4.0, device: str = "cuda", process_group=None, overlap: bool = True, teacher_dim: int = 1536,
-                 loss_type: str = "all", operand_dtype: torch.dtype = torch.float32, epilogue_stats: bool = True, deterministic: bool = False):
+                 loss_type: str = "all", operand_dtype: torch.dtype = torch.float32, epilogue_stats: bool = True, deterministic: bool = False,
+                 clip_grad_norm: float = 0.0, skip_nonfinite: bool = False):
         """loss_type 'all': the distillation recipe (four heads, KD branch, hard + soft + feature losses: `run.py:180-192`);
         'i' | 'v' | 't': a single-task student -- only that classifier exists (`network.py:34-41`) and the loss is its BCE alone
         (`run.py:165-179`)"""
@@ -70,7 +71,7 @@ class SpatialCnnTrainer(FlatTrainer):
         self.NH = sum(k for _, k in self.heads)
         self.NHP = (self.NH + 3) // 4 * 4
         # overlap: each gradient bucket is all-reduced as soon as the backward has written it (DDP, `FlatTrainer`)
-        super().__init__(lr, weight_decay, device, process_group, overlap)
+        super().__init__(lr, weight_decay, device, process_group, overlap, clip_grad_norm, skip_nonfinite)
         self.network, self.rates, self.temp = network, tuple(rates), float(temp)
         self.C = resnet_feat_dim(network)
         self.TD = int(teacher_dim)          # `--teacher_dim` (`Spatial_cnn/run.py:82`): width of the teachers' frame features
@@ -120,13 +121,21 @@ class SpatialCnnTrainer(FlatTrainer):
                 fp.lin(name, co, ci)
         self.fp = fp.build(sd, derive=False)    # (the derived copies: `_refresh_transposed`)
         trained = fp.keys() | {f"classifier_{t}.fc.{p}" for t, _ in self.heads for p in ("weight", "bias")}
+        # the running statistics of every BatchNorm in ONE flat buffer (a unit's mean, then its variance, each padded to 4 floats; `u.rmean` / `u.rvar`
+        # are views): --skip_nonfinite copies it aside before a step and `mt4_restore_if_skipped_f32` puts it back when the step is skipped
+        self._rstats = torch.zeros(sum(2 * _r4(co) for _, _, _, co, _, _, _ in specs), dtype=F32, device=dev)
+        self._rstats_keep = None
+        ro = 0
         for conv, bn, ci, co, k, s, pad in specs:
             u = _Unit()
             u.name, u.bn, u.cin, u.cout, u.k, u.stride, u.pad = conv, bn, ci, co, k, s, pad
             u.w, u.gw = fp.L[conv].w, fp.L[conv].gw
             u.gamma, u.ggamma = fp.V[bn + ".weight"].p, fp.V[bn + ".weight"].g
             u.beta, u.gbeta = fp.V[bn + ".bias"].p, fp.V[bn + ".bias"].g
-            u.rmean, u.rvar = sd[bn + ".running_mean"].float().to(dev).clone(), sd[bn + ".running_var"].float().to(dev).clone()
+            u.rmean, u.rvar = self._rstats[ro:ro + co], self._rstats[ro + _r4(co):ro + _r4(co) + co]
+            ro += 2 * _r4(co)
+            u.rmean.copy_(sd[bn + ".running_mean"].float())
+            u.rvar.copy_(sd[bn + ".running_var"].float())
             self.nbt[bn] = int(sd[bn + ".num_batches_tracked"])
             u.wt, u.phase_w = None, None
             u.w16, u.wt16, u.phase_w16 = None, None, None
@@ -186,6 +195,12 @@ class SpatialCnnTrainer(FlatTrainer):
         # (the linear layers' data gradients transpose their small weights on the fly in _linear_bwd)
 
     _refresh = _refresh_transposed      # (what `FlatTrainer.apply_update` runs after the update)
+
+    def _restore_skipped(self, state: torch.Tensor):
+        """a skipped step (--skip_nonfinite) leaves the BatchNorm running statistics as `train_step` found them; `num_batches_tracked`, a host
+        integer, has advanced all the same (as torch's does for a step GradScaler skips)"""
+        if self.skip_nonfinite and self._rstats_keep is not None:
+            ops.restore_if_skipped(self._rstats, self._rstats_keep, state)
 
     # ------------------------------------------------------------------ deterministic mode: the workspace
     def workspace_bytes(self, b: int, h: int, w: int) -> int:
@@ -351,6 +366,10 @@ class SpatialCnnTrainer(FlatTrainer):
         if self.deterministic:
             self._ensure_workspace(B, *(frames.shape[1:3] if frames.dtype == torch.uint8 else frames.shape[2:4]))
         self.bucket_order = []            # gradient buckets in the order their all-reduce was issued this step (DDP)
+        if self.skip_nonfinite:           # the running statistics as they are before the step, in one launch (`_restore_skipped`)
+            if self._rstats_keep is None or self._rstats_keep.shape != self._rstats.shape:
+                self._rstats_keep = torch.empty_like(self._rstats)
+            self._rstats_keep.copy_(self._rstats)
         if use_graph:
             col_loss, soft, kdl = self._graph_step((tuple(frames.shape), frames.dtype), lambda f, zz, *t: self._fwd_bwd(f, zz, t[:3], t[3:]),
                                                    [frames, z, *tp, *tf])

@@ -7,6 +7,7 @@ import argparse
 import hashlib
 import io
 import json
+import math
 import os
 import time
 from typing import Callable, Dict, List, Tuple
@@ -60,6 +61,25 @@ def deal(order: list, batch: int, world: int, rank: int) -> List[list]:
     in step s of ceil(nb / world), so every rank runs the same number of steps (the last step wraps around to the first batches)"""
     nb = (len(order) + batch - 1) // batch
     return [order[bi * batch:(bi + 1) * batch] for bi in ((s * world + rank) % nb for s in range((nb + world - 1) // world))]
+
+
+def guard_flags(F) -> Tuple[float, bool]:
+    """(--clip_grad_norm, --skip_nonfinite) of a trainer's flags; (0.0, False) where they are not declared"""
+    return float(getattr(F, "clip_grad_norm", 0.0) or 0.0), bool(getattr(F, "skip_nonfinite", False))
+
+
+class LossMean:
+    """the loss an epoch logs: `add(loss)` per step -> `total` / `steps`.  finite_only (--skip_nonfinite): a step whose loss is NaN or Inf is
+    left out of both, so the epoch's loss is the mean over the steps with a finite loss; otherwise the plain running sum over every step"""
+
+    def __init__(self, finite_only: bool = False):
+        self.finite_only, self.total, self.steps = bool(finite_only), 0.0, 0
+
+    def add(self, loss: float):
+        if self.finite_only and not math.isfinite(loss):
+            return
+        self.total += loss
+        self.steps += 1
 
 
 def save_atomic(state: Dict[str, torch.Tensor], path: str):
@@ -222,10 +242,16 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
     ranks > 0 write their own generators' states), AFTER the epoch's validation and best `.pth`, so the record holds the score of its own
     epoch.  `resume` = what `load_resume(latest, rank, world)` returned at the start of the run (loaded here when not given; the driver has
     loaded `resume.state_dict()` into `tr`): the loop starts at the epoch after the recorded one with that `top` and those generator states.
-    {} when nothing is left to train."""
+    {} when nothing is left to train.
+
+    --clip_grad_norm / --skip_nonfinite (`guard_flags`; both off: every byte and line as above): after an epoch's steps `tr.guard_stats(reset=True)`
+    is read once and the `Traning |` line gets `| gnorm mean M max X | clipped c | skipped k`; an epoch whose steps were ALL skipped raises a
+    RuntimeError before `latest` or `best` is written.  `train_epoch` sums its losses with `LossMean(skip_nonfinite)`."""
     val_interval = max(1, F.epochs - 1 if F.val_interval == -1 else F.val_interval)
     top, last, first = 0.0, {}, 0
     resuming = bool(getattr(F, "resume", False))
+    clip, skip_nonfinite = guard_flags(F)
+    guarded = clip > 0 or skip_nonfinite
     if resuming:
         world = _dist()[1] if world is None else world
         generators = generators or {}
@@ -246,10 +272,20 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
         tr.lr = lr_at_epoch(epoch, F.initial_learning_rates[2], F.power, F.warmups[2], F.decay_rate)
         t0 = time.time()
         tot, steps = train_epoch(epoch)
+        note = epoch_note() if epoch_note else ""
+        if guarded:                                                # one read of the trainer's device record per epoch; the same on every rank
+            gs = tr.guard_stats(reset=True)
+            if gs["steps"] > 0 and gs["skipped"] == gs["steps"]:   # before anything is written: a run that can no longer learn stops here
+                raise RuntimeError(f"epoch {epoch}: --skip_nonfinite skipped all {gs['steps']} steps (every gradient held a NaN or an Inf); no "
+                                   f"checkpoint was written for this epoch.  The parameters or the inputs are no longer finite: look at the data "
+                                   f"and at {latest} before starting again")
+            note += f" | gnorm mean {gs['norm_mean']:.4g} max {gs['norm_max']:.4g} | clipped {gs['clipped']} | skipped {gs['skipped']}"
+            if not steps:                                          # (no step with a finite loss, though some were applied)
+                tot, steps = float("nan"), 1
         last = {"loss": tot / steps, "lr": tr.lr}
         val = epoch % val_interval == 0
         if rank == 0:
-            _log(logfile, f"Traning | lr: {tr.lr:.6f} | epoch {epoch} | loss {tot / steps:.4f} | {time.time() - t0:.2f} secs" + (epoch_note() if epoch_note else ""))
+            _log(logfile, f"Traning | lr: {tr.lr:.6f} | epoch {epoch} | loss {tot / steps:.4f} | {time.time() - t0:.2f} secs" + note)
             if val or latest_every_epoch:
                 state = tr.state_dict()
                 if not resuming:

@@ -502,6 +502,41 @@ int mt4_mse_det_plan(int64_t n, int32_t* form, int32_t* nparts, int64_t* part_el
 int mt4_mse_det_f32(const float* a, const float* b, float* da, float* loss, int64_t n, float grad_scale, float* ws, int64_t ws_bytes, void* stream);
 /* torch.optim.SGD without momentum (run.py:343): p -= lr * (grad_scale * g + weight_decay * p) */
 int mt4_sgd_step_f32(float* p, const float* g, int64_t n, float lr, float weight_decay, float grad_scale, void* stream);
+/*
+ * Guarded update (no reference counterpart: torch.nn.utils.clip_grad_norm_ and GradScaler's skipped step are the nearest relatives).  Between "the
+ * flat gradient g is complete" and "p is updated" nothing is copied to the host: the norm, the clip coefficient and the decision to skip are made on
+ * the device and read by the update launch from device memory, so the sequence parts -> finalize -> update (-> restore) is legal inside a stream capture.
+ *
+ * mt4_grad_norm_plan (host only): nparts = ceil(n / part_elems) workgroups, each owning part_elems consecutive elements of g (a constant of the
+ * library: a function of n alone, not of the device), ws_bytes = nparts x 16.
+ * mt4_grad_norm_parts_f32: workgroup z reads g[z part_elems, min(n, (z + 1) part_elems)) once and STORES part z = { double sum of squares (a float's
+ * square is exact in double: only the additions round), int64 count of NaN / +-Inf elements } with one 16-byte store.  No atomics, nothing zeroed
+ * beforehand.  Order of additions: lane t of 256 takes the float4s t, t + 256, ... of the part, component e into its accumulator e front to back,
+ * then ((a0 + a1) + a2) + a3, the xor-shuffle tree 32, 16, .. 1 over a wave, the four waves front to back.  g 16-byte aligned, parts 16-byte aligned.
+ */
+typedef struct mt4_guard_state {
+    double sumsq;      /* sum of g[i]^2 */
+    double norm;       /* |grad_scale| sqrt(sumsq): the norm of the gradient the update applies */
+    float coef;        /* max_norm > 0 and no non-finite element: min(1, max_norm / (norm + 1e-6)) evaluated in double, rounded to float; else 1 */
+    int32_t skip;      /* skip_nonfinite && nonfinite > 0 */
+    int64_t nonfinite; /* NaN / +-Inf elements of g */
+} mt4_guard_state;
+typedef struct mt4_guard_stats {
+    int64_t steps, skipped, clipped; /* finalize calls; of them skipped; of the others, those with coef < 1 */
+    double norm_sum, norm_max;       /* over the steps that were not skipped */
+} mt4_guard_stats;
+int mt4_grad_norm_plan(int64_t n, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes);
+int mt4_grad_norm_parts_f32(const float* g, int64_t n, void* parts, int64_t parts_bytes, void* stream);
+/* One workgroup: sumsq = the parts' sums in the order of mt4_fold_parts_chunked_f64, nonfinite = the sum of their counts; writes *state and advances
+ * *stats (zeroed by its owner once), plain stores from one lane.  A gradient with non-finite elements and skip_nonfinite 0 is applied as it is: coef 1. */
+int mt4_grad_guard_finalize(const void* parts, int32_t nparts, float grad_scale, double max_norm, int32_t skip_nonfinite, mt4_guard_state* state,
+                            mt4_guard_stats* stats, void* stream);
+/* mt4_sgd_step_f32 with grad_scale * state->coef (one float multiply: coef 1 gives the bits of mt4_sgd_step_f32) in place of grad_scale; nothing is
+ * written when state->skip.  Weight decay is not part of the clipped norm, as in torch (the optimizer adds wd * p behind the clip). */
+int mt4_sgd_step_guarded_f32(float* p, const float* g, int64_t n, float lr, float weight_decay, float grad_scale, const mt4_guard_state* state,
+                             void* stream);
+/* dst[i] = src[i] for i < n when state->skip, nothing otherwise (buffers a skipped step must leave as they were: BatchNorm running statistics) */
+int mt4_restore_if_skipped_f32(float* dst, const float* src, int64_t n, const mt4_guard_state* state, void* stream);
 /* y = a * b (+ c): dropout masks (network.py:194-196) forward and backward */
 int mt4_mul_add_f32(const float* a, const float* b, const float* c, float* y, int64_t n, void* stream);
 /* packed Conv1d weight [Cout][Kpad(Cin,taps)] -> packed weight of its data-gradient conv [Cin][Kpad(Cout,taps)] */
