@@ -201,3 +201,152 @@ extern "C" int mt4_restore_if_skipped_f32(float* dst, const float* src, int64_t 
                        (long long)n, state);
     return mt4_check_launch();
 }
+
+// ------------------------------------------------------------------------------------------------ optimizer state (--momentum, --nesterov, --optimizer adamw)
+// Elementwise over the flat fp32 buffers: 16-byte loads and stores, the n % 4 tail element by element in the thread whose float4 it would be.  Every
+// operation below is ONE round-to-nearest IEEE operation in the order written (no FMA contraction: the pragma in each body), so that the numpy float32
+// restatement `ops.optim_step_host` gives the same bits.  guard == NULL: unguarded (coef 1, never skipped).
+
+// the step record of AdamW: advanced by one thread ahead of the update unless the guard says skip; IEEE double multiplies
+__global__ void optim_advance_kernel(mt4_optim_state* __restrict__ os, double beta1, double beta2, const mt4_guard_state* __restrict__ guard) {
+    if (guard && guard->skip) return;
+    os->t += 1;
+    os->beta1_pow *= beta1;
+    os->beta2_pow *= beta2;
+}
+
+extern "C" int mt4_optim_advance(mt4_optim_state* optim_state, double beta1, double beta2, const mt4_guard_state* guard_state, void* stream) {
+    mt4_clear_error();
+    if (!optim_state || !(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.)) return MT4_EINVAL;
+    if ((((uintptr_t)optim_state) | (uintptr_t)guard_state) & 7) return MT4_EINVAL;
+    hipLaunchKernelGGL(optim_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, optim_state, beta1, beta2, guard_state);
+    return mt4_check_launch();
+}
+
+// torch.optim.SGD(momentum, dampening 0, nesterov).  Per thread: s = grad_scale * coef (float).  Per element, all float:
+//   d = g * s + wd * p;   m' = mom * m + d;   u = nesterov ? d + mom * m' : m';   p' = p - lr * u
+__device__ __forceinline__ void sgdm_elem(float& p, float g, float& m, float lr, float wd, float s, float mom, int nesterov) {
+#pragma clang fp contract(off)
+    const float gs = g * s;
+    const float wp = wd * p;
+    const float d = gs + wp;
+    const float mm = mom * m;
+    const float mn = mm + d;
+    float u = mn;
+    if (nesterov) {
+        const float t = mom * mn;
+        u = d + t;
+    }
+    const float lu = lr * u;
+    p = p - lu;
+    m = mn;
+}
+
+__global__ void sgd_momentum_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, long long n, float lr, float wd,
+                                    float grad_scale, float mom, int nesterov, const mt4_guard_state* __restrict__ guard) {
+#pragma clang fp contract(off)
+    if (guard && guard->skip) return;
+    const float s = guard ? grad_scale * guard->coef : grad_scale;
+    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i + 3 < n) {
+        float4 pv = *(float4*)(p + i), mv = *(float4*)(m + i);
+        const float4 gv = *(const float4*)(g + i);
+        sgdm_elem(pv.x, gv.x, mv.x, lr, wd, s, mom, nesterov); sgdm_elem(pv.y, gv.y, mv.y, lr, wd, s, mom, nesterov);
+        sgdm_elem(pv.z, gv.z, mv.z, lr, wd, s, mom, nesterov); sgdm_elem(pv.w, gv.w, mv.w, lr, wd, s, mom, nesterov);
+        *(float4*)(p + i) = pv;
+        *(float4*)(m + i) = mv;
+    } else {
+        for (long long j = i; j < n; ++j) sgdm_elem(p[j], g[j], m[j], lr, wd, s, mom, nesterov);
+    }
+}
+
+extern "C" int mt4_sgd_momentum_step_f32(float* p, const float* g, float* m, int64_t n, float lr, float weight_decay, float grad_scale,
+                                         float momentum, int32_t nesterov, const mt4_guard_state* guard_state, void* stream) {
+    mt4_clear_error();
+    if (!p || !g || !m || n <= 0 || !(momentum >= 0.f && momentum < 1.f) || (nesterov && momentum == 0.f)) return MT4_EINVAL;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m) & 15) || ((uintptr_t)guard_state & 7)) return MT4_EINVAL;
+    const long long threads = (n + 3) / 4;
+    if ((threads + 255) / 256 > 0x7fffffffLL) return MT4_EINVAL;
+    hipLaunchKernelGGL(sgd_momentum_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, (long long)n, lr,
+                       weight_decay, grad_scale, momentum, nesterov ? 1 : 0, guard_state);
+    return mt4_check_launch();
+}
+
+// torch.optim.AdamW (amsgrad off).  Per thread (K = the scalars every element shares):
+//   s    = grad_scale * coef                     float
+//   b1, b2 = (float)beta1, (float)beta2          float  (the betas arrive as doubles)
+//   c1   = (float)(1.0 - beta1), c2 = (float)(1.0 - beta2)        the subtraction in double, one rounding to float
+//   lw   = lr * wd                               float
+//   step = (float)((double)lr / (1.0 - beta1_pow))                double subtraction and division, one rounding to float
+//   r2   = (float)sqrt(1.0 - beta2_pow)                           double subtraction and square root, one rounding to float
+// Per element, all float:
+//   q = p - lw * p;   h = g * s;   m' = b1 * m + c1 * h;   v' = b2 * v + c2 * (h * h);   den = sqrt(v') / r2 + eps;   p' = q - step * (m' / den)
+struct adamw_k {
+    float s, b1, b2, c1, c2, lw, step, r2, eps;
+};
+
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, const adamw_k& K) {
+#pragma clang fp contract(off)
+    const float lp = K.lw * p;
+    const float q = p - lp;
+    const float h = g * K.s;
+    const float m1 = K.b1 * m;
+    const float m2 = K.c1 * h;
+    const float mn = m1 + m2;
+    const float hh = h * h;
+    const float v1 = K.b2 * v;
+    const float v2 = K.c2 * hh;
+    const float vn = v1 + v2;
+    const float sq = sqrtf(vn);                 // correctly rounded (llvm.sqrt.f32 under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt);
+    const float sr = sq / K.r2;                 // HIP's __fsqrt_rn is the native 1-ulp square root, so it is NOT used here; `/` is the IEEE quotient
+    const float den = sr + K.eps;
+    const float qu = mn / den;
+    const float up = K.step * qu;
+    p = q - up;
+    m = mn;
+    v = vn;
+}
+
+__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n, float lr,
+                             float wd, float grad_scale, double beta1, double beta2, float eps, const mt4_optim_state* __restrict__ os,
+                             const mt4_guard_state* __restrict__ guard) {
+#pragma clang fp contract(off)
+    if (guard && guard->skip) return;
+    adamw_k K;
+    K.s = guard ? grad_scale * guard->coef : grad_scale;
+    K.b1 = (float)beta1;
+    K.b2 = (float)beta2;
+    K.c1 = (float)(1.0 - beta1);
+    K.c2 = (float)(1.0 - beta2);
+    K.lw = lr * wd;
+    const double bc1 = 1.0 - os->beta1_pow, bc2 = 1.0 - os->beta2_pow;
+    K.step = (float)((double)lr / bc1);
+    K.r2 = (float)sqrt(bc2);
+    K.eps = eps;
+    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i + 3 < n) {
+        float4 pv = *(float4*)(p + i), mv = *(float4*)(m + i), vv = *(float4*)(v + i);
+        const float4 gv = *(const float4*)(g + i);
+        adamw_elem(pv.x, gv.x, mv.x, vv.x, K); adamw_elem(pv.y, gv.y, mv.y, vv.y, K);
+        adamw_elem(pv.z, gv.z, mv.z, vv.z, K); adamw_elem(pv.w, gv.w, mv.w, vv.w, K);
+        *(float4*)(p + i) = pv;
+        *(float4*)(m + i) = mv;
+        *(float4*)(v + i) = vv;
+    } else {
+        for (long long j = i; j < n; ++j) adamw_elem(p[j], g[j], m[j], v[j], K);
+    }
+}
+
+extern "C" int mt4_adamw_step_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float weight_decay, float grad_scale,
+                                  double beta1, double beta2, float eps, const mt4_optim_state* optim_state, const mt4_guard_state* guard_state,
+                                  void* stream) {
+    mt4_clear_error();
+    if (!p || !g || !m || !v || !optim_state || n <= 0 || !(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.) || !(eps > 0.f))
+        return MT4_EINVAL;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) || (((uintptr_t)optim_state | (uintptr_t)guard_state) & 7)) return MT4_EINVAL;
+    const long long threads = (n + 3) / 4;
+    if ((threads + 255) / 256 > 0x7fffffffLL) return MT4_EINVAL;
+    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, lr,
+                       weight_decay, grad_scale, beta1, beta2, eps, optim_state, guard_state);
+    return mt4_check_launch();
+}

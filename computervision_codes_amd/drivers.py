@@ -88,6 +88,22 @@ _GUARD = [
                "(mt4_sgd_step_guarded_f32, mt4_restore_if_skipped_f32; num_batches_tracked still advances), the epoch's loss is the mean over the "
                "steps with a finite loss, and an epoch in which every step was skipped ends the run before a checkpoint is written"),
 ]
+# --momentum / --nesterov / --optimizer / --adam_betas / --adam_eps: every trainer, `FlatTrainer.apply_update` (`flatparams.Optim`)
+_OPTIM = [
+    _flag("--momentum", type=float, default=0.0,
+          help="SGD momentum M in [0, 1) (torch.optim.SGD, dampening 0; mt4_sgd_momentum_step_f32).  The default 0.0 is the reference's EFFECTIVE "
+               "value: every driver of it declares --momentum with default 0.95 (Spatial_cnn/run.py:72, Spatial_transformer/run.py:72, "
+               "Temporal_mstct/run.py:73, Temporal_tenco/run.py:66) and none hands it to torch.optim.SGD (:344, :360, :345, :346).  The clip of "
+               "--clip_grad_norm scales the gradient before it enters the momentum buffer; without --skip_nonfinite a non-finite gradient "
+               "poisons the buffer for good, as it does in torch"),
+    _flag("--nesterov", action="store_true", help="the Nesterov form of the momentum update (needs --momentum > 0)"),
+    _flag("--optimizer", type=str, default="sgd", choices=["sgd", "adamw"],
+          help="the update rule: sgd (with --momentum / --nesterov) or adamw (torch.optim.AdamW, amsgrad off, decoupled --weight_decay; "
+               "mt4_optim_advance + mt4_adamw_step_f32, the step count kept on the device).  Without --skip_nonfinite a non-finite gradient "
+               "poisons the moments for good, as it does in torch.  The schedule flags -l, -w, --power, --decay_rate keep their meaning"),
+    _flag("--adam_betas", type=float, nargs=2, default=[0.9, 0.999], metavar=("B1", "B2"), help="AdamW's betas, each in [0, 1)"),
+    _flag("--adam_eps", type=float, default=1e-8, help="AdamW's epsilon (> 0)"),
+]
 _DETERMINISTIC_STAGES = ("spatial_cnn", "tenco")
 _NOT_DETERMINISTIC = {
     "spatial_transformer": "the sequence trainers' reductions are not covered yet (csrc/seq_train_kernels.hip: LayerNorm dgamma/dbeta, the "
@@ -116,7 +132,7 @@ _FRAME_TRAIN = [
     _OPERAND_DTYPE,
     _DETERMINISTIC,
     _RESUME,
-] + _GUARD
+] + _GUARD + _OPTIM
 # stage -> (the flags every entry point of the stage parses, the flags of its trainer alone), on top of `_common` and -- the trainer --
 # `add_schedule_flags`.  --teacher_dim: the student mixes in the 1536-wide Swin-L feature (`Spatial_cnn/run.py`), the transformer stage's
 # `loss_type all` variant the 512-wide ResNet-18 one (`Spatial_transformer/run.py:82`, `test.py:82`)
@@ -136,7 +152,7 @@ _FLAGS = {
     "mstct": ([_flag("--input_dim", type=int, default=1536),
                _flag("--final_embedding_dim", type=int, default=512)],
               [_flag("--num_clips", type=int, default=256, help="window length (the reference hard-codes 256, dataloader.py:237)"), _OPERAND_DTYPE,
-               _DETERMINISTIC, _RESUME] + _GUARD),
+               _DETERMINISTIC, _RESUME] + _GUARD + _OPTIM),
     # --mask_draw / --subclip (not in the reference) device: the step's random pieces are drawn by HIP kernels from (seed, step) and whole-video
     # steps replay as hipGraphs; host: drawn with torch's generator and uploaded.  reference: `Temporal_tenco/dataloader.py:219-222` sub-clip sampling
     "tenco": ([_flag("--num_layers_PG", default=11, type=int),
@@ -149,7 +165,7 @@ _FLAGS = {
                _flag("--input_dim", type=int, default=512)],
               [_flag("--mask_draw", choices=("host", "device"), default="host"),
                _flag("--subclip", choices=("off", "reference"), default="off"),
-               _DETERMINISTIC, _RESUME] + _GUARD),
+               _DETERMINISTIC, _RESUME] + _GUARD + _OPTIM),
 }
 _LATEST = {"spatial_cnn": "_latest.pth", "spatial_transformer": "_latest.pth", "tenco": "_latest.pth",
            "mstct": "latest.pth"}                            # <stem> + this = the trainer's newest checkpoint; MS-TCT: no underscore (`Temporal_mstct/run.py:268`)
@@ -190,10 +206,45 @@ def _guard(F) -> dict:
     return {"clip_grad_norm": clip, "skip_nonfinite": skip}
 
 
-def _resume(F, latest: str):
+def _optim(F) -> dict:
+    """--optimizer / --momentum / --nesterov / --adam_betas / --adam_eps of a trainer, read before any model is built: contradictions and values
+    out of range are refused, a rule other than plain SGD is said once at start; -> the trainer's keyword argument"""
+    from .flatparams import Optim
+    kind, mom, nest = getattr(F, "optimizer", "sgd"), float(getattr(F, "momentum", 0.0)), bool(getattr(F, "nesterov", False))
+    betas, eps = [float(b) for b in getattr(F, "adam_betas", (0.9, 0.999))], float(getattr(F, "adam_eps", 1e-8))
+    if kind == "adamw":
+        if mom != 0 or nest:
+            raise ValueError("--momentum / --nesterov belong to --optimizer sgd; adamw takes --adam_betas")
+        if not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError(f"--adam_betas {betas[0]:g} {betas[1]:g}: each in [0, 1)")
+        if not eps > 0:
+            raise ValueError(f"--adam_eps {eps:g}: a positive number")
+        o = Optim("adamw", 0.0, False, betas[0], betas[1], eps)
+    else:
+        if not 0 <= mom < 1:
+            raise ValueError(f"--momentum {mom:g}: in [0, 1)")
+        if nest and mom == 0:
+            raise ValueError("--nesterov needs --momentum > 0")
+        o = Optim("sgd", mom, nest)
+    o.check()
+    if o.stateful:
+        print("update rule: " + (f"adamw betas ({o.beta1:g}, {o.beta2:g}) eps {o.eps:g}, decoupled weight decay" if kind == "adamw" else
+                                 f"sgd momentum {o.momentum:g}" + (" nesterov" if o.nesterov else ""))
+              + " (state in flat fp32 buffers beside the parameters; --resume keeps it)", flush=True)
+    return {"optim": o if o.stateful else None}
+
+
+def _resume(F, latest: str, optim=None):
     """--resume of a trainer, read before any model is built: what `trainloop.load_resume` finds beside `latest` for this rank (a fresh run,
-    the state to continue from, or its ValueError); None without the flag"""
-    return load_resume(latest, *_dist()) if getattr(F, "resume", False) else None
+    the state to continue from, or its ValueError -- also when the recorded optimizer state does not belong to the flags `optim` was made from);
+    None without the flag"""
+    return load_resume(latest, *_dist(), optim=optim.config() if optim is not None else None) if getattr(F, "resume", False) else None
+
+
+def _load_optim(tr, resume):
+    """the optimizer state `load_resume` read beside the checkpoint goes into the trainer (after its `load_state_dict`)"""
+    if resume is not None and resume.optim_state is not None:
+        tr.load_optimizer_state_dict(resume.optim_state())
 
 
 def _latest_state(latest: str, resume):
@@ -582,17 +633,18 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     if F.loss_type not in ("all", "i", "v", "t"):
         raise ValueError("--loss_type all | i | v | t (`Spatial_cnn/run.py:165-192`)")
     single = F.loss_type != "all"
-    guard = _guard(F)
+    guard = dict(_guard(F), **_optim(F))
     rank, world = _dist()
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold)
     latest = stem + _LATEST["spatial_cnn"]
-    resume = _resume(F, latest)
+    resume = _resume(F, latest, guard["optim"])
     sd = student_start(F, latest, resume, say=print if rank == 0 else None)
     tr = SpatialCnnTrainer(F.network, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay, rates=F.rates, temp=float(F.temp),
                            teacher_dim=F.teacher_dim, loss_type=F.loss_type,
                            operand_dtype=_dtype(F.operand_dtype), deterministic=_deterministic("spatial_cnn", F), **guard)
     tr.load_state_dict(sd)
+    _load_optim(tr, resume)
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, kfold)
     labels = {v: cholect.load_labels(F.data_dir, v) for v in train_videos + val_videos}
     tpred, tfeat = _teacher_files(F, kfold)
@@ -695,9 +747,9 @@ def _tenco_train(F):
         # `loss_v`, `loss_t` stay the int 0 they start as (`run.py:190`) and `loss_i.item()` raises AttributeError at `run.py:214` in the first step
         raise NotImplementedError("Temporal_tenco training needs --fpn (Scripts/train_fold1.sh:28): without it the reference's train loop itself fails "
                                   "in its first step (run.py:190,214: .item() on the int 0 that loss_i stays when the model returns no per-component logits)")
-    guard = _guard(F)
+    guard = dict(_guard(F), **_optim(F))
     init = stem + _LATEST["tenco"]
-    resume = _resume(F, init)
+    resume = _resume(F, init, guard["optim"])
     tr = TencoTrainer(F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                       hier=bool(getattr(F, "hier", False)),      # --hier True: pooled refinement levels (`network.py:147,154-155`, `run.py:159-179`)
                       deterministic=_deterministic("tenco", F), **guard)
@@ -708,6 +760,7 @@ def _tenco_train(F):
     else:   # no torch.nn init here: deterministic synthetic start (the reference starts from torch's default init)
         tr.load_state_dict(synth.fill_from_shapes(shapes.tenco_shapes(F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100, fpn=True),
                                                   seed=F.seed))
+    _load_optim(tr, resume)
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, F.kfold)
     feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, "all"))
     # features and labels of every training video are uploaded ONCE (a per-step pageable host->device copy stalls the step)
@@ -925,14 +978,14 @@ def _mstct_train(F):
     from .mstct_train import NCLS, MstctTrainer, draw_windows
     from . import shapes, synth
     _deterministic("mstct", F)
-    guard = _guard(F)
+    guard = dict(_guard(F), **_optim(F))
     rank, world = _dist()
     lt = F.loss_type
     if lt not in NCLS:
         raise ValueError("Temporal_mstct trains one task at a time: --loss_type i | v | t | ivt (Scripts/train_fold1.sh:16)")
     stem = _stem(F, task_dir=True)
     latest = stem + _LATEST["mstct"]
-    resume = _resume(F, latest)
+    resume = _resume(F, latest, guard["optim"])
     tr = MstctTrainer(*_MSTCT_ARCH, F.input_dim, F.final_embedding_dim, lt, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                       operand_dtype=_dtype(F.operand_dtype), **guard)
     state = _latest_state(latest, resume)
@@ -940,6 +993,7 @@ def _mstct_train(F):
         tr.load_state_dict(state)
     else:   # no torch.nn init here: deterministic synthetic start (the reference starts from its trunc_normal_ init)
         tr.load_state_dict(synth.fill_from_shapes(shapes.mstct_shapes(F.input_dim, _MSTCT_ARCH[0], _MSTCT_ARCH[1], _MSTCT_ARCH[3], F.final_embedding_dim, lt), seed=F.seed))
+    _load_optim(tr, resume)
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, F.kfold)
     feats = featfile.read_feats(featfile.feats_path("..", F.version1, F.kfold, lt))                # `dataloader.py:220-222`
     xs, zs = {}, {}
@@ -998,7 +1052,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     from . import shapes, synth
     F = _parser("spatial_transformer", True).parse_known_args(argv)[0]
     _deterministic("spatial_transformer", F)
-    guard = _guard(F)
+    guard = dict(_guard(F), **_optim(F))
     if F.loss_type not in ("i", "v", "t", "all"):
         raise ValueError("--loss_type i | v | t | all (`Spatial_transformer/run.py:168-197`)")
     single = F.loss_type != "all"
@@ -1007,7 +1061,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold, task_dir=True)
     logfile, latest = stem + ".log", stem + _LATEST["spatial_transformer"]
-    resume = _resume(F, latest)
+    resume = _resume(F, latest, guard["optim"])
     tr = Q2LTrainer(F.backbone, F.img_size, F.hidden_dim, F.loss_type, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                     drop_path_rate=F.drop_path_rate, operand_dtype=_dtype(F.operand_dtype),
                     teacher_dim=F.teacher_dim, rates=F.rates, temp=float(F.temp), **guard)
@@ -1028,6 +1082,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     if state is not None:
         sd.update({k: v for k, v in state.items() if k in sd})
     tr.load_state_dict(sd)
+    _load_optim(tr, resume)
     train_videos, val_videos, _ = cholect.split_videos(F.dataset_variant, kfold)
     labels = {v: cholect.load_labels(F.data_dir, v) for v in train_videos + val_videos}
     samples = [(v, i) for v in train_videos for i in range(len(labels[v]["ivt"]))]

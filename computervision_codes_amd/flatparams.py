@@ -2,7 +2,8 @@
 GEMM layouts, every slot padded to 4 floats), the weight copies derived from the masters by one launch, and the data-parallel exchange of G
 -- per-bucket all-reduces behind the backward or one flat all-reduce after it -- ahead of one `mt4_sgd_step_f32`, or, with a gradient-norm clip or
 the non-finite guard on, of the guarded update (norm and decisions taken on the device: `mt4_grad_norm_parts_f32`, `mt4_grad_guard_finalize`,
-`mt4_sgd_step_guarded_f32`).
+`mt4_sgd_step_guarded_f32`), or, with momentum or AdamW (`Optim`), of the update that also carries flat state buffers of P's layout
+(`mt4_sgd_momentum_step_f32`, `mt4_optim_advance` + `mt4_adamw_step_f32`).
 
 * `FlatParams` lays the slots out in the order they are declared, loads them from the reference state dict and exports P or G back in the
   reference's key names and shapes;
@@ -11,7 +12,7 @@ the non-finite guard on, of the guarded update (norm and decisions taken on the 
 """
 from __future__ import annotations
 
-from typing import Dict, List
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -22,6 +23,49 @@ F32 = torch.float32
 
 def _r4(n: int) -> int:
     return (n + 3) // 4 * 4
+
+
+class Optim(NamedTuple):
+    """the update rule of a `FlatTrainer` (--optimizer, --momentum, --nesterov, --adam_betas, --adam_eps).  The default is plain SGD, the
+    reference's effective rule: no state, the existing update launches"""
+    kind: str = "sgd"
+    momentum: float = 0.0
+    nesterov: bool = False
+    beta1: float = 0.9
+    beta2: float = 0.999
+    eps: float = 1e-8
+
+    @property
+    def stateful(self) -> bool:
+        return self.kind == "adamw" or self.momentum > 0
+
+    @property
+    def buffers(self) -> tuple:
+        """the flat state buffers by the key torch.optim gives them"""
+        return ("exp_avg", "exp_avg_sq") if self.kind == "adamw" else ("momentum_buffer",) if self.momentum > 0 else ()
+
+    def config(self) -> dict:
+        """what is written beside a checkpoint and compared on --resume: the fields the rule reads"""
+        if self.kind == "adamw":
+            return {"kind": "adamw", "beta1": float(self.beta1), "beta2": float(self.beta2), "eps": float(self.eps)}
+        return {"kind": "sgd", "momentum": float(self.momentum), "nesterov": bool(self.nesterov)}
+
+    def check(self) -> "Optim":
+        if self.kind not in ("sgd", "adamw"):
+            raise ValueError(f"optimizer {self.kind!r}: sgd | adamw")
+        if self.kind == "adamw":
+            if self.momentum != 0 or self.nesterov:
+                raise ValueError("momentum / nesterov belong to sgd: adamw has its betas")
+            if not (0 <= self.beta1 < 1 and 0 <= self.beta2 < 1):
+                raise ValueError(f"adamw betas ({self.beta1}, {self.beta2}): each in [0, 1)")
+            if not self.eps > 0:
+                raise ValueError(f"adamw eps {self.eps}: positive")
+        else:
+            if not 0 <= self.momentum < 1:
+                raise ValueError(f"momentum {self.momentum}: in [0, 1)")
+            if self.nesterov and self.momentum == 0:
+                raise ValueError("nesterov needs a momentum > 0")
+        return self
 
 
 class Lin:
@@ -46,6 +90,7 @@ class FlatParams:
         self.L: Dict[str, Lin] = {}
         self.V: Dict[str, Vec] = {}
         self.ranges: Dict[str, list] = {}            # flat range [a, b) of every gradient bucket
+        self.S: Dict[str, torch.Tensor] = {}         # optimizer state buffers by name: flat fp32 of P's length and layout (`FlatTrainer`)
         self._slots: list = []
         self._n = 0
         self._bucket = None
@@ -139,19 +184,25 @@ class FlatParams:
         """the reference keys the slots hold"""
         return {k for s in self._slots for k in ((s.key,) if isinstance(s, Vec) else (s.wkey, s.bkey)) if k}
 
-    def export(self, which: str) -> Dict[str, torch.Tensor]:
-        """P ('p') or G ('g') in the reference's key names and shapes, on the CPU"""
+    def export(self, which) -> Dict[str, torch.Tensor]:
+        """P ('p'), G ('g'), a named state buffer of `S`, or any flat tensor of P's length (a buffer of flat indices gives the map back into the
+        flat layout) in the reference's key names and shapes, on the CPU"""
+        buf = which if isinstance(which, torch.Tensor) else self.P if which == "p" else self.G if which == "g" else self.S[which]
+        assert buf.numel() == self._n and buf.is_contiguous()
         out = {}
         for s in self._slots:
             if isinstance(s, Vec):
-                out[s.key] = (s.p if which == "p" else s.g).reshape(s.ref).clone().cpu()
+                n = int(torch.tensor(s.shape).prod())
+                out[s.key] = buf[s.off:s.off + n].reshape(s.ref).clone().cpu()
                 continue
-            w, b = (s.w, s.b) if which == "p" else (s.gw, s.gb)
+            kp = ops.packed_k(s.cin, s.kh, s.taps, F32)
+            n = s.cout * kp
+            w = buf[s.off:s.off + n].view(s.cout, kp)
             tapw = _r4(s.cin)
             w = w[:s.cout_real, :s.kh * s.taps * tapw].reshape(s.cout_real, s.kh, s.taps, tapw)[..., :s.cin].permute(0, 3, 1, 2)
             out[s.wkey] = w.reshape(s.ref).contiguous().cpu()
             if s.bkey:
-                out[s.bkey] = b[:s.cout_real].clone().cpu()
+                out[s.bkey] = buf[s.off + n:s.off + n + s.cout_real].clone().cpu()
         return out
 
 
@@ -172,11 +223,17 @@ class FlatTrainer:
     all-reduces the whole of G once."""
 
     def __init__(self, lr: float, weight_decay: float, device, process_group, overlap: bool = False, clip_grad_norm: float = 0.0,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, optim: Optional[Optim] = None):
         """clip_grad_norm > 0: the exchanged gradient is scaled to that global L2 norm when it is longer; skip_nonfinite: a step whose exchanged
-        gradient holds a NaN or an Inf changes nothing (`apply_update`, the guarded update).  Both off: the plain `mt4_sgd_step_f32`."""
+        gradient holds a NaN or an Inf changes nothing (`apply_update`, the guarded update).  Both off: the plain `mt4_sgd_step_f32`.
+        optim: the update rule (`Optim`); None or the default: plain SGD, today's launches, no state buffer.  With momentum or AdamW the state
+        lives in flat buffers of P's layout (`fp.S`), allocated by `load_state_dict`; see `apply_update`."""
         if not clip_grad_norm >= 0:
             raise ValueError(f"clip_grad_norm {clip_grad_norm}: 0 (off) or a positive norm")
+        optim = Optim(*optim).check() if optim is not None else None
+        self.optim = optim if optim is not None and optim.stateful else None
+        self._ostate = None                         # AdamW: the device step record (mt4_optim_state)
+        self._omap = None                           # reference key -> flat indices (`load_optimizer_state_dict`)
         self.lr, self.wd = lr, weight_decay
         self.clip_grad_norm, self.skip_nonfinite = float(clip_grad_norm), bool(skip_nonfinite)
         self._guard = None                          # (workspace, state, stats) of the guarded update, allocated at its first use
@@ -264,6 +321,9 @@ class FlatTrainer:
             scale = 1.0 / self._ddp_world()
         else:
             scale = allreduce_sum_flat(self.G, self.pg) if self.exchange else 1.0
+        if self.optim is not None:
+            self._stateful_update(scale)
+            return
         if not self.guarded:
             ops.sgd_step(self.P, self.G, self.lr, self.wd, scale)
             self._refresh()
@@ -287,6 +347,86 @@ class FlatTrainer:
 
     def _restore_skipped(self, state: torch.Tensor):
         """buffers besides P that a skipped step must leave as they were (the student's BatchNorm running statistics)"""
+
+    # ------------------------------------------------------------------ optimizer state
+    def _stateful_update(self, scale: float):
+        """the update with momentum or AdamW: the guard pass as in the plain path when guarded, `mt4_optim_advance` for AdamW, ONE update launch
+        that reads the guard record on the device.  The clip coefficient scales the gradient before it enters the state (torch clips ahead of
+        `step()`); a skipped step leaves P, the state buffers and the step count as they were.  Every rank updates from the same exchanged G,
+        so the state is the same on every rank and is never exchanged."""
+        o, S = self.optim, self.fp.S
+        state = None
+        if self.guarded:
+            ws, state, stats = self._guard_buffers()
+            ops.grad_guard(self.G, scale, self.clip_grad_norm, self.skip_nonfinite, ws, state, stats)
+        if o.kind == "adamw":
+            ops.optim_advance(self._ostate, o.beta1, o.beta2, state)
+            ops.adamw_step(self.P, self.G, S["exp_avg"], S["exp_avg_sq"], self.lr, self.wd, scale, o.beta1, o.beta2, o.eps, self._ostate, state)
+        else:
+            ops.sgd_momentum_step(self.P, self.G, S["momentum_buffer"], self.lr, self.wd, scale, o.momentum, o.nesterov, state)
+        if state is not None:
+            self._restore_skipped(state)
+        self._refresh()
+
+    def _optim_buffers(self):
+        """`load_state_dict`, once `fp` is built and before any graph capture: the zero-filled state buffers of the update rule (padding columns
+        and reserved slots stay exact zeros, as in G: their gradient and parameter are zero) and a fresh step record.  Nothing for plain SGD."""
+        self._omap = None
+        if self.optim is None:
+            return
+        for name in self.optim.buffers:
+            self.fp.S[name] = torch.zeros_like(self.fp.P)
+        if self.optim.kind == "adamw":
+            self._ostate = ops.optim_state_buffer(self.dev)
+
+    def _export_any(self, which) -> Dict[str, torch.Tensor]:
+        """`fp.export` through the trainer's own `_export` where it has one (fused heads cut back into the reference's tensors)"""
+        return (getattr(self, "_export", None) or self.fp.export)(which)
+
+    def optim_config(self) -> Optional[dict]:
+        """the rule's config as --resume records it; None for plain SGD"""
+        return self.optim.config() if self.optim is not None else None
+
+    def optim_record(self) -> dict:
+        """the step record on the host: t, beta1_pow, beta2_pow (AdamW; one device-to-host copy) or {} where the rule keeps none"""
+        return ops.read_optim_state(self._ostate) if self._ostate is not None else {}
+
+    def optimizer_state_dict(self) -> Optional[dict]:
+        """{"optim": the rule's config, "step": AdamW's step count (0 for SGD), "state": {reference parameter name: {"momentum_buffer"} |
+        {"exp_avg", "exp_avg_sq"}}} on the CPU, in the names and shapes of `grads()` -- what the matching torch.optim object holds per
+        parameter.  None for plain SGD."""
+        if self.optim is None:
+            return None
+        bufs = {name: self._export_any(name) for name in self.optim.buffers}
+        keys = next(iter(bufs.values())).keys()
+        return {"optim": self.optim.config(), "step": int(self.optim_record().get("t", 0)),
+                "state": {k: {name: bufs[name][k] for name in self.optim.buffers} for k in keys}}
+
+    def load_optimizer_state_dict(self, osd: dict):
+        """the inverse of `optimizer_state_dict`: the tensors go back to their flat places (found by exporting a buffer of flat indices, so every
+        packing and head fusion of the export is inverted by construction), the step record is rebuilt by `step` double multiplies"""
+        if self.optim is None:
+            raise ValueError("this trainer keeps no optimizer state (plain SGD)")
+        if osd.get("optim") != self.optim.config():
+            raise ValueError(f"optimizer state of {osd.get('optim')} does not belong to this trainer's {self.optim.config()}")
+        if self._omap is None:
+            n = self.fp.P.numel()
+            self._omap = self._export_any(torch.arange(n, dtype=torch.int32 if n < 2 ** 31 else torch.int64, device=self.dev))
+        if set(osd["state"]) != set(self._omap):
+            raise ValueError("optimizer state holds other parameters than this trainer's")
+        for name in self.optim.buffers:
+            flat = torch.zeros(self.fp.P.numel(), dtype=F32)
+            for k, idx in self._omap.items():
+                t = osd["state"][k][name]
+                if tuple(t.shape) != tuple(idx.shape):
+                    raise ValueError(f"optimizer state {k}.{name}: shape {tuple(t.shape)}, expected {tuple(idx.shape)}")
+                flat[idx.reshape(-1).long()] = t.reshape(-1).to(F32)
+            self.fp.S[name].copy_(flat.to(self.dev))
+        if self._ostate is not None:
+            rec = {"t": 0, "beta1_pow": 1.0, "beta2_pow": 1.0}
+            for _ in range(int(osd["step"])):
+                rec = ops.optim_advance_host(rec, self.optim.beta1, self.optim.beta2)
+            ops.write_optim_state(self._ostate, rec["t"], rec["beta1_pow"], rec["beta2_pow"])
 
     def guard_state(self) -> dict:
         """what the last guarded update decided: sumsq, norm, coef, skip, nonfinite (one device-to-host copy)"""

@@ -41,9 +41,9 @@ class MstctTrainer(GemmTrainer):
     def __init__(self, inter_channels: Sequence[int] = (256, 384, 576, 864), num_block: int = 2, head: int = 8, mlp_ratio: int = 8,
                  in_feat_dim: int = 1536, final_embedding_dim: int = 512, loss_type: str = "i", lr: float = 0.1, weight_decay: float = 1e-5,
                  device: str = "cuda", process_group=None, operand_dtype: torch.dtype = torch.float32, clip_grad_norm: float = 0.0,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, optim=None):
         assert loss_type in NCLS
-        super().__init__(lr, weight_decay, device, process_group, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
+        super().__init__(lr, weight_decay, device, process_group, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, optim=optim)
         assert operand_dtype in (torch.float32, torch.bfloat16)
         # bfloat16: the nn.Linear GEMMs (forward, data and weight gradients) read bf16 copies of their operands -- activations are cast on the
         # way in (`mt4_cast_f32_bf16`), weights re-derived from the fp32 masters after every step -- and accumulate / store in fp32; everything
@@ -92,6 +92,7 @@ class MstctTrainer(GemmTrainer):
         for name, shp in vec:
             fp.vec(name, shp)
         self.fp = fp.build(sd)
+        self._optim_buffers()
         self.lins = fp.L
         E = self.E
         kp = ops.packed_k(E, 1, 1, F32)

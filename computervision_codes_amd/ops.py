@@ -1040,6 +1040,139 @@ def guarded_sgd_host(p: torch.Tensor, g: torch.Tensor, lr: float, weight_decay: 
     return torch.from_numpy(np.ascontiguousarray(pn, dtype=np.float32)), {"sumsq": sumsq, "norm": norm, "coef": float(coef), "skip": int(skip), "nonfinite": bad}
 
 
+# ----------------------------------------------------------------------------------------- optimizer state (--momentum, --nesterov, --optimizer adamw)
+OPTIM_STATE_BYTES = 24        # mt4_optim_state: int64 t, double beta1_pow, double beta2_pow
+
+
+def optim_state_buffer(device) -> torch.Tensor:
+    """a fresh mt4_optim_state on the device: t = 0, both products 1.0 (a float64 tensor of three 8-byte words, like the guard records)"""
+    return torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=device)
+
+
+def read_optim_state(optim_state: torch.Tensor) -> dict:
+    """mt4_optim_state on the host (one device-to-host copy): t, beta1_pow, beta2_pow"""
+    import struct
+    t, b1p, b2p = struct.unpack("<qdd", optim_state.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()[:OPTIM_STATE_BYTES])
+    return {"t": t, "beta1_pow": b1p, "beta2_pow": b2p}
+
+
+def write_optim_state(optim_state: torch.Tensor, t: int, beta1_pow: float, beta2_pow: float) -> None:
+    """set the record (loading a saved optimizer state)"""
+    import struct
+    import numpy as np
+    words = np.frombuffer(struct.pack("<qdd", int(t), float(beta1_pow), float(beta2_pow)), dtype=np.float64).copy()
+    optim_state[:3].copy_(torch.from_numpy(words).to(optim_state.device))
+
+
+def _guard_or_null(state: Optional[torch.Tensor], what: str):
+    return None if state is None else _guard_record(state, GUARD_STATE_BYTES, what)
+
+
+def _flat_f32(*ts):
+    _need_cuda(*ts)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == ts[0].numel() for t in ts)
+
+
+def optim_advance(optim_state: torch.Tensor, beta1: float, beta2: float, guard_state: Optional[torch.Tensor] = None) -> None:
+    """one AdamW step counted: t += 1 and both products multiplied once, unless the guard state says skip (`mt4_optim_advance`)"""
+    check(lib.mt4_optim_advance(_guard_record(optim_state, OPTIM_STATE_BYTES, "optim_advance optim_state"), float(beta1), float(beta2),
+                                _guard_or_null(guard_state, "optim_advance guard state"), _stream()), "mt4_optim_advance")
+
+
+def sgd_momentum_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, weight_decay: float, grad_scale: float = 1.0,
+                      momentum: float = 0.0, nesterov: bool = False, guard_state: Optional[torch.Tensor] = None) -> None:
+    """torch.optim.SGD with momentum (dampening 0) on the flat buffers, `m` the momentum buffer; guard_state: grad_scale x its clip coefficient,
+    nothing written when it says skip (`mt4_sgd_momentum_step_f32`)"""
+    _flat_f32(p, g, m)
+    check(lib.mt4_sgd_momentum_step_f32(p.data_ptr(), g.data_ptr(), m.data_ptr(), p.numel(), lr, weight_decay, grad_scale, momentum,
+                                        1 if nesterov else 0, _guard_or_null(guard_state, "sgd_momentum_step guard state"), _stream()),
+          "mt4_sgd_momentum_step_f32")
+
+
+def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, weight_decay: float, grad_scale: float,
+               beta1: float, beta2: float, eps: float, optim_state: torch.Tensor, guard_state: Optional[torch.Tensor] = None) -> None:
+    """torch.optim.AdamW (amsgrad off) on the flat buffers at the step `optim_state` holds -- `optim_advance` first (`mt4_adamw_step_f32`)"""
+    _flat_f32(p, g, m, v)
+    check(lib.mt4_adamw_step_f32(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, weight_decay, grad_scale, float(beta1),
+                                 float(beta2), eps, _guard_record(optim_state, OPTIM_STATE_BYTES, "adamw_step optim_state"),
+                                 _guard_or_null(guard_state, "adamw_step guard state"), _stream()), "mt4_adamw_step_f32")
+
+
+def optim_advance_host(record: dict, beta1: float, beta2: float, skip: bool = False) -> dict:
+    """`mt4_optim_advance` on the host: Python floats are IEEE doubles, so the products follow the device's exactly"""
+    if skip:
+        return dict(record)
+    return {"t": record["t"] + 1, "beta1_pow": record["beta1_pow"] * float(beta1), "beta2_pow": record["beta2_pow"] * float(beta2)}
+
+
+def optim_step_host(kind: str, p, g, m, v=None, *, lr: float, weight_decay: float, grad_scale: float = 1.0, coef: float = 1.0, skip: bool = False,
+                    momentum: float = 0.0, nesterov: bool = False, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                    record: Optional[dict] = None, trace: Optional[dict] = None) -> dict:
+    """`mt4_sgd_momentum_step_f32` (kind "sgd") / `mt4_adamw_step_f32` (kind "adamw") restated in numpy float32: the same single round-to-nearest
+    operations in the same order, so the kernels equal it bit for bit.  coef / skip: what the guard state holds (1, False: unguarded).  record:
+    AdamW's step record AFTER `optim_advance_host`.  trace (a dict): filled with every intermediate array.
+      sgd:    s = f32(grad_scale) * f32(coef);  d = g * s + wd * p;  m' = mom * m + d;  u = d + mom * m' (nesterov) | m';  p' = p - lr * u
+      adamw:  s as above;  b = f32(beta);  c = f32(1.0 - beta) (float64 subtraction);  lw = lr * wd;  step = f32(f64(lr) / (1.0 - beta1_pow));
+              r2 = f32(sqrt(1.0 - beta2_pow));  q = p - lw * p;  h = g * s;  m' = b1 * m + c1 * h;  v' = b2 * v + c2 * (h * h);
+              p' = q - step * (m' / (sqrt(v') / r2 + eps))
+    -> {"p", "m" (, "v")}: float32 tensors on the CPU (the inputs' own values when skipped)"""
+    import numpy as np
+    f32 = np.float32
+
+    def arr(x):
+        return None if x is None else (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)).astype(f32, copy=True)
+
+    pn, gn, mn, vn = arr(p), arr(g), arr(m), arr(v)
+    tr = {} if trace is None else trace
+    if not skip:
+        with np.errstate(all="ignore"):
+            s = f32(grad_scale) * f32(coef)
+            lr_, wd = f32(lr), f32(weight_decay)
+            if kind == "sgd":
+                mom = f32(momentum)
+                gs, wp = gn * s, wd * pn
+                d = gs + wp
+                mm = mom * mn
+                m2 = mm + d
+                tr.update(gs=gs, wp=wp, d=d, mm=mm, m=m2)
+                u = m2
+                if nesterov:
+                    t = mom * m2
+                    u = d + t
+                    tr.update(t=t, u=u)
+                lu = lr_ * u
+                pn, mn = pn - lu, m2
+                tr.update(lu=lu, p=pn)
+            elif kind == "adamw":
+                b1, b2 = f32(beta1), f32(beta2)
+                c1, c2 = f32(1.0 - float(beta1)), f32(1.0 - float(beta2))
+                lw = lr_ * wd
+                step = f32(np.float64(lr_) / np.float64(1.0 - record["beta1_pow"]))
+                r2 = f32(np.sqrt(np.float64(1.0 - record["beta2_pow"])))
+                lp = lw * pn
+                q = pn - lp
+                h = gn * s
+                m1, m2 = b1 * mn, c1 * h
+                m3 = m1 + m2
+                hh = h * h
+                v1, v2 = b2 * vn, c2 * hh
+                v3 = v1 + v2
+                sq = np.sqrt(v3)
+                sr = sq / r2
+                den = sr + f32(eps)
+                qu = m3 / den
+                up = step * qu
+                pn, mn, vn = q - up, m3, v3
+                tr.update(lp=lp, q=q, h=h, m1=m1, m2=m2, m=m3, hh=hh, v1=v1, v2=v2, v=v3, sq=sq, sr=sr, den=den, qu=qu, up=up, p=pn,
+                          scalars=np.array([s, c1, c2, lw, step, r2], dtype=f32))
+            else:
+                raise ValueError(f"kind {kind!r}: sgd | adamw")
+    out = {"p": torch.from_numpy(np.ascontiguousarray(pn, dtype=f32)), "m": torch.from_numpy(np.ascontiguousarray(mn, dtype=f32))}
+    if vn is not None:
+        out["v"] = torch.from_numpy(np.ascontiguousarray(vn, dtype=f32))
+    return out
+
+
 def mul_add(a: torch.Tensor, b: torch.Tensor, c: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _need_cuda(a, b, c)
     assert a.is_contiguous() and b.is_contiguous() and a.dtype == torch.float32 and a.numel() == b.numel()

@@ -44,7 +44,7 @@ class Q2LTrainer(GemmTrainer):
     def __init__(self, backbone: str = "swin_L_384_22k", img_size: int = 384, hidden_dim: int = 1536, loss_type: str = "i", lr: float = 0.01,
                  weight_decay: float = 1e-5, drop_path_rate: float = 0.1, device: str = "cuda", process_group=None,
                  operand_dtype: torch.dtype = torch.float32, teacher_dim: int = 512, rates=(1.0, 0.0, 0.1), temp: float = 4.0,
-                 clip_grad_norm: float = 0.0, skip_nonfinite: bool = False):
+                 clip_grad_norm: float = 0.0, skip_nonfinite: bool = False, optim=None):
         if loss_type not in ("i", "v", "t", "all"):
             raise ValueError("loss_type: i | v | t | all (Spatial_transformer/run.py:168-197)")
         self.backbone, self.S, self.d, self.loss_type = backbone, int(img_size), int(hidden_dim), loss_type
@@ -53,7 +53,7 @@ class Q2LTrainer(GemmTrainer):
         self.teacher_dim, self.rates, self.temp = int(teacher_dim), tuple(float(r) for r in rates), float(temp)   # `run.py:66,70` (--rates default 1 0 0.1)
         self.cfg = SWIN_CFG[backbone]
         assert self.d == self.cfg["embed_dim"] * 8, "hidden_dim is the backbone's final width (backbone.py:188-201)"
-        super().__init__(lr, weight_decay, device, process_group, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
+        super().__init__(lr, weight_decay, device, process_group, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, optim=optim)
         assert operand_dtype in (torch.float32, torch.bfloat16)
         # bfloat16: the nn.Linear / patch-embedding GEMMs (forward, data and weight gradients) read bf16 copies of their operands; activations,
         # accumulation, everything between the GEMMs and the master weights stay fp32 (as in `MstctTrainer`)
@@ -120,6 +120,7 @@ class Q2LTrainer(GemmTrainer):
         for key, shape in vecs:
             fp.vec(key, shape)
         self.fp = fp.build(sd)
+        self._optim_buffers()
         self.att = {tag: tuple(fp.rows(tag + ".in", i * d, (i + 1) * d) for i in range(3)) for tag, *_ in layers}
         self._refresh()
         self.layer_prefix = {tag: lp for tag, lp, _, _ in layers}

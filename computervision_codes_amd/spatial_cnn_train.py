@@ -46,7 +46,7 @@ class SpatialCnnTrainer(FlatTrainer):
     def __init__(self, network: str = "resnet50", lr: float = 0.01, weight_decay: float = 1e-5, rates: Sequence[float] = (1.0, 1.0, 1.0),
                  temp: float = 4.0, device: str = "cuda", process_group=None, overlap: bool = True, teacher_dim: int = 1536,
                  loss_type: str = "all", operand_dtype: torch.dtype = torch.float32, epilogue_stats: bool = True, deterministic: bool = False,
-                 clip_grad_norm: float = 0.0, skip_nonfinite: bool = False):
+                 clip_grad_norm: float = 0.0, skip_nonfinite: bool = False, optim=None):
         """loss_type 'all': the distillation recipe (four heads, KD branch, hard + soft + feature losses: `run.py:180-192`);
         'i' | 'v' | 't': a single-task student -- only that classifier exists (`network.py:34-41`) and the loss is its BCE alone
         (`run.py:165-179`)"""
@@ -71,7 +71,7 @@ class SpatialCnnTrainer(FlatTrainer):
         self.NH = sum(k for _, k in self.heads)
         self.NHP = (self.NH + 3) // 4 * 4
         # overlap: each gradient bucket is all-reduced as soon as the backward has written it (DDP, `FlatTrainer`)
-        super().__init__(lr, weight_decay, device, process_group, overlap, clip_grad_norm, skip_nonfinite)
+        super().__init__(lr, weight_decay, device, process_group, overlap, clip_grad_norm, skip_nonfinite, optim)
         self.network, self.rates, self.temp = network, tuple(rates), float(temp)
         self.C = resnet_feat_dim(network)
         self.TD = int(teacher_dim)          # `--teacher_dim` (`Spatial_cnn/run.py:82`): width of the teachers' frame features
@@ -120,6 +120,7 @@ class SpatialCnnTrainer(FlatTrainer):
             for name, co, ci in (("wi", TD, C), ("wv", TD, C), ("wt", TD, C), ("mi", C, TD), ("mv", C, TD), ("mt", C, TD)):
                 fp.lin(name, co, ci)
         self.fp = fp.build(sd, derive=False)    # (the derived copies: `_refresh_transposed`)
+        self._optim_buffers()
         trained = fp.keys() | {f"classifier_{t}.fc.{p}" for t, _ in self.heads for p in ("weight", "bias")}
         # the running statistics of every BatchNorm in ONE flat buffer (a unit's mean, then its variance, each padded to 4 floats; `u.rmean` / `u.rvar`
         # are views): --skip_nonfinite copies it aside before a step and `mt4_restore_if_skipped_f32` puts it back when the step is skipped

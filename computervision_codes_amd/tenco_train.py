@@ -35,9 +35,9 @@ NHP = 132  # padded to a multiple of 4 (16-byte rows for the gradient GEMMs)
 class TencoTrainer(FlatTrainer):
     def __init__(self, num_layers_PG=11, num_layers_R=10, num_R=3, num_f_maps=512, dim=512, num_classes=100, lr=0.1, weight_decay=1e-5,
                  device: str = "cuda", process_group=None, overlap: bool = True, hier: bool = False, max_graphs: int = 64,
-                 deterministic: bool = False, clip_grad_norm: float = 0.0, skip_nonfinite: bool = False):
+                 deterministic: bool = False, clip_grad_norm: float = 0.0, skip_nonfinite: bool = False, optim=None):
         # overlap: a stage's gradients are all-reduced as soon as its backward has written them (DDP, `FlatTrainer`)
-        super().__init__(lr, weight_decay, device, process_group, overlap, clip_grad_norm, skip_nonfinite)
+        super().__init__(lr, weight_decay, device, process_group, overlap, clip_grad_norm, skip_nonfinite, optim)
         # hier = `args.hier` (`network.py:147,154-155`): AvgPool1d(7, 3) behind every refinement stage, so level l has its own length T_l, the FPN
         # resamples (`:96`) and `fusion` scores every level against the labels resized to it (`run.py:159-179,196-212`)
         self.hier = bool(hier)
@@ -80,6 +80,7 @@ class TencoTrainer(FlatTrainer):
         fp.lin("heads", NH, C, src=(torch.cat([sd[f"conv_out{s}.weight"] for s, _, _ in HEADS], 0),   # [131 (+1 zero row), C, 1]
                                     torch.cat([sd[f"conv_out{s}.bias"] for s, _, _ in HEADS], 0)))
         self.fp, self.convs = fp.build(sd), fp.L
+        self._optim_buffers()
         trained = fp.keys() | {f"conv_out{s}.{p}" for s, _, _ in HEADS for p in ("weight", "bias")}
         self._extra = {k: sd[k].detach().clone() for k in names if k not in trained}
         if self.deterministic and self._ws is None:

@@ -101,7 +101,13 @@ def save_atomic(state: Dict[str, torch.Tensor], path: str):
 #   <latest>.resume.rank<r>  rank r > 0: {"format", "world", "rank", "records": [...]}, a record = {"epoch", "generators"} -- that rank's own draws
 # JSON, readable with any editor.  TWO records are kept because the pair cannot be replaced in one step: the sidecar is replaced first, then
 # `<latest>`; a run killed in between leaves the new sidecar beside the old `<latest>`, whose digest the older record still names.
+# A trainer with optimizer state (--momentum, --optimizer adamw) adds
+#   <latest>.optim.e<epoch>  rank 0: torch.save of `tr.optimizer_state_dict()` behind that epoch, written BEFORE the sidecar whose record names it:
+#                            "optim": {"file": its base name, "digest": "sha256:<hex of its bytes>", "config": the rule's config}
+# Both records' files are kept; older ones are removed once the pair is written, so a kill at any point leaves every named file in place.  Every
+# rank reads the file on resume (the state is the same on every rank).  Without optimizer state nothing of this is written.
 RESUME_SUFFIX = ".resume"
+OPTIM_SUFFIX = ".optim.e"
 _RESUME_FORMAT = 1
 
 
@@ -168,17 +174,54 @@ class Resume:
     """what `load_resume` found: `epoch` = the last completed epoch (-1: a fresh run), `top`, this rank's generator states by name, and
     `state_dict()` = the tensors of exactly the `<latest>` bytes the digest was checked on (None for a fresh run)"""
 
-    def __init__(self, epoch: int = -1, top: float = 0.0, generators: dict = None, data: bytes = None, record: dict = None):
+    def __init__(self, epoch: int = -1, top: float = 0.0, generators: dict = None, data: bytes = None, record: dict = None,
+                 optim_data: bytes = None):
         self.epoch, self.top, self.generators, self._data, self.record = epoch, top, generators or {}, data, record
+        # `optim_state()` = the optimizer state of exactly the bytes the record's digest was checked on; None where the record names none
+        self.optim_state = None if optim_data is None else (lambda: torch.load(io.BytesIO(optim_data), map_location="cpu"))
 
     def state_dict(self):
         return None if self._data is None else torch.load(io.BytesIO(self._data), map_location="cpu")
 
 
-def load_resume(latest: str, rank: int = 0, world: int = 1) -> Resume:
+def optim_file(latest: str, epoch: int) -> str:
+    """the file the optimizer state behind `epoch` is kept in, beside the checkpoint `latest`"""
+    return latest + OPTIM_SUFFIX + str(epoch)
+
+
+def _load_optim_bytes(latest: str, side: str, rec: dict, optim) -> bytes:
+    """the optimizer file a record names, checked against the record and against this run's flags (`optim` = their config, None: plain SGD)"""
+    named = rec.get("optim")
+    if named is None:
+        if optim is not None:
+            raise ValueError(f"--resume: {side} (epoch {rec.get('epoch')}) holds no optimizer state and this run asks for {optim}: the run that wrote "
+                             "it used plain SGD.  Drop --momentum / --optimizer to continue it as it was, or drop --resume to start again at epoch "
+                             "0 from the weights with the new update rule")
+        return None
+    path = os.path.join(os.path.dirname(latest), named["file"])
+    if optim is None:
+        raise ValueError(f"--resume: {side} (epoch {rec.get('epoch')}) was written with optimizer state ({named['config']}, {path}) and this run has no "
+                         "optimizer flags: give the flags of the run that wrote it, or drop --resume to start again at epoch 0 from the weights")
+    if named["config"] != optim:
+        raise ValueError(f"--resume: the optimizer state {path} belongs to {named['config']} and this run asks for {optim}; changing the update rule "
+                         "across a resume is not supported.  Give the recorded flags, or drop --resume to start again at epoch 0 from the weights")
+    if not os.path.exists(path):
+        raise ValueError(f"--resume: the optimizer state {path} that {side} names is missing.  Put it back, or drop --resume to start again at epoch 0 "
+                         "from the weights (momentum and moments start at zero)")
+    with open(path, "rb") as f:
+        data = f.read()
+    if _digest(data) != named["digest"]:
+        raise ValueError(f"--resume: {path} ({_digest(data)[:19]}...) is not the optimizer state {side} was written for ({named['digest'][:19]}...): it "
+                         "was replaced or its write was torn.  Put the matching file back, or drop --resume to start again at epoch 0 from the weights")
+    return data
+
+
+def load_resume(latest: str, rank: int = 0, world: int = 1, optim: dict = None) -> Resume:
     """--resume at the start of a run, before any model is built and without touching a file: a fresh `Resume` when there is no `latest`, the
     state to continue from when its sidecar names the bytes of `latest`, ValueError otherwise (no sidecar: the checkpoint was written without
-    --resume; another `world`; no record with the digest of `latest`; rank > 0: no record of that epoch in its own file)"""
+    --resume; another `world`; no record with the digest of `latest`; rank > 0: no record of that epoch in its own file).  optim: the config of
+    this run's update rule (`flatparams.Optim.config()`), None for plain SGD: the record's optimizer file must be there with the recorded
+    digest and config, a record without one takes no optimizer flags and one with it needs them (ValueError otherwise)"""
     if not os.path.exists(latest):
         return Resume()                                            # (a sidecar alone: the run died before its first checkpoint; it is overwritten)
     side = resume_file(latest)
@@ -197,6 +240,7 @@ def load_resume(latest: str, rank: int = 0, world: int = 1) -> Resume:
         raise ValueError(f"--resume: {latest} ({digest[:19]}...) is not the checkpoint {side} was written for (epochs "
                          f"{[r.get('epoch') for r in obj['records']]}): it was replaced or its write was torn.  Put the matching file back, or move "
                          "both away to start a fresh run, or drop --resume to start again at epoch 0 from these weights")
+    optim_data = _load_optim_bytes(latest, side, rec, optim)
     gens = rec["generators"]
     if rank:
         mine = resume_file(latest, rank)
@@ -208,20 +252,38 @@ def load_resume(latest: str, rank: int = 0, world: int = 1) -> Resume:
             raise ValueError(f"--resume: {mine} (world {own.get('world')}, epochs {[r.get('epoch') for r in own['records']]}) does not belong to "
                              f"epoch {rec['epoch']} of {side} (world {world}); restore the matching file or start a fresh run")
         gens = own_rec["generators"]
-    return Resume(int(rec["epoch"]), float(rec["top"]), gens, data, rec)
+    return Resume(int(rec["epoch"]), float(rec["top"]), gens, data, rec, optim_data)
 
 
-def _save_pair(state, latest: str, record: dict, older: list, world: int):
+def _save_pair(state, latest: str, record: dict, older: list, world: int, optim_state: dict = None):
     """`latest` and its sidecar: the checkpoint is written to its temporary file and digested there, the sidecar (the new record in front of
     the one before) is replaced, then `latest` is.  Killed before the first replace: the old pair; between the two: the new sidecar, whose
-    older record names the old `latest`; after: the new pair"""
+    older record names the old `latest`; after: the new pair.  optim_state (a trainer with optimizer state): written to `optim_file` of the
+    record's epoch (temporary file, then replace) BEFORE the sidecar that names it; the optimizer files neither kept record names are removed
+    behind the pair -- a kill at any point leaves a pair whose optimizer file exists"""
     os.makedirs(os.path.dirname(latest) or ".", exist_ok=True)
     tmp = latest + ".tmp"
     try:
         torch.save(state, tmp)
         record["digest"] = _file_digest(tmp)
+        if optim_state is not None:
+            opath = optim_file(latest, record["epoch"])
+            otmp = opath + ".tmp"
+            try:
+                torch.save(optim_state, otmp)
+                record["optim"] = {"file": os.path.basename(opath), "digest": _file_digest(otmp), "config": optim_state["optim"]}
+                os.replace(otmp, opath)
+            finally:
+                if os.path.exists(otmp):
+                    os.remove(otmp)
         _write_json_atomic({"format": _RESUME_FORMAT, "world": world, "records": [record] + older[:1]}, resume_file(latest))
         os.replace(tmp, latest)
+        if optim_state is not None:
+            keep = {r["optim"]["file"] for r in [record] + older[:1] if r.get("optim")}
+            head = os.path.basename(latest) + OPTIM_SUFFIX
+            for name in os.listdir(os.path.dirname(latest) or "."):
+                if name.startswith(head) and name[len(head):].isdigit() and name not in keep:
+                    os.remove(os.path.join(os.path.dirname(latest) or ".", name))
     finally:
         if os.path.exists(tmp):
             os.remove(tmp)
@@ -246,7 +308,11 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
 
     --clip_grad_norm / --skip_nonfinite (`guard_flags`; both off: every byte and line as above): after an epoch's steps `tr.guard_stats(reset=True)`
     is read once and the `Traning |` line gets `| gnorm mean M max X | clipped c | skipped k`; an epoch whose steps were ALL skipped raises a
-    RuntimeError before `latest` or `best` is written.  `train_epoch` sums its losses with `LossMean(skip_nonfinite)`."""
+    RuntimeError before `latest` or `best` is written.  `train_epoch` sums its losses with `LossMean(skip_nonfinite)`.
+
+    Optimizer state (`tr.optimizer_state_dict()` not None: --momentum, --optimizer adamw) under --resume: rank 0 writes it beside every `latest`
+    (`optim_file`, named and digested in the record; `_save_pair`), the driver has loaded `resume.optim_state()` into `tr`.  Without --resume no
+    optimizer file is written; without optimizer state the sidecar is byte for byte what it was."""
     val_interval = max(1, F.epochs - 1 if F.val_interval == -1 else F.val_interval)
     top, last, first = 0.0, {}, 0
     resuming = bool(getattr(F, "resume", False))
@@ -255,7 +321,7 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
     if resuming:
         world = _dist()[1] if world is None else world
         generators = generators or {}
-        resume = load_resume(latest, rank, world) if resume is None else resume
+        resume = load_resume(latest, rank, world, getattr(tr, "optim_config", lambda: None)()) if resume is None else resume
         older = [resume.record] if resume.record else []           # rank 0: the record on disk that names the `latest` on disk
         own_older = [{"epoch": resume.epoch, "generators": resume.generators}] if resume.epoch >= 0 else []
         if resume.epoch >= 0:
@@ -290,6 +356,8 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
                 state = tr.state_dict()
                 if not resuming:
                     save_atomic(state, latest)
+                else:                                              # (None: the trainer keeps no optimizer state)
+                    optim_state = getattr(tr, "optimizer_state_dict", lambda: None)()
             if val:
                 t1 = time.time()
                 score, shown = validate(state)
@@ -308,7 +376,7 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
             _barrier()                                             # every other rank's record of this epoch is on disk before rank 0's names it
             if rank == 0:
                 rec = {"epoch": epoch, "top": top, "generators": gens}
-                _save_pair(state, latest, rec, older, world)
+                _save_pair(state, latest, rec, older, world, optim_state)
                 older = [rec]
         _barrier()
     _barrier()                                                     # the last checkpoint is on disk before any rank goes on to -e

@@ -537,6 +537,36 @@ int mt4_sgd_step_guarded_f32(float* p, const float* g, int64_t n, float lr, floa
                              void* stream);
 /* dst[i] = src[i] for i < n when state->skip, nothing otherwise (buffers a skipped step must leave as they were: BatchNorm running statistics) */
 int mt4_restore_if_skipped_f32(float* dst, const float* src, int64_t n, const mt4_guard_state* state, void* stream);
+/*
+ * Optimizer state (--momentum, --nesterov, --optimizer adamw; the reference parses --momentum and hands nothing to torch.optim.SGD).  Elementwise over
+ * the flat fp32 buffers p, g and the state buffers m (, v) of the same length: 16-byte accesses, the n % 4 tail element by element; no atomics.
+ * Every operation is one round-to-nearest IEEE operation in the order written below, without FMA contraction (`ops.optim_step_host` restates it in
+ * numpy float32 and gives the same bits).  guard_state: the record mt4_grad_guard_finalize wrote, read on the device -- grad_scale * coef (one float
+ * multiply) replaces grad_scale and nothing at all is written when it says skip; NULL: unguarded.
+ * All refusals are MT4_EINVAL before any launch: a NULL buffer, n <= 0, p / g / m / v off the 16-byte grid (a record off the 8-byte grid), momentum
+ * outside [0, 1), a beta outside [0, 1), eps <= 0, nesterov with momentum 0.
+ *
+ * mt4_optim_state (24 bytes, 8-byte aligned; sizeof next to mt4_guard_state's 32): AdamW's step count and the running products beta^t.  It lives on the
+ * device because the skip decision does: the host never learns whether a step counted.  Its owner initialises it to {0, 1.0, 1.0}.
+ */
+typedef struct mt4_optim_state {
+    int64_t t;         /* steps applied */
+    double beta1_pow;  /* beta1^t, t IEEE double multiplies from 1.0 */
+    double beta2_pow;  /* beta2^t */
+} mt4_optim_state;
+/* One thread: unless guard_state says skip, t += 1, beta1_pow *= beta1, beta2_pow *= beta2 (one IEEE double multiply each).  Ahead of mt4_adamw_step_f32. */
+int mt4_optim_advance(mt4_optim_state* optim_state, double beta1, double beta2, const mt4_guard_state* guard_state, void* stream);
+/* torch.optim.SGD(momentum, dampening 0, nesterov); s = grad_scale * coef; all float:
+ *   d = g * s + wd * p;   m <- momentum * m + d;   p <- p - lr * (nesterov ? d + momentum * m : m)
+ * A zeroed m gives torch's first step (its buffer starts as d). */
+int mt4_sgd_momentum_step_f32(float* p, const float* g, float* m, int64_t n, float lr, float weight_decay, float grad_scale, float momentum,
+                              int32_t nesterov, const mt4_guard_state* guard_state, void* stream);
+/* torch.optim.AdamW (amsgrad off) at the step optim_state holds (advance it first).  Scalars, once per thread: s = grad_scale * coef, lw = lr * wd (float);
+ * b1, b2 = (float)beta; c1 = (float)(1.0 - beta1), c2 = (float)(1.0 - beta2), step = (float)((double)lr / (1.0 - beta1_pow)),
+ * r2 = (float)sqrt(1.0 - beta2_pow) (evaluated in double, rounded to float once).  Per element, all float:
+ *   q = p - lw * p;  h = g * s;  m <- b1 * m + c1 * h;  v <- b2 * v + c2 * (h * h);  p <- q - step * (m / (sqrt(v) / r2 + eps)) */
+int mt4_adamw_step_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float weight_decay, float grad_scale, double beta1,
+                       double beta2, float eps, const mt4_optim_state* optim_state, const mt4_guard_state* guard_state, void* stream);
 /* y = a * b (+ c): dropout masks (network.py:194-196) forward and backward */
 int mt4_mul_add_f32(const float* a, const float* b, const float* c, float* y, int64_t n, void* stream);
 /* packed Conv1d weight [Cout][Kpad(Cin,taps)] -> packed weight of its data-gradient conv [Cin][Kpad(Cout,taps)] */
