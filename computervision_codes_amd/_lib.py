@@ -104,6 +104,8 @@ SIGNATURES = {
     "mt4_layernorm": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, C.c_float, _i32, _vp]),
     "mt4_attention": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                 C.c_float, _i32, _vp]),
+    "mt4_attention_plan": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                     C.c_float, _i32] + [C.POINTER(_i32)] * 4),
     "mt4_window_attention_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
     "mt4_window_attention_rel_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp]),
     "mt4_patchify": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _FLOAT3, _FLOAT3, _i32, _vp]),

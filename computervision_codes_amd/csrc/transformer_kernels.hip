@@ -1,6 +1,7 @@
 // Kernels around the GEMMs of the transformer-shaped stages (Swin + Query2Label, MS-TCT): LayerNorm with
 // row gather, multi-head attention core, patch extraction, small element-wise pieces.  All HBM-bound or tiny.
 #include "mt4_common.h"
+#include <algorithm>
 #include <type_traits>
 
 // ------------------------------------------------------------------------------------------------ vector helpers
@@ -131,6 +132,29 @@ __global__ __launch_bounds__(256) void layernorm_narrow_kernel(const T* __restri
     }
 }
 
+// the instantiations, narrowest first: a row of nch 16-byte chunks takes the first narrow kernel with nch <= LPR lanes per row, else the first
+// wide kernel whose MAXCH chunks per lane cover it (nch <= 64 * MAXCH)
+#define MT4_LN_NARROW(X) X(16) X(32)
+#define MT4_LN_WIDE(X) X(2) X(4) X(8) X(16)
+constexpr int kLnMaxChunks = 64 * 16;   // of the widest kernel
+
+template <typename T>
+static int layernorm_launch(const void* x, const float* gamma, const float* beta, void* y, int M_out, int C, int G, const int32_t* map, int L_out,
+                            int L_in, float eps, int nch, hipStream_t s) {
+#define X(LPR) \
+    if (nch <= LPR) \
+        return mt4_launch<layernorm_narrow_kernel<T, LPR>>(dim3(cdiv(M_out, 4 * (64 / LPR))), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)y, M_out, C, G, \
+                                                           map, L_out, L_in, eps);
+    MT4_LN_NARROW(X)
+#undef X
+#define X(MAXCH) \
+    if (nch <= 64 * MAXCH) \
+        return mt4_launch<layernorm_kernel<T, MAXCH>>(dim3(cdiv(M_out, 4)), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)y, M_out, C, G, map, L_out, L_in, eps);
+    MT4_LN_WIDE(X)
+#undef X
+    return MT4_EUNSUPPORTED;
+}
+
 extern "C" int mt4_layernorm(const void* x, const float* gamma, const float* beta, void* y, int32_t M_out, int32_t C, int32_t G,
                              const int32_t* map, int32_t L_out, int32_t L_in, float eps, int32_t dtype, void* stream) {
     mt4_clear_error();
@@ -141,27 +165,10 @@ extern "C" int mt4_layernorm(const void* x, const float* gamma, const float* bet
     const int V = dtype == MT4_BF16 ? 8 : 4;
     if (C % V != 0 || (((uintptr_t)x | (uintptr_t)y) & 15)) return MT4_EALIGN;
     const int nch = G * C / V;
-    if (nch > 64 * 16) return MT4_EUNSUPPORTED;
+    if (nch > kLnMaxChunks) return MT4_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(cdiv(M_out, 4)), block(256);
-#define LN_LAUNCH(TT, MC) hipLaunchKernelGGL((layernorm_kernel<TT, MC>), grid, block, 0, s, (const TT*)x, gamma, beta, (TT*)y, M_out, C, G, map, L_out, L_in, eps)
-    if (nch <= 32) {
-        const int lpr = nch <= 16 ? 16 : 32;
-        const dim3 g2(cdiv(M_out, 4 * (64 / lpr)));
-#define LN_NARROW(TT, LL) hipLaunchKernelGGL((layernorm_narrow_kernel<TT, LL>), g2, block, 0, s, (const TT*)x, gamma, beta, (TT*)y, M_out, C, G, map, L_out, L_in, eps)
-        if (dtype == MT4_BF16) { if (lpr == 16) LN_NARROW(u16, 16); else LN_NARROW(u16, 32); }
-        else { if (lpr == 16) LN_NARROW(float, 16); else LN_NARROW(float, 32); }
-#undef LN_NARROW
-        return mt4_check_launch();
-    }
-    const int need = cdiv(nch, 64);
-    if (dtype == MT4_BF16) {
-        if (need <= 2) LN_LAUNCH(u16, 2); else if (need <= 4) LN_LAUNCH(u16, 4); else if (need <= 8) LN_LAUNCH(u16, 8); else LN_LAUNCH(u16, 16);
-    } else {
-        if (need <= 2) LN_LAUNCH(float, 2); else if (need <= 4) LN_LAUNCH(float, 4); else if (need <= 8) LN_LAUNCH(float, 8); else LN_LAUNCH(float, 16);
-    }
-#undef LN_LAUNCH
-    return mt4_check_launch();
+    if (dtype == MT4_BF16) return layernorm_launch<u16>(x, gamma, beta, y, M_out, C, G, map, L_out, L_in, eps, nch, s);
+    return layernorm_launch<float>(x, gamma, beta, y, M_out, C, G, map, L_out, L_in, eps, nch, s);
 }
 
 // ------------------------------------------------------------------------------------------------ attention core
@@ -169,13 +176,22 @@ extern "C" int mt4_layernorm(const void* x, const float* gamma, const float* bet
 // One query per LPQ lanes (each lane owns DPL head dims), keys/values staged in LDS as fp32 in chunks of KC keys,
 // online softmax in fp32.  Covers Swin windows (hd 32, N 49/144, bias + shift mask), nn.MultiheadAttention of the
 // Q2L transformer (hd 256) and the MS-TCT global block (hd 32..108, T 256).
+constexpr int kMaxLds = 64 * 1024;   // dynamic LDS a launch of this file may ask for: a plan that needs more is refused
+
+// LDS of attention_kernel<T, DPL, LPQ>, in floats: the K rows of a chunk of KC keys, then its V rows; a row = LPQ slices of DPL head dims
+struct AttnLds {
+    static constexpr int slice(int dpl) { return dpl + 4; }   // slice stride: staggers the LPQ slices over banks
+    static constexpr int row(int dpl, int lpq) { return lpq * slice(dpl); }
+    static constexpr int max_keys(int dpl, int lpq) { return kMaxLds / (2 * (int)sizeof(float)) / row(dpl, lpq) / 4 * 4; }   // groups of 4 keys within 64 KiB
+    static constexpr int bytes(int dpl, int lpq, int kc) { return 2 * kc * row(dpl, lpq) * (int)sizeof(float); }
+};
+
 template <typename T, int DPL, int LPQ>
 __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                         T* __restrict__ out, const float* __restrict__ bias,
                                                         const float* __restrict__ mask, int Nq, int Nk, int hd, int q_stride,
                                                         int k_stride, int v_stride, int o_stride, int nW, float scale, int KC, int vec_ok) {
-    constexpr int SL = DPL + 4;        // slice stride in LDS (floats): staggers the LPQ slices over banks
-    constexpr int ROW = LPQ * SL;
+    constexpr int SL = AttnLds::slice(DPL), ROW = AttnLds::row(DPL, LPQ);
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Ks = lds;
     float* Vs = lds + (size_t)KC * ROW;
@@ -310,22 +326,30 @@ __device__ __forceinline__ uint2 wa_read_tr(const char* p) {     // ds_read_b64_
 // O^T = V^T P^T.  The head dim runs through LDS in chunks of 64: K rows [key][64] for the scores, then V rows [key][64] for the output, read
 // back transposed by `ds_read_b64_tr_b16` (the V^T image of rounds 1-3 was written with two-byte stores: 67 % of the kernel's LDS cycles were
 // bank conflicts); the wave's Q fragments (16 queries x HD, pre-scaled) stay in registers.
+// LDS of mha_mfma_kernel<NKT, HD>, in bytes: the K rows [NKP][K_PITCH] of a 64-dim chunk, then its V rows [NKP2][V_PITCH]
+struct MhaBf16Lds {
+    static constexpr int K_PITCH = 160;   // bytes per K row of a chunk (128 used): conflict-free b128 fragment reads under the REAL lane grouping of
+                                          // ds_read_b128 ({0-3, 12-15, 20-27}, ...: MI355X_MICROARCH.md); 144 (rounds 1-3: conflict-free for 16 consecutive
+                                          // lanes) measured SQ_LDS_BANK_CONFLICT = 69 % of this kernel's LDS cycles (profiles/r04_swin_kernel_counters.txt)
+    static constexpr int V_PITCH = 128;   // bytes per V row of a chunk: 4 spans of 32 B (16 head dims each); span dt of key k sits at dt ^ ((k >> 1) & 3), so the
+                                          // 8 keys a 32-lane half of a transposed read takes fall on 8 different bank groups
+    static constexpr int nkp(int nkt) { return nkt * 16; }
+    static constexpr int nkp2(int nkt) { return (nkt + 1) / 2 * 32; }   // keys padded to whole 32-key MFMA blocks
+    static constexpr int v_off(int nkt) { return nkp(nkt) * K_PITCH; }
+    static constexpr int bytes(int nkt) { return v_off(nkt) + nkp2(nkt) * V_PITCH; }
+};
+
 template <int NKT, int HD>
 __global__ __launch_bounds__(256) void mha_mfma_kernel(const u16* __restrict__ q, const u16* __restrict__ k, const u16* __restrict__ v,
                                                        u16* __restrict__ out, int Nq, int Nk, int q_stride, int k_stride, int v_stride,
                                                        int o_stride, float scale) {
-    constexpr int NKP = NKT * 16;
-    constexpr int NKP2 = ((NKT + 1) / 2) * 32;   // keys padded to whole 32-key MFMA blocks
-    constexpr int K_PITCH = 160;                 // bytes per K row of a chunk (128 used): conflict-free b128 fragment reads under the REAL lane grouping of
-                                                 // ds_read_b128 ({0-3, 12-15, 20-27}, ...: MI355X_MICROARCH.md); 144 (rounds 1-3: conflict-free for 16 consecutive
-                                                 // lanes) measured SQ_LDS_BANK_CONFLICT = 69 % of this kernel's LDS cycles (profiles/r04_swin_kernel_counters.txt)
-    constexpr int V_PITCH = 128;                 // bytes per V row of a chunk: 4 spans of 32 B (16 head dims each); span dt of key k sits at dt ^ ((k >> 1) & 3), so the
-                                                 // 8 keys a 32-lane half of a transposed read takes fall on 8 different bank groups
+    constexpr int NKP = MhaBf16Lds::nkp(NKT), NKP2 = MhaBf16Lds::nkp2(NKT);
+    constexpr int K_PITCH = MhaBf16Lds::K_PITCH, V_PITCH = MhaBf16Lds::V_PITCH;
     constexpr int NCH = HD / 64;
     static_assert(HD % 64 == 0, "shape");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Ks = smem;                    // [NKP][K_PITCH]
-    char* Vs = smem + NKP * K_PITCH;    // [NKP2][V_PITCH]
+    char* Ks = smem;                                // [NKP][K_PITCH]
+    char* Vs = smem + MhaBf16Lds::v_off(NKT);       // [NKP2][V_PITCH]
     const int h = blockIdx.x, b = blockIdx.y, q0 = blockIdx.z * 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, qd = lane >> 4;
@@ -458,156 +482,41 @@ __global__ __launch_bounds__(256) void mha_mfma_kernel(const u16* __restrict__ q
 // both operands agree, so within a group of 16 dims MFMA j takes dim 4*qd + j from lane group qd: a lane's 4 slots are 4 CONSECUTIVE
 // floats = one 16-byte read (K rows, Q registers); likewise the 4 MFMAs of a 16-key tile take key 4*qd + e, which is what a lane of the
 // score tile already holds.  Head dims run through LDS in chunks of 32 (K rows, then V^T), zero-padded to whole groups.
-template <int NKT>
-__global__ __launch_bounds__(256) void mha_mfma_f32_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                           float* __restrict__ out, int Nq, int Nk, int hd, int q_stride, int k_stride,
-                                                           int v_stride, int o_stride, float scale) {
-    constexpr int NKP = NKT * 16;
-    constexpr int K_PITCH = 40;          // floats per K row of a chunk (32 used): 160 B = conflict-free b128 reads under the real lane grouping (36: 2-way)
-    constexpr int VT_PITCH = NKP + 4;    // floats per V^T row: = 4 mod 64 for NKP = 128, 256
-    constexpr int MAXG = 8;              // hd <= 128: at most 8 groups of 16 dims
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* Ks = (float*)smem;            // [NKP][K_PITCH]; the V^T chunk [32][VT_PITCH] reuses the space
-    float* Vt = (float*)smem;
-    const int h = blockIdx.x, b = blockIdx.y, q0 = blockIdx.z * 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r16 = lane & 15, qd = lane >> 4;
-    const int query = q0 + wave * 16 + r16;
-    const bool q_ok = query < Nq;
-    const int nch = (hd + 31) / 32;
-
-    float4 qf[MAXG];
-    {
-        const float* qp = q + ((long long)b * Nq + (q_ok ? query : 0)) * q_stride + h * hd;
-#pragma unroll
-        for (int g = 0; g < MAXG; ++g) {
-            const int d = g * 16 + qd * 4;
-            float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (q_ok && d < hd) t = *(const float4*)(qp + d);
-            qf[g] = make_float4(t.x * scale, t.y * scale, t.z * scale, t.w * scale);
-        }
-    }
-    f32x4 s[NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < MAXG / 2; ++c) {
-        if (c < nch) {   // (uniform)
-            if (c) __syncthreads();
-            {   // K chunk: rows of 32 dims = 8 pieces of 4 floats; every load issued before the first LDS store (clamped address + select)
-                constexpr int SI = (NKP * 8 + 255) / 256;
-                float4 kreg[SI];
-#pragma unroll
-                for (int i = 0; i < SI; ++i) {
-                    const int e = tid + i * 256, row = e >> 3, pc = e & 7;
-                    const int d = c * 32 + pc * 4;
-                    const float4 t = *(const float4*)(k + ((long long)b * Nk + min(row, Nk - 1)) * k_stride + h * hd + min(d, hd - 4));
-                    kreg[i] = (row < Nk && d < hd) ? t : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-#pragma unroll
-                for (int i = 0; i < SI; ++i) {
-                    const int e = tid + i * 256, row = e >> 3, pc = e & 7;
-                    if (e < NKP * 8) *(float4*)(Ks + row * K_PITCH + pc * 4) = kreg[i];
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    const float4 kf = *(const float4*)(Ks + (kt * 16 + r16) * K_PITCH + g * 16 + qd * 4);
-                    const float4 qv = qf[c * 2 + g];
-                    s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qv.x, s[kt], 0, 0, 0);
-                    s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qv.y, s[kt], 0, 0, 0);
-                    s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qv.z, s[kt], 0, 0, 0);
-                    s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qv.w, s[kt], 0, 0, 0);
-                }
-        }
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (kt * 16 + qd * 4 + e >= Nk) s[kt][e] = -1e30f;
-            mx = fmaxf(mx, s[kt][e]);
-        }
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { s[kt][e] = __expf(s[kt][e] - mx); sum += s[kt][e]; }
-    sum += __shfl_xor(sum, 16);
-    sum += __shfl_xor(sum, 32);
-    const float inv = 1.0f / sum;
-    for (int c = 0; c < nch; ++c) {
-        __syncthreads();
-        {   // V chunk, transposed: Vt[d][key] (loads first, as for K)
-            constexpr int SI = (NKP * 8 + 255) / 256;
-            float4 vreg[SI];
-#pragma unroll
-            for (int i = 0; i < SI; ++i) {
-                const int e = tid + i * 256, row = e >> 3, pc = e & 7;
-                const int d = c * 32 + pc * 4;
-                const float4 t = *(const float4*)(v + ((long long)b * Nk + min(row, Nk - 1)) * v_stride + h * hd + min(d, hd - 4));
-                vreg[i] = (row < Nk && d < hd) ? t : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-            for (int i = 0; i < SI; ++i) {
-                const int e = tid + i * 256, row = e >> 3, pc = e & 7;
-                if (e < NKP * 8) {
-                    Vt[(pc * 4 + 0) * VT_PITCH + row] = vreg[i].x;
-                    Vt[(pc * 4 + 1) * VT_PITCH + row] = vreg[i].y;
-                    Vt[(pc * 4 + 2) * VT_PITCH + row] = vreg[i].z;
-                    Vt[(pc * 4 + 3) * VT_PITCH + row] = vreg[i].w;
-                }
-            }
-        }
-        __syncthreads();
-        f32x4 o[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                const float4 vf = *(const float4*)(Vt + (dt * 16 + r16) * VT_PITCH + kt * 16 + qd * 4);   // keys 16kt + 4qd .. +3 of dim row r16
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.x, s[kt][0], o[dt], 0, 0, 0);
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.y, s[kt][1], o[dt], 0, 0, 0);
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.z, s[kt][2], o[dt], 0, 0, 0);
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.w, s[kt][3], o[dt], 0, 0, 0);
-            }
-        if (q_ok) {   // lane (r16 = query, qd): dims 32c + 16dt + 4qd .. +3
-            float* op = out + ((long long)b * Nq + query) * o_stride + h * hd;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                const int d = c * 32 + dt * 16 + qd * 4;
-                if (d < hd) *(float4*)(op + d) = make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
-            }
-        }
-    }
-}
-
-// The same core for a launch that cannot fill the chip with one wave per 16 queries (one MS-TCT window: 8 heads x 256 queries = 128 waves,
+//
+// KSPLIT: the same core for a launch that cannot fill the chip with one wave per 16 queries (one MS-TCT window: 8 heads x 256 queries = 128 waves,
 // each busy 1.7 us per 32-dim chunk with its 128 fp32 matrix instructions): the four waves of a workgroup share 16 queries and split the KEYS
 // (key tiles 4w .. 4w+3 of 16), so 4x the waves carry a quarter of the matrix work each.  Row maxima and sums meet in LDS (fixed order
 // wave 0..3: deterministic), the partial P.V tiles of a chunk likewise, and 128 threads store the summed chunk.
-template <int NKT>
-__global__ __launch_bounds__(256) void mha_mfma_f32_ksplit_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                                  float* __restrict__ out, int Nq, int Nk, int hd, int q_stride, int k_stride,
-                                                                  int v_stride, int o_stride, float scale) {
-    constexpr int NKP = NKT * 16, NKW = NKT / 4;
-    constexpr int K_PITCH = 40, VT_PITCH = NKP + 4, MAXG = 8;
-    constexpr int MAIN = NKP * K_PITCH > 32 * VT_PITCH ? NKP * K_PITCH : 32 * VT_PITCH;
+
+// LDS of mha_mfma_f32_kernel<NKT, KSPLIT>, in floats: the K rows [NKP][K_PITCH] of a 32-dim chunk, whose space the V^T chunk [32][VT_PITCH] reuses;
+// with KSPLIT then the row maxima and row sums per wave [2][4][16] and a chunk's partial output tiles per wave [4][16][32]
+struct MhaF32Lds {
+    static constexpr int K_PITCH = 40;   // floats per K row of a chunk (32 used): 160 B = conflict-free b128 reads under the real lane grouping (36: 2-way)
+    static constexpr int nkp(int nkt) { return nkt * 16; }
+    static constexpr int vt_pitch(int nkt) { return nkp(nkt) + 4; }   // floats per V^T row: = 4 mod 64 for NKP = 128, 256
+    static constexpr int red_off(int nkt) { return nkp(nkt) * K_PITCH > 32 * vt_pitch(nkt) ? nkp(nkt) * K_PITCH : 32 * vt_pitch(nkt); }
+    static constexpr int part_off(int nkt) { return red_off(nkt) + 2 * 4 * 16; }
+    static constexpr int bytes(int nkt, bool ksplit) { return (int)sizeof(float) * (ksplit ? part_off(nkt) + 4 * 16 * 32 : red_off(nkt)); }
+};
+
+template <int NKT, bool KSPLIT>
+__global__ __launch_bounds__(256) void mha_mfma_f32_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                           float* __restrict__ out, int Nq, int Nk, int hd, int q_stride, int k_stride,
+                                                           int v_stride, int o_stride, float scale) {
+    constexpr int NKP = MhaF32Lds::nkp(NKT), K_PITCH = MhaF32Lds::K_PITCH, VT_PITCH = MhaF32Lds::vt_pitch(NKT);
+    constexpr int NKW = KSPLIT ? NKT / 4 : NKT;   // key tiles of a wave
+    constexpr int QPB = KSPLIT ? 16 : 64;         // queries of a workgroup
+    constexpr int MAXG = 8;                       // hd <= 128: at most 8 groups of 16 dims
+    constexpr int SI = (NKP * 8 + 255) / 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* Ks = (float*)smem;
     float* Vt = (float*)smem;
-    float* red = (float*)smem + MAIN;          // [2][4][16]: row maxima, row sums per wave
-    float* part = red + 128;                   // [4][16][32]: a chunk's partial output tiles per wave
-    const int h = blockIdx.x, b = blockIdx.y, q0 = blockIdx.z * 16;
+    float* red = (float*)smem + MhaF32Lds::red_off(NKT);     // KSPLIT only, as is `part`
+    float* part = (float*)smem + MhaF32Lds::part_off(NKT);
+    const int h = blockIdx.x, b = blockIdx.y, q0 = blockIdx.z * QPB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, qd = lane >> 4;
-    const int query = q0 + r16;
+    const int query = KSPLIT ? q0 + r16 : q0 + wave * 16 + r16;
     const bool q_ok = query < Nq;
     const int nch = (hd + 31) / 32;
 
@@ -622,15 +531,14 @@ __global__ __launch_bounds__(256) void mha_mfma_f32_ksplit_kernel(const float* _
             qf[g] = make_float4(t.x * scale, t.y * scale, t.z * scale, t.w * scale);
         }
     }
-    f32x4 s[NKW];
+    f32x4 s[NKW];   // score tile j of this wave = key tile j, or wave * NKW + j with KSPLIT
 #pragma unroll
     for (int j = 0; j < NKW; ++j) s[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < MAXG / 2; ++c) {
         if (c < nch) {   // (uniform)
             if (c) __syncthreads();
-            {
-                constexpr int SI = (NKP * 8 + 255) / 256;
+            {   // K chunk: rows of 32 dims = 8 pieces of 4 floats; every load issued before the first LDS store (clamped address + select)
                 float4 kreg[SI];
 #pragma unroll
                 for (int i = 0; i < SI; ++i) {
@@ -650,7 +558,8 @@ __global__ __launch_bounds__(256) void mha_mfma_f32_ksplit_kernel(const float* _
             for (int j = 0; j < NKW; ++j)
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
-                    const float4 kf = *(const float4*)(Ks + ((wave * NKW + j) * 16 + r16) * K_PITCH + g * 16 + qd * 4);
+                    const int kt = KSPLIT ? wave * NKW + j : j;
+                    const float4 kf = *(const float4*)(Ks + (kt * 16 + r16) * K_PITCH + g * 16 + qd * 4);
                     const float4 qv = qf[c * 2 + g];
                     s[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qv.x, s[j], 0, 0, 0);
                     s[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qv.y, s[j], 0, 0, 0);
@@ -664,14 +573,17 @@ __global__ __launch_bounds__(256) void mha_mfma_f32_ksplit_kernel(const float* _
     for (int j = 0; j < NKW; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            if ((wave * NKW + j) * 16 + qd * 4 + e >= Nk) s[j][e] = -1e30f;
+            const int kt = KSPLIT ? wave * NKW + j : j;
+            if (kt * 16 + qd * 4 + e >= Nk) s[j][e] = -1e30f;
             mx = fmaxf(mx, s[j][e]);
         }
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     mx = fmaxf(mx, __shfl_xor(mx, 32));
-    if (qd == 0) red[wave * 16 + r16] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[r16], red[16 + r16]), fmaxf(red[32 + r16], red[48 + r16]));
+    if constexpr (KSPLIT) {   // red[0][wave][query]
+        if (qd == 0) red[wave * 16 + r16] = mx;
+        __syncthreads();
+        mx = fmaxf(fmaxf(red[r16], red[16 + r16]), fmaxf(red[32 + r16], red[48 + r16]));
+    }
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < NKW; ++j)
@@ -679,13 +591,14 @@ __global__ __launch_bounds__(256) void mha_mfma_f32_ksplit_kernel(const float* _
         for (int e = 0; e < 4; ++e) { s[j][e] = __expf(s[j][e] - mx); sum += s[j][e]; }
     sum += __shfl_xor(sum, 16);
     sum += __shfl_xor(sum, 32);
-    if (qd == 0) red[64 + wave * 16 + r16] = sum;
-    __syncthreads();
-    const float inv = 1.0f / (((red[64 + r16] + red[80 + r16]) + red[96 + r16]) + red[112 + r16]);
+    if constexpr (KSPLIT) {   // red[1][wave][query]: the storing threads add the four in wave order
+        if (qd == 0) red[64 + wave * 16 + r16] = sum;
+        __syncthreads();
+    }
+    const float inv = 1.0f / sum;   // (not KSPLIT)
     for (int c = 0; c < nch; ++c) {
-        __syncthreads();      // the K chunk / the previous V chunk and its partial tiles are done with
-        {
-            constexpr int SI = (NKP * 8 + 255) / 256;
+        __syncthreads();      // the K chunk / the previous V chunk (and its partial tiles) are done with
+        {   // V chunk, transposed: Vt[d][key] (loads first, as for K)
             float4 vreg[SI];
 #pragma unroll
             for (int i = 0; i < SI; ++i) {
@@ -711,133 +624,204 @@ __global__ __launch_bounds__(256) void mha_mfma_f32_ksplit_kernel(const float* _
         for (int j = 0; j < NKW; ++j)
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
-                const float4 vf = *(const float4*)(Vt + (dt * 16 + r16) * VT_PITCH + (wave * NKW + j) * 16 + qd * 4);
+                const int kt = KSPLIT ? wave * NKW + j : j;
+                const float4 vf = *(const float4*)(Vt + (dt * 16 + r16) * VT_PITCH + kt * 16 + qd * 4);   // keys 16kt + 4qd .. +3 of dim row r16
                 o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.x, s[j][0], o[dt], 0, 0, 0);
                 o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.y, s[j][1], o[dt], 0, 0, 0);
                 o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.z, s[j][2], o[dt], 0, 0, 0);
                 o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.w, s[j][3], o[dt], 0, 0, 0);
             }
-        // lane (r16 = query, qd) holds dims 16dt + 4qd .. +3 of the chunk: part[wave][query][dim]
+        if constexpr (!KSPLIT) {
+            if (q_ok) {   // lane (r16 = query, qd): dims 32c + 16dt + 4qd .. +3
+                float* op = out + ((long long)b * Nq + query) * o_stride + h * hd;
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-            *(float4*)(part + (wave * 16 + r16) * 32 + dt * 16 + qd * 4) = make_float4(o[dt][0], o[dt][1], o[dt][2], o[dt][3]);
-        __syncthreads();
-        if (tid < 128) {      // thread: query tid / 8, dims 4 (tid % 8) .. +3 of the chunk
-            const int qq = tid >> 3, d4 = (tid & 7) * 4;
-            const float4 a0 = *(const float4*)(part + (0 * 16 + qq) * 32 + d4), a1 = *(const float4*)(part + (1 * 16 + qq) * 32 + d4);
-            const float4 a2 = *(const float4*)(part + (2 * 16 + qq) * 32 + d4), a3 = *(const float4*)(part + (3 * 16 + qq) * 32 + d4);
-            const float iv = 1.0f / (((red[64 + qq] + red[80 + qq]) + red[96 + qq]) + red[112 + qq]);
-            const int d = c * 32 + d4;
-            if (q0 + qq < Nq && d < hd)
-                *(float4*)(out + ((long long)b * Nq + q0 + qq) * o_stride + h * hd + d) =
-                    make_float4((((a0.x + a1.x) + a2.x) + a3.x) * iv, (((a0.y + a1.y) + a2.y) + a3.y) * iv,
-                                (((a0.z + a1.z) + a2.z) + a3.z) * iv, (((a0.w + a1.w) + a2.w) + a3.w) * iv);
+                for (int dt = 0; dt < 2; ++dt) {
+                    const int d = c * 32 + dt * 16 + qd * 4;
+                    if (d < hd) *(float4*)(op + d) = make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
+                }
+            }
+        } else {
+            // lane (r16 = query, qd) holds dims 16dt + 4qd .. +3 of the chunk: part[wave][query][dim]
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+                *(float4*)(part + (wave * 16 + r16) * 32 + dt * 16 + qd * 4) = make_float4(o[dt][0], o[dt][1], o[dt][2], o[dt][3]);
+            __syncthreads();
+            if (tid < 128) {      // thread: query tid / 8, dims 4 (tid % 8) .. +3 of the chunk
+                const int qq = tid >> 3, d4 = (tid & 7) * 4;
+                const float4 a0 = *(const float4*)(part + (0 * 16 + qq) * 32 + d4), a1 = *(const float4*)(part + (1 * 16 + qq) * 32 + d4);
+                const float4 a2 = *(const float4*)(part + (2 * 16 + qq) * 32 + d4), a3 = *(const float4*)(part + (3 * 16 + qq) * 32 + d4);
+                const float iv = 1.0f / (((red[64 + qq] + red[80 + qq]) + red[96 + qq]) + red[112 + qq]);
+                const int d = c * 32 + d4;
+                if (q0 + qq < Nq && d < hd)
+                    *(float4*)(out + ((long long)b * Nq + q0 + qq) * o_stride + h * hd + d) =
+                        make_float4((((a0.x + a1.x) + a2.x) + a3.x) * iv, (((a0.y + a1.y) + a2.y) + a3.y) * iv,
+                                    (((a0.z + a1.z) + a2.z) + a3.z) * iv, (((a0.w + a1.w) + a2.w) + a3.w) * iv);
+            }
         }
     }
-    (void)inv;
+}
+
+// ---- what mt4_attention launches.  Every instantiation stands once in the lists below; the choice (attention_plan) and the launch
+// (attention_launch) are both generated from them.
+// attention_kernel<T, DPL, LPQ>, DPL * LPQ >= hd.  BASE: fewest lanes per query first; FEW: 8 lanes per query, few dims per lane (launches that
+// cannot fill the chip); WIDE: head dims 257 .. 512 (Q2L over Swin-L: 1536 / 4 heads = 384)
+#define MT4_ATTN_BASE(X) X(32, 1) X(24, 2) X(32, 2) X(20, 4) X(28, 4) X(32, 4) X(32, 8)
+#define MT4_ATTN_FEW(X) X(4, 8) X(8, 8) X(12, 8) X(16, 8) X(24, 8)
+#define MT4_ATTN_WIDE(X) X(48, 8) X(64, 8)
+#define MT4_ATTN_GENERIC_VARIANTS(X) MT4_ATTN_BASE(X) MT4_ATTN_FEW(X) MT4_ATTN_WIDE(X)
+// mha_mfma_kernel<NKT, HD>: Nk <= 16 NKT keys, head dim HD (256: Q2L over Swin-B, d = 1024 / 4 heads; 384: over Swin-L, d = 1536 -- the shipped
+// teacher, Scripts/train_fold1.sh:5-12)
+#define MT4_MHA_BF16_NKT(X, HD) X(1, HD) X(2, HD) X(3, HD) X(4, HD) X(5, HD) X(6, HD) X(7, HD) X(8, HD) X(9, HD) X(10, HD)
+#define MT4_MHA_BF16_VARIANTS(X) MT4_MHA_BF16_NKT(X, 256) MT4_MHA_BF16_NKT(X, 384)
+// mha_mfma_f32_kernel<NKT, KSPLIT>
+#define MT4_MHA_F32_NKT(X, KSPLIT) X(8, KSPLIT) X(16, KSPLIT)
+#define MT4_MHA_F32_VARIANTS(X) MT4_MHA_F32_NKT(X, false) MT4_MHA_F32_NKT(X, true)
+
+struct AttnCfg { int a, b; };   // the two template parameters of a variant
+#define X(A, B) {A, B},
+constexpr AttnCfg kAttnWalk[] = {MT4_ATTN_BASE(X) MT4_ATTN_WIDE(X)};   // the first that covers hd is taken
+constexpr AttnCfg kAttnFew[] = {MT4_ATTN_FEW(X)};                      // likewise, where the few-workgroups rule applies
+constexpr AttnCfg kAttnAll[] = {MT4_ATTN_GENERIC_VARIANTS(X)};
+constexpr AttnCfg kMhaBf16[] = {MT4_MHA_BF16_VARIANTS(X)};
+constexpr AttnCfg kMhaF32[] = {MT4_MHA_F32_NKT(X, 0)};                  // ascending NKT
+#undef X
+constexpr bool attn_variants_ok() {
+    for (const AttnCfg& c : kAttnAll) {
+        int seen = 0;
+        for (const AttnCfg& d : kAttnAll) seen += c.a == d.a && c.b == d.b;
+        // DPL % 4: a staged 4-vector never straddles slices; LPQ lanes of a query exchange by xor-shuffles inside a wave; a chunk holds >= 4 keys
+        if (seen != 1 || c.a % 4 != 0 || (c.b & (c.b - 1)) != 0 || 64 % c.b != 0 || AttnLds::max_keys(c.a, c.b) < 4) return false;
+    }
+    return sizeof(kAttnAll) / sizeof(kAttnAll[0]) == 14;
+}
+static_assert(attn_variants_ok(), "a (DPL, LPQ) pair names one instantiation of attention_kernel");
+
+template <int N>
+constexpr const AttnCfg* generic_covering(const AttnCfg (&list)[N], int hd) {   // first (DPL, LPQ) with DPL * LPQ >= hd
+    for (const AttnCfg& c : list)
+        if (c.a * c.b >= hd) return &c;
+    return nullptr;
+}
+template <int N>
+constexpr const AttnCfg* mha_covering(const AttnCfg (&list)[N], int nkt, int b) {   // first (NKT, b) with NKT >= nkt key tiles
+    for (const AttnCfg& c : list)
+        if (c.a >= nkt && c.b == b) return &c;
+    return nullptr;
+}
+
+struct AttnArgs {   // the arguments of mt4_attention
+    const void *q, *k, *v;
+    void* out;
+    const float *bias, *mask;
+    int B, H, Nq, Nk, hd, q_stride, k_stride, v_stride, o_stride, nW;
+    float scale;
+    int dtype;
+};
+struct AttnPlan {
+    int family, p0, p1;   // MT4_ATTN_* and the variant: (DPL, LPQ), (NKT, HD) or (NKT, key-split waves: 1 / 4)
+    dim3 grid, block;
+    int lds;              // dynamic LDS bytes
+    int KC, vec_ok;       // generic family: keys per LDS chunk; 4-element vector staging
+};
+
+// Every check of mt4_attention and what it launches; host arithmetic only (no HIP call, pointers looked at for NULL and alignment alone)
+static int attention_plan(const AttnArgs& a, AttnPlan* p) {
+    if (!a.q || !a.k || !a.v || !a.out || a.B <= 0 || a.H <= 0 || a.Nq <= 0 || a.Nk <= 0 || a.hd <= 0) return MT4_EINVAL;
+    if (a.dtype != MT4_F32 && a.dtype != MT4_BF16) return MT4_EUNSUPPORTED;
+    if (a.mask && a.nW <= 0) return MT4_EINVAL;
+    if (a.hd > 512 || a.B > 65535 || a.H > 65535) return MT4_EUNSUPPORTED;
+    const int es = a.dtype == MT4_BF16 ? 2 : 4;
+    const uintptr_t qkv = (uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v;
+    const bool plain = !a.bias && !a.mask && cdiv(a.Nq, 64) <= 65535;
+    const int nkt = cdiv(a.Nk, 16);
+    const AttnCfg *const bf16 = mha_covering(kMhaBf16, nkt, a.hd), *const f32 = mha_covering(kMhaF32, nkt, 0);
+    p->KC = 0;
+    // 4-element vector staging needs every (row, head) start 4-element aligned
+    p->vec_ok = (a.hd % 4 == 0) && (a.k_stride * es) % (4 * es) == 0 && (a.v_stride * es) % (4 * es) == 0 &&
+                (((uintptr_t)a.k | (uintptr_t)a.v) & (4 * es - 1)) == 0;
+    p->block = dim3(256);
+    if (a.dtype == MT4_BF16 && plain && bf16 && (a.q_stride % 8) == 0 && (a.k_stride % 8) == 0 && (a.v_stride % 8) == 0 && (a.o_stride % 4) == 0 &&
+        (qkv & 15) == 0 && ((uintptr_t)a.out & 7) == 0) {
+        // large head dim, bf16, no bias / mask, keys fit one workgroup's score registers: matrix-unit kernel, 64 queries per workgroup
+        p->family = MT4_ATTN_MFMA_BF16, p->p0 = bf16->a, p->p1 = bf16->b;
+        p->grid = dim3(a.H, a.B, cdiv(a.Nq, 64));
+        p->lds = MhaBf16Lds::bytes(p->p0);
+    } else if (a.dtype == MT4_F32 && plain && f32 && a.hd <= 128 && (a.hd % 4) == 0 && (a.q_stride % 4) == 0 && (a.k_stride % 4) == 0 &&
+               (a.v_stride % 4) == 0 && (a.o_stride % 4) == 0 && ((qkv | (uintptr_t)a.out) & 15) == 0) {
+        // fp32 (parity mode), no bias / mask, <= 256 keys, head dim <= 128: exact-fp32 matrix-unit kernel (MS-TCT's global block).
+        // Too few 64-query workgroups for the chip (one MS-TCT window: 32): four waves per 16 queries, keys split between them
+        const bool ksplit = (long long)a.H * a.B * cdiv(a.Nq, 64) < 128 && cdiv(a.Nq, 16) <= 65535;
+        p->family = MT4_ATTN_MFMA_F32, p->p0 = f32->a, p->p1 = ksplit ? 4 : 1;
+        p->grid = dim3(a.H, a.B, cdiv(a.Nq, ksplit ? 16 : 64));
+        p->lds = MhaF32Lds::bytes(p->p0, ksplit);
+    } else {
+        const AttnCfg* c = generic_covering(kAttnWalk, a.hd);
+        if (!c) return MT4_EUNSUPPORTED;
+        int threads = ((a.Nq * c->b + 63) / 64) * 64;
+        if (threads > 256) threads = 256;
+        // a launch that cannot fill the chip (one short sequence: MS-TCT's global block has T = 256 queries x 8 heads) takes 8 lanes per
+        // query instead: 8x less serial work per lane, 8x more workgroups (workgroup size: 64/128/256 threads within 2 %, A/B)
+        if (a.hd <= 64 && (long long)cdiv(a.Nq, threads / c->b) * a.H * a.B < 128) {   // (measured: 103 -> 72 us at hd 32, 94 -> 88 at hd 48; slower for hd >= 72)
+            if (const AttnCfg* few = generic_covering(kAttnFew, a.hd)) { c = few; threads = 256; }
+        }
+        p->family = MT4_ATTN_GENERIC, p->p0 = c->a, p->p1 = c->b;
+        p->KC = std::min(AttnLds::max_keys(c->a, c->b), (a.Nk + 3) / 4 * 4);
+        p->grid = dim3(cdiv(a.Nq, threads / c->b), a.H, a.B), p->block = dim3(threads);
+        p->lds = AttnLds::bytes(c->a, c->b, p->KC);
+    }
+    return p->lds > kMaxLds ? MT4_EUNSUPPORTED : MT4_OK;
+}
+
+template <typename T>
+static int attention_launch_generic(const AttnArgs& a, const AttnPlan& p, hipStream_t s) {
+#define X(DPL, LPQ) \
+    if (p.p0 == DPL && p.p1 == LPQ) \
+        return mt4_launch<attention_kernel<T, DPL, LPQ>>(p.grid, p.block, p.lds, s, (const T*)a.q, (const T*)a.k, (const T*)a.v, (T*)a.out, a.bias, a.mask, a.Nq, \
+                                                         a.Nk, a.hd, a.q_stride, a.k_stride, a.v_stride, a.o_stride, a.nW, a.scale, p.KC, p.vec_ok);
+    MT4_ATTN_GENERIC_VARIANTS(X)
+#undef X
+    return MT4_EINVAL;
+}
+
+static int attention_launch(const AttnArgs& a, const AttnPlan& p, hipStream_t s) {
+    if (p.family == MT4_ATTN_GENERIC) return a.dtype == MT4_BF16 ? attention_launch_generic<u16>(a, p, s) : attention_launch_generic<float>(a, p, s);
+#define X(NKT, HD) \
+    if (p.family == MT4_ATTN_MFMA_BF16 && p.p0 == NKT && p.p1 == HD) \
+        return mt4_launch<mha_mfma_kernel<NKT, HD>>(p.grid, p.block, p.lds, s, (const u16*)a.q, (const u16*)a.k, (const u16*)a.v, (u16*)a.out, a.Nq, a.Nk, \
+                                                    a.q_stride, a.k_stride, a.v_stride, a.o_stride, a.scale);
+    MT4_MHA_BF16_VARIANTS(X)
+#undef X
+#define X(NKT, KSPLIT) \
+    if (p.family == MT4_ATTN_MFMA_F32 && p.p0 == NKT && (p.p1 > 1) == KSPLIT) \
+        return mt4_launch<mha_mfma_f32_kernel<NKT, KSPLIT>>(p.grid, p.block, p.lds, s, (const float*)a.q, (const float*)a.k, (const float*)a.v, (float*)a.out, \
+                                                            a.Nq, a.Nk, a.hd, a.q_stride, a.k_stride, a.v_stride, a.o_stride, a.scale);
+    MT4_MHA_F32_VARIANTS(X)
+#undef X
+    return MT4_EINVAL;
 }
 
 extern "C" int mt4_attention(const void* q, const void* k, const void* v, void* out, const float* bias, const float* mask,
                              int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t hd, int32_t q_stride, int32_t k_stride,
                              int32_t v_stride, int32_t o_stride, int32_t nW, float scale, int32_t dtype, void* stream) {
     mt4_clear_error();
-    if (!q || !k || !v || !out || B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0 || hd <= 0) return MT4_EINVAL;
-    if (dtype != MT4_F32 && dtype != MT4_BF16) return MT4_EUNSUPPORTED;
-    if (mask && nW <= 0) return MT4_EINVAL;
-    if (hd > 512 || B > 65535 || H > 65535) return MT4_EUNSUPPORTED;
-    const int es = dtype == MT4_BF16 ? 2 : 4;
-    // 4-element vector staging needs every (row, head) start 4-element aligned
-    const int vec_ok = (hd % 4 == 0) && (k_stride * es) % (4 * es) == 0 && (v_stride * es) % (4 * es) == 0 &&
-                       (((uintptr_t)k | (uintptr_t)v) & (4 * es - 1)) == 0;
-    hipStream_t s = (hipStream_t)stream;
-    // large head dim, bf16, no bias / mask, keys fit one workgroup's score registers: matrix-unit kernel 
-    // (head dim 256: Q2L over Swin-B, d = 1024 / 4 heads; 384: over Swin-L, d = 1536 -- the shipped teacher, Scripts/train_fold1.sh:5-12)
-    if (dtype == MT4_BF16 && (hd == 256 || hd == 384) && !bias && !mask && Nk <= 160 && (q_stride % 8) == 0 && (k_stride % 8) == 0 && (v_stride % 8) == 0 &&
-        (o_stride % 4) == 0 && ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0) && (((uintptr_t)out & 7) == 0) && cdiv(Nq, 64) <= 65535) {
-        {
-            const int nkt = cdiv(Nk, 16);
-            const dim3 grid(H, B, cdiv(Nq, 64)), block(256);
-#define MHA_LAUNCH_HD(NKTV, HDV) { constexpr int nkp = NKTV * 16, nkp2 = ((NKTV + 1) / 2) * 32; const size_t lds = (size_t)nkp * 160 + (size_t)nkp2 * 128; \
-            hipLaunchKernelGGL((mha_mfma_kernel<NKTV, HDV>), grid, block, lds, s, (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out, Nq, Nk, \
-                               q_stride, k_stride, v_stride, o_stride, scale); }
-#define MHA_LAUNCH(NKTV) { if (hd == 256) MHA_LAUNCH_HD(NKTV, 256) else MHA_LAUNCH_HD(NKTV, 384) }
-            switch (nkt) {
-                case 1: MHA_LAUNCH(1) break; case 2: MHA_LAUNCH(2) break; case 3: MHA_LAUNCH(3) break; case 4: MHA_LAUNCH(4) break;
-                case 5: MHA_LAUNCH(5) break; case 6: MHA_LAUNCH(6) break; case 7: MHA_LAUNCH(7) break; case 8: MHA_LAUNCH(8) break;
-                case 9: MHA_LAUNCH(9) break; default: MHA_LAUNCH(10) break;
-            }
-#undef MHA_LAUNCH_HD
-#undef MHA_LAUNCH
-            return mt4_check_launch();
-        }
-    }
-    // fp32 (parity mode), no bias / mask, <= 256 keys, head dim <= 128: exact-fp32 matrix-unit kernel (MS-TCT's global block)
-    if (dtype == MT4_F32 && hd <= 128 && (hd % 4) == 0 && !bias && !mask && Nk <= 256 && (q_stride % 4) == 0 && (k_stride % 4) == 0 &&
-        (v_stride % 4) == 0 && (o_stride % 4) == 0 && ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0) &&
-        cdiv(Nq, 64) <= 65535) {
-        const dim3 block(256);
-        // too few 64-query workgroups for the chip (one MS-TCT window: 32): four waves per 16 queries, keys split between them
-        if ((long long)H * B * cdiv(Nq, 64) < 128 && cdiv(Nq, 16) <= 65535) {
-            const dim3 grid(H, B, cdiv(Nq, 16));
-            if (Nk <= 128) {
-                const size_t lds = sizeof(float) * (size_t)((128 * 40 > 32 * 132 ? 128 * 40 : 32 * 132) + 128 + 4 * 16 * 32);
-                hipLaunchKernelGGL((mha_mfma_f32_ksplit_kernel<8>), grid, block, lds, s, (const float*)q, (const float*)k, (const float*)v, (float*)out,
-                                   Nq, Nk, hd, q_stride, k_stride, v_stride, o_stride, scale);
-            } else {
-                const size_t lds = sizeof(float) * (size_t)((256 * 40 > 32 * 260 ? 256 * 40 : 32 * 260) + 128 + 4 * 16 * 32);
-                hipLaunchKernelGGL((mha_mfma_f32_ksplit_kernel<16>), grid, block, lds, s, (const float*)q, (const float*)k, (const float*)v, (float*)out,
-                                   Nq, Nk, hd, q_stride, k_stride, v_stride, o_stride, scale);
-            }
-            return mt4_check_launch();
-        }
-        const dim3 grid(H, B, cdiv(Nq, 64));
-        if (Nk <= 128) {
-            const size_t lds = sizeof(float) * (size_t)(128 * 40 > 32 * 132 ? 128 * 40 : 32 * 132);
-            hipLaunchKernelGGL((mha_mfma_f32_kernel<8>), grid, block, lds, s, (const float*)q, (const float*)k, (const float*)v, (float*)out, Nq, Nk, hd,
-                               q_stride, k_stride, v_stride, o_stride, scale);
-        } else {
-            const size_t lds = sizeof(float) * (size_t)(256 * 40 > 32 * 260 ? 256 * 40 : 32 * 260);
-            hipLaunchKernelGGL((mha_mfma_f32_kernel<16>), grid, block, lds, s, (const float*)q, (const float*)k, (const float*)v, (float*)out, Nq, Nk, hd,
-                               q_stride, k_stride, v_stride, o_stride, scale);
-        }
-        return mt4_check_launch();
-    }
-    // (DPL, LPQ) with DPL*LPQ >= hd, fewest lanes per query first
-    static const int cfgs[][2] = {{32, 1}, {24, 2}, {32, 2}, {20, 4}, {28, 4}, {32, 4}, {32, 8},
-                                  {4, 8}, {8, 8}, {12, 8}, {16, 8}, {24, 8},   // 8 lanes per query, few dims per lane
-                                  {48, 8}, {64, 8}};                           // head dims 257 .. 512 (Q2L over Swin-L: 1536 / 4 heads = 384)
-    int ci = -1;
-    for (int i = 0; i < 7; ++i)
-        if (cfgs[i][0] * cfgs[i][1] >= hd) { ci = i; break; }
-    if (ci < 0)
-        for (int i = 12; i < 14; ++i)
-            if (cfgs[i][0] * cfgs[i][1] >= hd) { ci = i; break; }
-    if (ci < 0) return MT4_EUNSUPPORTED;
-    int threads = ((Nq * cfgs[ci][1] + 63) / 64) * 64;
-    if (threads > 256) threads = 256;
-    // a launch that cannot fill the chip (one short sequence: MS-TCT's global block has T = 256 queries x 8 heads) takes 8 lanes per
-    // query instead: 8x less serial work per lane, 8x more workgroups (workgroup size: 64/128/256 threads within 2 %, A/B)
-    if (hd <= 64 && (long long)cdiv(Nq, threads / cfgs[ci][1]) * H * B < 128) {   // (measured: 103 -> 72 us at hd 32, 94 -> 88 at hd 48; slower for hd >= 72)
-        for (int i = 7; i < 12; ++i)
-            if (cfgs[i][0] * 8 >= hd) { ci = i; threads = 256; break; }
-    }
-    const int DPL = cfgs[ci][0], LPQ = cfgs[ci][1];
-    const int row = LPQ * (DPL + 4);
-    int KC = 8192 / row;             // 2 * KC * row * 4 bytes <= 64 KiB
-    KC = (KC / 4) * 4;
-    if (KC > ((Nk + 3) / 4) * 4) KC = ((Nk + 3) / 4) * 4;
-    const size_t lds = (size_t)2 * KC * row * sizeof(float);
-    const int qpb = threads / LPQ;
-    const dim3 grid(cdiv(Nq, qpb), H, B), block(threads);
-#define ATT_LAUNCH(TT, D, L) hipLaunchKernelGGL((attention_kernel<TT, D, L>), grid, block, lds, s, (const TT*)q, (const TT*)k, (const TT*)v, (TT*)out, bias, mask, Nq, Nk, hd, q_stride, k_stride, v_stride, o_stride, nW, scale, KC, vec_ok)
-#define ATT_DISPATCH(TT) switch (ci) { case 0: ATT_LAUNCH(TT, 32, 1); break; case 1: ATT_LAUNCH(TT, 24, 2); break; case 2: ATT_LAUNCH(TT, 32, 2); break; \
-        case 3: ATT_LAUNCH(TT, 20, 4); break; case 4: ATT_LAUNCH(TT, 28, 4); break; case 5: ATT_LAUNCH(TT, 32, 4); break; case 6: ATT_LAUNCH(TT, 32, 8); break; \
-        case 7: ATT_LAUNCH(TT, 4, 8); break; case 8: ATT_LAUNCH(TT, 8, 8); break; case 9: ATT_LAUNCH(TT, 12, 8); break; case 10: ATT_LAUNCH(TT, 16, 8); break; \
-        case 11: ATT_LAUNCH(TT, 24, 8); break; case 12: ATT_LAUNCH(TT, 48, 8); break; default: ATT_LAUNCH(TT, 64, 8); }
-    if (dtype == MT4_BF16) { ATT_DISPATCH(u16) } else { ATT_DISPATCH(float) }
-#undef ATT_DISPATCH
-#undef ATT_LAUNCH
-    return mt4_check_launch();
+    const AttnArgs a = {q, k, v, out, bias, mask, B, H, Nq, Nk, hd, q_stride, k_stride, v_stride, o_stride, nW, scale, dtype};
+    AttnPlan p;
+    if (const int rc = attention_plan(a, &p)) return rc;
+    return attention_launch(a, p, (hipStream_t)stream);
+}
+
+extern "C" int mt4_attention_plan(const void* q, const void* k, const void* v, void* out, const float* bias, const float* mask, int32_t B,
+                                  int32_t H, int32_t Nq, int32_t Nk, int32_t hd, int32_t q_stride, int32_t k_stride, int32_t v_stride,
+                                  int32_t o_stride, int32_t nW, float scale, int32_t dtype, int32_t* family, int32_t* p0, int32_t* p1,
+                                  int32_t* lds_bytes) {
+    const AttnArgs a = {q, k, v, out, bias, mask, B, H, Nq, Nk, hd, q_stride, k_stride, v_stride, o_stride, nW, scale, dtype};
+    AttnPlan p;
+    if (const int rc = attention_plan(a, &p)) return rc;
+    if (family) *family = p.family;
+    if (p0) *p0 = p.p0;
+    if (p1) *p1 = p.p1;
+    if (lds_bytes) *lds_bytes = p.lds;
+    return MT4_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ patch extraction
@@ -915,18 +899,15 @@ extern "C" int mt4_patchify(const void* in, void* out, int32_t B, int32_t H, int
     const float s0 = from_u8 ? std[0] : 1, s1 = from_u8 ? std[1] : 1, s2 = from_u8 ? std[2] : 1;
     if (dtype == MT4_BF16 && from_u8 && P == 4 && (((uintptr_t)in & 3) == 0) && (((uintptr_t)out & 7) == 0)) {
         const long long threads = (long long)B * H * (W / 4);
-        hipLaunchKernelGGL(patchify_u8_p4_bf16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, (const uint8_t*)in, (u16*)out, B, H, W, m0, m1, m2,
-                           s0, s1, s2);
-        return mt4_check_launch();
+        return mt4_launch<patchify_u8_p4_bf16_kernel>(dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, (const uint8_t*)in, (u16*)out, B, H, W, m0, m1, m2,
+                                                      s0, s1, s2);
     }
     if (dtype == MT4_BF16) {
-        if (from_u8) hipLaunchKernelGGL((patchify_kernel<u16, true>), dim3(grid), dim3(256), 0, s, in, (u16*)out, B, H, W, P, m0, m1, m2, s0, s1, s2);
-        else hipLaunchKernelGGL((patchify_kernel<u16, false>), dim3(grid), dim3(256), 0, s, in, (u16*)out, B, H, W, P, m0, m1, m2, s0, s1, s2);
-    } else {
-        if (from_u8) hipLaunchKernelGGL((patchify_kernel<float, true>), dim3(grid), dim3(256), 0, s, in, (float*)out, B, H, W, P, m0, m1, m2, s0, s1, s2);
-        else hipLaunchKernelGGL((patchify_kernel<float, false>), dim3(grid), dim3(256), 0, s, in, (float*)out, B, H, W, P, m0, m1, m2, s0, s1, s2);
+        if (from_u8) return mt4_launch<patchify_kernel<u16, true>>(dim3(grid), dim3(256), 0, s, in, (u16*)out, B, H, W, P, m0, m1, m2, s0, s1, s2);
+        return mt4_launch<patchify_kernel<u16, false>>(dim3(grid), dim3(256), 0, s, in, (u16*)out, B, H, W, P, m0, m1, m2, s0, s1, s2);
     }
-    return mt4_check_launch();
+    if (from_u8) return mt4_launch<patchify_kernel<float, true>>(dim3(grid), dim3(256), 0, s, in, (float*)out, B, H, W, P, m0, m1, m2, s0, s1, s2);
+    return mt4_launch<patchify_kernel<float, false>>(dim3(grid), dim3(256), 0, s, in, (float*)out, B, H, W, P, m0, m1, m2, s0, s1, s2);
 }
 
 // ------------------------------------------------------------------------------------------------ y = x + p[row % L]
@@ -954,9 +935,8 @@ extern "C" int mt4_add_rowbcast(const void* x, const void* p, void* y, int64_t M
     if (C % V || (((uintptr_t)x | (uintptr_t)p | (uintptr_t)y) & 15)) return MT4_EALIGN;
     const long long total = M * (C / V);
     const int grid = (int)((total + 255) / 256);
-    if (dtype == MT4_BF16) hipLaunchKernelGGL(add_rowbcast_kernel<u16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const u16*)x, (const u16*)p, (u16*)y, (long long)M, L, C);
-    else hipLaunchKernelGGL(add_rowbcast_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)p, (float*)y, (long long)M, L, C);
-    return mt4_check_launch();
+    if (dtype == MT4_BF16) return mt4_launch<add_rowbcast_kernel<u16>>(dim3(grid), dim3(256), 0, (hipStream_t)stream, (const u16*)x, (const u16*)p, (u16*)y, (long long)M, L, C);
+    return mt4_launch<add_rowbcast_kernel<float>>(dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)p, (float*)y, (long long)M, L, C);
 }
 
 // ------------------------------------------------------------------------------------------------ GroupWiseLinear
@@ -980,9 +960,8 @@ extern "C" int mt4_groupwise_linear(const void* hs, const float* w, const float*
     if (!hs || !w || !out || B <= 0 || K <= 0 || D <= 0) return MT4_EINVAL;
     if (dtype != MT4_F32 && dtype != MT4_BF16) return MT4_EUNSUPPORTED;
     const int grid = cdiv(B * K, 4);
-    if (dtype == MT4_BF16) hipLaunchKernelGGL(groupwise_linear_kernel<u16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const u16*)hs, w, bias, out, B * K, K, D);
-    else hipLaunchKernelGGL(groupwise_linear_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)hs, w, bias, out, B * K, K, D);
-    return mt4_check_launch();
+    if (dtype == MT4_BF16) return mt4_launch<groupwise_linear_kernel<u16>>(dim3(grid), dim3(256), 0, (hipStream_t)stream, (const u16*)hs, w, bias, out, B * K, K, D);
+    return mt4_launch<groupwise_linear_kernel<float>>(dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)hs, w, bias, out, B * K, K, D);
 }
 
 // ------------------------------------------------------------------------------------------------ depthwise conv1d k3 (+GELU)
@@ -1029,9 +1008,8 @@ extern "C" int mt4_dwconv1d_k3(const void* x, const float* w, const float* bias,
     if (C % V || (((uintptr_t)x | (uintptr_t)y) & 15)) return MT4_EALIGN;
     const long long total = (long long)B * T * (C / V);
     const int grid = (int)((total + 255) / 256);
-    if (dtype == MT4_BF16) hipLaunchKernelGGL(dwconv1d_k3_kernel<u16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const u16*)x, w, bias, (u16*)y, B, T, C, act);
-    else hipLaunchKernelGGL(dwconv1d_k3_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)x, w, bias, (float*)y, B, T, C, act);
-    return mt4_check_launch();
+    if (dtype == MT4_BF16) return mt4_launch<dwconv1d_k3_kernel<u16>>(dim3(grid), dim3(256), 0, (hipStream_t)stream, (const u16*)x, w, bias, (u16*)y, B, T, C, act);
+    return mt4_launch<dwconv1d_k3_kernel<float>>(dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)x, w, bias, (float*)y, B, T, C, act);
 }
 
 // ------------------------------------------------------------------------------------------------ KD teacher mixing
@@ -1070,8 +1048,7 @@ extern "C" int mt4_kd_mix(const float* s, const float* tea_i, const float* tea_v
                           float* out_t, int32_t B, int32_t C, void* stream) {
     mt4_clear_error();
     if (!s || !tea_i || !tea_v || !tea_t || !out_i || !out_v || !out_t || B <= 0 || C <= 0) return MT4_EINVAL;
-    hipLaunchKernelGGL(kd_mix_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, s, tea_i, tea_v, tea_t, out_i, out_v, out_t, C);
-    return mt4_check_launch();
+    return mt4_launch<kd_mix_kernel>(dim3(B), dim3(256), 0, (hipStream_t)stream, s, tea_i, tea_v, tea_t, out_i, out_v, out_t, C);
 }
 
 // ------------------------------------------------------------------------------------------------ MFMA window attention (bf16, hd = 32)
@@ -1084,8 +1061,25 @@ extern "C" int mt4_kd_mix(const float* s, const float* tea_i, const float* tea_v
 // B-operand layout for O^T = V^T P^T (k-slot (q,e) of a 32-key block = key 16*kt + 4q + e for e < 4, the next tile's
 // for e >= 4; the V^T fragment is read in the same order), so P never touches LDS.
 
+// LDS of window_attention_mfma_kernel<NT, NW>, in bytes: Q, K rows [NP][PITCH], V rows [NP2][PITCH]; with a relative-position table of window
+// size ws then the reversed table + -1e30 pad area [2T + 4] floats, the key index per token [NP] ints and, 16-byte aligned, the region image Oh [NP][PITCH]
+struct WindowLds {
+    static constexpr int PITCH = 64;   // bytes per Q/K row, no padding: the 16-byte slot of head dims 8 q .. 8 q + 7 is XORed with (row >> 1) & 3.
+                                       // A ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... (MI355X_MICROARCH.md,
+                                       // LDS table): under THAT grouping this layout is conflict-free, while the 80-byte pitch of rounds 1-3 (conflict-free
+                                       // for 16 consecutive lanes) was 2-way conflicted on every Q / K fragment read
+    static constexpr int np(int nt) { return nt * 16; }
+    static constexpr int np2(int nt) { return (nt + 1) / 2 * 32; }   // keys padded to whole 32-key MFMA blocks
+    static constexpr int k_off(int nt) { return np(nt) * PITCH; }
+    static constexpr int v_off(int nt) { return 2 * np(nt) * PITCH; }
+    static constexpr int tb_off(int nt) { return v_off(nt) + np2(nt) * PITCH; }
+    static constexpr int table(int ws) { return (2 * ws - 1) * (2 * ws - 1); }   // T entries per head
+    static constexpr int kidx_off(int nt, int t) { return tb_off(nt) + (2 * t + 4) * 4; }   // t = table(ws): the table reversed, the -1e30 pad area behind it
+    static constexpr int oh_off(int nt, int t) { return (kidx_off(nt, t) + np(nt) * 4 + 15) & ~15; }
+    static constexpr int bytes(int nt, int ws, bool rel) { return rel ? kidx_off(nt, table(ws)) + np(nt) * 4 + 16 + np(nt) * PITCH : tb_off(nt); }
+};
 
-template <int NT, int NW = 4>  // key/query tiles of 16; waves per workgroup
+template <int NT, int NW>  // key/query tiles of 16; waves per workgroup
 // (at 8 - 9 tiles -- Swin's 12 x 12 windows -- the kernel is held to 168 registers = three waves per SIMD: 10 spilled registers, +3 % unmasked and
 //  +11 % on shifted blocks, same-box; four waves per SIMD spill 50 and lose 60 %.  9 tiles run in workgroups of THREE waves: over 4 waves
 //  three of them idle for a third of the loop -- 0.207 -> 0.167 ms on stage 3 of Swin-B/384 at batch 128, 0.451 -> 0.335 on a shifted block)
@@ -1100,20 +1094,14 @@ __global__ __launch_bounds__(NW * 64, (NT >= 8 && NT <= 9) ? 3 : 1) void window_
     // (region[w][i] != region[w][j]) ? -100 : 0 (`:222-229`) from the per-token region ids of the window type.  With the
     // expanded tables the kernel pulled 2 x N*N*4 bytes per (window, head) through L2 inside its softmax loop: 28 % of the
     // time of an unshifted block and 60 % more in a shifted one.
-    constexpr int NP = NT * 16;
-    constexpr int NP2 = ((NT + 1) / 2) * 32;  // keys padded to whole 32-key MFMA blocks
-    constexpr int QK_PITCH = 64;              // bytes per Q/K row, no padding: the 16-byte slot of head dims 8 q .. 8 q + 7 is XORed with (row >> 1) & 3.
-                                              // A ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... (MI355X_MICROARCH.md,
-                                              // LDS table): under THAT grouping this layout is conflict-free, while the 80-byte pitch of rounds 1-3 (conflict-free
-                                              // for 16 consecutive lanes) was 2-way conflicted on every Q / K fragment read
-    // V rows of 64 bytes like K; keys NP .. NP2 - 1 (the padding half of the last 32-key block) are zero rows.  The 32-byte half of head dims
+    constexpr int NP = WindowLds::np(NT), NP2 = WindowLds::np2(NT), QK_PITCH = WindowLds::PITCH;
+    // V rows like K; keys NP .. NP2 - 1 (the padding half of the last 32-key block) are zero rows.  The 32-byte half of head dims
     // 16 dt .. 16 dt + 15 is swapped on keys 4 .. 7 (mod 8): the two 4-key blocks a 32-lane half of a transposed read takes then sit on different banks
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qs = smem;
-    char* Ks = smem + NP * QK_PITCH;
-    char* Vs = smem + 2 * NP * QK_PITCH;
-    constexpr int V_BYTES = NP2 * QK_PITCH;
-    float* Tb = (float*)(smem + 2 * NP * QK_PITCH + V_BYTES);   // rel mode: [2T] table + -1e30 pad area, then key index, region id per token
+    char* Ks = smem + WindowLds::k_off(NT);
+    char* Vs = smem + WindowLds::v_off(NT);
+    float* Tb = (float*)(smem + WindowLds::tb_off(NT));   // rel mode: [2T] table + -1e30 pad area, then key index, region id per token
     const int b = blockIdx.y, h = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int nth = NW * 64, nw = NW;          // 4 waves, or 3 (9 tiles)
@@ -1171,13 +1159,13 @@ __global__ __launch_bounds__(NW * 64, (NT >= 8 && NT <= 9) ? 3 : 1) void window_
         *(uint4*)(Ks + row * QK_PITCH + ((pc ^ ((row >> 1) & 3)) << 4)) = kv[i];
         *(uint4*)(Vs + row * QK_PITCH + ((pc ^ (((row >> 2) & 1) << 1)) << 4)) = vv[i];
     }
-    const int T = (2 * ws - 1) * (2 * ws - 1);
+    const int T = (2 * ws - 1) * (2 * ws - 1);      // = WindowLds::table(ws)
     int* Kidx = (int*)(Tb + 2 * T + 4);
     // shifted blocks: the mask -100 [region(i) != region(j)] (`swin_transformer.py:222-229`) enters as +100 [region(i) == region(j)] -- the same softmax,
     // every score of a row moved by the same 100 -- and that is a dot product of one-hot region vectors scaled by 10: one more MFMA per key tile
     // on a second operand image Oh [token][32 bf16] (dims 16 .. 31 zeros; rows laid out like Q / K) instead of a compare, a select and an add per
     // score (12 VALU per key tile: windows holding more than one region ran 1.3-1.8 x the time of the others)
-    char* const Oh = smem + ((2 * NP * QK_PITCH + V_BYTES + (2 * T + 4) * 4 + NP * 4 + 15) & ~15);     // (an offset from `smem`: the compiler keeps it an LDS address)
+    char* const Oh = smem + WindowLds::oh_off(NT, T);     // (an offset from `smem`: the compiler keeps it an LDS address)
     int mixed = 0;   // shifted block: does this window type hold more than one region?  (only the last row / column of windows do)
     if (rel_table) {
         if (tb_regs) {
@@ -1331,49 +1319,58 @@ __global__ __launch_bounds__(NW * 64, (NT >= 8 && NT <= 9) ? 3 : 1) void window_
     }
 }
 
-static int window_attention_launch(const void* q, const void* k, const void* v, void* out, const float* bias_padded,
-                                   const float* mask_padded, const float* rel_table, const int32_t* region, int32_t ws, int32_t B, int32_t H,
-                                   int32_t N, int32_t q_stride, int32_t k_stride, int32_t v_stride, int32_t o_stride, int32_t nW, float scale,
-                                   void* stream) {
-    mt4_clear_error();
-    if (!q || !k || !v || !out || (!bias_padded && !rel_table) || B <= 0 || H <= 0 || N <= 0 || N > 256) return MT4_EINVAL;
-    if ((mask_padded || region) && nW <= 0) return MT4_EINVAL;
-    if (rel_table && (ws <= 0 || ws * ws != N)) return MT4_EINVAL;
-    if (B > 65535) return MT4_EUNSUPPORTED;
-    if ((q_stride | k_stride | v_stride) % 8 || o_stride % 4 || (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || ((uintptr_t)out & 7))
+// window_attention_mfma_kernel<NT, NW>: one instantiation per number of 16-token tiles.  9 tiles run on three waves: 9 query tiles over 4 waves
+// leave three of them idle for a third of the loop
+#define MT4_WINDOW_VARIANTS(X) \
+    X(1, 4) X(2, 4) X(3, 4) X(4, 4) X(5, 4) X(6, 4) X(7, 4) X(8, 4) X(9, 3) X(10, 4) X(11, 4) X(12, 4) X(13, 4) X(14, 4) X(15, 4) X(16, 4)
+constexpr int kWindowMaxTokens = 256;   // 16 tiles
+
+struct WindowArgs {   // the arguments of the two window entries: the expanded [NP][NP] bias (+ mask), or the table (+ region ids) of window size ws
+    const void *q, *k, *v;
+    void* out;
+    const float *bias_padded, *mask_padded, *rel_table;
+    const int32_t* region;
+    int ws, B, H, N, q_stride, k_stride, v_stride, o_stride, nW;
+    float scale;
+};
+
+// every check of the window entries, then the tiles and the dynamic LDS bytes of the launch (host arithmetic only)
+static int window_attention_plan(const WindowArgs& a, int* nt, int* lds) {
+    if (!a.q || !a.k || !a.v || !a.out || (!a.bias_padded && !a.rel_table) || a.B <= 0 || a.H <= 0 || a.N <= 0 || a.N > kWindowMaxTokens) return MT4_EINVAL;
+    if ((a.mask_padded || a.region) && a.nW <= 0) return MT4_EINVAL;
+    if (a.rel_table && (a.ws <= 0 || a.ws * a.ws != a.N)) return MT4_EINVAL;
+    if (a.B > 65535) return MT4_EUNSUPPORTED;
+    if ((a.q_stride | a.k_stride | a.v_stride) % 8 || a.o_stride % 4 || (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) & 15) || ((uintptr_t)a.out & 7))
         return MT4_EALIGN;
-    const int NT = (N + 15) / 16;
-    const int NP = NT * 16, NP2 = ((NT + 1) / 2) * 32;
-    size_t lds = (size_t)2 * NP * 64 + (size_t)NP2 * 64;
-    if (rel_table) lds += ((size_t)2 * (2 * ws - 1) * (2 * ws - 1) + 4) * 4 + (size_t)NP * 4 + 16 + (size_t)NP * 64;
-    if (!rel_table) ws = 1;
-    const dim3 grid(H, B), block(256);
-    hipStream_t s = (hipStream_t)stream;
-#define WA(NTV) hipLaunchKernelGGL((window_attention_mfma_kernel<NTV>), grid, block, lds, s, (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out, bias_padded, mask_padded, N, q_stride, k_stride, v_stride, o_stride, nW, scale, rel_table, region, ws)
-    switch (NT) {
-        case 1: WA(1); break; case 2: WA(2); break; case 3: WA(3); break; case 4: WA(4); break;
-        case 5: WA(5); break; case 6: WA(6); break; case 7: WA(7); break; case 8: WA(8); break;
-        case 9:       // three waves: 9 query tiles over 4 waves leave three of them idle for a third of the loop
-            hipLaunchKernelGGL((window_attention_mfma_kernel<9, 3>), grid, dim3(192), lds, s, (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out, bias_padded,
-                               mask_padded, N, q_stride, k_stride, v_stride, o_stride, nW, scale, rel_table, region, ws);
-            break;
-        case 10: WA(10); break; case 11: WA(11); break; case 12: WA(12); break;
-        case 13: WA(13); break; case 14: WA(14); break; case 15: WA(15); break; default: WA(16); break;
-    }
-#undef WA
-    return mt4_check_launch();
+    *nt = cdiv(a.N, 16);
+    *lds = WindowLds::bytes(*nt, a.ws, a.rel_table != nullptr);
+    return *lds > kMaxLds ? MT4_EUNSUPPORTED : MT4_OK;   // (the table form from ws = 15 on)
+}
+
+static int window_attention_launch(const WindowArgs& a, void* stream) {
+    mt4_clear_error();
+    int nt = 0, lds = 0;
+    if (const int rc = window_attention_plan(a, &nt, &lds)) return rc;
+#define X(NT, NW) \
+    if (nt == NT) \
+        return mt4_launch<window_attention_mfma_kernel<NT, NW>>(dim3(a.H, a.B), dim3(NW * 64), lds, (hipStream_t)stream, (const u16*)a.q, (const u16*)a.k, \
+                                                                (const u16*)a.v, (u16*)a.out, a.bias_padded, a.mask_padded, a.N, a.q_stride, a.k_stride, \
+                                                                a.v_stride, a.o_stride, a.nW, a.scale, a.rel_table, a.region, a.rel_table ? a.ws : 1);
+    MT4_WINDOW_VARIANTS(X)
+#undef X
+    return MT4_EINVAL;
 }
 
 extern "C" int mt4_window_attention_bf16(const void* q, const void* k, const void* v, void* out, const float* bias_padded,
                                          const float* mask_padded, int32_t B, int32_t H, int32_t N, int32_t q_stride, int32_t k_stride,
                                          int32_t v_stride, int32_t o_stride, int32_t nW, float scale, void* stream) {
-    return window_attention_launch(q, k, v, out, bias_padded, mask_padded, nullptr, nullptr, 0, B, H, N, q_stride, k_stride, v_stride, o_stride,
-                                   nW, scale, stream);
+    return window_attention_launch({q, k, v, out, bias_padded, mask_padded, nullptr, nullptr, 0, B, H, N, q_stride, k_stride, v_stride, o_stride, nW, scale},
+                                   stream);
 }
 
 extern "C" int mt4_window_attention_rel_bf16(const void* q, const void* k, const void* v, void* out, const float* rel_table,
                                              const int32_t* region, int32_t ws, int32_t B, int32_t H, int32_t q_stride, int32_t k_stride,
                                              int32_t v_stride, int32_t o_stride, int32_t nW, float scale, void* stream) {
-    return window_attention_launch(q, k, v, out, nullptr, nullptr, rel_table, region, ws, B, H, ws * ws, q_stride, k_stride, v_stride, o_stride,
-                                   nW, scale, stream);
+    return window_attention_launch({q, k, v, out, nullptr, nullptr, rel_table, region, ws, B, H, ws * ws, q_stride, k_stride, v_stride, o_stride, nW, scale},
+                                   stream);
 }

@@ -363,6 +363,17 @@ int mt4_layernorm(const void* x, const float* gamma, const float* beta, void* y,
 int mt4_attention(const void* q, const void* k, const void* v, void* out, const float* bias, const float* mask, int32_t B,
                   int32_t H, int32_t Nq, int32_t Nk, int32_t hd, int32_t q_stride, int32_t k_stride, int32_t v_stride,
                   int32_t o_stride, int32_t nW, float scale, int32_t dtype, void* stream);
+/* Host only, no reference counterpart (added without an ABI version step, like mt4_conv_plan): every check mt4_attention makes on its arguments
+ * before it launches, in the same order and through the same code, and the kernel it would launch -- and nothing else: no launch, no HIP call, and
+ * no access to the memory behind the pointers (they are checked for NULL and alignment only).  Returns the code mt4_attention returns for every
+ * call it refuses, MT4_OK where it would launch; then *family (MT4_ATTN_*), the variant (*p0, *p1) and the launch's dynamic LDS *lds_bytes say
+ * what.  Nothing is written on a refusal.  Any output pointer may be NULL. */
+#define MT4_ATTN_GENERIC 0   /* attention_kernel: p0 = head dims per lane, p1 = lanes per query (p0 * p1 >= hd) */
+#define MT4_ATTN_MFMA_BF16 1 /* the bf16 matrix-unit kernel: p0 = key tiles of 16 (>= Nk / 16), p1 = head dim (256 / 384) */
+#define MT4_ATTN_MFMA_F32 2  /* the exact-fp32 matrix-unit kernel: p0 = key tiles of 16 (8 / 16), p1 = waves the keys of a query are split over (1 / 4) */
+int mt4_attention_plan(const void* q, const void* k, const void* v, void* out, const float* bias, const float* mask, int32_t B,
+                       int32_t H, int32_t Nq, int32_t Nk, int32_t hd, int32_t q_stride, int32_t k_stride, int32_t v_stride,
+                       int32_t o_stride, int32_t nW, float scale, int32_t dtype, int32_t* family, int32_t* p0, int32_t* p1, int32_t* lds_bytes);
 
 /* Same core on the matrix units for the Swin shape: bf16, head dim 32, N <= 256 tokens per window (q, k, v from one
  * packed qkv projection), one workgroup per (window, head).  bias_padded [H][NP][NP] / mask_padded [nW][NP][NP] float32
@@ -374,7 +385,7 @@ int mt4_window_attention_bf16(const void* q, const void* k, const void* v, void*
  * (`relative_position_bias_table` transposed, swin_transformer.py:81-83), bias(i,j) = table[(yi-yj+ws-1)(2ws-1) + xi-xj+ws-1]
  * (:92-103); region [nW][ws*ws] int32 = the shifted-window region id of every token of each window type (`img_mask` of :210-221
  * after window_partition; ids 0 .. 15 -- the reference uses 0 .. 8), mask = -100 where the ids differ (:222-229), applied as +100 where they are
- * equal (the same softmax); NULL for an unshifted block.  N = ws*ws <= 256. */
+ * equal (the same softmax); NULL for an unshifted block.  N = ws*ws <= 256; ws >= 15 needs more than 64 KiB of LDS: MT4_EUNSUPPORTED. */
 int mt4_window_attention_rel_bf16(const void* q, const void* k, const void* v, void* out, const float* rel_table, const int32_t* region,
                                   int32_t ws, int32_t B, int32_t H, int32_t q_stride, int32_t k_stride, int32_t v_stride, int32_t o_stride,
                                   int32_t nW, float scale, void* stream);

@@ -1,0 +1,143 @@
+"""The variant lists of `mt4_attention`, the window entries and `mt4_layernorm`, and what `mt4_attention` launches for which call, as Python literals.
+
+The lists mirror `MT4_ATTN_*`, `MT4_MHA_*`, `MT4_WINDOW_VARIANTS` and `MT4_LN_*` of csrc/transformer_kernels.hip.  `DISPATCH` holds probes whose
+expectation (family, variant, dynamic LDS bytes -- or an error code) is worked out BY HAND from the rules of `attention_plan` with the arithmetic
+written beside each row; none was produced by running the library.  `test_attention_plan_cpu.py` asserts them through the host-only
+`mt4_attention_plan` on a CPU, and the GPU tests ask `plan(...)` which kernel a shape gets instead of restating the rule.  Shorthand:
+  generic   attention_kernel<T, DPL, LPQ>: the first (DPL, LPQ) of BASE + WIDE with DPL LPQ >= hd; threads = min(256, roundup64(Nq LPQ));
+            few-workgroups rule: hd <= 64 and ceil(Nq / (threads / LPQ)) H B < 128 -> the first of FEW with 8 DPL >= hd, 256 threads
+            row = LPQ (DPL + 4) floats; KC = min(8192 // row // 4 * 4, roundup4(Nk)); LDS = 2 KC row 4 bytes
+  bf16 MFMA bf16, hd 256 / 384, no bias / mask, Nk <= 160, strides % 8: NKT = ceil(Nk / 16); LDS = 16 NKT 160 + 32 ceil(NKT / 2) 128 bytes
+  fp32 MFMA fp32, hd <= 128, hd % 4 == 0, no bias / mask, Nk <= 256, strides % 4: NKT = 8 (Nk <= 128) or 16; the keys of a query are split
+            over 4 waves where H B ceil(Nq / 64) < 128; LDS = 4 (max(16 NKT 40, 32 (16 NKT + 4)) [+ 128 + 2048 with the split]) bytes
+
+This is a plain module beside `conv_tiles.py` (`tests/` is on sys.path while pytest runs), not a conftest.
+"""
+import ctypes
+
+MT4_OK, MT4_EINVAL, MT4_EALIGN, MT4_ELAUNCH, MT4_EUNSUPPORTED = 0, -1, -2, -3, -4
+GENERIC, MFMA_BF16, MFMA_F32 = 0, 1, 2            # MT4_ATTN_* of include/mt4hip.h
+F32, BF16 = 0, 1                                  # MT4_F32, MT4_BF16
+
+# (DPL, LPQ) of attention_kernel
+ATTN_BASE = [(32, 1), (24, 2), (32, 2), (20, 4), (28, 4), (32, 4), (32, 8)]
+ATTN_FEW = [(4, 8), (8, 8), (12, 8), (16, 8), (24, 8)]
+ATTN_WIDE = [(48, 8), (64, 8)]
+ATTN_GENERIC = ATTN_BASE + ATTN_FEW + ATTN_WIDE
+MHA_BF16 = [(nkt, hd) for hd in (256, 384) for nkt in range(1, 11)]          # (NKT, HD) of mha_mfma_kernel
+MHA_F32 = [(8, 1), (16, 1), (8, 4), (16, 4)]                                 # (NKT, waves the keys are split over) of mha_mfma_f32_kernel
+WINDOW = [(nt, 3 if nt == 9 else 4) for nt in range(1, 17)]                  # (NT, waves) of window_attention_mfma_kernel
+LN_NARROW, LN_WIDE = [16, 32], [2, 4, 8, 16]                                 # LPR of layernorm_narrow_kernel, MAXCH of layernorm_kernel
+
+_anchor = (ctypes.c_char * 64)()
+FAKE_PTR = (ctypes.addressof(_anchor) + 15) & ~15     # a 16-byte aligned address of a small live buffer: never dereferenced by a plan or a refusal
+
+
+def attn(note, dt, B, H, Nq, Nk, hd, expect, *, bias=False, nw=0, q_stride=None, kv_stride=None, q=FAKE_PTR):
+    """one probe: packed [B N, H hd] rows unless strides are given; expect = (family, p0, p1, lds bytes) or an MT4_E* code"""
+    c = H * hd
+    return dict(note=note, dt=dt, B=B, H=H, Nq=Nq, Nk=Nk, hd=hd, expect=expect, bias=bias, nw=nw, q_stride=q_stride or c, kv_stride=kv_stride or c, q=q)
+
+
+DISPATCH = [
+    # ---- the probes of the refactor's issue, re-derived
+    # generic: (32, 1) covers 32; threads = roundup64(144) = 192; few: ceil(144 / 192) 4 8 = 32 < 128 -> (4, 8); row = 8 * 8 = 64,
+    # KC = min(8192 // 64 = 128, 144) = 128; LDS = 2 * 128 * 64 * 4 = 65536
+    attn("Swin w12 + shift mask", BF16, 8, 4, 144, 144, 32, (GENERIC, 4, 8, 65536), bias=True, nw=4),
+    attn("Swin w12 + shift mask", F32, 8, 4, 144, 144, 32, (GENERIC, 4, 8, 65536), bias=True, nw=4),
+    # fp32 MFMA: Nk 256 -> NKT 16; 8 * 2 * ceil(256 / 64) = 64 < 128 -> split; max(256 * 40, 32 * 260) = 10240; 4 * (10240 + 2176) = 49664
+    attn("MS-TCT stage 4", F32, 2, 8, 256, 256, 108, (MFMA_F32, 16, 4, 49664)),
+    # Nk 200 -> NKT 16; 8 * 16 * 1 = 128 is not < 128 -> one wave per 16 queries; 4 * 10240 = 40960
+    attn("fp32, enough workgroups", F32, 16, 8, 64, 200, 48, (MFMA_F32, 16, 1, 40960)),
+    # Nk 16 -> NKT 8; 1 * 3 * 1 = 3 < 128 -> split; max(128 * 40, 32 * 132) = 5120; 4 * (5120 + 2176) = 29184
+    attn("fp32, tiny", F32, 3, 1, 5, 16, 128, (MFMA_F32, 8, 4, 29184)),
+    # bf16 MFMA: NKT = 9; 144 * 160 + 160 * 128 = 23040 + 20480 = 43520
+    attn("Q2L decoder cross-attention", BF16, 3, 4, 6, 144, 256, (MFMA_BF16, 9, 256, 43520)),
+    # NKT = 1; 16 * 160 + 32 * 128 = 2560 + 4096 = 6656
+    attn("bf16 MFMA, 7 keys", BF16, 2, 1, 10, 7, 384, (MFMA_BF16, 1, 384, 6656)),
+    # ceil(161 / 16) = 11 key tiles: no such variant.  generic: 32 * 8 = 256 is the first to cover 256; row = 8 * 36 = 288, 8192 // 288 = 28 -> 28,
+    # roundup4(161) = 164 -> KC 28; 2 * 28 * 288 * 4 = 64512
+    attn("bf16 hd 256, 161 keys", BF16, 2, 4, 16, 161, 256, (GENERIC, 32, 8, 64512)),
+    # a bias keeps it off the matrix-unit kernel; KC = min(28, 144) = 28
+    attn("bf16 hd 256 with a bias", BF16, 2, 4, 16, 144, 256, (GENERIC, 32, 8, 64512), bias=True),
+    # q_stride 866 % 4 = 2 -> generic: 28 * 4 = 112 is the first to cover 108 (32, 48, 64, 80 fall short); hd > 64: no few rule;
+    # row = 4 * 32 = 128, KC = min(64, 256) = 64; 2 * 64 * 128 * 4 = 65536
+    attn("fp32 hd 108, q_stride % 4 != 0", F32, 2, 8, 256, 256, 108, (GENERIC, 28, 4, 65536), q_stride=866),
+    # hd % 4 != 0 -> no fp32 MFMA (and vec_ok = 0: element-wise staging).  (32, 1); threads = 64; few: ceil(40 / 64) 8 2 = 16 < 128 -> (4, 8),
+    # 256 threads; row 64, KC = min(128, 40) = 40; 2 * 40 * 64 * 4 = 20480
+    attn("hd 6", F32, 2, 8, 40, 40, 6, (GENERIC, 4, 8, 20480)),
+    attn("hd 6", BF16, 2, 8, 40, 40, 6, (GENERIC, 4, 8, 20480)),
+    # fp32 hd 384 > 128; BASE ends at 256 -> WIDE: 48 * 8 = 384; row = 8 * 52 = 416, 8192 // 416 = 19 -> 16; 2 * 16 * 416 * 4 = 53248
+    attn("hd 384, fp32", F32, 2, 4, 144, 144, 384, (GENERIC, 48, 8, 53248)),
+    # 64 * 8 = 512; row = 8 * 68 = 544, 8192 // 544 = 15 -> 12, roundup4(33) = 36 -> KC 12; 2 * 12 * 544 * 4 = 52224
+    attn("hd 512", F32, 1, 2, 20, 33, 512, (GENERIC, 64, 8, 52224), bias=True),
+    attn("hd 512", BF16, 1, 2, 20, 33, 512, (GENERIC, 64, 8, 52224), bias=True),
+    # ---- the remaining shapes of test_attention_core
+    # generic: (32, 1); threads = 64; few: ceil(49 / 64) 3 6 = 18 < 128 -> (4, 8); KC = min(128, 52) = 52; 2 * 52 * 64 * 4 = 26624
+    attn("Swin w7", BF16, 6, 3, 49, 49, 32, (GENERIC, 4, 8, 26624), bias=True),
+    attn("Swin w7", F32, 6, 3, 49, 49, 32, (GENERIC, 4, 8, 26624), bias=True),
+    # bf16 hd 108: (28, 4); hd > 64; row 128, KC = 64; 65536
+    attn("MS-TCT stage 4, bf16", BF16, 2, 8, 256, 256, 108, (GENERIC, 28, 4, 65536)),
+    # fp32 MFMA: Nk 101 -> NKT 8; 8 * 2 * 2 = 32 < 128 -> split; 29184
+    attn("MS-TCT stage 2, ragged T", F32, 2, 8, 101, 101, 48, (MFMA_F32, 8, 4, 29184)),
+    # bf16 hd 48: (24, 2); threads = roundup64(202) = 256; few: ceil(101 / 128) 8 2 = 16 < 128 -> (8, 8) (4 * 8 = 32 < 48); row = 8 * 12 = 96,
+    # 8192 // 96 = 85 -> 84, roundup4(101) = 104 -> KC 84; 2 * 84 * 96 * 4 = 64512
+    attn("MS-TCT stage 2, bf16", BF16, 2, 8, 101, 101, 48, (GENERIC, 8, 8, 64512)),
+    # hd 192: (32, 8) (32 * 4 = 128 < 192); KC 28; 64512.  fp32: hd > 128, the same
+    attn("Q2L encoder over Swin-T", BF16, 2, 4, 144, 144, 192, (GENERIC, 32, 8, 64512)),
+    attn("Q2L encoder over Swin-T", F32, 2, 4, 144, 144, 192, (GENERIC, 32, 8, 64512)),
+    attn("Q2L encoder over Swin-L", BF16, 2, 4, 144, 144, 384, (MFMA_BF16, 9, 384, 43520)),
+    attn("Q2L decoder over Swin-L", BF16, 3, 4, 6, 144, 384, (MFMA_BF16, 9, 384, 43520)),
+    # fp32 hd 256 > 128: (32, 8), KC 28
+    attn("Q2L decoder, fp32", F32, 3, 4, 6, 144, 256, (GENERIC, 32, 8, 64512)),
+    # ---- the edges of the matrix-unit families
+    attn("bf16 MFMA, 160 keys", BF16, 1, 4, 70, 160, 256, (MFMA_BF16, 10, 256, 160 * 160 + 160 * 128)),
+    # q 8 bytes off a 16-byte boundary -> generic (32, 8)
+    attn("bf16 hd 256, q misaligned", BF16, 3, 4, 6, 144, 256, (GENERIC, 32, 8, 64512), q=FAKE_PTR + 8),
+    # Nk 257 -> 17 key tiles: no variant.  generic: hd 32 -> (32, 1); threads 256; ceil(256 / 256) 8 1 = 8 < 128 -> (4, 8); KC 128; 65536
+    attn("fp32, 257 keys", F32, 1, 8, 256, 257, 32, (GENERIC, 4, 8, 65536)),
+    # Nk 128 -> NKT 8, Nk 129 -> NKT 16; 2 * 8 * 4 = 64 < 128 -> split
+    attn("fp32, 128 keys", F32, 2, 8, 256, 128, 32, (MFMA_F32, 8, 4, 29184)),
+    attn("fp32, 129 keys", F32, 2, 8, 256, 129, 32, (MFMA_F32, 16, 4, 49664)),
+    # 8 * 4 * 4 = 128: not < 128
+    attn("fp32, 128 workgroups", F32, 4, 8, 250, 256, 108, (MFMA_F32, 16, 1, 40960)),
+    # Nk 100 -> NKT 8; 8 * 16 * 1 = 128 -> no split; 4 * 5120 = 20480
+    attn("fp32, 128 workgroups, 100 keys", F32, 16, 8, 64, 100, 48, (MFMA_F32, 8, 1, 20480)),
+    # hd 72 > 64: no few rule although 8 workgroups: 20 * 4 = 80 covers 72; row = 4 * 24 = 96, KC = min(84, 256) = 84; 64512
+    attn("bf16 hd 72, one window", BF16, 1, 8, 256, 256, 72, (GENERIC, 20, 4, 64512)),
+    # enough workgroups: (32, 1) stays; threads = 192 -> ceil(144 / 192) 4 128 = 512; row 36, 8192 // 36 = 227 -> 224 > 144 -> KC 144; 2 * 144 * 36 * 4 = 41472
+    attn("Swin w12, 128 windows", BF16, 128, 4, 144, 144, 32, (GENERIC, 32, 1, 41472), bias=True, nw=4),
+    # ---- refusals, in the order of the checks
+    attn("NULL q", BF16, 2, 4, 16, 16, 32, MT4_EINVAL, q=None),
+    attn("Nk 0", BF16, 2, 4, 16, 0, 32, MT4_EINVAL),
+    attn("unknown dtype", 7, 2, 4, 16, 16, 32, MT4_EUNSUPPORTED),
+    attn("mask with nW 0", BF16, 2, 4, 16, 16, 32, MT4_EINVAL, bias=True, nw=-1),
+    attn("hd 513", F32, 2, 4, 16, 16, 513, MT4_EUNSUPPORTED),
+    attn("B 65536", F32, 65536, 1, 16, 16, 32, MT4_EUNSUPPORTED),
+]
+
+
+def plan_args(r):
+    """the leading arguments of `mt4_attention` / `mt4_attention_plan` for probe `r` (nw = -1: a mask with nW = 0)"""
+    bias = FAKE_PTR if r["bias"] else None
+    mask = FAKE_PTR if r["nw"] else None
+    c = r["H"] * r["hd"]
+    return [r["q"], FAKE_PTR, FAKE_PTR, FAKE_PTR, bias, mask, r["B"], r["H"], r["Nq"], r["Nk"], r["hd"], r["q_stride"], r["kv_stride"], r["kv_stride"], c,
+            max(r["nw"], 0), float(r["hd"]) ** -0.5, r["dt"]]
+
+
+def plan_call(args):
+    """`mt4_attention_plan(args...)` -> (return code, family, p0, p1, lds bytes); -9 where nothing was written"""
+    from computervision_codes_amd import _lib
+    out = [ctypes.c_int32(-9) for _ in range(4)]
+    rc = _lib.lib.mt4_attention_plan(*args, *[ctypes.byref(o) for o in out])
+    return (rc,) + tuple(o.value for o in out)
+
+
+def plan(dt, B, H, Nq, Nk, hd, *, bias=False, mask=False, q_stride=None, k_stride=None, v_stride=None, o_stride=None):
+    """what `ops.attention` launches for 16-byte aligned tensors of these shapes: (family, p0, p1, lds bytes)"""
+    c = H * hd
+    rc, fam, p0, p1, lds = plan_call([FAKE_PTR, FAKE_PTR, FAKE_PTR, FAKE_PTR, FAKE_PTR if bias else None, FAKE_PTR if mask else None, B, H, Nq, Nk, hd,
+                                      q_stride or c, k_stride or c, v_stride or c, o_stride or c, 1 if mask else 0, float(hd) ** -0.5, dt])
+    assert rc == MT4_OK, rc
+    return fam, p0, p1, lds
