@@ -190,6 +190,8 @@ SIGNATURES = {
     "mt4_bottleneck_pack_next_bf16": (C.c_int, [_vp, _vp, _vp]),
     "mt4_bottleneck_fused_next_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "mt4_fpn_topdown": (C.c_int, [_vp, _vp, _i32, C.c_int64, _i32, _vp]),
+    "mt4_tcn_stream_conv_f32": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp] + [_i32] * 6 + [_vp, _vp]),
+    "mt4_tcn_stream_advance": (C.c_int, [_vp, _i32, _vp]),
     "mt4_tcn_layer_fused_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mt4_tcn_linear_ln_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _i32, _vp, _vp, _vp]),
     "mt4_tcn_linear_stats_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),

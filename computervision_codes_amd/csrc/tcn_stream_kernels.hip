@@ -1,0 +1,168 @@
+// The streaming step of the causal temporal head on gfx950 (MI355X): a handful of NEW frames through one causal Conv1d against the layer's own
+// history (`DilatedResidualCausalLayer`, Temporal_tenco/network.py:165-183: front padding 2 d, taps at t - 2d, t - d, t), fp32.
+//
+// Every layer keeps its input in a ring of L rows (L a power of two >= (taps - 1) d + 32): frame f lives in row f & (L - 1).  A launch computes the
+// n <= 32 frames f = t0 + i, t0 read from a device counter; tap k of frame f is frame f - (taps - 1 - k) d of the input ring, or zeros when that
+// frame is negative: the front padding is the counter, not a zero-filled buffer, so a reset is one store to the counter and no gather pass ever
+// builds a contiguous window.
+//
+// The GEMM is skinny (<= 32 rows, K = taps Cin, Cout columns) and bound by the weight read.  Geometry of `tcn_conv_kernel` (tcn_kernels.hip): one
+// workgroup per 16 output channels, K split over the 8 waves by 128-byte step (step s belongs to wave s & 7, a wave walks its steps upwards, six in flight), the 8
+// partial tiles meet in LDS and are added in the order wave 0..7.  Each lane's operands come straight from global memory into registers (a weight
+// element is used by one lane; the <= 32 x 128 bytes of frames per step are L2 hits shared by all workgroups), so there is no barrier in the K loop.
+// An output element's sum therefore has ONE order, fixed by (taps, Cin) alone: not by n, the row's place in the chunk, t0 or the ring position --
+// any two chunkings of a video give the same bits.
+#include "mt4_common.h"
+
+namespace {
+
+constexpr int kStreamMaxChunk = 32, kStreamBN = 16, kStreamWaves = 8;
+
+struct StreamK {
+    const float* x;        // input ring [Lin][Cin] (Lin == 0: plain [n][Cin])
+    const float* w;        // [Cout][taps * Cin]
+    const float* bias;     // [Cout] or NULL
+    const float* res;      // residual ring [Lres][Cout] (Lres == 0: plain) or NULL
+    float* y;              // output ring [Lout][Cout] (Lout == 0: plain)
+    const long long* t0;   // frames pushed before this chunk
+    int Lin, Lres, Lout;
+    int Cin, Cout, d, n, relu;
+    int SPT;               // 128-byte K-steps per tap
+};
+
+template <int TAPS>
+__global__ __launch_bounds__(kStreamWaves * 64) void tcn_stream_conv_kernel(const StreamK a) {
+    __shared__ f32x4 red[kStreamWaves * 2 * 64];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r16 = lane & 15, q = lane >> 4;
+    const int n0 = blockIdx.x * kStreamBN;
+    const long long t0 = *a.t0;
+    const bool two = a.n > 16;                       // a second 16-frame tile (block-uniform)
+
+    // this lane's B fragments: chunk rows i = mt * 16 + r16; tap k of frame f = t0 + i is frame f - (TAPS - 1 - k) d of the ring, zeros when that
+    // frame is negative or the row is beyond the chunk
+    const int wn = min(n0 + r16, a.Cout - 1);        // rows >= Cout feed accumulator rows that are never stored
+    const float* const wrow = a.w + (long long)wn * (TAPS * a.Cin) + q * 4;
+    const int SPT = a.SPT, NS = TAPS * SPT;
+    struct Frag { float4 w[2], x[2][2]; bool ok[2]; };
+    // step s = tap * SPT + cs covers K elements [32 s, 32 s + 32) of the packed row
+    auto load = [&](int s, Frag& f) {
+        const int tap = TAPS == 1 ? 0 : (s >= SPT) + (s >= 2 * SPT);
+        const int cs = s - tap * SPT;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) f.w[kk] = *(const float4*)(wrow + s * 32 + kk * 16);
+        // the loads are unconditional (a row that is always inside the buffer: any frame's ring row, a row of the chunk in a plain buffer) and the
+        // zeros are selected where the values are consumed (`compute`): a load under a per-lane condition becomes a branch and a full wait, and a
+        // select behind the load waits for it there -- either way the ring of fragment sets is lost
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            if (mt == 1 && !two) break;
+            const int i = mt * 16 + r16, ic = min(i, a.n - 1);      // lanes beyond the chunk load its last row again (one more hit, no new line)
+            const long long fr = t0 + ic - (long long)(TAPS - 1 - tap) * a.d;
+            const long long row = a.Lin ? (fr & (long long)(a.Lin - 1)) : (long long)ic;
+            f.ok[mt] = i < a.n && fr >= 0;
+            const float* xp = a.x + row * a.Cin + cs * 32 + q * 4;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) f.x[kk][mt] = *(const float4*)(xp + kk * 16);
+        }
+    };
+    f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+    auto compute = [&](const Frag& f) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                if (mt == 1 && !two) break;
+                const float4 v = f.x[kk][mt];
+                const bool ok = f.ok[mt];
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.w[kk].x, ok ? v.x : 0.f, acc[mt], 0, 0, 0);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.w[kk].y, ok ? v.y : 0.f, acc[mt], 0, 0, 0);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.w[kk].z, ok ? v.z : 0.f, acc[mt], 0, 0, 0);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.w[kk].w, ok ? v.w : 0.f, acc[mt], 0, 0, 0);
+            }
+        }
+    };
+    // wave w takes steps w, w + 8, ... in rising order through a ring of kDepth fragment sets: the loads of kDepth steps are in flight at once (at
+    // K = 3 x 512 a wave has 6 steps: one round trip to memory for the whole K loop)
+    constexpr int NW = kStreamWaves, kDepth = 6;
+    Frag fs[kDepth];
+    int s = wave;
+#pragma unroll
+    for (int j = 0; j < kDepth; ++j)
+        if (s + j * NW < NS) load(s + j * NW, fs[j]);
+    while (s < NS) {
+#pragma unroll
+        for (int j = 0; j < kDepth; ++j) {
+            if (s + j * NW >= NS) break;
+            compute(fs[j]);
+            if (s + (j + kDepth) * NW < NS) load(s + (j + kDepth) * NW, fs[j]);
+        }
+        s += kDepth * NW;
+    }
+
+    // ---- partial tiles -> LDS, fixed-order sum and fused epilogue by waves 0 / 1 (frame tile mt = wave)
+    red[(wave * 2 + 0) * 64 + lane] = acc[0];
+    red[(wave * 2 + 1) * 64 + lane] = acc[1];
+    __syncthreads();
+    if (wave >= 2) return;
+    const int i = wave * 16 + r16;                   // row of the chunk
+    const int en = n0 + q * 4;                       // Cout % 4 == 0: en < Cout implies en + 3 < Cout
+    if (i >= a.n || en >= a.Cout) return;
+    f32x4 sum = red[wave * 64 + lane];
+#pragma unroll
+    for (int v = 1; v < kStreamWaves; ++v) sum += red[(v * 2 + wave) * 64 + lane];
+    const long long f = t0 + i;
+    if (a.bias) {
+        const float4 b = *(const float4*)(a.bias + en);
+        sum += (f32x4){b.x, b.y, b.z, b.w};
+    }
+    if (a.res) {
+        const long long rr = a.Lres ? (f & (long long)(a.Lres - 1)) : (long long)i;
+        const float4 r = *(const float4*)(a.res + rr * a.Cout + en);
+        sum += (f32x4){r.x, r.y, r.z, r.w};
+    }
+    if (a.relu) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sum[e] = fmaxf(sum[e], 0.f);
+    }
+    const long long yr = a.Lout ? (f & (long long)(a.Lout - 1)) : (long long)i;
+    *(float4*)(a.y + yr * a.Cout + en) = make_float4(sum[0], sum[1], sum[2], sum[3]);
+}
+
+__global__ void tcn_stream_advance_kernel(long long* t0, int n) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *t0 += n;
+}
+
+bool ring_ok(int L) { return L == 0 || (L > 0 && (L & (L - 1)) == 0); }
+
+}  // namespace
+
+extern "C" int mt4_tcn_stream_conv_f32(const float* x, int32_t Lin, const float* residual, int32_t Lres, float* y, int32_t Lout, const float* w,
+                                       const float* bias, int32_t Cin, int32_t Cout, int32_t taps, int32_t dilation, int32_t relu, int32_t n,
+                                       const int64_t* t0, void* stream) {
+    mt4_clear_error();
+    if (!x || !y || !w || !t0) return MT4_EINVAL;
+    if (n < 1 || n > kStreamMaxChunk || Cin <= 0 || Cout <= 0 || dilation <= 0 || (taps != 1 && taps != 3) || relu < 0 || relu > 1) return MT4_EINVAL;
+    if (!ring_ok(Lin) || !ring_ok(Lres) || !ring_ok(Lout)) return MT4_EINVAL;
+    if (taps == 3 && Lin == 0) return MT4_EINVAL;                                       // a history needs a ring
+    const long long span = (long long)(taps - 1) * dilation + n;                         // frames t0 - (taps - 1) d .. t0 + n - 1 must all be in the ring
+    if (Lin && Lin < span) return MT4_EINVAL;
+    if ((Lres && Lres < n) || (Lout && Lout < n)) return MT4_EINVAL;
+    if ((Cin * 4) % 128 != 0 || Cout % 4 != 0) return MT4_EUNSUPPORTED;
+    if ((long long)taps * Cin * Cout > 0x3fffffffLL) return MT4_EUNSUPPORTED;
+    if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)residual | (uintptr_t)bias) & 15) return MT4_EALIGN;
+    if ((uintptr_t)t0 & 7) return MT4_EALIGN;
+    StreamK k{x, w, bias, residual, y, (const long long*)t0, Lin, residual ? Lres : 0, Lout, Cin, Cout, taps == 1 ? 1 : dilation, n, relu, Cin * 4 / 128};
+    const dim3 grid(cdiv(Cout, kStreamBN)), block(kStreamWaves * 64);
+    if (taps == 3) return mt4_launch<tcn_stream_conv_kernel<3>>(grid, block, 0, (hipStream_t)stream, k);
+    return mt4_launch<tcn_stream_conv_kernel<1>>(grid, block, 0, (hipStream_t)stream, k);
+}
+
+extern "C" int mt4_tcn_stream_advance(int64_t* t0, int32_t n, void* stream) {
+    mt4_clear_error();
+    if (!t0 || ((uintptr_t)t0 & 7) || n < 0 || n > kStreamMaxChunk) return MT4_EINVAL;
+    hipLaunchKernelGGL(tcn_stream_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (long long*)t0, (int)n);
+    return mt4_check_launch();
+}

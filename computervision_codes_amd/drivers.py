@@ -162,6 +162,9 @@ _FLAGS = {
                _flag("--mask", action="store_true"),
                _flag("--output", default=False, type=bool),
                _flag("--hier", default=False, type=bool),
+               _flag("--causal", action="store_true",
+                     help="the causal temporal head (the reference's unused `DilatedResidualCausalLayer`, network.py:165-183): every dilated conv reads "
+                          "frames t - 2d, t - d, t, so frame t's answer needs no later frame; same checkpoint keys -- train, evaluate and predict with it"),
                _flag("--input_dim", type=int, default=512)],
               [_flag("--mask_draw", choices=("host", "device"), default="host"),
                _flag("--subclip", choices=("off", "reference"), default="off"),
@@ -191,6 +194,17 @@ def _deterministic(stage: str, F) -> bool:
     if stage not in _DETERMINISTIC_STAGES:
         raise NotImplementedError(f"--deterministic: {_NOT_DETERMINISTIC[stage]}")
     print("--deterministic: fixed-order sums (per-workgroup partials + mt4_fold_parts_f32 / _f64) in place of float atomics", flush=True)
+    return True
+
+
+def _causal(F) -> bool:
+    """--causal of the temporal head, read before any model is built: refused with --hier True, said once at start"""
+    if not getattr(F, "causal", False):
+        return False
+    if getattr(F, "hier", False):
+        from .temporal_tenco import CAUSAL_HIER_REASON
+        raise ValueError(CAUSAL_HIER_REASON)
+    print("--causal: dilated convs read frames t - 2d, t - d, t (front padding 2d): frame t's logits depend on no later frame", flush=True)
     return True
 
 
@@ -349,7 +363,8 @@ def _eval_model(stage: str, F, src):
         model = VideoNas(F, *_MSTCT_ARCH, F.input_dim, F.final_embedding_dim, dtype=dtype)
     else:
         from .temporal_tenco import VideoNas
-        model = VideoNas(F, F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100)         # (fp32 whatever --dtype says)
+        model = VideoNas(F, F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, 100,         # (fp32 whatever --dtype says)
+                         causal=bool(getattr(F, "causal", False)))
     if from_file:
         files = [F.test_ckpt or src[0]] + list(src[1:])
         src = torch.load(next((f for f in files if os.path.exists(f)), files[-1]), map_location="cpu")
@@ -689,6 +704,7 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
 # ------------------------------------------------------------------------------------------------ Temporal_tenco/run.py -e
 def tenco_eval(argv=None) -> Dict[str, float]:
     F = _parser("tenco", True).parse_known_args(argv)[0]      # (this is the stage's `run.py`: -t trains first)
+    _causal(F)
     if F.train:
         _tenco_train(F)
         if not F.test:
@@ -752,6 +768,7 @@ def _tenco_train(F):
     resume = _resume(F, init, guard["optim"])
     tr = TencoTrainer(F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                       hier=bool(getattr(F, "hier", False)),      # --hier True: pooled refinement levels (`network.py:147,154-155`, `run.py:159-179`)
+                      causal=bool(getattr(F, "causal", False)),
                       deterministic=_deterministic("tenco", F), **guard)
     from . import shapes, synth
     state = _latest_state(init, resume)
@@ -1149,6 +1166,10 @@ def _predict_parser() -> argparse.ArgumentParser:
     p.add_argument("--names", type=str, default="", help="one line per triplet id, with an optional `id:` prefix")
     p.add_argument("--save_scores", action="store_true", help="the four heads' full sigmoid score matrices into the .npz")
     p.add_argument("--segments", action="store_true", help="also <video>.segments.csv: runs of frames in which a triplet is above --threshold")
+    p.add_argument("--online", action="store_true",
+                   help="frame-by-frame mode (needs --causal and --temporal_ckpt): frames go through the student and `tenco_stream.TencoStream` "
+                        "--online_chunk at a time, each answer computed from the frames seen so far; the log line adds per-chunk latencies")
+    p.add_argument("--online_chunk", type=int, default=1, help="frames per step of --online, 1..32")
     return p
 
 
@@ -1156,6 +1177,16 @@ def _predict_inputs(F):
     """everything of predict.py's command line that can be wrong, looked at BEFORE any model is built -> ([(video name, frame paths)], triplet
     names or None); every message names its flag"""
     from . import ops, predict as P
+    _causal(F)
+    if F.online:
+        if not F.causal:
+            raise ValueError("--online needs --causal: a head that pads symmetrically needs frames that have not arrived yet")
+        if not F.temporal_ckpt:
+            raise ValueError("--online needs --temporal_ckpt FILE: it is the temporal head that streams")
+        if not 1 <= F.online_chunk <= ops.STREAM_MAX_CHUNK:
+            raise ValueError(f"--online_chunk {F.online_chunk}: 1..{ops.STREAM_MAX_CHUNK}")
+        if _dtype(F.dtype) != torch.float32:
+            raise ValueError(f"--online with --dtype {F.dtype}: the streaming step (mt4_tcn_stream_conv_f32) is fp32 only")
     if not F.student_ckpt:
         raise ValueError("--student_ckpt FILE is required")
     for flag, path in (("--student_ckpt", F.student_ckpt), ("--temporal_ckpt", F.temporal_ckpt), ("--names", F.names)):
@@ -1197,7 +1228,7 @@ def predict(argv=None):
     if temporal is None:
         print("no --temporal_ckpt: the student's own i / v / t / ivt heads are decoded, frame by frame", flush=True)
     pr = P.Predictor(student, temporal, height=F.image_height, width=F.image_width, device_batch=F.device_batch, png_decode=F.png_decode,
-                     decode_workers=F.decode_workers, topk=F.topk, threshold=F.threshold)
+                     decode_workers=F.decode_workers, topk=F.topk, threshold=F.threshold, online_chunk=F.online_chunk if F.online else 0)
     os.makedirs(F.out, exist_ok=True)
     out = {}
     for name, paths in videos:
@@ -1212,6 +1243,9 @@ def predict(argv=None):
             segs = P.segments(pred)
             P.save_segments(os.path.join(F.out, name + ".segments.csv"), segs, pred.frames, names)
             note = f" | {len(segs)} segments"
+        if F.online:
+            lat = np.asarray(pr.chunk_latencies_ms)
+            note += f" | online, {F.online_chunk} frames per chunk: median {float(np.median(lat)):.3f} ms, max {float(lat.max()):.3f} ms per chunk"
         print(f"{name}: {len(paths)} frames | {float(pred.n_active.mean()):.2f} triplets above {F.threshold:g} per frame{note} | {time.time() - t0:.3f} s", flush=True)
         out[name] = pred
     return out

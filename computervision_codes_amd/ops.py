@@ -371,6 +371,42 @@ def tcn_layer(x: torch.Tensor, w_dilated: torch.Tensor, b_dilated: torch.Tensor,
     return y
 
 
+STREAM_MAX_CHUNK = 32       # frames per `tcn_stream_conv` launch (kStreamMaxChunk of csrc/tcn_stream_kernels.hip)
+
+
+def tcn_stream_conv(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, t0: torch.Tensor, *, n: int,
+                    taps: int = 1, dilation: int = 1, residual: Optional[torch.Tensor] = None, relu: bool = False, x_ring: bool = True,
+                    residual_ring: bool = True, out_ring: bool = True) -> torch.Tensor:
+    """The causal head's streaming step (`mt4_tcn_stream_conv_f32`): frames t0 .. t0 + n - 1 of a causal Conv1d, fp32.  x / residual / out are
+    2-D [rows, C]: a ring (frame f in row f mod rows, rows a power of two) or, with `*_ring=False`, a plain buffer whose row i is the chunk's
+    frame i.  t0: int64 [1] on the device, the frames pushed before this chunk (read only).  Tap k reads frame f - (taps - 1 - k) * dilation, zeros
+    before frame 0.  Returns `out`."""
+    _need_cuda(x, w_packed, bias, residual, out, t0)
+    for t in (x, w_packed, out, residual):
+        assert t is None or (t.dim() == 2 and t.is_contiguous() and t.dtype == torch.float32)
+    assert t0.dtype == torch.int64 and t0.numel() == 1
+    cin, cout = x.shape[1], w_packed.shape[0]
+    assert w_packed.shape[1] == packed_k(cin, 1, taps, torch.float32) and out.shape[1] == cout
+    assert x_ring or x.shape[0] >= n
+    assert out_ring or out.shape[0] >= n
+    if residual is not None:
+        assert residual.shape[1] == cout and (residual_ring or residual.shape[0] >= n)
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == cout
+    check(lib.mt4_tcn_stream_conv_f32(x.data_ptr(), x.shape[0] if x_ring else 0, residual.data_ptr() if residual is not None else None,
+                                      residual.shape[0] if residual is not None and residual_ring else 0, out.data_ptr(),
+                                      out.shape[0] if out_ring else 0, w_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                      cin, cout, taps, dilation, 1 if relu else 0, n, t0.data_ptr(), _stream()), "mt4_tcn_stream_conv_f32")
+    return out
+
+
+def tcn_stream_advance(t0: torch.Tensor, n: int) -> None:
+    """t0 += n on the device (`mt4_tcn_stream_advance`): the last launch of a streaming chain"""
+    _need_cuda(t0)
+    assert t0.dtype == torch.int64 and t0.numel() == 1
+    check(lib.mt4_tcn_stream_advance(t0.data_ptr(), n, _stream()), "mt4_tcn_stream_advance")
+
+
 def fpn_topdown(lat: torch.Tensor, levels: torch.Tensor) -> None:
     """levels[l] = lat[l] + levels[l+1], l = nlev-2 .. 0, in place (`mt4_fpn_topdown`)"""
     _need_cuda(lat, levels)

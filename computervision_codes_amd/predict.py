@@ -130,10 +130,13 @@ def save_segments(path: str, segs, frames: Sequence[str], names: Optional[Sequen
 class Predictor:
     """student: a loaded `spatial_cnn.VideoNas`; temporal: a loaded `temporal_tenco.VideoNas` or None (the student's own four heads are decoded).
     height, width: the Resize target; device_batch: frames per student pass (a frame's result does not depend on it); png_decode / decode_workers:
-    as the extraction drivers' flags; topk <= 32; threshold in (0, 1): a triplet counts as on when its logit is above logit(threshold)."""
+    as the extraction drivers' flags; topk <= 32; threshold in (0, 1): a triplet counts as on when its logit is above logit(threshold).
+    online_chunk N > 0: the latency mode -- the frames go N at a time through the student, `tenco_stream.TencoStream.push` (temporal must be a
+    causal head) and the top-K decode, every answer computed from the frames seen so far; `chunk_latencies_ms` holds the last video's per-chunk
+    times (frames on the device -> decoded rows on the device, one synchronise per chunk).  0: the whole-video pass."""
 
     def __init__(self, student, temporal=None, *, height: int = 256, width: int = 448, device_batch: int = 512, png_decode: str = "host",
-                 decode_workers: int = 8, topk: int = 5, threshold: float = 0.5):
+                 decode_workers: int = 8, topk: int = 5, threshold: float = 0.5, online_chunk: int = 0):
         from . import ops
         if not 1 <= int(topk) <= ops.TOPK_MAX_K:
             raise ValueError(f"topk {topk}: 1..{ops.TOPK_MAX_K} (`mt4_topk_rows_f32` keeps a row's winners in one wave's lanes)")
@@ -145,6 +148,14 @@ class Predictor:
         self.height, self.width, self.device_batch = int(height), int(width), max(1, int(device_batch))
         self.png_decode, self.decode_workers = png_decode, int(decode_workers)
         self.topk, self.threshold = int(topk), float(threshold)
+        self.online_chunk, self.chunk_latencies_ms, self._stream = int(online_chunk), [], None
+        if self.online_chunk:
+            from .tenco_stream import TencoStream
+            if not 1 <= self.online_chunk <= ops.STREAM_MAX_CHUNK:
+                raise ValueError(f"online_chunk {online_chunk}: 1..{ops.STREAM_MAX_CHUNK} frames per `TencoStream.push`")
+            if self.temporal is None:
+                raise ValueError("online_chunk: the streaming mode needs a temporal head")
+            self._stream = TencoStream(self.temporal)                         # (refuses a non-causal, --hier or bf16 head with the reason)
 
     def features(self, paths: Sequence[str]):
         """the student over the frames -> (features fp32 [T, D], logits fp32 (i, v, t, ivt)), all on the device.  Loads run ahead of the model
@@ -175,15 +186,11 @@ class Predictor:
         out, out_i, out_v, out_t, _, _ = self.temporal(feat.unsqueeze(0), False)
         return {h: lg[0][0].transpose(0, 1) for h, lg in (("ivt", out), ("i", out_i), ("v", out_v), ("t", out_t))}
 
-    def predict_paths(self, paths: Sequence[str], keep_scores: bool = False) -> Prediction:
+    def _decode(self, lg, keep_scores: bool):
+        """{head -> logits [n, K]} -> the device pieces of a `Prediction`: top-K ids, scores, counts, the component heads' picks[, score matrices]"""
         import torch
 
         from . import ops
-        paths = list(paths)
-        if not paths:
-            raise ValueError("predict_paths: no frames")
-        lg = self.logits(paths)
-        n = lg["ivt"].shape[0]
         k = min(self.topk, lg["ivt"].shape[1])
         ids, vals, n_act = ops.topk_rows(lg["ivt"], k, count_above=math.log(self.threshold / (1.0 - self.threshold)))
         parts = [ids, torch.sigmoid(vals), n_act]
@@ -192,6 +199,41 @@ class Predictor:
             parts += [hid, torch.sigmoid(hval)]
         if keep_scores:
             parts += [torch.sigmoid(lg[h]) for h in HEADS]
+        return parts
+
+    def _online_parts(self, paths: Sequence[str], keep_scores: bool):
+        """the frames in order, `online_chunk` at a time: student pass -> `TencoStream.push` -> decode of the chunk's rows; the pieces of the
+        chunks are joined on the device.  A frame's rows do not depend on the chunk size (the student's and the stream's results do not)."""
+        import time
+
+        import torch
+
+        from . import cholect
+        self._stream.reset()
+        self.chunk_latencies_ms = []
+        chunks = []
+        for s in range(0, len(paths), self.online_chunk):
+            fr = cholect.load_files_device(paths[s:s + self.online_chunk], self.height, self.width, workers=self.decode_workers, decode=self.png_decode)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            feat = self.student.extract_u8(fr)[3][0]
+            chunks.append(self._decode(self._stream.push(feat.float().contiguous()), keep_scores))
+            torch.cuda.synchronize()
+            self.chunk_latencies_ms.append((time.perf_counter() - t0) * 1e3)
+        return [torch.cat([c[j] for c in chunks]) for j in range(len(chunks[0]))]
+
+    def predict_paths(self, paths: Sequence[str], keep_scores: bool = False) -> Prediction:
+        import torch
+        paths = list(paths)
+        if not paths:
+            raise ValueError("predict_paths: no frames")
+        if self.online_chunk:
+            parts = self._online_parts(paths, keep_scores)
+            n = parts[0].shape[0]
+        else:
+            lg = self.logits(paths)
+            n = lg["ivt"].shape[0]
+            parts = self._decode(lg, keep_scores)
         # every piece is 4 bytes wide: one buffer, ONE device-to-host copy per video
         flat = torch.cat([p.reshape(-1).view(torch.int32) for p in parts]).cpu().numpy()
         pieces, at = [], 0

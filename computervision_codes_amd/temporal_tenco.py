@@ -28,6 +28,10 @@ from .statemodule import StateModule
 TCN_PATH_MAX_ROWS = {torch.float32: 896, torch.bfloat16: 640}
 
 
+CAUSAL_HIER_REASON = ("--causal with --hier True: AvgPool1d(7, 3) behind every refinement stage, the FPN's linear resampling and the nearest-label "
+                      "resampling of the levels all look ahead (network.py:147,154-155,96; run.py:169-175)")
+
+
 class VideoNas(StateModule):
     """Drop-in for `Temporal_tenco.network.VideoNas` (inference path; eval semantics).
 
@@ -37,8 +41,10 @@ class VideoNas(StateModule):
     """
 
     def __init__(self, args, num_layers_PG, num_layers_R, num_R, num_f_maps, dim, num_classes, num_i=6, num_v=10,
-                 num_t=15, device: str = "cuda", dtype: torch.dtype = torch.float32, path: str = "auto"):
-        """dtype float32: the parity mode (exact-fp32 MFMA chain); bfloat16: throughput mode (bf16 weights / activations, fp32
+                 num_t=15, device: str = "cuda", dtype: torch.dtype = torch.float32, path: str = "auto", causal: bool = False):
+        """causal: every dilated conv is the reference's unused `DilatedResidualCausalLayer` (`network.py:165-183`): y[t] = b + sum_k W_k x[t - (2 - k) d],
+        zeros before frame 0 -- frame t's logits depend on no later frame.  Same checkpoint keys and shapes; the user's statement, as fpn / hier are.
+        dtype float32: the parity mode (exact-fp32 MFMA chain); bfloat16: throughput mode (bf16 weights / activations, fp32
         accumulate and epilogue, fp32 logits).  path: "auto" (by B*T), "tcn" (latency path), "igemm" (implicit-GEMM kernel)"""
         self.dtype = dtype
         assert path in ("auto", "tcn", "igemm")
@@ -48,6 +54,9 @@ class VideoNas(StateModule):
                                       "(Refinement.conv_1x1 takes num_classes channels, network.py:141, and is handed the num_f_maps-channel "
                                       "feature, :58,150-151)")
         self.hier = bool(getattr(args, "hier", False))
+        self.causal = bool(causal)
+        if self.causal and self.hier:
+            raise ValueError(CAUSAL_HIER_REASON)
         self.args = args
         self.use_fpn = bool(getattr(args, "fpn", False))
         self.num_layers_PG, self.num_layers_R, self.num_R = num_layers_PG, num_layers_R, num_R
@@ -104,13 +113,14 @@ class VideoNas(StateModule):
     def _layer(self, x, prefix, d):
         p = self._p
         b, _, t, _ = x.shape
-        if (prefix + ".conv_dilated.wf") in p and not self.hier and self.fused_layer_min_tiles <= b * ((t + 63) // 64) <= self.fused_layer_max_tiles:
+        if (prefix + ".conv_dilated.wf") in p and not self.hier and not self.causal and self.fused_layer_min_tiles <= b * ((t + 63) // 64) <= self.fused_layer_max_tiles:
             # throughput mode (several videos per forward): the whole DilatedResidualLayer in ONE launch, the 512-channel hidden map stays in LDS
             # (`ops.tcn_layer_fused`, bit-identical to the two launches below; gated on the tile count: one 64-frame tile per CU)
             return ops.tcn_layer_fused(x.view(b, t, self.C), p[prefix + ".conv_dilated.wf"], p[prefix + ".conv_dilated.b"], p[prefix + ".conv_1x1.wf"],
                                        p[prefix + ".conv_1x1.b"], d).view(b, 1, t, self.C)
-        h = ops.conv_nhwc(x, p[prefix + ".conv_dilated.w"], p[prefix + ".conv_dilated.b"], kh=1, kw=3, pad=(0, d), dil=(1, d),
-                          relu=True, tile=self.tile)
+        # causal: the whole padding 2 d in front (taps at t - 2d, t - d, t); the output grid stays the T frames
+        h = ops.conv_nhwc(x, p[prefix + ".conv_dilated.w"], p[prefix + ".conv_dilated.b"], kh=1, kw=3, pad=(0, 2 * d if self.causal else d), dil=(1, d),
+                          relu=True, tile=self.tile, out_hw=(1, t) if self.causal else None)
         return ops.conv_nhwc(h, p[prefix + ".conv_1x1.w"], p[prefix + ".conv_1x1.b"], kh=1, kw=1, residual=x, tile=self.tile)
 
     def _stage(self, x, prefix, n):
@@ -120,6 +130,10 @@ class VideoNas(StateModule):
 
     def _use_tcn_path(self, rows: int) -> bool:
         ok = ops.tcn_supported(self.C, self.dtype) and ops.tcn_supported(self.D, self.dtype)
+        if self.causal:          # `mt4_tcn_conv` pads 'same' only: the causal head runs on the implicit-GEMM kernel at every length
+            if self.path == "tcn":
+                raise ValueError("the latency path (mt4_tcn_conv) pads symmetrically: a causal head runs path 'auto' or 'igemm'")
+            return False
         if self.path == "tcn":
             if not ok:
                 raise ValueError("latency path needs channel counts that are whole 128-byte K-steps")

@@ -35,12 +35,18 @@ NHP = 132  # padded to a multiple of 4 (16-byte rows for the gradient GEMMs)
 class TencoTrainer(FlatTrainer):
     def __init__(self, num_layers_PG=11, num_layers_R=10, num_R=3, num_f_maps=512, dim=512, num_classes=100, lr=0.1, weight_decay=1e-5,
                  device: str = "cuda", process_group=None, overlap: bool = True, hier: bool = False, max_graphs: int = 64,
-                 deterministic: bool = False, clip_grad_norm: float = 0.0, skip_nonfinite: bool = False, optim=None):
+                 deterministic: bool = False, clip_grad_norm: float = 0.0, skip_nonfinite: bool = False, optim=None, causal: bool = False):
         # overlap: a stage's gradients are all-reduced as soon as its backward has written them (DDP, `FlatTrainer`)
         super().__init__(lr, weight_decay, device, process_group, overlap, clip_grad_norm, skip_nonfinite, optim)
         # hier = `args.hier` (`network.py:147,154-155`): AvgPool1d(7, 3) behind every refinement stage, so level l has its own length T_l, the FPN
         # resamples (`:96`) and `fusion` scores every level against the labels resized to it (`run.py:159-179,196-212`)
         self.hier = bool(hier)
+        # causal (`temporal_tenco.VideoNas(causal=True)`): the dilated convs pad 2 d in front (`network.py:165-183`) -- the same launches with other
+        # padding arguments: forward pad 2 d, data gradient the flipped-tap operator with pad 0, weight gradient pad 2 d
+        self.causal = bool(causal)
+        if self.causal and self.hier:
+            from .temporal_tenco import CAUSAL_HIER_REASON
+            raise ValueError(CAUSAL_HIER_REASON)
         # deterministic: every sum of the step that crosses workgroups (the weight and bias gradients, the BCE column sums) goes through the `_det`
         # entry points -- partials stored into `_ws`, folded in index order -- so a step is a pure function of its inputs, eager or replayed, at any
         # length.  Up to two ranks the all-reduce is one commutative add; beyond, the step is as reproducible as the collective.
@@ -147,6 +153,9 @@ class TencoTrainer(FlatTrainer):
         w = c.wt if transposed else c.w
         b = None if transposed else (c.b if cout is None else c.b[:cout])
         pad = dil if c.taps == 3 else 0
+        if self.causal and c.taps == 3:      # y[t] = sum_k W_k x[t - (2 - k) d]; dx[s] = sum_k' wt[k'] dy[s + k' d] (taps past the last frame read zeros)
+            return ops.conv_nhwc(x, w, b, kh=1, kw=3, pad=(0, 0 if transposed else 2 * dil), dil=(1, dil), residual=residual, act=act,
+                                 out_hw=(1, x.shape[2]))
         return ops.conv_nhwc(x, w, b, kh=1, kw=c.taps, pad=(0, pad), dil=(1, dil), residual=residual, act=act)
 
     @ops.with_latency_tiles
@@ -295,7 +304,7 @@ class TencoTrainer(FlatTrainer):
                 do = ops.dropout_mul_add(df, state, sl[p], 0.5) if state is not None else ops.mul_add(df, lm[p]) if p in lm else df
                 ops.wgrad_conv1d(do.view(ts, C), u.view(ts, C), w1.gw, batch=1, t=ts, taps=1, dil=1, pad=0, accumulate=True, bias_grad=w1.gb, workspace=ws)
                 du = self._conv(do, w1, transposed=True, residual=u, act="relu_gate")
-                ops.wgrad_conv1d(du.view(ts, C), zin.view(ts, C), wd.gw, batch=1, t=ts, taps=3, dil=d, pad=d, accumulate=True, bias_grad=wd.gb, workspace=ws)
+                ops.wgrad_conv1d(du.view(ts, C), zin.view(ts, C), wd.gw, batch=1, t=ts, taps=3, dil=d, pad=2 * d if self.causal else d, accumulate=True, bias_grad=wd.gb, workspace=ws)
                 df = self._conv(du, wd, dil=d, transposed=True, residual=df)
             if si > 0:
                 df = ops.mul_add(df, torch.ones_like(df), dstage[si - 1])      # + gradient of this stage's input as lateral c

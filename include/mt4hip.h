@@ -736,6 +736,23 @@ int mt4_tcn_linear_ln_f32(const void* x, const void* w_folded, const float* cols
  * Temporal_Encoder.py:86,40) that also writes stats_out [Cout / 16][rows][2] for the mt4_tcn_linear_ln_f32 launch that normalises its output. */
 int mt4_tcn_linear_stats_f32(const void* x, const void* w, const float* bias, const void* residual, void* y, int32_t rows, int32_t Cin, int32_t Cout,
                              int32_t relu, float* stats_out, void* stream);
+/* The streaming step of the CAUSAL temporal head, fp32: n new frames of one causal Conv1d against the layer's own history --
+ * `DilatedResidualCausalLayer` (Temporal_tenco/network.py:165-183: front padding 2 d, taps at t - 2d, t - d, t) and the 1-tap convs around it.
+ *   x        input ring [Lin][Cin]: frame f lives in row f & (Lin - 1); Lin == 0: a plain [n][Cin] buffer, row i (taps == 1 only)
+ *   residual NULL or a ring [Lres][Cout] / plain buffer (Lres == 0);  y  output ring [Lout][Cout] / plain buffer (Lout == 0)
+ *   w        [Cout][taps * Cin] packed by mt4_pack_conv_weight(Cout, Cin, 1, taps, MT4_F32);  bias [Cout] or NULL
+ *   t0       DEVICE pointer to an int64: the number of frames pushed before this chunk (read by the launch, never written)
+ * Output row i < n is frame f = t0 + i:  y[f] = act(bias + sum_k W_k . x[f - (taps - 1 - k) d] + residual[f]), a negative frame reading zeros:
+ * the front padding is the counter, so a reset is one store to it.  Ring lengths are powers of two; Lin >= (taps - 1) d + n, Lres, Lout >= n.
+ * 1 <= n <= 32; Cin * 4 % 128 == 0 and Cout % 4 == 0 (MT4_EUNSUPPORTED otherwise); pointers 16-byte aligned, t0 8-byte (MT4_EALIGN); every other
+ * refusal is MT4_EINVAL, all before any launch.  A row's result does not depend on n, on its index in the chunk, on t0 or on the ring position: one
+ * fixed K order per output element (K steps of 128 bytes dealt to 8 waves, partial tiles added in wave order), so any two chunkings of a video
+ * are bit-identical.  Enqueue-only, capturable. */
+int mt4_tcn_stream_conv_f32(const float* x, int32_t Lin, const float* residual, int32_t Lres, float* y, int32_t Lout, const float* w,
+                            const float* bias, int32_t Cin, int32_t Cout, int32_t taps, int32_t dilation, int32_t relu, int32_t n,
+                            const int64_t* t0, void* stream);
+/* *t0 += n (0 <= n <= 32) in one tiny launch: the end of a streaming chain, so a captured chain replays with the counter as its state. */
+int mt4_tcn_stream_advance(int64_t* t0, int32_t n, void* stream);
 /* FPN top-down pathway at equal lengths (network.py:93-106; `F.interpolate(x, size=W, mode='linear')` to the same length is the
  * identity): levels[l] = lat[l] + levels[l+1] for l = nlev-2 .. 0, in place.  lat [nlev-1][n], levels [nlev][n] of dtype, n % 4 == 0. */
 int mt4_fpn_topdown(const void* lat, void* levels, int32_t nlev, int64_t n, int32_t dtype, void* stream);

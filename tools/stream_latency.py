@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""What a frame costs online (GPU box): `TencoStream.push` of the causal head at the shipped configuration (11 / 10 / 3 layers, 512 maps, fp32)
+against the only way to answer frame t without it -- the whole-video forward over the history (2000 frames).
+
+  python3 tools/stream_latency.py [--parent DIR] [--reps 3] [--steps 200] [--history 2000]
+        every repetition starts one fresh child process per variant, alternating: the offline forward of the checkout at DIR (a built parent
+        checkout carried in the tree, when given), the offline forwards of this tree (symmetric and causal), the stream of this tree.  A child
+        times with device events after a warm-up that includes the graph captures and reports medians; the table gives the median of the
+        repetitions' medians and their spread.  Each child runs under a time limit of its own; the run stops at the first child that fails.
+  python3 tools/stream_latency.py --child offline|stream [--root DIR]
+        one such process: one JSON line.
+
+stream child: `push` of 1, 8 and 32 frames (hipGraph replay, the staging copy and the copy of the logits included), and the kernel's own time per
+launch: 64 launches of one dilated conv (d = 1 and d = 1024, 512 -> 512, three taps, 3 MB of weights) replayed as one graph, divided by 64, with
+the weight bytes over that time as GB/s."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import types
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CFG = (11, 10, 3, 512, 512, 100)
+
+
+def _timed(fn, steps, warmup):
+    import torch
+    ms = []
+    for i in range(warmup + steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            ms.append(a.elapsed_time(b))
+    return round(statistics.median(ms), 4)
+
+
+def _model(root, **kw):
+    sys.path.insert(0, root)
+    from computervision_codes_amd import shapes, synth
+    from computervision_codes_amd.temporal_tenco import VideoNas
+    sd = synth.fill_from_shapes(shapes.tenco_shapes(*CFG, fpn=True), seed=1)
+    return VideoNas(types.SimpleNamespace(fpn=True, output=False, hier=False), *CFG, **kw).eval().load_state_dict(sd)
+
+
+def _offline(model, history, steps, warmup):
+    from computervision_codes_amd import synth
+    from computervision_codes_amd.graph import GraphedForward
+    x = synth.synthetic_features(history, CFG[4], seed=2).cuda()
+    g = GraphedForward(lambda xx: model(xx, False)[0][0], [x])
+    return _timed(lambda: g(x), steps, warmup)
+
+
+def child_offline(root, history, steps, warmup, causal):
+    out = {"root": os.path.relpath(root, HERE), "ms": {f"offline symmetric T={history}": _offline(_model(root), history, steps, warmup)}}
+    if causal:
+        out["ms"][f"offline causal T={history}"] = _offline(_model(root, causal=True), history, steps, warmup)
+    print(json.dumps(out), flush=True)
+
+
+def child_stream(root, steps, warmup):
+    import torch
+    model = _model(root, causal=True)
+    from computervision_codes_amd import ops, synth
+    from computervision_codes_amd.tenco_stream import TencoStream
+    st = TencoStream(model)
+    out = {"root": os.path.relpath(root, HERE), "ms": {}, "ring_bytes": st.ring_bytes()}
+    x = synth.synthetic_features(64, CFG[4], seed=3)[0].cuda().contiguous()
+    for n in (1, 8, 32):
+        out["ms"][f"push {n}"] = _timed(lambda: st.push(x[:n]), steps, warmup)
+    reps = 64
+    st.counter.fill_(5000)                       # every tap of d = 1024 reads a real row, as in a running video
+    for d in (1, 1024):
+        i = {1: 0, 1024: 10}[d]
+        ring, w, b = st.rings[0][i], model._p[f"PG.layers.{i}.conv_dilated.w"], model._p[f"PG.layers.{i}.conv_dilated.b"]
+        for n in (1, 32):
+            chain = lambda: [ops.tcn_stream_conv(ring, w, b, st.h, st.counter, n=n, taps=3, dilation=d, relu=True, out_ring=False) for _ in range(reps)]
+            chain()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                chain()
+            ms = _timed(g.replay, steps, warmup) / reps
+            out["ms"][f"kernel d={d} n={n}"] = round(ms, 5)
+            out["ms"][f"kernel d={d} n={n} weight GB/s"] = round(w.numel() * 4 / (ms * 1e-3) / 1e9, 1)
+    print(json.dumps(out), flush=True)
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--child", choices=["offline", "stream"])
+    p.add_argument("--root", default=HERE)
+    p.add_argument("--parent", default=None)
+    p.add_argument("--reps", type=int, default=3)
+    p.add_argument("--steps", type=int, default=200)
+    p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--history", type=int, default=2000)
+    p.add_argument("--no_causal", action="store_true", help="(--child offline) a checkout that does not know the `causal` argument")
+    a = p.parse_args()
+    if a.child == "offline":
+        return child_offline(os.path.abspath(a.root), a.history, a.steps, a.warmup, not a.no_causal)
+    if a.child == "stream":
+        return child_stream(os.path.abspath(a.root), a.steps, a.warmup)
+    variants = ([("parent", ["--child", "offline", "--no_causal", "--root", os.path.abspath(a.parent)])] if a.parent else []) + \
+        [("this tree", ["--child", "offline"]), ("this tree", ["--child", "stream"])]
+    res, extra = {}, {}
+    for rep in range(a.reps):
+        for name, argv in variants:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv + ["--steps", str(a.steps), "--warmup", str(a.warmup), "--history",
+                                                                                     str(a.history)], capture_output=True, text=True, timeout=240)
+            if r.returncode != 0:
+                sys.exit(f"{name} {argv[1]}: exit status {r.returncode}\n{r.stdout[-1000:]}{r.stderr[-2000:]}")
+            line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+            print(f"rep {rep} {name}: {json.dumps(line)}", flush=True)
+            extra.update({k: v for k, v in line.items() if k not in ("ms", "root")})
+            for k, v in line["ms"].items():
+                res.setdefault((name, k), []).append(v)
+    print(f"\ncausal temporal head, 11 / 10 / 3 x 512, fp32; hipGraph replay; median of {a.reps} process medians of {a.steps} (min .. max); ms unless named")
+    for (name, k), v in res.items():
+        print(f"  {name:10s} {k:34s} {statistics.median(v):10.4f}  ({min(v):.4f} .. {max(v):.4f})")
+    for k, v in extra.items():
+        print(f"  {k}: {v}")
+
+
+if __name__ == "__main__":
+    main()
