@@ -664,9 +664,10 @@ __global__ __launch_bounds__(256) void mha_mfma_f32_kernel(const float* __restri
 // ---- what mt4_attention launches.  Every instantiation stands once in the lists below; the choice (attention_plan) and the launch
 // (attention_launch) are both generated from them.
 // attention_kernel<T, DPL, LPQ>, DPL * LPQ >= hd.  BASE: fewest lanes per query first; FEW: 8 lanes per query, few dims per lane (launches that
-// cannot fill the chip); WIDE: head dims 257 .. 512 (Q2L over Swin-L: 1536 / 4 heads = 384)
+// cannot fill the chip; its rule holds for hd <= 64 only, so (8, 8) is the widest it can take); WIDE: head dims 257 .. 512 (Q2L over Swin-L:
+// 1536 / 4 heads = 384)
 #define MT4_ATTN_BASE(X) X(32, 1) X(24, 2) X(32, 2) X(20, 4) X(28, 4) X(32, 4) X(32, 8)
-#define MT4_ATTN_FEW(X) X(4, 8) X(8, 8) X(12, 8) X(16, 8) X(24, 8)
+#define MT4_ATTN_FEW(X) X(4, 8) X(8, 8)
 #define MT4_ATTN_WIDE(X) X(48, 8) X(64, 8)
 #define MT4_ATTN_GENERIC_VARIANTS(X) MT4_ATTN_BASE(X) MT4_ATTN_FEW(X) MT4_ATTN_WIDE(X)
 // mha_mfma_kernel<NKT, HD>: Nk <= 16 NKT keys, head dim HD (256: Q2L over Swin-B, d = 1024 / 4 heads; 384: over Swin-L, d = 1536 -- the shipped
@@ -692,7 +693,7 @@ constexpr bool attn_variants_ok() {
         // DPL % 4: a staged 4-vector never straddles slices; LPQ lanes of a query exchange by xor-shuffles inside a wave; a chunk holds >= 4 keys
         if (seen != 1 || c.a % 4 != 0 || (c.b & (c.b - 1)) != 0 || 64 % c.b != 0 || AttnLds::max_keys(c.a, c.b) < 4) return false;
     }
-    return sizeof(kAttnAll) / sizeof(kAttnAll[0]) == 14;
+    return sizeof(kAttnAll) / sizeof(kAttnAll[0]) == 11;
 }
 static_assert(attn_variants_ok(), "a (DPL, LPQ) pair names one instantiation of attention_kernel");
 

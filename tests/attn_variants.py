@@ -11,6 +11,9 @@ written beside each row; none was produced by running the library.  `test_attent
   fp32 MFMA fp32, hd <= 128, hd % 4 == 0, no bias / mask, Nk <= 256, strides % 4: NKT = 8 (Nk <= 128) or 16; the keys of a query are split
             over 4 waves where H B ceil(Nq / 64) < 128; LDS = 4 (max(16 NKT 40, 32 (16 NKT + 4)) [+ 128 + 2048 with the split]) bytes
 
+Below `DISPATCH`, the launch probes (`GENERIC_PROBES`, `MHA_*_PROBES`, `WINDOW_*PROBES`, `LN_*PROBES`): the rows test_gpu_attention_variants.py
+launches, one or more per variant of the lists; test_variant_probes_cpu.py asks the planner that they reach every variant.
+
 This is a plain module beside `conv_tiles.py` (`tests/` is on sys.path while pytest runs), not a conftest.
 """
 import ctypes
@@ -21,7 +24,7 @@ F32, BF16 = 0, 1                                  # MT4_F32, MT4_BF16
 
 # (DPL, LPQ) of attention_kernel
 ATTN_BASE = [(32, 1), (24, 2), (32, 2), (20, 4), (28, 4), (32, 4), (32, 8)]
-ATTN_FEW = [(4, 8), (8, 8), (12, 8), (16, 8), (24, 8)]
+ATTN_FEW = [(4, 8), (8, 8)]
 ATTN_WIDE = [(48, 8), (64, 8)]
 ATTN_GENERIC = ATTN_BASE + ATTN_FEW + ATTN_WIDE
 MHA_BF16 = [(nkt, hd) for hd in (256, 384) for nkt in range(1, 11)]          # (NKT, HD) of mha_mfma_kernel
@@ -115,6 +118,111 @@ DISPATCH = [
     attn("hd 513", F32, 2, 4, 16, 16, 513, MT4_EUNSUPPORTED),
     attn("B 65536", F32, 65536, 1, 16, 16, 32, MT4_EUNSUPPORTED),
 ]
+
+
+# ---- launch probes: one row per GPU launch of test_gpu_attention_variants.py, each naming the variant it is meant to reach.  The CPU tests
+# (test_variant_probes_cpu.py) ask the library whether it does, and whether the rows together reach every member of the lists above.
+def max_keys(dpl, lpq):
+    """AttnLds::max_keys: the keys of one LDS chunk of attention_kernel<T, DPL, LPQ>"""
+    return 8192 // (lpq * (dpl + 4)) // 4 * 4
+
+
+# attention_kernel: ((DPL, LPQ), B, H, hd of row a, Nk of row a, hd of row b), for both dtypes.
+#   row a: hd = DPL LPQ (vector staging), a bias and a -100 / 0 mask with nW = 2, Nk = max_keys + 5: two LDS chunks, the last one no multiple of 4
+#          (32, 1): 8192 // 36 = 227 -> 224; (24, 2): 8192 // 56 = 146 -> 144; (32, 2): 8192 // 72 = 113 -> 112; (20, 4): 8192 // 96 = 85 -> 84;
+#          (28, 4): 8192 // 128 = 64; (32, 4): 8192 // 144 = 56; (32, 8): 8192 // 288 = 28; (4, 8): 8192 // 64 = 128; (8, 8): 8192 // 96 = 85 -> 84;
+#          (48, 8): 8192 // 416 = 19 -> 16; (64, 8): 8192 // 544 = 15 -> 12
+#   row b: an hd of the variant's range with hd % 4 != 0 (element-wise staging, zero-padded head dims), no bias, Nk = 7
+#   Nq = 5.  B H = 128 workgroups keep a BASE variant with hd <= 64 off the few-workgroups rule; B H = 4 puts (4, 8) and (8, 8) on it
+GENERIC_ROWS = [
+    ((32, 1), 32, 4, 32, 229, 30),
+    ((24, 2), 32, 4, 48, 149, 45),
+    ((32, 2), 32, 4, 64, 117, 61),
+    ((20, 4), 2, 2, 80, 89, 73),
+    ((28, 4), 2, 2, 112, 69, 101),
+    ((32, 4), 2, 2, 128, 61, 125),
+    ((32, 8), 2, 2, 256, 33, 250),
+    ((4, 8), 2, 2, 32, 133, 13),
+    ((8, 8), 2, 2, 64, 89, 50),
+    ((48, 8), 2, 2, 384, 21, 381),
+    ((64, 8), 2, 2, 512, 17, 509),
+]
+GENERIC_NQ = 5
+
+
+def probe(dt, variant, B, H, Nq, Nk, hd, *, bias=False, nw=0):
+    """one launch through `ops.attention` with q rows [B Nq, H hd] and k, v the two halves of rows [B Nk, 2 H hd]"""
+    return dict(dt=dt, variant=variant, B=B, H=H, Nq=Nq, Nk=Nk, hd=hd, bias=bias, nw=nw)
+
+
+GENERIC_PROBES = [p for dt in (F32, BF16) for (var, B, H, hd_a, nk_a, hd_b) in GENERIC_ROWS
+                  for p in (probe(dt, var, B, H, GENERIC_NQ, nk_a, hd_a, bias=True, nw=2), probe(dt, var, B, H, GENERIC_NQ, 7, hd_b))]
+
+# mha_mfma_kernel<NKT, HD>: Nq = 70 (the second 64-query workgroup holds 6), Nk = 16 NKT - 3; and Nk = 16 NKT for one even and one odd NKT
+# (odd: the upper half of the last 32-key block of P and V is zeros)
+MHA_BF16_PROBES = [probe(BF16, (nkt, hd), 2, 2, 70, 16 * nkt - 3, hd) for hd in (256, 384) for nkt in range(1, 11)] + \
+                  [probe(BF16, (nkt, hd), 2, 2, 70, 16 * nkt, hd) for hd in (256, 384) for nkt in (4, 7)]
+
+# mha_mfma_f32_kernel<NKT, KSPLIT>: (NKT, waves the keys are split over).  No split from H B ceil(Nq / 64) = 128 workgroups on
+MHA_F32_PROBES = [
+    probe(F32, (8, 1), 16, 8, 64, 100, 108),       # 16 * 8 * 1 = 128
+    probe(F32, (8, 1), 8, 8, 65, 128, 4),          # 8 * 8 * 2 = 128; the second workgroup holds one query
+    probe(F32, (16, 1), 8, 8, 65, 129, 128),
+    probe(F32, (16, 1), 16, 8, 64, 256, 4),
+    probe(F32, (8, 4), 2, 2, 17, 1, 128),          # 2 * 2 * 1 = 4 < 128: split; the second 16-query workgroup holds one query
+    probe(F32, (8, 4), 2, 2, 17, 128, 108),
+    probe(F32, (16, 4), 2, 2, 17, 129, 4),
+    probe(F32, (16, 4), 2, 2, 17, 256, 128),
+]
+
+# window_attention_mfma_kernel<NT, NW> with expanded bias (+ mask) tables: (N, nW of the mask or 0); B = 4, H = 2.  N = 16 NT - 5 (3 for NT = 1) and
+# N = 16 NT for NT = 8 and 15; a mask on every other row
+WINDOW_B, WINDOW_H = 4, 2
+WINDOW_PROBES = [(3, 2)] + [(16 * nt - 5, 2 if nt % 2 else 0) for nt in range(2, 17)] + [(128, 2), (240, 0)]
+# ... from the relative-position table: (ws, heads, res, shift); shifted rows pass region ids.  The first five are the shapes of
+# test_window_attention_from_relative_table_equals_expanded_tables; then every ws the form accepts (2 .. 14: test_window_refusals), unshifted on one
+# window and shifted by ws // 2 on 2 x 2 windows
+WINDOW_REL_PROBES = [(12, 4, 24, 6), (12, 4, 24, 0), (7, 8, 14, 3), (7, 3, 7, 0), (4, 2, 8, 2)] + \
+                    [r for ws in range(2, 15) for r in ((ws, 2, ws, 0), (ws, 2, 2 * ws, ws // 2))]
+
+
+def window_nt(n):
+    """key / query tiles of 16 of a window of n tokens: the NT of the variant `window_attention_plan` takes"""
+    return -(-n // 16)
+
+
+# LayerNorm: (dtype, rows, C, G).  nch = G C / V 16-byte chunks per row; every kernel at the two ends of its range (the one before's limit + 1, its own
+# limit), rows ragged against the 16 / 8 (narrow) and 4 (wide) rows of a workgroup
+LN_V = {F32: 4, BF16: 8}
+LN_NCH = [1, 16, 17, 32, 33, 128, 129, 256, 257, 512, 513, 1024]
+LN_ROWS = [1, 7, 37]
+LN_PROBES = [(dt, m, nch * LN_V[dt], 1) for dt in (F32, BF16) for nch in LN_NCH for m in LN_ROWS]
+# (dtype, batch, res, C) of the G = 4 patch-merging gather: 4 C = 2048 in bf16 is Swin-B's last merge (nch 256: wide<4>), 4 C = 512 in fp32 (nch 128: wide<2>)
+LN_MERGE_PROBES = [(BF16, 2, 4, 512), (F32, 2, 4, 128)]
+# (dtype, batch, res, ws, shift, C) of the window gather on a wide kernel: nch 64 (bf16) / 128 (fp32): wide<2>
+LN_WINDOW_PROBES = [(BF16, 2, 14, 7, 3, 512), (F32, 2, 14, 7, 3, 512)]
+
+
+def ln_kernel(dt, G, C):
+    """which kernel `mt4_layernorm` launches (`layernorm_launch`): ("narrow", LPR) for the first LPR with nch <= LPR, else ("wide", MAXCH) for the
+    first MAXCH with nch <= 64 MAXCH; None where it refuses (C % V != 0, or more chunks than the widest kernel holds)"""
+    v = LN_V[dt]
+    if C % v:
+        return None
+    nch = G * C // v
+    for lpr in LN_NARROW:
+        if nch <= lpr:
+            return ("narrow", lpr)
+    for maxch in LN_WIDE:
+        if nch <= 64 * maxch:
+            return ("wide", maxch)
+    return None
+
+
+def probe_plan(p):
+    """(family, p0, p1) that `mt4_attention_plan` answers for a `probe` row with the strides `ops.attention` is given by the GPU test"""
+    c = p["H"] * p["hd"]
+    return plan(p["dt"], p["B"], p["H"], p["Nq"], p["Nk"], p["hd"], bias=p["bias"], mask=bool(p["nw"]), q_stride=c, k_stride=2 * c, v_stride=2 * c)[:3]
 
 
 def plan_args(r):

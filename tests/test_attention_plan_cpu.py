@@ -32,7 +32,7 @@ def test_dispatch_table_covers_what_it_claims():
     assert generic <= set(av.ATTN_GENERIC) and generic & set(av.ATTN_BASE) and generic & set(av.ATTN_FEW) and generic == generic | set(av.ATTN_WIDE)
     assert {r["expect"] for r in av.DISPATCH if not isinstance(r["expect"], tuple)} == {av.MT4_EINVAL, av.MT4_EUNSUPPORTED}
     assert all(e[3] <= 65536 for e in exp)
-    assert len(av.ATTN_GENERIC) == 14 and len(set(av.ATTN_GENERIC)) == 14 and len(av.MHA_BF16) == 20 and len(av.WINDOW) == 16
+    assert len(av.ATTN_GENERIC) == 11 and len(set(av.ATTN_GENERIC)) == 11 and len(av.MHA_BF16) == 20 and len(av.WINDOW) == 16
 
 
 @pytest.mark.parametrize("dt", [av.F32, av.BF16])

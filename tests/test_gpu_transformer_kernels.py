@@ -8,7 +8,9 @@ import attn_variants as av
 import pytest
 import torch
 import torch.nn.functional as F
-from bf16_bounds import GELU_APPROX_ERR, GELU_MAX_SLOPE, check_bf16, rne_bf16
+from attn_checks import check_attn_bf16 as _check_attn_bf16
+from attn_checks import ln64 as _ln64
+from bf16_bounds import GELU_APPROX_ERR, GELU_MAX_SLOPE, check_bf16
 
 pytestmark = pytest.mark.gpu
 DT = [torch.float32, torch.bfloat16]
@@ -21,17 +23,6 @@ def _rand(shape, seed, scale=1.0):
 
 def _tol(dtype, f32=2e-5, bf16=2e-2):
     return f32 if dtype == torch.float32 else bf16
-
-
-def _ln64(x64, g, b, eps=1e-5):
-    """float64 LayerNorm over the last dim and its accumulation scale: `layernorm_kernel` (transformer_kernels.hip:38-84) sums the row in fp32,
-    then the squared deviations from that mean (two passes), and stores (x - mean) * rstd * gamma + beta with one rounding.  The fp32 error of
-    the mean reaches the output as |gamma| rstd mean|x|, that of rstd as |gamma x_hat|."""
-    mu = x64.mean(-1, keepdim=True)
-    r = 1.0 / torch.sqrt(((x64 - mu) ** 2).mean(-1, keepdim=True) + eps)
-    xh = (x64 - mu) * r
-    g64, b64 = g.double(), b.double()
-    return xh * g64 + b64, g64.abs() * (xh.abs() + r * x64.abs().mean(-1, keepdim=True)) + b64.abs()
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -106,42 +97,6 @@ def _attn_ref(q, k, v, scale, bias, mask, nw):
         b = q.shape[0]
         s = (s.view(b // nw, nw, *s.shape[1:]) + mask.unsqueeze(1).unsqueeze(0)).view(*s.shape)
     return s.softmax(-1) @ v
-
-
-def _check_attn_bf16(out, q, k, v, scale, bias, mask, nw, *, mfma, region=False, what=""):
-    """`out` [B*N, H*hd] of a bf16 attention core against float64 on the same bf16 q / k / v ([B,H,N,hd]).
-
-    mfma: the matrix-unit kernels (mha_mfma_kernel, window_attention_mfma_kernel) multiply Q by the scale in fp32 and round it to bf16 before
-    the score MFMA (transformer_kernels.hip:344,1176) -- the reference rounds it there too; they round the unnormalised probabilities
-    p_j = exp(s_j - max) to bf16 as the B operand of the P.V MFMA while the normaliser is the fp32 sum of the unrounded p_j, and scale the fp32
-    result by 1 / sum before the one rounding of the store (:403-458, :1302-1337).  That P rounding is not emulated: it adds at most
-    2^-9 * sum_j p_j |v_j| per output, and the bound allows 2^-8 of it.  The generic kernel (attention_kernel, :179-307) keeps q * scale and P in
-    fp32 (online softmax, one rounding at the store): single rounding.
-    The fp32 score error (a dot product of hd terms, the bias / mask added, exp2 of s * log2 e - max * log2 e) reaches an output as
-    sum_j p_j |ds_j| (|v_j| + |o|): in the accumulation term with sum_d |q_d k_d| + |bias| + |mask| (+ 100 on the region form, which adds 100
-    where the regions are equal) + the row's largest such sum as the size of ds_j."""
-    q64, k64, v64 = q.double(), k.double(), v.double()
-    qs = rne_bf16(q.float() * scale) if mfma else q64 * scale
-    s = qs @ k64.transpose(-1, -2)
-    sa = qs.abs() @ k64.abs().transpose(-1, -2)
-    if bias is not None:
-        s, sa = s + bias.double().unsqueeze(0), sa + bias.double().abs().unsqueeze(0)
-    if mask is not None:
-        b = q.shape[0]
-        m64 = mask.double().unsqueeze(1).unsqueeze(0)
-        s = (s.view(b // nw, nw, *s.shape[1:]) + m64).view(*s.shape)
-        sa = (sa.view(b // nw, nw, *sa.shape[1:]) + m64.abs()).view(*sa.shape)
-    if region:
-        sa = sa + 100.0
-    sa = sa + sa.amax(-1, keepdim=True)
-    p = torch.softmax(s, -1)
-    o = p @ v64
-    pv = p @ v64.abs()
-    acc = pv + (p * sa) @ v64.abs() + (p * sa).sum(-1, keepdim=True) * o.abs()
-    B, H, N, hd = o.shape
-    flat = lambda t: t.permute(0, 2, 1, 3).reshape(B * N, H * hd)
-    kk = max(k.shape[2], hd)
-    check_bf16(out.cpu(), flat(o), acc64=flat(acc), k=kk, extra=flat(pv) * 2.0 ** -8 if mfma else 0.0, single_rounding=not mfma, what=what)
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -360,7 +315,7 @@ def test_window_attention_mfma_bf16(cuda, cfg):
     assert (out.float() - gen.float()).abs().max().item() < 3e-2
 
 
-@pytest.mark.parametrize("ws,H,res,shift", [(12, 4, 24, 6), (12, 4, 24, 0), (7, 8, 14, 3), (7, 3, 7, 0), (4, 2, 8, 2)])
+@pytest.mark.parametrize("ws,H,res,shift", av.WINDOW_REL_PROBES[:5])     # (12, 4, 24, 6), (12, 4, 24, 0), (7, 8, 14, 3), (7, 3, 7, 0), (4, 2, 8, 2)
 def test_window_attention_from_relative_table_equals_expanded_tables(cuda, ws, H, res, shift):
     """the table / region-id form of the Swin core (`mt4_window_attention_rel_bf16`) against the same kernel fed with the expanded
     [H,N,N] bias and [nW,N,N] mask the reference materialises (`swin_transformer.py:92-103,129-132,210-229`): bit-identical on unshifted
