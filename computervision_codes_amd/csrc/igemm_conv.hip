@@ -460,6 +460,100 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * KS * 64) void igemm_conv_kernel
     constexpr bool MIXED = sizeof(T) == 2 && OUT_F32;          // bf16 operands, fp32 output: the residual may be fp32 (a.res_f32)
     if ((a.Cout % CH) == 0) {
         // (the K loop ended with a barrier: every wave is done reading the operand stages)
+        if constexpr (sizeof(T) == 2 && !OUT_F32 && !STATS && KS == 1) {
+            // The forms the inference trunks launch -- bf16 in and out, no residual or a bf16 one (dense or a column slice), no row map, ReLU or
+            // nothing -- without a conditional memory instruction: residual rows and output rows go through buffer descriptors that start at the
+            // tile's first row and end with the tensor (capped like the operand descriptors, so maps above 2 GiB stay here), and a row at or
+            // beyond M, a channel at or beyond Cout or a row the pass does not cover gets an out-of-range offset: the load returns zeros, the
+            // store is dropped, no address outside the tensor is formed.  hipcc can then COUNT every load and store: the residual rows of pass
+            // p + 1 are requested before the read-back of pass p and waited for with a counted vmcnt that leaves the stores of pass p, younger,
+            // in flight.  (With loads and stores behind execz branches every pass waited with vmcnt(0): for its own residual rows, requested one
+            // barrier earlier, and for the previous pass's stores.)  Same arithmetic in the same order as the general form below: bit-identical.
+            if (!a.row_map && a.relu <= 1) {
+                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+                const int rc = tid % TPR, rr = tid / TPR;
+                const int n = n0 + rc * CH;
+                auto srd_rows = [&](const char* base, int ld) {   // rows m0 .. M - 1 of a [M][ld] bf16 tensor whose rows hold Cout channels
+                    const long long left = ((long long)(a.M - 1 - m0) * ld + a.Cout) * 2;
+                    const unsigned long long u = (unsigned long long)(base + (long long)m0 * ld * 2);
+                    const unsigned long long lo = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)u);
+                    const unsigned long long hi = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+                    return __builtin_amdgcn_make_buffer_rsrc((void*)((hi << 32) | lo), (short)0, (int)(left < 0x7fffffffLL ? left : 0x7fffffffLL), 0x00020000);
+                };
+                auto voff = [&](int p, int it, int ld) -> unsigned {   // byte offset of this thread's vector in row `it` of pass p, from the tile's first row
+                    const int lrow = rr + it * RPI;
+                    const int trow = (lrow / WMP) * WM + p * WMP + (lrow % WMP);
+                    const bool ok = (ITERS * RPI <= BMP || lrow < BMP) && m0 + trow < a.M && n < a.Cout;
+                    return ok ? (unsigned)((trow * ld + n) * 2) : 0x80000000u;
+                };
+                // (a variant per residual / cache-policy choice: with the two policies as arms of a branch hipcc's wait counts fell back to 0)
+                auto run = [&](auto has_res, auto non_temporal) {
+                    constexpr bool RES = decltype(has_res)::value;
+                    constexpr int AUX = decltype(non_temporal)::value ? 2 : 0;   // each row is touched once by this launch: the nt bit for the large maps
+                    const auto rsy = srd_rows(a.y, a.y_ld);
+                    const auto rsr = srd_rows(RES ? a.res : a.y, RES ? a.res_ld : a.y_ld);
+                    u32x4 rcur[ITERS], rnext[ITERS];
+                    auto request = [&](int p, u32x4 (&r)[ITERS]) {
+#pragma unroll
+                        for (int it = 0; it < ITERS; ++it) r[it] = __builtin_amdgcn_raw_buffer_load_b128(rsr, voff(p, it, a.res_ld), 0, AUX);
+                    };
+                    if constexpr (RES) request(0, rcur);
+#pragma unroll
+                    for (int p = 0; p < PASSES; ++p) {
+                        if (p) __syncthreads();
+#pragma unroll
+                        for (int jj = 0; jj < MTP; ++jj) {
+                            const int lrow = wave_m * WMP + jj * 16 + r16;
+#pragma unroll
+                            for (int i = 0; i < NT; ++i) {
+                                const int nl = wave_n * WN + i * 16 + q * 4;
+                                *(f32x4*)(smem + lrow * ROWB + nl * 4) = acc[i][p * MTP + jj];
+                            }
+                        }
+                        if constexpr (RES) {
+                            if (p + 1 < PASSES) request(p + 1, rnext);
+                        }
+                        __syncthreads();
+#pragma unroll
+                        for (int it = 0; it < ITERS; ++it) {
+                            const int lrow = (ITERS * RPI <= BMP) ? rr + it * RPI : min(rr + it * RPI, BMP - 1);
+                            float v[CH];
+                            *(float4*)&v[0] = *(const float4*)(smem + lrow * ROWB + rc * CH * 4);
+                            *(float4*)&v[4] = *(const float4*)(smem + lrow * ROWB + rc * CH * 4 + 16);
+                            if constexpr (RES) {
+                                const uint32_t u[4] = {rcur[it].x, rcur[it].y, rcur[it].z, rcur[it].w};
+#pragma unroll
+                                for (int e = 0; e < CH / 2; ++e) {
+                                    v[2 * e] += __uint_as_float(u[e] << 16);
+                                    v[2 * e + 1] += __uint_as_float(u[e] & 0xffff0000u);
+                                }
+                            }
+                            if (a.relu == 1) {
+#pragma unroll
+                                for (int e = 0; e < CH; ++e) v[e] = fmaxf(v[e], 0.f);
+                            }
+                            const u32x4 ov = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+                            const unsigned o = voff(p, it, a.y_ld);
+                            __builtin_amdgcn_raw_buffer_store_b128(ov, rsy, o, 0, AUX);
+                        }
+                        if constexpr (RES) {
+                            if (p + 1 < PASSES) {
+#pragma unroll
+                                for (int it = 0; it < ITERS; ++it) rcur[it] = rnext[it];
+                            }
+                        }
+                    }
+                };
+                if (a.res) {
+                    if (a.nt_epi) run(std::true_type{}, std::true_type{});
+                    else run(std::true_type{}, std::false_type{});
+                } else {
+                    if (a.nt_epi) run(std::false_type{}, std::true_type{});
+                    else run(std::false_type{}, std::false_type{});
+                }
+                return;
+            }
+        }
         const int rc = tid % TPR, rr = tid / TPR;
         const int n = n0 + rc * CH;
         double cs[STATS ? CH : 1], cq[STATS ? CH : 1];
