@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """MI355X entry point without a reference counterpart: frames of a video -> per-frame top-K triplet predictions in one pass
-(student -> temporal head -> `mt4_topk_rows_f32`; see computervision_codes_amd/drivers.py `predict`).  One process; no label files."""
+(student -> temporal head -> `mt4_topk_rows_f32`; see computervision_codes_amd/drivers.py `predict`).  One process; no label files.  `--causal --online [--online_chunk N] [--online_streams S]` answers frame by frame, S videos at once."""
 import os
 import sys
 

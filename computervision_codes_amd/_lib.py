@@ -192,6 +192,8 @@ SIGNATURES = {
     "mt4_fpn_topdown": (C.c_int, [_vp, _vp, _i32, C.c_int64, _i32, _vp]),
     "mt4_tcn_stream_conv_f32": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp] + [_i32] * 6 + [_vp, _vp]),
     "mt4_tcn_stream_advance": (C.c_int, [_vp, _i32, _vp]),
+    "mt4_tcn_stream_conv_rows_f32": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp] + [_i32] * 7 + [_vp] * 5),
+    "mt4_tcn_stream_advance_rows": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "mt4_tcn_layer_fused_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mt4_tcn_linear_ln_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _i32, _vp, _vp, _vp]),
     "mt4_tcn_linear_stats_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),

@@ -135,6 +135,152 @@ __global__ void tcn_stream_advance_kernel(long long* t0, int n) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *t0 += n;
 }
 
+// ---- the row-table form: one launch for one chunk of EACH of several videos (`tenco_stream.StreamBank`).  Row r of the launch is frame
+// counters[row_slot[r]] + row_idx[r] of the stream in slot row_slot[r], whose rings are slice row_slot[r] of [n_slots][L][C] operands; blockIdx.y
+// picks a block of 32 rows (two 16-row tiles, as above) and the number of valid rows is a device word, so one captured launch serves any mix of
+// per-stream counts.  The K split, the step order inside a wave and the fold order are those of `tcn_stream_conv_kernel`, and an MFMA column is
+// one row's sum: a row's bits are the solo kernel's, whatever shares its launch.  The solo kernel keeps its own body: it is the measured baseline.
+constexpr int kStreamMaxSlots = 64;
+
+struct StreamRowsK {
+    const float* x;            // input rings [n_slots][Lin][Cin] (Lin == 0: plain [max_rows][Cin], row r)
+    const float* w;            // [Cout][taps * Cin]
+    const float* bias;         // [Cout] or NULL
+    const float* res;          // residual rings [n_slots][Lres][Cout] (Lres == 0: plain) or NULL
+    float* y;                  // output rings [n_slots][Lout][Cout] (Lout == 0: plain)
+    const int* row_slot;       // [max_rows] the stream of row r
+    const int* row_idx;        // [max_rows] which of that stream's new frames row r is, 0..31
+    const int* n_rows;         // valid rows of this launch (<= max_rows)
+    const long long* counters; // [n_slots] frames pushed before this chunk, per stream
+    int Lin, Lres, Lout;
+    int Cin, Cout, d, relu;
+    int n_slots, max_rows;
+    int SPT;                   // 128-byte K-steps per tap
+};
+
+template <int TAPS>
+__global__ __launch_bounds__(kStreamWaves * 64) void tcn_stream_conv_rows_kernel(const StreamRowsK a) {
+    __shared__ f32x4 red[kStreamWaves * 2 * 64];
+    const int rb0 = blockIdx.y * kStreamMaxChunk;
+    const int nr = min(*a.n_rows, a.max_rows);
+    if (rb0 >= nr) return;                           // a block behind the valid rows: the whole workgroup, before any load or barrier
+    const int nb = min(nr - rb0, kStreamMaxChunk);   // valid rows of this block, >= 1
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r16 = lane & 15, q = lane >> 4;
+    const int n0 = blockIdx.x * kStreamBN;
+    const bool two = nb > 16;                        // a second 16-row tile (block-uniform)
+
+    // this lane's two rows (tile mt: block row i = mt * 16 + r16): the frame, the stream's input ring and whether the row counts.  Lanes beyond
+    // the valid rows take the block's last valid row again; a slot or index outside its range is clamped for the loads and the row is not valid
+    long long fr0[2];
+    const float* xs[2];
+    bool valid[2];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+        const int i = mt * 16 + r16, r = rb0 + min(i, nb - 1);
+        const int slot = a.row_slot[r], idx = a.row_idx[r];
+        const int sc = min(max(slot, 0), a.n_slots - 1), ic = min(max(idx, 0), kStreamMaxChunk - 1);
+        valid[mt] = i < nb && slot == sc && idx == ic;
+        fr0[mt] = a.counters[sc] + ic;
+        xs[mt] = a.Lin ? a.x + (long long)sc * a.Lin * a.Cin : a.x + (long long)r * a.Cin;
+    }
+
+    const int wn = min(n0 + r16, a.Cout - 1);        // rows >= Cout feed accumulator rows that are never stored
+    const float* const wrow = a.w + (long long)wn * (TAPS * a.Cin) + q * 4;
+    const int SPT = a.SPT, NS = TAPS * SPT;
+    struct Frag { float4 w[2], x[2][2]; bool ok[2]; };
+    auto load = [&](int s, Frag& f) {
+        const int tap = TAPS == 1 ? 0 : (s >= SPT) + (s >= 2 * SPT);
+        const int cs = s - tap * SPT;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) f.w[kk] = *(const float4*)(wrow + s * 32 + kk * 16);
+        // unconditional loads, zeros selected in `compute`: see `tcn_stream_conv_kernel`
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            if (mt == 1 && !two) break;
+            const long long fr = fr0[mt] - (long long)(TAPS - 1 - tap) * a.d;
+            const long long row = a.Lin ? (fr & (long long)(a.Lin - 1)) : 0;
+            f.ok[mt] = valid[mt] && fr >= 0;
+            const float* xp = xs[mt] + row * a.Cin + cs * 32 + q * 4;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) f.x[kk][mt] = *(const float4*)(xp + kk * 16);
+        }
+    };
+    f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+    auto compute = [&](const Frag& f) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                if (mt == 1 && !two) break;
+                const float4 v = f.x[kk][mt];
+                const bool ok = f.ok[mt];
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.w[kk].x, ok ? v.x : 0.f, acc[mt], 0, 0, 0);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.w[kk].y, ok ? v.y : 0.f, acc[mt], 0, 0, 0);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.w[kk].z, ok ? v.z : 0.f, acc[mt], 0, 0, 0);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.w[kk].w, ok ? v.w : 0.f, acc[mt], 0, 0, 0);
+            }
+        }
+    };
+    constexpr int NW = kStreamWaves, kDepth = 6;
+    Frag fs[kDepth];
+    int s = wave;
+#pragma unroll
+    for (int j = 0; j < kDepth; ++j)
+        if (s + j * NW < NS) load(s + j * NW, fs[j]);
+    while (s < NS) {
+#pragma unroll
+        for (int j = 0; j < kDepth; ++j) {
+            if (s + j * NW >= NS) break;
+            compute(fs[j]);
+            if (s + (j + kDepth) * NW < NS) load(s + (j + kDepth) * NW, fs[j]);
+        }
+        s += kDepth * NW;
+    }
+
+    // ---- partial tiles -> LDS, fixed-order sum and fused epilogue by waves 0 / 1 (row tile mt = wave)
+    red[(wave * 2 + 0) * 64 + lane] = acc[0];
+    red[(wave * 2 + 1) * 64 + lane] = acc[1];
+    __syncthreads();
+    if (wave >= 2) return;
+    const int i = wave * 16 + r16;                   // row of the block
+    const int en = n0 + q * 4;                       // Cout % 4 == 0: en < Cout implies en + 3 < Cout
+    if (i >= nb || en >= a.Cout) return;
+    const int r = rb0 + i;
+    const int slot = a.row_slot[r], idx = a.row_idx[r];
+    if (slot < 0 || slot >= a.n_slots || idx < 0 || idx >= kStreamMaxChunk) return;
+    f32x4 sum = red[wave * 64 + lane];
+#pragma unroll
+    for (int v = 1; v < kStreamWaves; ++v) sum += red[(v * 2 + wave) * 64 + lane];
+    const long long f = a.counters[slot] + idx;
+    if (a.bias) {
+        const float4 b = *(const float4*)(a.bias + en);
+        sum += (f32x4){b.x, b.y, b.z, b.w};
+    }
+    if (a.res) {
+        const long long rr = a.Lres ? (long long)slot * a.Lres + (f & (long long)(a.Lres - 1)) : (long long)r;
+        const float4 rv = *(const float4*)(a.res + rr * a.Cout + en);
+        sum += (f32x4){rv.x, rv.y, rv.z, rv.w};
+    }
+    if (a.relu) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sum[e] = fmaxf(sum[e], 0.f);
+    }
+    const long long yr = a.Lout ? (long long)slot * a.Lout + (f & (long long)(a.Lout - 1)) : (long long)r;
+    *(float4*)(a.y + yr * a.Cout + en) = make_float4(sum[0], sum[1], sum[2], sum[3]);
+}
+
+// counters[push_slot[a]] += push_count[a], a < *n_push: one thread per entry (the table names a slot once)
+__global__ void tcn_stream_advance_rows_kernel(long long* counters, int n_slots, const int* push_slot, const int* push_count, const int* n_push) {
+    const int a = threadIdx.x;
+    if (blockIdx.x != 0 || a >= min(*n_push, n_slots)) return;
+    const int slot = push_slot[a], c = push_count[a];
+    if (slot < 0 || slot >= n_slots || c < 0 || c > kStreamMaxChunk) return;
+    counters[slot] += c;
+}
+
 bool ring_ok(int L) { return L == 0 || (L > 0 && (L & (L - 1)) == 0); }
 
 }  // namespace
@@ -158,6 +304,40 @@ extern "C" int mt4_tcn_stream_conv_f32(const float* x, int32_t Lin, const float*
     const dim3 grid(cdiv(Cout, kStreamBN)), block(kStreamWaves * 64);
     if (taps == 3) return mt4_launch<tcn_stream_conv_kernel<3>>(grid, block, 0, (hipStream_t)stream, k);
     return mt4_launch<tcn_stream_conv_kernel<1>>(grid, block, 0, (hipStream_t)stream, k);
+}
+
+extern "C" int mt4_tcn_stream_conv_rows_f32(const float* x, int32_t Lin, const float* residual, int32_t Lres, float* y, int32_t Lout, const float* w,
+                                            const float* bias, int32_t Cin, int32_t Cout, int32_t taps, int32_t dilation, int32_t relu,
+                                            int32_t n_slots, int32_t max_rows, const int32_t* row_slot, const int32_t* row_idx,
+                                            const int32_t* n_rows, const int64_t* counters, void* stream) {
+    mt4_clear_error();
+    if (!x || !y || !w || !row_slot || !row_idx || !n_rows || !counters) return MT4_EINVAL;
+    if (n_slots < 1 || n_slots > kStreamMaxSlots || max_rows < 1 || max_rows > kStreamMaxChunk * n_slots) return MT4_EINVAL;
+    if (Cin <= 0 || Cout <= 0 || dilation <= 0 || (taps != 1 && taps != 3) || relu < 0 || relu > 1) return MT4_EINVAL;
+    if (!ring_ok(Lin) || !ring_ok(Lres) || !ring_ok(Lout)) return MT4_EINVAL;
+    if (taps == 3 && Lin == 0) return MT4_EINVAL;                                       // a history needs a ring
+    // a stream may bring a full chunk: frames t0 - (taps - 1) d .. t0 + 31 must all be in its ring
+    if (Lin && Lin < (long long)(taps - 1) * dilation + kStreamMaxChunk) return MT4_EINVAL;
+    if ((Lres && Lres < kStreamMaxChunk) || (Lout && Lout < kStreamMaxChunk)) return MT4_EINVAL;
+    if ((Cin * 4) % 128 != 0 || Cout % 4 != 0) return MT4_EUNSUPPORTED;
+    if ((long long)taps * Cin * Cout > 0x3fffffffLL) return MT4_EUNSUPPORTED;
+    if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)residual | (uintptr_t)bias) & 15) return MT4_EALIGN;
+    if (((uintptr_t)counters & 7) || (((uintptr_t)row_slot | (uintptr_t)row_idx | (uintptr_t)n_rows) & 3)) return MT4_EALIGN;
+    StreamRowsK k{x, w, bias, residual, y, (const int*)row_slot, (const int*)row_idx, (const int*)n_rows, (const long long*)counters,
+                  Lin, residual ? Lres : 0, Lout, Cin, Cout, taps == 1 ? 1 : dilation, relu, n_slots, max_rows, Cin * 4 / 128};
+    const dim3 grid(cdiv(Cout, kStreamBN), cdiv(max_rows, kStreamMaxChunk)), block(kStreamWaves * 64);
+    if (taps == 3) return mt4_launch<tcn_stream_conv_rows_kernel<3>>(grid, block, 0, (hipStream_t)stream, k);
+    return mt4_launch<tcn_stream_conv_rows_kernel<1>>(grid, block, 0, (hipStream_t)stream, k);
+}
+
+extern "C" int mt4_tcn_stream_advance_rows(int64_t* counters, int32_t n_slots, const int32_t* push_slot, const int32_t* push_count,
+                                           const int32_t* n_push, void* stream) {
+    mt4_clear_error();
+    if (!counters || !push_slot || !push_count || !n_push || n_slots < 1 || n_slots > kStreamMaxSlots) return MT4_EINVAL;
+    if (((uintptr_t)counters & 7) || (((uintptr_t)push_slot | (uintptr_t)push_count | (uintptr_t)n_push) & 3)) return MT4_EALIGN;
+    hipLaunchKernelGGL(tcn_stream_advance_rows_kernel, dim3(1), dim3(kStreamMaxSlots), 0, (hipStream_t)stream, (long long*)counters, (int)n_slots,
+                       (const int*)push_slot, (const int*)push_count, (const int*)n_push);
+    return mt4_check_launch();
 }
 
 extern "C" int mt4_tcn_stream_advance(int64_t* t0, int32_t n, void* stream) {

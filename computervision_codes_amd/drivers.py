@@ -1170,6 +1170,9 @@ def _predict_parser() -> argparse.ArgumentParser:
                    help="frame-by-frame mode (needs --causal and --temporal_ckpt): frames go through the student and `tenco_stream.TencoStream` "
                         "--online_chunk at a time, each answer computed from the frames seen so far; the log line adds per-chunk latencies")
     p.add_argument("--online_chunk", type=int, default=1, help="frames per step of --online, 1..32")
+    p.add_argument("--online_streams", type=int, default=1,
+                   help="videos answered at once by --online, 1..64: each tick takes --online_chunk frames of every open video through one "
+                        "student pass and one `tenco_stream.StreamBank` push; the files are those of 1, a closing line reports the ticks")
     return p
 
 
@@ -1178,6 +1181,10 @@ def _predict_inputs(F):
     names or None); every message names its flag"""
     from . import ops, predict as P
     _causal(F)
+    if not 1 <= F.online_streams <= ops.STREAM_MAX_SLOTS:
+        raise ValueError(f"--online_streams {F.online_streams}: 1..{ops.STREAM_MAX_SLOTS} videos at once")
+    if F.online_streams > 1 and not F.online:
+        raise ValueError(f"--online_streams {F.online_streams} needs --online: only the frame-by-frame mode answers several videos at once")
     if F.online:
         if not F.causal:
             raise ValueError("--online needs --causal: a head that pads symmetrically needs frames that have not arrived yet")
@@ -1218,7 +1225,8 @@ def predict(argv=None):
     --videos under --data_dir/data) goes through `predict.Predictor`: PNG decode + Resize, the student in passes of --device_batch, the
     whole-video TCN of --temporal_ckpt on the features left on the device (without it: the student's own heads), `mt4_topk_rows_f32`, one D2H
     copy; --out/<video>.npz and .csv (`Prediction.save`), with --segments also <video>.segments.csv.  No label file is opened.
-    -> {video -> Prediction}"""
+    --online: frame by frame (`Predictor._online_parts`); with --online_streams S > 1, S videos at once (`Predictor.predict_streams`), the same
+    files and one closing line about the ticks.  -> {video -> Prediction}"""
     from . import predict as P
     F = _predict_parser().parse_known_args(argv)[0]
     videos, names = _predict_inputs(F)
@@ -1228,15 +1236,12 @@ def predict(argv=None):
     if temporal is None:
         print("no --temporal_ckpt: the student's own i / v / t / ivt heads are decoded, frame by frame", flush=True)
     pr = P.Predictor(student, temporal, height=F.image_height, width=F.image_width, device_batch=F.device_batch, png_decode=F.png_decode,
-                     decode_workers=F.decode_workers, topk=F.topk, threshold=F.threshold, online_chunk=F.online_chunk if F.online else 0)
+                     decode_workers=F.decode_workers, topk=F.topk, threshold=F.threshold, online_chunk=F.online_chunk if F.online else 0,
+                     online_streams=F.online_streams)
     os.makedirs(F.out, exist_ok=True)
     out = {}
-    for name, paths in videos:
-        t0 = time.time()
-        try:
-            pred = pr.predict_paths(paths, keep_scores=F.save_scores)
-        except ValueError as e:                                      # (--hier on a video too short for the pooled levels: the model's own words)
-            raise ValueError(f"{name} ({len(paths)} frames): {e}") from e
+
+    def done(name, pred, lat, t0):
         pred.save(os.path.join(F.out, name), names)
         note = ""
         if F.segments:
@@ -1244,10 +1249,25 @@ def predict(argv=None):
             P.save_segments(os.path.join(F.out, name + ".segments.csv"), segs, pred.frames, names)
             note = f" | {len(segs)} segments"
         if F.online:
-            lat = np.asarray(pr.chunk_latencies_ms)
+            lat = np.asarray(lat)
             note += f" | online, {F.online_chunk} frames per chunk: median {float(np.median(lat)):.3f} ms, max {float(lat.max()):.3f} ms per chunk"
-        print(f"{name}: {len(paths)} frames | {float(pred.n_active.mean()):.2f} triplets above {F.threshold:g} per frame{note} | {time.time() - t0:.3f} s", flush=True)
+        print(f"{name}: {len(pred.frames)} frames | {float(pred.n_active.mean()):.2f} triplets above {F.threshold:g} per frame{note} | {time.time() - t0:.3f} s", flush=True)
         out[name] = pred
+
+    if F.online_streams > 1:
+        for name, pred, lat, t0 in pr.predict_streams(videos, keep_scores=F.save_scores):
+            done(name, pred, lat, t0)
+        lat = np.asarray(pr.tick_latencies_ms)
+        print(f"online, {F.online_streams} streams: {len(lat)} ticks | median {float(np.median(lat)):.3f} ms, max {float(lat.max()):.3f} ms per tick | "
+              f"median {float(np.median(pr.tick_frames)):g} frames per tick", flush=True)
+        return {name: out[name] for name, _ in videos}
+    for name, paths in videos:
+        t0 = time.time()
+        try:
+            pred = pr.predict_paths(paths, keep_scores=F.save_scores)
+        except ValueError as e:                                      # (--hier on a video too short for the pooled levels: the model's own words)
+            raise ValueError(f"{name} ({len(paths)} frames): {e}") from e
+        done(name, pred, pr.chunk_latencies_ms, t0)
     return out
 
 

@@ -407,6 +407,54 @@ def tcn_stream_advance(t0: torch.Tensor, n: int) -> None:
     check(lib.mt4_tcn_stream_advance(t0.data_ptr(), n, _stream()), "mt4_tcn_stream_advance")
 
 
+STREAM_MAX_SLOTS = 64       # streams per `tcn_stream_conv_rows` launch (kStreamMaxSlots)
+
+
+def tcn_stream_conv_rows(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, row_slot: torch.Tensor,
+                         row_idx: torch.Tensor, n_rows: torch.Tensor, counters: torch.Tensor, *, max_rows: int, taps: int = 1, dilation: int = 1,
+                         residual: Optional[torch.Tensor] = None, relu: bool = False, x_ring: bool = True, residual_ring: bool = True,
+                         out_ring: bool = True) -> torch.Tensor:
+    """`tcn_stream_conv` for one chunk of each of several streams in one launch (`mt4_tcn_stream_conv_rows_f32`).  Row r < n_rows is frame
+    counters[row_slot[r]] + row_idx[r] of the stream in slot row_slot[r].  x / residual / out are rings [n_slots, rows, C] (slice s is stream s's
+    ring) or, with `*_ring=False`, plain 2-D buffers of >= max_rows rows whose row r is the launch's row r.  row_slot / row_idx: int32
+    [>= max_rows], n_rows: int32 [1], counters: int64 [n_slots], all on the device and read only.  The launch covers max_rows rows in blocks of
+    32; blocks behind n_rows return at once.  Returns `out`."""
+    _need_cuda(x, w_packed, bias, residual, out, row_slot, row_idx, n_rows, counters)
+    n_slots = counters.numel()
+    for t, ring in ((x, x_ring), (out, out_ring), (residual, residual_ring)):
+        if t is not None:
+            assert t.is_contiguous() and t.dtype == torch.float32
+            assert (t.dim() == 3 and t.shape[0] == n_slots) if ring else (t.dim() == 2 and t.shape[0] >= max_rows)
+    assert w_packed.dim() == 2 and w_packed.is_contiguous() and w_packed.dtype == torch.float32
+    assert counters.dtype == torch.int64 and counters.is_contiguous()
+    for t in (row_slot, row_idx, n_rows):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert row_slot.numel() >= max_rows and row_idx.numel() >= max_rows and n_rows.numel() == 1
+    cin, cout = x.shape[-1], w_packed.shape[0]
+    assert w_packed.shape[1] == packed_k(cin, 1, taps, torch.float32) and out.shape[-1] == cout
+    if residual is not None:
+        assert residual.shape[-1] == cout
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == cout
+    check(lib.mt4_tcn_stream_conv_rows_f32(x.data_ptr(), x.shape[1] if x_ring else 0, residual.data_ptr() if residual is not None else None,
+                                           residual.shape[1] if residual is not None and residual_ring else 0, out.data_ptr(),
+                                           out.shape[1] if out_ring else 0, w_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                           cin, cout, taps, dilation, 1 if relu else 0, n_slots, max_rows, row_slot.data_ptr(), row_idx.data_ptr(),
+                                           n_rows.data_ptr(), counters.data_ptr(), _stream()), "mt4_tcn_stream_conv_rows_f32")
+    return out
+
+
+def tcn_stream_advance_rows(counters: torch.Tensor, push_slot: torch.Tensor, push_count: torch.Tensor, n_push: torch.Tensor) -> None:
+    """counters[push_slot[a]] += push_count[a], a < n_push, on the device (`mt4_tcn_stream_advance_rows`): the last launch of a row-table chain"""
+    _need_cuda(counters, push_slot, push_count, n_push)
+    assert counters.dtype == torch.int64 and counters.is_contiguous()
+    for t in (push_slot, push_count, n_push):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert push_slot.numel() >= counters.numel() and push_count.numel() >= counters.numel() and n_push.numel() == 1
+    check(lib.mt4_tcn_stream_advance_rows(counters.data_ptr(), counters.numel(), push_slot.data_ptr(), push_count.data_ptr(), n_push.data_ptr(),
+                                          _stream()), "mt4_tcn_stream_advance_rows")
+
+
 def fpn_topdown(lat: torch.Tensor, levels: torch.Tensor) -> None:
     """levels[l] = lat[l] + levels[l+1], l = nlev-2 .. 0, in place (`mt4_fpn_topdown`)"""
     _need_cuda(lat, levels)

@@ -133,10 +133,11 @@ class Predictor:
     as the extraction drivers' flags; topk <= 32; threshold in (0, 1): a triplet counts as on when its logit is above logit(threshold).
     online_chunk N > 0: the latency mode -- the frames go N at a time through the student, `tenco_stream.TencoStream.push` (temporal must be a
     causal head) and the top-K decode, every answer computed from the frames seen so far; `chunk_latencies_ms` holds the last video's per-chunk
-    times (frames on the device -> decoded rows on the device, one synchronise per chunk).  0: the whole-video pass."""
+    times (frames on the device -> decoded rows on the device, one synchronise per chunk).  0: the whole-video pass.
+    online_streams S > 1 (with online_chunk): S videos at once through `tenco_stream.StreamBank`, see `predict_streams`."""
 
     def __init__(self, student, temporal=None, *, height: int = 256, width: int = 448, device_batch: int = 512, png_decode: str = "host",
-                 decode_workers: int = 8, topk: int = 5, threshold: float = 0.5, online_chunk: int = 0):
+                 decode_workers: int = 8, topk: int = 5, threshold: float = 0.5, online_chunk: int = 0, online_streams: int = 1):
         from . import ops
         if not 1 <= int(topk) <= ops.TOPK_MAX_K:
             raise ValueError(f"topk {topk}: 1..{ops.TOPK_MAX_K} (`mt4_topk_rows_f32` keeps a row's winners in one wave's lanes)")
@@ -149,13 +150,21 @@ class Predictor:
         self.png_decode, self.decode_workers = png_decode, int(decode_workers)
         self.topk, self.threshold = int(topk), float(threshold)
         self.online_chunk, self.chunk_latencies_ms, self._stream = int(online_chunk), [], None
+        self.online_streams, self.tick_latencies_ms, self.tick_frames, self._bank = int(online_streams), [], [], None
+        if not 1 <= self.online_streams <= ops.STREAM_MAX_SLOTS:
+            raise ValueError(f"online_streams {online_streams}: 1..{ops.STREAM_MAX_SLOTS} videos open at once")
+        if self.online_streams > 1 and not self.online_chunk:
+            raise ValueError("online_streams > 1 needs the streaming mode (online_chunk > 0)")
         if self.online_chunk:
-            from .tenco_stream import TencoStream
+            from .tenco_stream import StreamBank, TencoStream
             if not 1 <= self.online_chunk <= ops.STREAM_MAX_CHUNK:
                 raise ValueError(f"online_chunk {online_chunk}: 1..{ops.STREAM_MAX_CHUNK} frames per `TencoStream.push`")
             if self.temporal is None:
                 raise ValueError("online_chunk: the streaming mode needs a temporal head")
-            self._stream = TencoStream(self.temporal)                         # (refuses a non-causal, --hier or bf16 head with the reason)
+            if self.online_streams > 1:
+                self._bank = StreamBank(self.temporal, self.online_streams)
+            else:
+                self._stream = TencoStream(self.temporal)                     # (refuses a non-causal, --hier or bf16 head with the reason)
 
     def features(self, paths: Sequence[str]):
         """the student over the frames -> (features fp32 [T, D], logits fp32 (i, v, t, ivt)), all on the device.  Loads run ahead of the model
@@ -222,18 +231,69 @@ class Predictor:
             self.chunk_latencies_ms.append((time.perf_counter() - t0) * 1e3)
         return [torch.cat([c[j] for c in chunks]) for j in range(len(chunks[0]))]
 
-    def predict_paths(self, paths: Sequence[str], keep_scores: bool = False) -> Prediction:
+    def predict_streams(self, videos: Sequence, keep_scores: bool = False):
+        """online_streams > 1: [(name, frame paths)] -> yields (name, Prediction, that video's tick latencies in ms, the `time.time()` it was
+        opened at) as each video ends.  Up to `online_streams` videos are open at once; a tick takes the next `online_chunk` frames of every open video through
+        ONE load, ONE student pass, ONE `StreamBank.push_rows` and ONE decode, whose rows are then dealt to the videos (slot order).  A frame's rows
+        are those of `predict_paths`: neither the student's, the bank's nor the decode's results depend on what shares a pass.  `tick_latencies_ms`
+        / `tick_frames` hold every tick of the call."""
+        import time
+
         import torch
+
+        from . import cholect
+        if self._bank is None:
+            raise ValueError("predict_streams: a Predictor built with online_streams > 1")
+        waiting = [(name, list(paths)) for name, paths in videos]
+        if any(not paths for _, paths in waiting):
+            raise ValueError("predict_streams: a video without frames")
+        waiting.reverse()
+        bank, live = self._bank, {}                       # slot -> [name, paths, frames taken, chunks, latencies, opened at]
+        self.tick_latencies_ms, self.tick_frames = [], []
+        while waiting or live:
+            while waiting and len(live) < self.online_streams:
+                name, paths = waiting.pop()
+                live[bank.open()] = [name, paths, 0, [], [], time.time()]
+            slots = sorted(live)
+            take = {s: live[s][1][live[s][2]:live[s][2] + self.online_chunk] for s in slots}
+            fr = cholect.load_files_device([p for s in slots for p in take[s]], self.height, self.width, workers=self.decode_workers,
+                                           decode=self.png_decode)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            feat = self.student.extract_u8(fr)[3][0]
+            parts = self._decode(bank.push_rows({s: len(take[s]) for s in slots}, feat.float().contiguous()), keep_scores)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3
+            self.tick_latencies_ms.append(ms)
+            self.tick_frames.append(fr.shape[0])
+            at = 0
+            for s in slots:
+                v, n = live[s], len(take[s])
+                v[3].append([p[at:at + n] for p in parts])
+                v[4].append(ms)
+                v[2] += n
+                at += n
+                if v[2] == len(v[1]):
+                    bank.close(s)
+                    del live[s]
+                    joined = [torch.cat([c[j] for c in v[3]]) for j in range(len(parts))]
+                    yield v[0], self._to_prediction(v[1], joined, keep_scores), v[4], v[5]
+
+    def predict_paths(self, paths: Sequence[str], keep_scores: bool = False) -> Prediction:
         paths = list(paths)
         if not paths:
             raise ValueError("predict_paths: no frames")
+        if self._bank is not None:
+            raise ValueError("predict_paths: a Predictor with online_streams > 1 answers through predict_streams")
         if self.online_chunk:
             parts = self._online_parts(paths, keep_scores)
-            n = parts[0].shape[0]
         else:
-            lg = self.logits(paths)
-            n = lg["ivt"].shape[0]
-            parts = self._decode(lg, keep_scores)
+            parts = self._decode(self.logits(paths), keep_scores)
+        return self._to_prediction(paths, parts, keep_scores)
+
+    def _to_prediction(self, paths: Sequence[str], parts, keep_scores: bool) -> Prediction:
+        import torch
+        n = parts[0].shape[0]
         # every piece is 4 bytes wide: one buffer, ONE device-to-host copy per video
         flat = torch.cat([p.reshape(-1).view(torch.int32) for p in parts]).cpu().numpy()
         pieces, at = [], 0

@@ -753,6 +753,26 @@ int mt4_tcn_stream_conv_f32(const float* x, int32_t Lin, const float* residual, 
                             const int64_t* t0, void* stream);
 /* *t0 += n (0 <= n <= 32) in one tiny launch: the end of a streaming chain, so a captured chain replays with the counter as its state. */
 int mt4_tcn_stream_advance(int64_t* t0, int32_t n, void* stream);
+/* The row-table form of mt4_tcn_stream_conv_f32: ONE launch for one chunk of each of several videos (the same causal conv,
+ * Temporal_tenco/network.py:165-183, fp32).  Row r < *n_rows of the launch is frame counters[row_slot[r]] + row_idx[r] of the stream in slot
+ * row_slot[r] (0 .. n_slots - 1; row_idx 0 .. 31: which of that stream's new frames), and is computed as that stream's solo launch computes it.
+ *   x / residual / y   rings [n_slots][L][C], stream s using slice s (frame f in row f & (L - 1)); L == 0: a plain buffer of >= max_rows rows,
+ *                      row r of the launch (x: taps == 1 only)
+ *   row_slot, row_idx  DEVICE int32 [>= max_rows];  n_rows  DEVICE int32: the valid rows, at most max_rows (a larger value counts as max_rows);
+ *   counters           DEVICE int64 [n_slots]: the frames pushed before this chunk, per stream (read, never written)
+ * The grid has one block of 32 rows per 32 of max_rows; blocks behind *n_rows return at once, so a captured launch serves any row count up to
+ * max_rows.  A row whose slot or index is out of range is not stored.  1 <= n_slots <= 64, 1 <= max_rows <= 32 n_slots; ring lengths are powers
+ * of two, Lin >= (taps - 1) d + 32, Lres, Lout >= 32; taps 1 or 3; Cin * 4 % 128 == 0 and Cout % 4 == 0 (MT4_EUNSUPPORTED otherwise); x, w, y,
+ * residual, bias 16-byte aligned, counters 8-byte, the tables 4-byte (MT4_EALIGN); every other refusal is MT4_EINVAL, all before any launch.
+ * K order and fold order are those of mt4_tcn_stream_conv_f32: a row's bits do not depend on what shares its launch.  Enqueue-only, capturable. */
+int mt4_tcn_stream_conv_rows_f32(const float* x, int32_t Lin, const float* residual, int32_t Lres, float* y, int32_t Lout, const float* w,
+                                 const float* bias, int32_t Cin, int32_t Cout, int32_t taps, int32_t dilation, int32_t relu, int32_t n_slots,
+                                 int32_t max_rows, const int32_t* row_slot, const int32_t* row_idx, const int32_t* n_rows, const int64_t* counters,
+                                 void* stream);
+/* counters[push_slot[a]] += push_count[a] for a < *n_push (DEVICE int32 tables and count, a slot named once, counts 0 .. 32): the end of a
+ * row-table chain of the streaming conv above (Temporal_tenco/network.py:165-183), as mt4_tcn_stream_advance ends a solo one.  1 <= n_slots <= 64. */
+int mt4_tcn_stream_advance_rows(int64_t* counters, int32_t n_slots, const int32_t* push_slot, const int32_t* push_count, const int32_t* n_push,
+                                void* stream);
 /* FPN top-down pathway at equal lengths (network.py:93-106; `F.interpolate(x, size=W, mode='linear')` to the same length is the
  * identity): levels[l] = lat[l] + levels[l+1] for l = nlev-2 .. 0, in place.  lat [nlev-1][n], levels [nlev][n] of dtype, n % 4 == 0. */
 int mt4_fpn_topdown(const void* lat, void* levels, int32_t nlev, int64_t n, int32_t dtype, void* stream);

@@ -1,0 +1,133 @@
+"""GPU: `mt4_tcn_stream_conv_rows_f32`, one launch for one chunk of each of several streams, against `mt4_tcn_stream_conv_f32` run once per
+stream on the same device buffers: every pushed row equal TO THE BIT (`bf16_bounds.check_exact`; the solo kernel is held to float64 by
+test_gpu_tcn_stream.py), no other row written, no operand changed.  Three streams in slots 0, 1 and 3 of four (slot 2 stays idle), rings of 64
+rows filled with NaN outside the rows a correct kernel reads -- all of the idle slot's and of a stream that brings no frame.  Row totals on both
+sides of the 16-row tile and the 32-row block; counters at 0, inside the front padding, just behind it, at a wrapping write and three wraps on,
+mixed inside one launch."""
+import pytest
+import torch
+
+import bf16_bounds as bb
+from computervision_codes_amd import ops
+from computervision_codes_amd.tenco_stream import row_table
+
+pytestmark = pytest.mark.gpu
+L, NS, BLOCK = 64, 4, ops.STREAM_MAX_CHUNK
+SLOTS = (0, 1, 3)
+NAN = float("nan")
+# total rows -> frames of slots 0, 1, 3 (0: the stream is not in the push)
+COUNTS = {1: (0, 1, 0), 16: (5, 10, 1), 17: (16, 0, 1), 32: (7, 20, 5), 33: (32, 1, 0), 38: (3, 32, 3), 96: (32, 32, 32)}
+
+
+def _mixes(d):
+    """counters of slots 0, 1, 3: (inside the front padding, a write that wraps, three wraps on) and (a fresh stream, just behind the padding,
+    a write that wraps)"""
+    return [(d - 1, L - 3, 3 * L + 7), (0, 2 * d, L - 3)]
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def _case(cuda, g, wp, bias, cin, cout, plain, taps, d, counts, t0s, valid=None):
+    """one table, the four residual / ReLU forms.  counts / t0s: {slot: frames} / {slot: counter}; valid: the device row count when it is below
+    the table's length (the launch still covers the whole table)"""
+    row_slot, row_idx, _, _ = row_table(counts, NS)
+    total = len(row_slot)
+    max_rows = (total + BLOCK - 1) // BLOCK * BLOCK
+    valid = total if valid is None else valid
+    done = {s: sum(1 for r in range(valid) if row_slot[r] == s) for s in counts}          # rows of each stream the launch computes
+    first = {s: row_slot.index(s) for s in counts}
+    x_plain = plain and taps == 1
+    if x_plain:
+        xb = torch.full((BLOCK * NS, cin), NAN)
+        xb[:valid] = torch.randn((valid, cin), generator=g)
+    else:
+        xb = torch.full((NS, L, cin), NAN)                                                 # a read of any row but the right ones poisons the result
+        for s, n in done.items():
+            rows = [f % L for f in range(max(t0s[s] - (taps - 1) * d, 0), t0s[s] + n)]
+            xb[s, rows] = torch.randn((len(rows), cin), generator=g)
+    if plain:
+        rb = torch.full((BLOCK * NS, cout), NAN)
+        rb[:valid] = torch.randn((valid, cout), generator=g)
+    else:
+        rb = torch.full((NS, L, cout), NAN)
+        for s, n in done.items():
+            rb[s, [(t0s[s] + i) % L for i in range(n)]] = torch.randn((n, cout), generator=g)
+    counters = torch.full((NS,), 5, dtype=torch.int64)
+    for s, t0 in t0s.items():
+        counters[s] = t0
+    xd, rd, cd = xb.to(cuda), rb.to(cuda), counters.to(cuda)
+    rs, ri = (torch.tensor(t + [0] * (max_rows - total), dtype=torch.int32, device=cuda) for t in (row_slot, row_idx))
+    nr = torch.tensor([valid], dtype=torch.int32, device=cuda)
+    shape = (BLOCK * NS, cout) if plain else (NS, L, cout)
+    for with_res in (False, True):
+        for relu in (False, True):
+            what = f"rows conv {cin}->{cout} taps {taps} d {d} plain {plain} counts {counts} t0 {t0s} valid {valid} res {with_res} relu {relu}"
+            out = torch.full(shape, 7.0, device=cuda)
+            ops.tcn_stream_conv_rows(xd, wp, bias, out, rs, ri, nr, cd, max_rows=max_rows, taps=taps, dilation=d, residual=rd if with_res else None,
+                                     relu=relu, x_ring=not x_plain, residual_ring=not plain, out_ring=not plain)
+            want = torch.full(shape, 7.0, device=cuda)
+            pushed = torch.zeros(shape[:-1], dtype=torch.bool)
+            for s, n in done.items():
+                if n == 0:
+                    continue
+                r0 = first[s]
+                if x_plain:
+                    sx = torch.full((BLOCK, cin), NAN, device=cuda)
+                    sx[:n] = xd[r0:r0 + n]
+                else:
+                    sx = xd[s]
+                if plain:
+                    sr = torch.full((BLOCK, cout), NAN, device=cuda)
+                    sr[:n] = rd[r0:r0 + n]
+                    so = torch.full((BLOCK, cout), 7.0, device=cuda)
+                else:
+                    sr, so = rd[s], want[s]
+                ops.tcn_stream_conv(sx, wp, bias, so, cd[s:s + 1], n=n, taps=taps, dilation=d, residual=sr if with_res else None, relu=relu,
+                                    x_ring=not x_plain, residual_ring=not plain, out_ring=not plain)
+                if plain:
+                    want[r0:r0 + n] = so[:n]
+                    pushed[r0:r0 + n] = True
+                else:
+                    pushed[s, [(t0s[s] + i) % L for i in range(n)]] = True
+            got, want = out.cpu(), want.cpu()
+            assert int(pushed.sum()) == valid and not bool((want[pushed] == 7.0).any(dim=-1).all())          # (the solo launches did write)
+            bb.check_exact(got[pushed], want[pushed], what=what)
+            assert bool((got[~pushed] == 7.0).all()), what + ": a row outside the pushed ones was written"
+    assert torch.equal(_bits(xd.cpu()), _bits(xb)) and torch.equal(_bits(rd.cpu()), _bits(rb)) and torch.equal(cd.cpu(), counters), "an operand changed"
+
+
+def _weights(cuda, cin, cout, taps):
+    g = torch.Generator().manual_seed(1000 * cin + taps)
+    w = torch.randn((cout, cin, taps), generator=g) / (cin * taps) ** 0.5
+    return g, ops.pack_conv_weight(w.to(cuda)[:, :, None, :], None, torch.float32), torch.randn(cout, generator=g).to(cuda)
+
+
+@pytest.mark.parametrize("cin, cout, plain", [(64, 64, False), (32, 132, True)], ids=["rings", "plain"])
+@pytest.mark.parametrize("taps, d", [(1, 1), (3, 1), (3, 4), (3, 16)])
+def test_rows_launch_equals_the_solo_launches_to_the_bit(cuda, cin, cout, plain, taps, d):
+    g, wp, bias = _weights(cuda, cin, cout, taps)
+    for total, per_slot in COUNTS.items():
+        counts = {s: n for s, n in zip(SLOTS, per_slot) if n}
+        assert sum(counts.values()) == total
+        for mix in _mixes(d):
+            _case(cuda, g, wp, bias, cin, cout, plain, taps, d, counts, dict(zip(SLOTS, mix)))
+
+
+@pytest.mark.parametrize("cin, cout, plain", [(64, 64, False), (32, 132, True)], ids=["rings", "plain"])
+@pytest.mark.parametrize("valid", [38, 1])
+def test_device_row_count_below_the_launch(cuda, cin, cout, plain, valid):
+    """a table of 96 rows (three blocks) of which the device word admits 38 (the second block ends after six rows, the third returns) or 1"""
+    g, wp, bias = _weights(cuda, cin, cout, 3)
+    _case(cuda, g, wp, bias, cin, cout, plain, 3, 4, dict(zip(SLOTS, COUNTS[96])), dict(zip(SLOTS, _mixes(4)[0])), valid=valid)
+
+
+def test_advance_rows_adds_each_count_to_its_slot(cuda):
+    counters = torch.tensor([3, 100, 7, 2 ** 40], dtype=torch.int64, device=cuda)
+    ps = torch.tensor([3, 0, 2, 1], dtype=torch.int32, device=cuda)                       # the last two lie behind n_push
+    pc = torch.tensor([32, 1, 9, 9], dtype=torch.int32, device=cuda)
+    ops.tcn_stream_advance_rows(counters, ps, pc, torch.tensor([2], dtype=torch.int32, device=cuda))
+    assert counters.tolist() == [4, 100, 7, 2 ** 40 + 32]
+    ops.tcn_stream_advance_rows(counters, ps, pc, torch.tensor([0], dtype=torch.int32, device=cuda))
+    assert counters.tolist() == [4, 100, 7, 2 ** 40 + 32]
