@@ -359,12 +359,14 @@ def tcn_stage(stage: TcnStage, x: torch.Tensor, out: Optional[torch.Tensor] = No
 
 
 def tcn_layer(x: torch.Tensor, w_dilated: torch.Tensor, b_dilated: torch.Tensor, w_1x1: torch.Tensor, b_1x1: torch.Tensor,
-              dilation: int) -> torch.Tensor:
-    """one DilatedResidualLayer (`mt4_tcn_dilated_residual_layer`): x [B,T,C] -> x + conv_1x1(relu(conv_dilated(x)))"""
-    _need_cuda(x, w_dilated, b_dilated, w_1x1, b_1x1)
+              dilation: int, h_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """one DilatedResidualLayer (`mt4_tcn_dilated_residual_layer`): x [B,T,C] -> x + conv_1x1(relu(conv_dilated(x))).  h_out: where the hidden
+    activation relu(conv_dilated(x)) goes (the launch's scratch; same shape and dtype as x) when the caller wants to see it."""
+    _need_cuda(x, w_dilated, b_dilated, w_1x1, b_1x1, h_out)
     assert x.dim() == 3 and x.is_contiguous()
     b, t, c = x.shape
-    h, y = torch.empty_like(x), torch.empty_like(x)
+    h, y = (torch.empty_like(x) if h_out is None else h_out), torch.empty_like(x)
+    assert h.is_contiguous() and h.shape == x.shape and h.dtype == x.dtype and h.data_ptr() != x.data_ptr()
     check(lib.mt4_tcn_dilated_residual_layer(x.data_ptr(), w_dilated.data_ptr(), b_dilated.data_ptr(), w_1x1.data_ptr(), b_1x1.data_ptr(),
                                              h.data_ptr(), y.data_ptr(), b, t, c, dilation, dt_code(x.dtype), _stream()),
           "mt4_tcn_dilated_residual_layer")
