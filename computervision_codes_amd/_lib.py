@@ -221,6 +221,7 @@ SIGNATURES = {
     "mt4_component_max_f32": (C.c_int, [_vp, C.POINTER(_i32), _i32, _vp, C.c_int64, _vp]),
     "mt4_rank_hist_f32": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp]),
     "mt4_topk_rows_f32": (C.c_int, [_vp, C.c_int64, _i32, C.c_int64, C.c_int64, _i32, C.c_float, _vp, _vp, _vp, _vp]),
+    "mt4_class_maps": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp]),
 }
 
 

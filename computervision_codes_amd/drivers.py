@@ -1173,6 +1173,12 @@ def _predict_parser() -> argparse.ArgumentParser:
     p.add_argument("--online_streams", type=int, default=1,
                    help="videos answered at once by --online, 1..64: each tick takes --online_chunk frames of every open video through one "
                         "student pass and one `tenco_stream.StreamBank` push; the files are those of 1, a closing line reports the ticks")
+    p.add_argument("--localize", type=str, default="off", choices=["off", "i", "ivt"],
+                   help="where in the frame each top-K triplet is: class-activation maps of the student's instrument head (i: the column of the "
+                        "triplet's instrument) or triplet head (ivt: the triplet's own column); adds loc_* arrays to the .npz and <video>.loc.csv")
+    p.add_argument("--localize_frac", type=float, default=0.5,
+                   help="the region around a map's peak: the connected cells with map >= min + frac * (max - min), 0..1")
+    p.add_argument("--save_maps", action="store_true", help="with --localize: also the top-K maps themselves, loc_maps [T, k, h, w], into the .npz")
     return p
 
 
@@ -1194,6 +1200,12 @@ def _predict_inputs(F):
             raise ValueError(f"--online_chunk {F.online_chunk}: 1..{ops.STREAM_MAX_CHUNK}")
         if _dtype(F.dtype) != torch.float32:
             raise ValueError(f"--online with --dtype {F.dtype}: the streaming step (mt4_tcn_stream_conv_f32) is fp32 only")
+    if F.save_maps and F.localize == "off":
+        raise ValueError("--save_maps needs --localize i or --localize ivt: there are no maps to save")
+    if not 0.0 <= F.localize_frac <= 1.0:
+        raise ValueError(f"--localize_frac {F.localize_frac}: a fraction of the map's range, 0..1")
+    if F.localize != "off" and F.loss_type not in (F.localize, "all"):
+        raise ValueError(f"--localize {F.localize} with --loss_type {F.loss_type}: that student has no {F.localize} head to map")
     if not F.student_ckpt:
         raise ValueError("--student_ckpt FILE is required")
     for flag, path in (("--student_ckpt", F.student_ckpt), ("--temporal_ckpt", F.temporal_ckpt), ("--names", F.names)):
@@ -1237,7 +1249,11 @@ def predict(argv=None):
         print("no --temporal_ckpt: the student's own i / v / t / ivt heads are decoded, frame by frame", flush=True)
     pr = P.Predictor(student, temporal, height=F.image_height, width=F.image_width, device_batch=F.device_batch, png_decode=F.png_decode,
                      decode_workers=F.decode_workers, topk=F.topk, threshold=F.threshold, online_chunk=F.online_chunk if F.online else 0,
-                     online_streams=F.online_streams)
+                     online_streams=F.online_streams, localize=None if F.localize == "off" else F.localize, localize_frac=F.localize_frac,
+                     localize_maps=F.save_maps)
+    if F.localize != "off":
+        print(f"--localize {F.localize}: each top-K triplet is localised by the student's {'instrument' if F.localize == 'i' else 'triplet'} head "
+              f"(class-activation maps, region at {F.localize_frac:g} of the map's range{', maps saved' if F.save_maps else ''})", flush=True)
     os.makedirs(F.out, exist_ok=True)
     out = {}
 

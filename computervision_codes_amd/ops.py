@@ -1881,6 +1881,79 @@ def topk_rows_host(x, k: int, count_above: Optional[float] = None):
     return ids[:, :int(k)].to(torch.int32).contiguous(), vals[:, :int(k)].contiguous(), n_above
 
 
+# ----------------------------------------------------------------------------------------- class-activation maps (predict.py --localize)
+CLASS_MAPS_MAX_CELLS, CLASS_MAPS_MAX_COLS, CLASS_MAPS_MAX_C = 1024, 256, 8192     # the limits of `mt4_class_maps`
+
+
+def class_maps(feat: torch.Tensor, w: torch.Tensor, col_lo: int, ncol: int, frac: float):
+    """(maps fp32 [B, ncol, H, W], regions int32 [B, ncol, 8], range fp32 [B, ncol, 2]) of an NHWC map `feat` [B, H, W, C] (fp32 or bf16,
+    contiguous) under rows col_lo .. col_lo + ncol - 1 of `w` (fp32 row-major [rows, C], contiguous): maps[b, j, y, x] = sum_k w[col_lo + j, k]
+    feat[b, y, x, k] (no bias), range = (min, max) of each map, regions = peak_y, peak_x, y0, x0, y1, x1, area, 0 of the 4-connected component
+    of {map >= min + frac (max - min)} around the peak (`mt4_class_maps`; `class_regions_host` restates range and regions on the host)."""
+    _need_cuda(feat, w)
+    if feat.dim() != 4 or not feat.is_contiguous() or feat.dtype not in _DT:
+        raise ValueError(f"class_maps: a contiguous fp32 / bf16 [B, H, W, C] map, got {tuple(feat.shape)} {feat.dtype}")
+    if w.dim() != 2 or not w.is_contiguous() or w.dtype != torch.float32 or w.shape[1] != feat.shape[3]:
+        raise ValueError(f"class_maps: fp32 contiguous weight rows [rows, {feat.shape[3]}], got {tuple(w.shape)} {w.dtype}")
+    col_lo, ncol, frac = int(col_lo), int(ncol), float(frac)
+    if col_lo < 0 or ncol < 1 or col_lo + ncol > w.shape[0]:
+        raise ValueError(f"class_maps: columns {col_lo} .. {col_lo + ncol - 1} of {w.shape[0]} weight rows")
+    if not 0.0 <= frac <= 1.0:
+        raise ValueError(f"class_maps: frac {frac} outside [0, 1]")
+    b, h, wd, c = feat.shape
+    maps = torch.empty((b, ncol, h, wd), dtype=torch.float32, device=feat.device)
+    regions = torch.empty((b, ncol, 8), dtype=torch.int32, device=feat.device)
+    rng = torch.empty((b, ncol, 2), dtype=torch.float32, device=feat.device)
+    if b == 0:
+        return maps, regions, rng
+    check(lib.mt4_class_maps(feat.data_ptr(), dt_code(feat.dtype), w.data_ptr(), col_lo, ncol, b, h, wd, c, frac, maps.data_ptr(), regions.data_ptr(),
+                             rng.data_ptr(), _stream()), "mt4_class_maps")
+    return maps, regions, rng
+
+
+def class_regions_host(maps, frac: float):
+    """the contract of `mt4_class_maps`' range and regions on the host, in numpy float32: maps [..., H, W] -> (regions int32 [..., 8], range
+    float32 [..., 2]).  Range: the first minimum and the first maximum in y W + x order (their bits); peak: that maximum's cell; tau = mn +
+    frac (mx - mn) as three separately rounded float32 operations; S = {map >= tau} plus the peak; the region is the 4-connected component of S
+    that holds the peak, grown by sweeps of all maps at once until none changes.  Equal to the kernel bit for bit on any finite map."""
+    import numpy as np
+    m = np.ascontiguousarray(np.asarray(maps.detach().cpu() if isinstance(maps, torch.Tensor) else maps, dtype=np.float32))
+    if m.ndim < 2 or m.shape[-1] < 1 or m.shape[-2] < 1:
+        raise ValueError(f"class_regions_host: maps [..., H, W], got {m.shape}")
+    if not 0.0 <= float(frac) <= 1.0:
+        raise ValueError(f"class_regions_host: frac {frac} outside [0, 1]")
+    lead, (h, w) = m.shape[:-2], m.shape[-2:]
+    flat = m.reshape(-1, h * w)
+    n = flat.shape[0]
+    rows = np.arange(n)
+    ipk, imn = flat.argmax(axis=1), flat.argmin(axis=1)
+    mx, mn = flat[rows, ipk], flat[rows, imn]
+    with np.errstate(over="ignore", invalid="ignore"):
+        tau = (mn + (np.float32(frac) * (mx - mn).astype(np.float32)).astype(np.float32)).astype(np.float32)
+    inset = flat >= tau[:, None]
+    inset[rows, ipk] = True
+    inset = inset.reshape(n, h, w)
+    reach = np.zeros((n, h, w), dtype=bool)
+    reach.reshape(n, h * w)[rows, ipk] = True
+    for _ in range(h * w):
+        grown = reach.copy()
+        grown[:, 1:, :] |= reach[:, :-1, :]
+        grown[:, :-1, :] |= reach[:, 1:, :]
+        grown[:, :, 1:] |= reach[:, :, :-1]
+        grown[:, :, :-1] |= reach[:, :, 1:]
+        grown &= inset
+        if np.array_equal(grown, reach):
+            break
+        reach = grown
+    regions = np.zeros((n, 8), dtype=np.int32)
+    regions[:, 0], regions[:, 1] = ipk // w, ipk % w
+    ys, xs = reach.any(axis=2), reach.any(axis=1)
+    regions[:, 2], regions[:, 3] = ys.argmax(axis=1), xs.argmax(axis=1)
+    regions[:, 4], regions[:, 5] = h - 1 - ys[:, ::-1].argmax(axis=1), w - 1 - xs[:, ::-1].argmax(axis=1)
+    regions[:, 6] = reach.reshape(n, -1).sum(axis=1)
+    return regions.reshape(lead + (8,)), np.stack([mn, mx], axis=1).astype(np.float32).reshape(lead + (2,))
+
+
 # ----------------------------------------------------------------------------------------- Swin / Q2L training pieces (fp32)
 def gather_rows(x: torch.Tensor, row_map: torch.Tensor, *, l_out: int, l_in: int, group: int = 1, m_out: Optional[int] = None) -> torch.Tensor:
     """y[m][g*C:(g+1)*C] = x[(m // l_out) * l_in + map[(m % l_out) * group + g]]  (`mt4_gather_rows_f32`)"""

@@ -15,6 +15,8 @@ import numpy as np
 from .metrics import _TRIPLETS
 
 HEADS = ("ivt", "i", "v", "t")
+LOCALIZE_HEADS = ("i", "ivt")
+LOC_ARRAYS = ("loc_peak", "loc_box", "loc_area", "loc_range")
 
 
 def parse_names(path: str) -> List[str]:
@@ -49,9 +51,17 @@ class Prediction:
       n_active      int32 [T]       triplets whose logit is above logit(threshold)
       topk_ivt      int32 [T, k, 3] (instrument, verb, target) of every top-K triplet (`metrics._TRIPLETS`)
       top_i / top_v / top_t         (ids int32 [T], scores float32 [T]): the component heads' own first pick
-      scores        None, or {head -> float32 [T, K]} sigmoid scores of the four heads (keep_scores)"""
+      scores        None, or {head -> float32 [T, K]} sigmoid scores of the four heads (keep_scores)
+    and, when localisation ran (`loc`: a dict of the arrays below without the prefix; None otherwise, and then every attribute is None):
+      loc_peak      int32 [T, k, 2]   (y, x) cell of the maximum of each top-K triplet's class-activation map
+      loc_box       int32 [T, k, 4]   (y0, x0, y1, x1), inclusive, in cells: the region around the peak (`ops.class_maps`)
+      loc_area      int32 [T, k]      its cell count
+      loc_range     float32 [T, k, 2] minimum and maximum of the map
+      loc_cells / loc_frame           (h, w) of the layer4 grid / (H, W) of the resized frame
+      loc_head / loc_frac             "i" | "ivt": the head whose columns were mapped / the region's threshold fraction
+      loc_maps      None, or float32 [T, k, h, w] the maps themselves (--save_maps)"""
 
-    def __init__(self, frames: Sequence[str], topk_ids, topk_scores, n_active, top_i, top_v, top_t, threshold: float = 0.5, scores=None):
+    def __init__(self, frames: Sequence[str], topk_ids, topk_scores, n_active, top_i, top_v, top_t, threshold: float = 0.5, scores=None, loc=None):
         self.frames = [str(f) for f in frames]
         self.topk_ids = np.asarray(topk_ids, dtype=np.int32)
         self.topk_scores = np.asarray(topk_scores, dtype=np.float32)
@@ -62,6 +72,35 @@ class Prediction:
         if self.topk_ids.shape != self.topk_scores.shape or self.topk_ids.ndim != 2 or self.topk_ids.shape[0] != len(self.frames):
             raise ValueError(f"Prediction: {len(self.frames)} frames, top-K arrays {self.topk_ids.shape} / {self.topk_scores.shape}")
         self.topk_ivt = np.array(_TRIPLETS, dtype=np.int32)[self.topk_ids]
+        self.loc_peak = self.loc_box = self.loc_area = self.loc_range = self.loc_cells = self.loc_frame = self.loc_head = self.loc_frac = self.loc_maps = None
+        if loc is not None:
+            t, k = self.topk_ids.shape
+            self.loc_peak, self.loc_box, self.loc_area = (np.asarray(loc[n], dtype=np.int32) for n in ("peak", "box", "area"))
+            self.loc_range = np.asarray(loc["range"], dtype=np.float32)
+            self.loc_cells, self.loc_frame = tuple(int(v) for v in loc["cells"]), tuple(int(v) for v in loc["frame"])
+            self.loc_head, self.loc_frac = str(loc["head"]), float(loc["frac"])
+            if self.loc_head not in LOCALIZE_HEADS:
+                raise ValueError(f"Prediction: loc head {self.loc_head!r}: one of {LOCALIZE_HEADS}")
+            if (self.loc_peak.shape, self.loc_box.shape, self.loc_area.shape, self.loc_range.shape) != ((t, k, 2), (t, k, 4), (t, k), (t, k, 2)):
+                raise ValueError(f"Prediction: localisation arrays {self.loc_peak.shape} / {self.loc_box.shape} / {self.loc_area.shape} / "
+                                 f"{self.loc_range.shape} for top-K arrays {self.topk_ids.shape}")
+            if loc.get("maps") is not None:
+                self.loc_maps = np.asarray(loc["maps"], dtype=np.float32)
+                if self.loc_maps.shape != (t, k) + self.loc_cells:
+                    raise ValueError(f"Prediction: loc maps {self.loc_maps.shape}, expected {(t, k) + self.loc_cells}")
+
+    def loc_columns(self):
+        """int32 [T, k]: the column of `loc_head` that localised each top-K triplet (its own id, or its instrument)"""
+        return self.topk_ids if self.loc_head == "ivt" else np.ascontiguousarray(self.topk_ivt[..., 0])
+
+    def loc_pixels(self):
+        """(peak float64 [T, k, 2] as (x, y), box float64 [T, k, 4] as (x0, y0, x1, y1)) in resized-frame pixels: cell x covers
+        [x W / w, (x + 1) W / w), a box is written by its outer edges, the peak as its cell's centre"""
+        (h, w), (fh, fw) = self.loc_cells, self.loc_frame
+        sy, sx = fh / h, fw / w
+        peak = np.stack([(self.loc_peak[..., 1] + 0.5) * sx, (self.loc_peak[..., 0] + 0.5) * sy], axis=-1)
+        b = self.loc_box.astype(np.float64)
+        return peak, np.stack([b[..., 1] * sx, b[..., 0] * sy, (b[..., 3] + 1) * sx, (b[..., 2] + 1) * sy], axis=-1)
 
     def _arrays(self):
         out = {"frames": np.array(self.frames, dtype=str), "threshold": np.float64(self.threshold), "topk_ids": self.topk_ids,
@@ -70,11 +109,18 @@ class Prediction:
             out[f"top_{h}_ids"], out[f"top_{h}_scores"] = ids, sc
         if self.scores is not None:
             out.update({f"scores_{h}": self.scores[h] for h in HEADS})
+        if self.loc_head is not None:
+            out.update({n: getattr(self, n) for n in LOC_ARRAYS})
+            out.update(loc_cells=np.array(self.loc_cells, dtype=np.int32), loc_frame=np.array(self.loc_frame, dtype=np.int32),
+                       loc_head=np.array(self.loc_head), loc_frac=np.float64(self.loc_frac))
+            if self.loc_maps is not None:
+                out["loc_maps"] = self.loc_maps
         return out
 
     def save(self, stem: str, names: Optional[Sequence[str]] = None):
         """`<stem>.npz` with the arrays above (`scores_<head>` when kept) and `<stem>.csv`: a header and one line per (frame, rank),
-        `frame,rank,triplet,i,v,t,score[,name]`; names: 100 strings (`parse_names`)"""
+        `frame,rank,triplet,i,v,t,score[,name]`; names: 100 strings (`parse_names`).  With localisation also `<stem>.loc.csv`:
+        `frame,rank,triplet,column,peak_x,peak_y,x0,y0,x1,y1,area` in resized-frame pixels (`loc_pixels`), area in cells"""
         if names is not None and len(names) != len(_TRIPLETS):
             raise ValueError(f"names: {len(_TRIPLETS)} strings, one per triplet id; got {len(names)}")
         os.makedirs(os.path.dirname(os.path.abspath(stem)), exist_ok=True)
@@ -87,13 +133,26 @@ class Prediction:
                     i, v, t = (int(c) for c in self.topk_ivt[fi, r])
                     name = "" if names is None else ',"' + str(names[tid]).replace('"', '""') + '"'
                     f.write(f"{frame},{r},{tid},{i},{v},{t},{float(self.topk_scores[fi, r]):.6f}{name}\n")
+        if self.loc_head is not None:
+            peak, box = self.loc_pixels()
+            cols = self.loc_columns()
+            with open(stem + ".loc.csv", "w") as f:
+                f.write("frame,rank,triplet,column,peak_x,peak_y,x0,y0,x1,y1,area\n")
+                for fi, frame in enumerate(self.frames):
+                    for r in range(self.topk_ids.shape[1]):
+                        nums = ",".join(f"{float(v):.3f}" for v in (*peak[fi, r], *box[fi, r]))
+                        f.write(f"{frame},{r},{int(self.topk_ids[fi, r])},{int(cols[fi, r])},{nums},{int(self.loc_area[fi, r])}\n")
 
     @classmethod
     def load(cls, stem: str) -> "Prediction":
         with np.load(stem + ".npz") as z:
             scores = {h: z[f"scores_{h}"] for h in HEADS} if "scores_ivt" in z.files else None
+            loc = None
+            if "loc_head" in z.files:
+                loc = dict(peak=z["loc_peak"], box=z["loc_box"], area=z["loc_area"], range=z["loc_range"], cells=z["loc_cells"], frame=z["loc_frame"],
+                           head=str(z["loc_head"]), frac=float(z["loc_frac"]), maps=z["loc_maps"] if "loc_maps" in z.files else None)
             return cls([str(f) for f in z["frames"]], z["topk_ids"], z["topk_scores"], z["n_active"], (z["top_i_ids"], z["top_i_scores"]),
-                       (z["top_v_ids"], z["top_v_scores"]), (z["top_t_ids"], z["top_t_scores"]), float(z["threshold"]), scores)
+                       (z["top_v_ids"], z["top_v_scores"]), (z["top_t_ids"], z["top_t_scores"]), float(z["threshold"]), scores, loc)
 
 
 def segments(pred: Prediction, min_len: int = 1):
@@ -134,10 +193,20 @@ class Predictor:
     online_chunk N > 0: the latency mode -- the frames go N at a time through the student, `tenco_stream.TencoStream.push` (temporal must be a
     causal head) and the top-K decode, every answer computed from the frames seen so far; `chunk_latencies_ms` holds the last video's per-chunk
     times (frames on the device -> decoded rows on the device, one synchronise per chunk).  0: the whole-video pass.
-    online_streams S > 1 (with online_chunk): S videos at once through `tenco_stream.StreamBank`, see `predict_streams`."""
+    online_streams S > 1 (with online_chunk): S videos at once through `tenco_stream.StreamBank`, see `predict_streams`.
+    localize "i" | "ivt" (None: off, and then no launch, line or output byte differs): where in the frame each top-K triplet is.  The student's
+    heads are linear layers on the average of the layer4 map, so a column's class-activation map M_c = sum_k W[c, k] F[y, x, k] is exact
+    (mean(M_c) + b_c is the column's logit).  "ivt" maps each top-K triplet by its own column of the triplet head, "i" by the instrument-head
+    column of its instrument (`topk_ivt[..., 0]`).  In every mode each student pass calls `ops.class_maps` ONCE on that pass's layer4 map, for
+    all columns of the chosen head (6 or 100) -- the winners are only known after the decode, with a whole-video temporal head only after the
+    TCN -- and the map is released; peak, region (`localize_frac`: the region is the connected component of {M >= min + frac (max - min)} around
+    the peak) and range of ALL columns stay on the device, 10 words per frame and column, and the winners' rows are gathered with torch indexing
+    after `_decode` and join the one device-to-host copy.  localize_maps (--save_maps) keeps the dense maps too until the gather: T x ncol x h x w
+    x 4 bytes per video, 90 MB for 2000 frames of "ivt" at 8 x 14; without it the dense buffer is 8 MB for the same video."""
 
     def __init__(self, student, temporal=None, *, height: int = 256, width: int = 448, device_batch: int = 512, png_decode: str = "host",
-                 decode_workers: int = 8, topk: int = 5, threshold: float = 0.5, online_chunk: int = 0, online_streams: int = 1):
+                 decode_workers: int = 8, topk: int = 5, threshold: float = 0.5, online_chunk: int = 0, online_streams: int = 1,
+                 localize: Optional[str] = None, localize_frac: float = 0.5, localize_maps: bool = False):
         from . import ops
         if not 1 <= int(topk) <= ops.TOPK_MAX_K:
             raise ValueError(f"topk {topk}: 1..{ops.TOPK_MAX_K} (`mt4_topk_rows_f32` keeps a row's winners in one wave's lanes)")
@@ -145,6 +214,16 @@ class Predictor:
             raise ValueError(f"threshold {threshold}: a sigmoid score strictly between 0 and 1")
         if png_decode not in ("host", "device"):
             raise ValueError(f"png_decode {png_decode!r}: host | device")
+        if localize is not None and localize not in LOCALIZE_HEADS:
+            raise ValueError(f"localize {localize!r}: None | 'i' | 'ivt'")
+        if not 0.0 <= float(localize_frac) <= 1.0:
+            raise ValueError(f"localize_frac {localize_frac}: a fraction of the map's range, 0..1")
+        if localize_maps and localize is None:
+            raise ValueError("localize_maps needs localize 'i' or 'ivt'")
+        if localize is not None and localize not in getattr(student, "_head_slices", {}):
+            raise ValueError(f"localize {localize!r}: the student (loss_type {getattr(student, 'loss_type', None)!r}) has no {localize!r} head to map")
+        self.localize, self.localize_frac, self.localize_maps, self._loc_dense = localize, float(localize_frac), bool(localize_maps), None
+        self._loc_cells = None                                       # (h, w) of the layer4 grid, known after the first student pass
         self.student, self.temporal = student.eval(), temporal.eval() if temporal is not None else None
         self.height, self.width, self.device_batch = int(height), int(width), max(1, int(device_batch))
         self.png_decode, self.decode_workers = png_decode, int(decode_workers)
@@ -177,14 +256,39 @@ class Predictor:
         lb = (1023 // step + 1) * step if dev_dec else step
         spans = [(s, min(len(paths), s + lb)) for s in range(0, len(paths), lb)]
         load = lambda s, e: cholect.load_files_device(paths[s:e], self.height, self.width, workers=self.decode_workers, decode=self.png_decode)
-        feats, logits = [], [[], [], [], []]
+        feats, logits, locs = [], [[], [], [], []], []
         for span in extract.iter_chunks(spans, load, 2 if dev_dec else 1):
             for p0 in range(0, span.shape[0], step):
-                (_, li), (_, lv), (_, lt), (feat, livt) = self.student.extract_u8(span[p0:p0 + step])
+                ((_, li), (_, lv), (_, lt), (feat, livt)), loc = self._student_pass(span[p0:p0 + step])
                 feats.append(feat)
+                locs.append(loc)
                 for acc, lg in zip(logits, (li, lv, lt, livt)):
                     acc.append(lg)
+        # the dense localisation rows of the video, for the gather behind `_decode` (None without localize)
+        self._loc_dense = [torch.cat(c) for c in zip(*locs)] if self.localize else None
         return torch.cat(feats).float(), tuple(torch.cat(l).float() for l in logits)       # concatenated ON the device: [2000, 512] fp32 is 4 MB
+
+    def _student_pass(self, frames_u8):
+        """one student pass -> (the forward's tuple, None | [regions int32 [n, ncol, 8], range fp32 [n, ncol, 2][, maps fp32 [n, ncol, h, w]]] of
+        ALL columns of the localising head: ONE `ops.class_maps` launch on the pass's layer4 map, which is then released)"""
+        from . import ops
+        if self.localize is None:
+            return self.student.extract_u8(frames_u8), None
+        out, fmap = self.student.extract_u8(frames_u8, return_map=True)
+        lo, hi = self.student._head_slices[self.localize]
+        maps, regions, rng = ops.class_maps(fmap, self.student._p["heads.rows"], lo, hi - lo, self.localize_frac)
+        self._loc_cells = (int(fmap.shape[1]), int(fmap.shape[2]))
+        del fmap
+        return out, [regions, rng] + ([maps] if self.localize_maps else [])
+
+    def _gather_loc(self, ids, dense):
+        """top-K triplet ids int32 [n, k] + the dense rows of `_student_pass` -> the winners' rows [n, k, ...], on the device"""
+        import torch
+        cols = ids.long()
+        if self.localize == "i":
+            cols = torch.tensor([t[0] for t in _TRIPLETS], dtype=torch.long, device=ids.device)[cols]
+        rows = torch.arange(ids.shape[0], device=ids.device)[:, None]
+        return [d[rows, cols] for d in dense]
 
     def logits(self, paths: Sequence[str]):
         """{head -> fp32 [T, K] logits on the device, as VIEWS in the layout the model left them in}: the whole-video TCN on the student's
@@ -195,8 +299,9 @@ class Predictor:
         out, out_i, out_v, out_t, _, _ = self.temporal(feat.unsqueeze(0), False)
         return {h: lg[0][0].transpose(0, 1) for h, lg in (("ivt", out), ("i", out_i), ("v", out_v), ("t", out_t))}
 
-    def _decode(self, lg, keep_scores: bool):
-        """{head -> logits [n, K]} -> the device pieces of a `Prediction`: top-K ids, scores, counts, the component heads' picks[, score matrices]"""
+    def _decode(self, lg, keep_scores: bool, loc=None):
+        """{head -> logits [n, K]} -> the device pieces of a `Prediction`: top-K ids, scores, counts, the component heads' picks[, score matrices]
+        [, the winners' localisation rows out of `loc`, the dense rows of the same n frames]"""
         import torch
 
         from . import ops
@@ -208,6 +313,8 @@ class Predictor:
             parts += [hid, torch.sigmoid(hval)]
         if keep_scores:
             parts += [torch.sigmoid(lg[h]) for h in HEADS]
+        if loc is not None:
+            parts += self._gather_loc(ids, loc)
         return parts
 
     def _online_parts(self, paths: Sequence[str], keep_scores: bool):
@@ -225,8 +332,9 @@ class Predictor:
             fr = cholect.load_files_device(paths[s:s + self.online_chunk], self.height, self.width, workers=self.decode_workers, decode=self.png_decode)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            feat = self.student.extract_u8(fr)[3][0]
-            chunks.append(self._decode(self._stream.push(feat.float().contiguous()), keep_scores))
+            out, loc = self._student_pass(fr)
+            feat = out[3][0]
+            chunks.append(self._decode(self._stream.push(feat.float().contiguous()), keep_scores, loc))
             torch.cuda.synchronize()
             self.chunk_latencies_ms.append((time.perf_counter() - t0) * 1e3)
         return [torch.cat([c[j] for c in chunks]) for j in range(len(chunks[0]))]
@@ -260,8 +368,9 @@ class Predictor:
                                            decode=self.png_decode)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            feat = self.student.extract_u8(fr)[3][0]
-            parts = self._decode(bank.push_rows({s: len(take[s]) for s in slots}, feat.float().contiguous()), keep_scores)
+            out, loc = self._student_pass(fr)
+            feat = out[3][0]
+            parts = self._decode(bank.push_rows({s: len(take[s]) for s in slots}, feat.float().contiguous()), keep_scores, loc)
             torch.cuda.synchronize()
             ms = (time.perf_counter() - t0) * 1e3
             self.tick_latencies_ms.append(ms)
@@ -288,7 +397,8 @@ class Predictor:
         if self.online_chunk:
             parts = self._online_parts(paths, keep_scores)
         else:
-            parts = self._decode(self.logits(paths), keep_scores)
+            lg = self.logits(paths)
+            parts, self._loc_dense = self._decode(lg, keep_scores, self._loc_dense), None
         return self._to_prediction(paths, parts, keep_scores)
 
     def _to_prediction(self, paths: Sequence[str], parts, keep_scores: bool) -> Prediction:
@@ -303,5 +413,13 @@ class Predictor:
             at += p.numel()
         scores = dict(zip(HEADS, pieces[9:13])) if keep_scores else None
         flat1 = lambda a: a.reshape(n)
+        loc = None
+        if self.localize:
+            at = 13 if keep_scores else 9
+            reg, rng = pieces[at], pieces[at + 1]
+            maps = pieces[at + 2] if self.localize_maps else None
+            cells = self._loc_cells
+            loc = dict(peak=reg[..., 0:2], box=reg[..., 2:6], area=reg[..., 6], range=rng, cells=cells, frame=(self.height, self.width),
+                       head=self.localize, frac=self.localize_frac, maps=maps)
         return Prediction([os.path.basename(p) for p in paths], pieces[0], pieces[1], pieces[2], (flat1(pieces[3]), flat1(pieces[4])),
-                          (flat1(pieces[5]), flat1(pieces[6])), (flat1(pieces[7]), flat1(pieces[8])), self.threshold, scores)
+                          (flat1(pieces[5]), flat1(pieces[6])), (flat1(pieces[7]), flat1(pieces[8])), self.threshold, scores, loc)

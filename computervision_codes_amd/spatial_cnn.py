@@ -124,6 +124,7 @@ class VideoNas(StateModule):
         # the heads run as one fp32 GEMM (exact fp32 MFMA) through the 1x1 mode of the conv kernel
         p["heads.w"] = ops.pack_conv_weight(torch.cat(ws, 0).to(self.device)[:, :, None, None], None, torch.float32)
         p["heads.b"] = torch.cat(bs, 0).to(self.device).contiguous()
+        p["heads.rows"] = torch.cat(ws, 0).to(self.device).contiguous()      # fp32 row-major [sum of heads, C]: what `ops.class_maps` reads (`_head_slices`)
         if self.loss_type == "all":   # KD adaptors (`network.py:27-33`), fp32 like the heads
             for n in ("wi", "wv", "wt", "mi", "mv", "mt"):
                 p[n] = (ops.pack_linear_weight(self._sd[n + ".weight"].float().to(self.device), torch.float32), self._sd[n + ".bias"].float().to(self.device).contiguous())
@@ -210,7 +211,11 @@ class VideoNas(StateModule):
         (Running the HBM-bound head -- stem, max-pool, layer1[, layer2] -- in sub-batches of 64-167 frames so that producer ->
         consumer -> residual stays inside the 256 MB Infinity Cache was measured 4-15 % SLOWER at 1336 frames, twice; the whole
         batch goes through every layer.)"""
-        return ops.global_avgpool(self._layers(self._stem(xp, h, w), 1, 4))
+        return ops.global_avgpool(self.map_from_padded(xp, h, w))
+
+    def map_from_padded(self, xp: torch.Tensor, h: int, w: int) -> torch.Tensor:
+        """the layer4 map [B,h,w,C] in `self.dtype` that `trunk_from_padded` pools"""
+        return self._layers(self._stem(xp, h, w), 1, 4)
 
     def conv_plan(self, h: int, w: int):
         """Geometry of every conv launch of one forward, in launch order (algorithmic dims: the stem is the
@@ -329,22 +334,32 @@ class VideoNas(StateModule):
 
     __call__ = forward
 
-    def _trunk_u8(self, frames_u8: torch.Tensor) -> torch.Tensor:
+    def _map_u8(self, frames_u8: torch.Tensor) -> torch.Tensor:
+        """uint8 frames [B,H,W,3] -> the layer4 map [B,h,w,C] in `self.dtype` (pooling is the caller's last step)"""
         _, h, w, _ = frames_u8.shape
         if "stem_s2d" in self._p and h % 2 == 0 and w % 2 == 0:
             xs = ops.preprocess_u8_s2d(frames_u8, IMAGENET_MEAN, IMAGENET_STD)
             if self.fuse_stem_pool and ops.stem_maxpool_supported(h, w):   # conv1 / bn1 / relu / maxpool in one launch (bit-identical)
-                return ops.global_avgpool(self._layers(ops.stem_maxpool(xs, self._p["stem_s2d"], self._p["stem"][1]), 1, 4))
+                return self._layers(ops.stem_maxpool(xs, self._p["stem_s2d"], self._p["stem"][1]), 1, 4)
             y = ops.conv_nhwc(xs, self._p["stem_s2d"], self._p["stem"][1], kh=4, kw=1, relu=True, run_pixels=4, out_hw=(h // 2, w // 2))
-            return ops.global_avgpool(self._layers(ops.maxpool3x3s2(y), 1, 4))
-        return self.trunk_from_padded(ops.preprocess_u8(frames_u8, IMAGENET_MEAN, IMAGENET_STD, self.dtype), h, w)
+            return self._layers(ops.maxpool3x3s2(y), 1, 4)
+        return self.map_from_padded(ops.preprocess_u8(frames_u8, IMAGENET_MEAN, IMAGENET_STD, self.dtype), h, w)
 
-    def extract_u8(self, frames_u8: torch.Tensor, streams: int = 1):
+    def _trunk_u8(self, frames_u8: torch.Tensor) -> torch.Tensor:
+        return ops.global_avgpool(self._map_u8(frames_u8))
+
+    def extract_u8(self, frames_u8: torch.Tensor, streams: int = 1, return_map: bool = False):
         """Fused input path: uint8 frames [B,H,W,3] -> (ToTensor+Normalize on the GPU) -> forward.
+        return_map: -> (the forward's tuple, the layer4 map [B,h,w,C] in `self.dtype`): exactly the tensor that was pooled, for
+        `ops.class_maps` (the same launches as without it; single-stream only: the parts' maps are not joined).
         streams > 1: the batch is cut into that many contiguous parts which run on their own HIP streams -- frames are independent,
         and the HBM-bound layers of one part co-run with the MFMA-bound layers of another (+3 % frames/s with 2 parts of 1336 frames);
         the parts' results are byte-identical to the single-stream call."""
-        _, h, w, _ = frames_u8.shape
+        if return_map:
+            if streams > 1:
+                raise ValueError("extract_u8: return_map needs streams = 1 (the parts of a multi-stream pass keep their maps to themselves)")
+            fmap = self._map_u8(frames_u8)
+            return self._finish(ops.global_avgpool(fmap)), fmap
         if streams <= 1 or frames_u8.shape[0] < 2 * streams:
             return self._finish(self._trunk_u8(frames_u8))
         main = torch.cuda.current_stream()

@@ -904,6 +904,26 @@ int mt4_rank_hist_f32(const float* scores, const float* targets, int64_t rows, i
 int mt4_topk_rows_f32(const float* x, int64_t rows, int32_t cols, int64_t row_stride, int64_t col_stride, int32_t k, float count_above,
                       int32_t* ids, float* vals, int32_t* n_above, void* stream);
 
+/* Class-activation maps of the student's heads and the region around every map's peak.  The heads are nn.Linear layers on the global average of
+ * the layer4 map (Spatial_cnn/network.py:121-129), so mean_yx(maps[b, j]) + bias[col_lo + j] is column col_lo + j's logit; the reference pools
+ * the map and drops it (no counterpart of this call).
+ *   feat     [B][H][W][C] NHWC contiguous, dtype MT4_F32 or MT4_BF16 (bf16 is widened exactly)
+ *   w        float32 row-major [rows][C]; rows col_lo .. col_lo + ncol - 1 are used.  The bias is not added.
+ *   maps     float32 [B][ncol][H][W]: maps[b][j][y][x] = sum_k w[col_lo + j][k] feat[b][y][x][k], one fmaf chain over k = 0 .. C - 1 in ascending
+ *            order per element: the bits do not depend on B, b, ncol or col_lo
+ *   range    float32 [B][ncol][2]: minimum and maximum of the stored map (the element's bits; equal values: the lower y W + x supplies them)
+ *   regions  int32 [B][ncol][8]: peak_y, peak_x, y0, x0, y1, x1, area, 0.  The peak is the maximum under > on floats, equal values to the lower
+ *            y W + x.  tau = mn + frac (mx - mn), three separately rounded fp32 operations; S = {p : map[p] >= tau} plus the peak cell (at
+ *            frac = 1 the rounded tau can lie above the maximum); the region is the 4-connected component of S that holds the peak; y0, x0, y1,
+ *            x1 its inclusive bounding box in cells, area its cell count.
+ * A frame's map is read from HBM once per launch, for all columns (K-chunks staged through LDS); the region pass is a second kernel on the maps.
+ * B above 65535 is cut into several launches.  NaN / Inf in feat are OUTSIDE the numeric contract: nothing is written outside the three outputs,
+ * and the region growth runs at most H W sweeps.  Enqueue-only, capturable, no atomics on global memory: a repeated call gives the same bits.
+ * MT4_EINVAL: a NULL pointer, a dimension <= 0, col_lo < 0, frac outside [0, 1], a dtype that is neither code; MT4_EALIGN: feat or w off a 16-byte
+ * boundary, C % 8 != 0; MT4_EUNSUPPORTED: H W > 1024, ncol > 256, C > 8192 -- all before any launch: nothing is written. */
+int mt4_class_maps(const void* feat, int32_t dtype, const float* w, int32_t col_lo, int32_t ncol, int32_t B, int32_t H, int32_t W, int32_t C,
+                   float frac, float* maps, int32_t* regions, float* range, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Backward pieces of the Swin + Query2Label teacher (what torch autograd derives inside Spatial_transformer/run.py:150-229 for
  * Spatial_transformer/models/swin_transformer.py and models/transformer.py).  float32.  LayerNorm / GELU / softmax / batched-GEMM
