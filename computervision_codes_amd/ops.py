@@ -376,6 +376,26 @@ def tcn_layer(x: torch.Tensor, w_dilated: torch.Tensor, b_dilated: torch.Tensor,
 STREAM_MAX_CHUNK = 32       # frames per `tcn_stream_conv` launch (kStreamMaxChunk of csrc/tcn_stream_kernels.hip)
 
 
+def _stream_conv_operands(x, w_packed, bias, out, residual, rings, taps: int, lead: int, plain_rows: int, n_slots: int = 0):
+    """what `tcn_stream_conv` and `tcn_stream_conv_rows` ask of their common operands -> (cin, cout, the (pointer, ring rows) pairs of x, residual and
+    out as the library takes them).  rings: (x_ring, residual_ring, out_ring); a ring has `lead` dimensions ahead of [rows, C] (the first of
+    them n_slots long), a plain buffer is 2-D with >= plain_rows rows"""
+    assert w_packed.dim() == 2 and w_packed.is_contiguous() and w_packed.dtype == torch.float32
+    cin, cout = x.shape[-1], w_packed.shape[0]
+    assert w_packed.shape[1] == packed_k(cin, 1, taps, torch.float32)
+    pairs = []
+    for t, ring, c in zip((x, residual, out), rings, (cin, cout, cout)):
+        if t is None:
+            pairs += [None, 0]
+            continue
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.shape[-1] == c
+        assert (t.dim() == lead + 2 and (lead == 0 or t.shape[0] == n_slots)) if ring else (t.dim() == 2 and t.shape[0] >= plain_rows)
+        pairs += [t.data_ptr(), t.shape[-2] if ring else 0]
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == cout
+    return cin, cout, pairs
+
+
 def tcn_stream_conv(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, t0: torch.Tensor, *, n: int,
                     taps: int = 1, dilation: int = 1, residual: Optional[torch.Tensor] = None, relu: bool = False, x_ring: bool = True,
                     residual_ring: bool = True, out_ring: bool = True) -> torch.Tensor:
@@ -384,21 +404,10 @@ def tcn_stream_conv(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torc
     frame i.  t0: int64 [1] on the device, the frames pushed before this chunk (read only).  Tap k reads frame f - (taps - 1 - k) * dilation, zeros
     before frame 0.  Returns `out`."""
     _need_cuda(x, w_packed, bias, residual, out, t0)
-    for t in (x, w_packed, out, residual):
-        assert t is None or (t.dim() == 2 and t.is_contiguous() and t.dtype == torch.float32)
     assert t0.dtype == torch.int64 and t0.numel() == 1
-    cin, cout = x.shape[1], w_packed.shape[0]
-    assert w_packed.shape[1] == packed_k(cin, 1, taps, torch.float32) and out.shape[1] == cout
-    assert x_ring or x.shape[0] >= n
-    assert out_ring or out.shape[0] >= n
-    if residual is not None:
-        assert residual.shape[1] == cout and (residual_ring or residual.shape[0] >= n)
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.numel() == cout
-    check(lib.mt4_tcn_stream_conv_f32(x.data_ptr(), x.shape[0] if x_ring else 0, residual.data_ptr() if residual is not None else None,
-                                      residual.shape[0] if residual is not None and residual_ring else 0, out.data_ptr(),
-                                      out.shape[0] if out_ring else 0, w_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                      cin, cout, taps, dilation, 1 if relu else 0, n, t0.data_ptr(), _stream()), "mt4_tcn_stream_conv_f32")
+    cin, cout, pairs = _stream_conv_operands(x, w_packed, bias, out, residual, (x_ring, residual_ring, out_ring), taps, 0, n)
+    check(lib.mt4_tcn_stream_conv_f32(*pairs, w_packed.data_ptr(), bias.data_ptr() if bias is not None else None, cin, cout, taps, dilation,
+                                      1 if relu else 0, n, t0.data_ptr(), _stream()), "mt4_tcn_stream_conv_f32")
     return out
 
 
@@ -423,26 +432,14 @@ def tcn_stream_conv_rows(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional
     32; blocks behind n_rows return at once.  Returns `out`."""
     _need_cuda(x, w_packed, bias, residual, out, row_slot, row_idx, n_rows, counters)
     n_slots = counters.numel()
-    for t, ring in ((x, x_ring), (out, out_ring), (residual, residual_ring)):
-        if t is not None:
-            assert t.is_contiguous() and t.dtype == torch.float32
-            assert (t.dim() == 3 and t.shape[0] == n_slots) if ring else (t.dim() == 2 and t.shape[0] >= max_rows)
-    assert w_packed.dim() == 2 and w_packed.is_contiguous() and w_packed.dtype == torch.float32
     assert counters.dtype == torch.int64 and counters.is_contiguous()
     for t in (row_slot, row_idx, n_rows):
         assert t.dtype == torch.int32 and t.is_contiguous()
     assert row_slot.numel() >= max_rows and row_idx.numel() >= max_rows and n_rows.numel() == 1
-    cin, cout = x.shape[-1], w_packed.shape[0]
-    assert w_packed.shape[1] == packed_k(cin, 1, taps, torch.float32) and out.shape[-1] == cout
-    if residual is not None:
-        assert residual.shape[-1] == cout
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.numel() == cout
-    check(lib.mt4_tcn_stream_conv_rows_f32(x.data_ptr(), x.shape[1] if x_ring else 0, residual.data_ptr() if residual is not None else None,
-                                           residual.shape[1] if residual is not None and residual_ring else 0, out.data_ptr(),
-                                           out.shape[1] if out_ring else 0, w_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                           cin, cout, taps, dilation, 1 if relu else 0, n_slots, max_rows, row_slot.data_ptr(), row_idx.data_ptr(),
-                                           n_rows.data_ptr(), counters.data_ptr(), _stream()), "mt4_tcn_stream_conv_rows_f32")
+    cin, cout, pairs = _stream_conv_operands(x, w_packed, bias, out, residual, (x_ring, residual_ring, out_ring), taps, 1, max_rows, n_slots)
+    check(lib.mt4_tcn_stream_conv_rows_f32(*pairs, w_packed.data_ptr(), bias.data_ptr() if bias is not None else None, cin, cout, taps, dilation,
+                                           1 if relu else 0, n_slots, max_rows, row_slot.data_ptr(), row_idx.data_ptr(), n_rows.data_ptr(),
+                                           counters.data_ptr(), _stream()), "mt4_tcn_stream_conv_rows_f32")
     return out
 
 

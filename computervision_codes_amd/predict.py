@@ -317,26 +317,35 @@ class Predictor:
             parts += self._gather_loc(ids, loc)
         return parts
 
-    def _online_parts(self, paths: Sequence[str], keep_scores: bool):
-        """the frames in order, `online_chunk` at a time: student pass -> `TencoStream.push` -> decode of the chunk's rows; the pieces of the
-        chunks are joined on the device.  A frame's rows do not depend on the chunk size (the student's and the stream's results do not)."""
+    def _timed_tick(self, paths: Sequence[str], push, keep_scores: bool):
+        """one online tick: the frames of `paths` through ONE load, ONE student pass, `push(features fp32 [n, D])` (a `TencoStream.push` or a
+        `StreamBank.push_rows`) and ONE decode -> (the decoded pieces, the milliseconds from the loaded frames to the decoded rows, both ends
+        synchronised, and the number of frames)"""
         import time
 
         import torch
 
         from . import cholect
+        fr = cholect.load_files_device(paths, self.height, self.width, workers=self.decode_workers, decode=self.png_decode)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out, loc = self._student_pass(fr)
+        feat = out[3][0]
+        parts = self._decode(push(feat.float().contiguous()), keep_scores, loc)
+        torch.cuda.synchronize()
+        return parts, (time.perf_counter() - t0) * 1e3, fr.shape[0]
+
+    def _online_parts(self, paths: Sequence[str], keep_scores: bool):
+        """the frames in order, `online_chunk` at a time: student pass -> `TencoStream.push` -> decode of the chunk's rows; the pieces of the
+        chunks are joined on the device.  A frame's rows do not depend on the chunk size (the student's and the stream's results do not)."""
+        import torch
         self._stream.reset()
         self.chunk_latencies_ms = []
         chunks = []
         for s in range(0, len(paths), self.online_chunk):
-            fr = cholect.load_files_device(paths[s:s + self.online_chunk], self.height, self.width, workers=self.decode_workers, decode=self.png_decode)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out, loc = self._student_pass(fr)
-            feat = out[3][0]
-            chunks.append(self._decode(self._stream.push(feat.float().contiguous()), keep_scores, loc))
-            torch.cuda.synchronize()
-            self.chunk_latencies_ms.append((time.perf_counter() - t0) * 1e3)
+            parts, ms, _ = self._timed_tick(paths[s:s + self.online_chunk], self._stream.push, keep_scores)
+            chunks.append(parts)
+            self.chunk_latencies_ms.append(ms)
         return [torch.cat([c[j] for c in chunks]) for j in range(len(chunks[0]))]
 
     def predict_streams(self, videos: Sequence, keep_scores: bool = False):
@@ -348,8 +357,6 @@ class Predictor:
         import time
 
         import torch
-
-        from . import cholect
         if self._bank is None:
             raise ValueError("predict_streams: a Predictor built with online_streams > 1")
         waiting = [(name, list(paths)) for name, paths in videos]
@@ -364,17 +371,10 @@ class Predictor:
                 live[bank.open()] = [name, paths, 0, [], [], time.time()]
             slots = sorted(live)
             take = {s: live[s][1][live[s][2]:live[s][2] + self.online_chunk] for s in slots}
-            fr = cholect.load_files_device([p for s in slots for p in take[s]], self.height, self.width, workers=self.decode_workers,
-                                           decode=self.png_decode)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out, loc = self._student_pass(fr)
-            feat = out[3][0]
-            parts = self._decode(bank.push_rows({s: len(take[s]) for s in slots}, feat.float().contiguous()), keep_scores, loc)
-            torch.cuda.synchronize()
-            ms = (time.perf_counter() - t0) * 1e3
+            parts, ms, frames = self._timed_tick([p for s in slots for p in take[s]],
+                                                 lambda feat: bank.push_rows({s: len(take[s]) for s in slots}, feat), keep_scores)
             self.tick_latencies_ms.append(ms)
-            self.tick_frames.append(fr.shape[0])
+            self.tick_frames.append(frames)
             at = 0
             for s in slots:
                 v, n = live[s], len(take[s])

@@ -117,33 +117,64 @@ def _split_heads(model, y: torch.Tensor) -> Dict[str, torch.Tensor]:
     return {"ivt": y[:, :k0], "i": y[:, k0:k0 + k1], "v": y[:, k0 + k1:k0 + k1 + k2], "t": y[:, k0 + k1 + k2:k0 + k1 + k2 + k3]}
 
 
-class TencoStream:
-    """model: a loaded `temporal_tenco.VideoNas(causal=True)` with --fpn, fp32, not --hier.  use_graph: replay one hipGraph per chunk size."""
+class _StreamState:
+    """what a `TencoStream` and a `StreamBank` share: the buffers of a push -- `lead` is the shape ahead of a ring's [L, C], () or (capacity,), and
+    `rows` the rows of a plain buffer, MAX_CHUNK or MAX_CHUNK x capacity -- and the capture of its chain as a hipGraph.  A subclass supplies
+    `_chain(key, x)`, the launches of one push, and `_capture(key)` around `_capture_chain`."""
 
-    def __init__(self, model, use_graph: bool = True):
-        _require_streamable(model, "TencoStream")
+    def __init__(self, model, who: str, use_graph: bool, lead: Tuple[int, ...], rows: int):
+        _require_streamable(model, who)
         self.model, self.use_graph = model, bool(use_graph)
         dev, C = model.device, model.C
         self.stages = [("PG", model.num_layers_PG)] + [(f"Rs.{r}", model.num_layers_R) for r in range(model.num_R)]
         # one input ring per layer; rings[si][0] is stage si's input = level c_si of the FPN for si >= 1
-        self.rings = [[torch.zeros((ring_rows(2 ** i), C), device=dev) for i in range(n)] for _, n in self.stages]
-        self.counter = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.staging = torch.zeros((MAX_CHUNK, model.D), device=dev)
-        self.h = torch.zeros((MAX_CHUNK, C), device=dev)                 # a layer's hidden map (dilated conv + ReLU)
-        self.top = torch.zeros((MAX_CHUNK, C), device=dev)               # the last stage's output: p4
-        self.pl = [torch.zeros((MAX_CHUNK, C), device=dev) for _ in range(max(1, model.num_R))]   # p3, p2, p1
+        self.rings = [[torch.zeros(lead + (ring_rows(2 ** i), C), device=dev) for i in range(n)] for _, n in self.stages]
+        self.staging = torch.zeros((rows, model.D), device=dev)
+        self.h = torch.zeros((rows, C), device=dev)                      # a layer's hidden map (dilated conv + ReLU)
+        self.top = torch.zeros((rows, C), device=dev)                    # the last stage's output: p4
+        self.pl = [torch.zeros((rows, C), device=dev) for _ in range(max(1, model.num_R))]   # p3, p2, p1
         self.heads_w, self.heads_b = _heads_gemm(model)
-        self.logits = torch.zeros((MAX_CHUNK, self.heads_b.numel()), device=dev)
+        self.logits = torch.zeros((rows, self.heads_b.numel()), device=dev)
         self._graphs: Dict[int, "torch.cuda.CUDAGraph"] = {}
+
+    def ring_bytes(self) -> int:
+        """the rings' reservation (a bank's: capacity x a solo stream's)"""
+        return sum(r.numel() * 4 for st in self.rings for r in st)
+
+    def _graph(self, key: int) -> "torch.cuda.CUDAGraph":
+        g = self._graphs.get(key)
+        if g is None:
+            g = self._graphs[key] = self._capture(key)
+        return g
+
+    def _capture_chain(self, key: int) -> "torch.cuda.CUDAGraph":
+        """`_chain(key, staging)` as one hipGraph (the pattern of `graph.GraphedForward`; here the static input is the staging buffer itself and
+        the frame counters are graph state on the device, as {seed, step} is an input of `tenco_train`'s graphs).  The chain runs twice: the
+        warm-up and the capture"""
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):               # warm-up on a side stream (lazy module loading must not happen inside a capture)
+            self._chain(key, self.staging)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._chain(key, self.staging)
+        return g
+
+
+class TencoStream(_StreamState):
+    """model: a loaded `temporal_tenco.VideoNas(causal=True)` with --fpn, fp32, not --hier.  use_graph: replay one hipGraph per chunk size."""
+
+    def __init__(self, model, use_graph: bool = True):
+        super().__init__(model, "TencoStream", use_graph, (), MAX_CHUNK)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=model.device)
         self._seen = 0
 
     # ------------------------------------------------------------------ state
     @property
     def frames_seen(self) -> int:
         return self._seen
-
-    def ring_bytes(self) -> int:
-        return sum(r.numel() * 4 for st in self.rings for r in st)
 
     def reset(self) -> None:
         """a new video: the counter back to 0 -- whatever the rings hold lies behind frame 0 and is never read"""
@@ -159,20 +190,10 @@ class TencoStream:
         return self.logits
 
     def _capture(self, n: int) -> "torch.cuda.CUDAGraph":
-        """the chain of a chunk of n frames as one hipGraph (the pattern of `graph.GraphedForward`; here the static input is the staging buffer
-        itself and the frame counter is graph state on the device, as {seed, step} is an input of `tenco_train`'s graphs).  The warm-up run
-        advances the counter, which is put back behind it; the rows it wrote belong to frames >= the counter, and the replay rewrites them
-        before anything reads them."""
+        """the chain of a chunk of n frames as one hipGraph.  The warm-up run advances the counter, which is put back behind it; the rows it
+        wrote belong to frames >= the counter, and the replay rewrites them before anything reads them."""
         keep = self.counter.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):               # warm-up on a side stream (lazy module loading must not happen inside a capture)
-            self._chain(n, self.staging)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._chain(n, self.staging)
+        g = self._capture_chain(n)
         self.counter.copy_(keep)
         return g
 
@@ -186,37 +207,25 @@ class TencoStream:
         if not self.use_graph:
             out = self._chain(n, self.staging)
         else:
-            g = self._graphs.get(n)
-            if g is None:
-                g = self._graphs[n] = self._capture(n)
-            g.replay()
+            self._graph(n).replay()
             out = self.logits
         self._seen += n
         return _split_heads(self.model, out[:n].clone())
 
 
-class StreamBank:
+class StreamBank(_StreamState):
     """`capacity` (1..64) causal streams side by side, pushed together: model as for `TencoStream`.  `open()` hands out a slot, `push({slot:
     features[n_s, D]})` answers the n_s newest frames of every slot given, `close(slot)` frees it.  use_graph: replay one hipGraph per number of
     32-row blocks (the row count inside the last block is a device word, so differing per-stream counts share a graph)."""
 
     def __init__(self, model, capacity: int, use_graph: bool = True):
-        _require_streamable(model, "StreamBank")
         if not 1 <= int(capacity) <= MAX_STREAMS:
             raise ValueError(f"StreamBank: capacity {capacity}; 1..{MAX_STREAMS} streams")
-        self.model, self.capacity, self.use_graph = model, int(capacity), bool(use_graph)
-        dev, C, cap = model.device, model.C, self.capacity
+        self.capacity = cap = int(capacity)
         rows = MAX_CHUNK * cap
-        self.stages = [("PG", model.num_layers_PG)] + [(f"Rs.{r}", model.num_layers_R) for r in range(model.num_R)]
-        # as TencoStream's, one slice per slot
-        self.rings = [[torch.zeros((cap, ring_rows(2 ** i), C), device=dev) for i in range(n)] for _, n in self.stages]
+        super().__init__(model, "StreamBank", use_graph, (cap,), rows)       # TencoStream's buffers, one ring slice per slot
+        dev = model.device
         self.counters = torch.zeros(cap, dtype=torch.int64, device=dev)
-        self.staging = torch.zeros((rows, model.D), device=dev)
-        self.h = torch.zeros((rows, C), device=dev)
-        self.top = torch.zeros((rows, C), device=dev)
-        self.pl = [torch.zeros((rows, C), device=dev) for _ in range(max(1, model.num_R))]
-        self.heads_w, self.heads_b = _heads_gemm(model)
-        self.logits = torch.zeros((rows, self.heads_b.numel()), device=dev)
         # the tables of a push, one buffer on either side: [n_rows, n_push, 0, 0 | push_slot | push_count | row_slot | row_idx]
         self._host = torch.zeros(4 + 2 * cap + 2 * rows, dtype=torch.int32).pin_memory()
         self._host_np = self._host.numpy()                               # (the same pinned bytes)
@@ -226,14 +235,9 @@ class StreamBank:
         self._push_slot, self._push_count, self._row_slot, self._row_idx = (self._dev[a:b] for a, b in zip(at[:-1], at[1:]))
         self._at = at
         self._uploaded = torch.cuda.Event()
-        self._graphs: Dict[int, "torch.cuda.CUDAGraph"] = {}
         self._seen: List[int] = [-1] * cap                               # frames pushed per slot; -1: the slot is free
 
     # ------------------------------------------------------------------ state
-    def ring_bytes(self) -> int:
-        """the reservation: capacity x `TencoStream.ring_bytes()`"""
-        return sum(r.numel() * 4 for st in self.rings for r in st)
-
     def open(self) -> int:
         """the lowest free slot, its counter at 0 -- whatever its rings hold lies behind frame 0 and is never read"""
         free = [s for s, n in enumerate(self._seen) if n < 0]
@@ -267,16 +271,7 @@ class StreamBank:
         """as `TencoStream._capture`, with the device row count and push count at 0 for the warm-up: every workgroup returns and no counter
         moves, so nothing has to be put back"""
         self._dev[0:2].zero_()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._chain(max_rows, self.staging)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._chain(max_rows, self.staging)
-        return g
+        return self._capture_chain(max_rows)
 
     def push_rows(self, counts: Dict[int, int], features: torch.Tensor) -> Dict[str, torch.Tensor]:
         """`push` for features that already lie in one tensor: features fp32 [sum of counts, D], the streams in ascending slot order, each
@@ -287,11 +282,7 @@ class StreamBank:
         n = len(row_slot)
         assert features.shape == (n, self.model.D) and features.dtype == torch.float32 and features.is_cuda
         max_rows = (n + MAX_CHUNK - 1) // MAX_CHUNK * MAX_CHUNK
-        g = None
-        if self.use_graph:
-            g = self._graphs.get(max_rows)
-            if g is None:
-                g = self._graphs[max_rows] = self._capture(max_rows)
+        g = self._graph(max_rows) if self.use_graph else None
         self._uploaded.synchronize()                                     # the last push's upload has left the pinned buffer
         h, at = self._host_np, self._at
         h[0], h[1] = n, len(push_slot)

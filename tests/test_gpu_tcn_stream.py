@@ -28,7 +28,7 @@ def test_stream_conv_against_float64(cuda, cin, cout, plain_out, taps):
     w64 = w.double()
     worst = 0.0
     for d in (1, 4, 16):
-        for n in (1, 5, 32):
+        for n in (1, 5, 16, 17, 32):                                                    # 16 | 17: either side of the second 16-row tile
             for t0 in (0, d - 1, 2 * d, L - 3, 3 * L + 7):
                 lo = t0 - (taps - 1) * d                                               # oldest frame a tap can ask for (negative: padding)
                 frames = torch.randn((t0 + n - lo, cin), generator=g)                  # frames lo .. t0 + n - 1

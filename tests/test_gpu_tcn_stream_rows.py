@@ -3,7 +3,7 @@ stream on the same device buffers: every pushed row equal TO THE BIT (`bf16_boun
 test_gpu_tcn_stream.py), no other row written, no operand changed.  Three streams in slots 0, 1 and 3 of four (slot 2 stays idle), rings of 64
 rows filled with NaN outside the rows a correct kernel reads -- all of the idle slot's and of a stream that brings no frame.  Row totals on both
 sides of the 16-row tile and the 32-row block; counters at 0, inside the front padding, just behind it, at a wrapping write and three wraps on,
-mixed inside one launch."""
+mixed inside one launch.  Both entry points run one kernel body, so one table is also held to float64 directly, from the fp32 operands alone."""
 import pytest
 import torch
 
@@ -121,6 +121,68 @@ def test_device_row_count_below_the_launch(cuda, cin, cout, plain, valid):
     """a table of 96 rows (three blocks) of which the device word admits 38 (the second block ends after six rows, the third returns) or 1"""
     g, wp, bias = _weights(cuda, cin, cout, 3)
     _case(cuda, g, wp, bias, cin, cout, plain, 3, 4, dict(zip(SLOTS, COUNTS[96])), dict(zip(SLOTS, _mixes(4)[0])), valid=valid)
+
+
+def test_rows_launch_against_float64(cuda):
+    """the table form itself per element against float64 on the same fp32 operands, as test_gpu_tcn_stream.py holds the solo form (the two
+    share one kernel body, so the bit comparisons above say nothing about that body): 64 -> 64, rings, three taps, d = 4, the 38-row table --
+    3 rows inside the front padding, 32 that cross the tile edge, the block edge and a wrapping write, 3 three wraps on"""
+    cin = cout = 64
+    taps, d = 3, 4
+    g = torch.Generator().manual_seed(1938)
+    w = torch.randn((cout, cin, taps), generator=g) / (cin * taps) ** 0.5
+    bias = torch.randn(cout, generator=g)
+    wp = ops.pack_conv_weight(w.to(cuda)[:, :, None, :], None, torch.float32)
+    w64 = w.double()
+    counts = {s: n for s, n in zip(SLOTS, COUNTS[38]) if n}
+    t0s = dict(zip(SLOTS, _mixes(d)[0]))
+    row_slot, row_idx, _, _ = row_table(counts, NS)
+    total = len(row_slot)
+    max_rows = (total + BLOCK - 1) // BLOCK * BLOCK
+    assert total == 38 and max_rows == 64
+    xb = torch.full((NS, L, cin), NAN)                                                     # a read of any row but the right ones poisons the result
+    rb = torch.full((NS, L, cout), NAN)
+    pushed = torch.zeros((NS, L), dtype=torch.bool)
+    prod = torch.zeros((NS, L, cout), dtype=torch.float64)                                 # at the ring rows the launch writes
+    acc = torch.zeros((NS, L, cout), dtype=torch.float64)
+    for s, n in counts.items():
+        t0, lo = t0s[s], t0s[s] - (taps - 1) * d
+        frames = torch.randn((t0 + n - lo, cin), generator=g)                              # frames lo .. t0 + n - 1 (negative: padding, never stored)
+        for f in range(max(lo, 0), t0 + n):
+            xb[s, f % L] = frames[f - lo]
+        for i in range(n):
+            row = (t0 + i) % L
+            pushed[s, row] = True
+            rb[s, row] = torch.randn(cout, generator=g)
+            for k in range(taps):
+                f = t0 + i - (taps - 1 - k) * d
+                if f >= 0:
+                    prod[s, row] += w64[:, :, k] @ frames[f - lo].double()
+                    acc[s, row] += w64[:, :, k].abs() @ frames[f - lo].double().abs()
+    assert int(pushed.sum()) == total
+    counters = torch.full((NS,), 5, dtype=torch.int64)
+    for s, t0 in t0s.items():
+        counters[s] = t0
+    xd, rd, cd, bd = xb.to(cuda), rb.to(cuda), counters.to(cuda), bias.to(cuda)
+    rs, ri = (torch.tensor(t + [0] * (max_rows - total), dtype=torch.int32, device=cuda) for t in (row_slot, row_idx))
+    nr = torch.tensor([total], dtype=torch.int32, device=cuda)
+    res64 = rb[pushed].double()
+    worst = 0.0
+    for with_res in (False, True):
+        for relu in (False, True):
+            what = f"rows conv against float64 {cin}->{cout} taps {taps} d {d} counts {counts} t0 {t0s} res {with_res} relu {relu}"
+            out = torch.full((NS, L, cout), 7.0, device=cuda)
+            ops.tcn_stream_conv_rows(xd, wp, bd, out, rs, ri, nr, cd, max_rows=max_rows, taps=taps, dilation=d, residual=rd if with_res else None,
+                                     relu=relu)
+            ref = prod[pushed] + bias.double() + (res64 if with_res else 0.0)
+            a64 = acc[pushed] + bias.double().abs() + (res64.abs() if with_res else 0.0)
+            if relu:
+                ref = ref.clamp_min(0.0)
+            got = out.cpu()
+            st = bb.check_f32(got[pushed], ref, acc64=a64, k=taps * cin, what=what)
+            worst = max(worst, st["worst_ratio"])
+            assert bool((got[~pushed] == 7.0).all()), what + ": a row outside the pushed ones was written"
+    print(f"worst error / bound: {worst:.3f}")
 
 
 def test_advance_rows_adds_each_count_to_its_slot(cuda):
