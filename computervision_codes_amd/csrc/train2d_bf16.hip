@@ -5,6 +5,7 @@
 //   * train-mode BatchNorm forward / backward with bf16 tensors (the stem keeps an fp32 convolution output: its 7x7x3 geometry runs in fp32),
 //   * pooling backward with bf16 gradients, and the fp32 -> bf16 copy of a packed weight matrix.
 #include "mt4_common.h"
+#include "det_parts.h"
 
 namespace {
 
@@ -660,8 +661,7 @@ __global__ __launch_bounds__(256) void refresh_weights_kernel(const mt4_refresh_
 extern "C" int mt4_refresh_weights(const mt4_refresh_entry* table_dev, int32_t n_entries, int64_t n_blocks, void* stream) {
     mt4_clear_error();
     if (!table_dev || n_entries <= 0 || n_blocks <= 0 || n_blocks > 0x7fffffffLL) return MT4_EINVAL;
-    hipLaunchKernelGGL(refresh_weights_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table_dev, n_entries);
-    return mt4_check_launch();
+    return mt4_launch<refresh_weights_kernel>(dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table_dev, n_entries);
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
@@ -673,21 +673,20 @@ static int bn_stats_t(const void* x, int32_t x_dtype, double* sums, float* mean,
     if (C % 4 || (det && ((uintptr_t)ws & 15))) return MT4_EALIGN;
     if (x_dtype != MT4_BF16 && x_dtype != MT4_F32) return MT4_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    const int slabs = bn_reduce_slabs(M, C);
-    if (det && ws_bytes < (long long)slabs * 2 * C * (long long)sizeof(double)) return MT4_EINVAL;
-    const dim3 grid(cdiv(C, 64), slabs);
-    if (det) {
-        if (x_dtype == MT4_BF16) hipLaunchKernelGGL((bn_stats_t_kernel<u16, true>), grid, dim3(1024), 0, s, (const u16*)x, ws, (long long)M, C);
-        else hipLaunchKernelGGL((bn_stats_t_kernel<float, true>), grid, dim3(1024), 0, s, (const float*)x, ws, (long long)M, C);
-        const int lc = mt4_check_launch();
-        if (lc != MT4_OK) return lc;
-        const int fc = mt4_fold_parts_chunked_f64(ws, slabs, 2LL * C, 2LL * C, sums, 0, stream);
-        if (fc != MT4_OK) return fc;
-    } else if (x_dtype == MT4_BF16) hipLaunchKernelGGL((bn_stats_t_kernel<u16, false>), grid, dim3(1024), 0, s, (const u16*)x, sums, (long long)M, C);
-    else hipLaunchKernelGGL((bn_stats_t_kernel<float, false>), grid, dim3(1024), 0, s, (const float*)x, sums, (long long)M, C);
-    hipLaunchKernelGGL(bn_finalize_t_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, sums, mean, invstd, running_mean, running_var, (long long)M, C, momentum,
-                       eps);
-    return mt4_check_launch();
+    const DetParts p = bn_parts(M, C);
+    if (det && ws_bytes < p.bytes()) return MT4_EINVAL;
+    const dim3 grid(cdiv(C, 64), p.nparts);
+    double* dst = det ? ws : sums;
+    int rc;
+    if (x_dtype == MT4_BF16)
+        rc = det ? mt4_launch<bn_stats_t_kernel<u16, true>>(grid, dim3(1024), 0, s, (const u16*)x, dst, (long long)M, C)
+                 : mt4_launch<bn_stats_t_kernel<u16, false>>(grid, dim3(1024), 0, s, (const u16*)x, dst, (long long)M, C);
+    else
+        rc = det ? mt4_launch<bn_stats_t_kernel<float, true>>(grid, dim3(1024), 0, s, (const float*)x, dst, (long long)M, C)
+                 : mt4_launch<bn_stats_t_kernel<float, false>>(grid, dim3(1024), 0, s, (const float*)x, dst, (long long)M, C);
+    if (rc == MT4_OK && det) rc = mt4_fold_parts_chunked_f64(ws, p.nparts, p.part_elems, p.part_elems, sums, 0, stream);
+    if (rc != MT4_OK) return rc;
+    return mt4_launch<bn_finalize_t_kernel>(dim3(cdiv(C, 256)), dim3(256), 0, s, sums, mean, invstd, running_mean, running_var, (long long)M, C, momentum, eps);
 }
 
 extern "C" int mt4_bn_stats_t(const void* x, int32_t x_dtype, double* sums_zeroed, float* mean, float* invstd, float* running_mean, float* running_var,
@@ -708,13 +707,12 @@ extern "C" int mt4_bn_apply_t(const void* x, int32_t x_dtype, const float* mean,
     const dim3 grid(cdiv(C, 64), bn_row_slabs(M, C));
     hipStream_t s = (hipStream_t)stream;
     if (x_dtype == MT4_BF16)
-        hipLaunchKernelGGL((bn_apply_t_kernel<u16, false>), grid, dim3(256), 0, s, (const u16*)x, (float*)mean, (float*)invstd, gamma, beta, (const u16*)residual_bf16,
-                           (u16*)y_bf16, (long long)M, C, relu, (const double*)nullptr, (float*)nullptr, (float*)nullptr, 0.f, 0.f);
-    else if (x_dtype == MT4_F32)
-        hipLaunchKernelGGL((bn_apply_t_kernel<float, false>), grid, dim3(256), 0, s, (const float*)x, (float*)mean, (float*)invstd, gamma, beta,
-                           (const u16*)residual_bf16, (u16*)y_bf16, (long long)M, C, relu, (const double*)nullptr, (float*)nullptr, (float*)nullptr, 0.f, 0.f);
-    else return MT4_EUNSUPPORTED;
-    return mt4_check_launch();
+        return mt4_launch<bn_apply_t_kernel<u16, false>>(grid, dim3(256), 0, s, (const u16*)x, (float*)mean, (float*)invstd, gamma, beta, (const u16*)residual_bf16,
+                                                         (u16*)y_bf16, (long long)M, C, relu, (const double*)nullptr, (float*)nullptr, (float*)nullptr, 0.f, 0.f);
+    if (x_dtype == MT4_F32)
+        return mt4_launch<bn_apply_t_kernel<float, false>>(grid, dim3(256), 0, s, (const float*)x, (float*)mean, (float*)invstd, gamma, beta, (const u16*)residual_bf16,
+                                                           (u16*)y_bf16, (long long)M, C, relu, (const double*)nullptr, (float*)nullptr, (float*)nullptr, 0.f, 0.f);
+    return MT4_EUNSUPPORTED;
 }
 
 extern "C" int mt4_bn_apply_sums_t(const void* x, int32_t x_dtype, const double* stat_sums, float* mean, float* invstd, float* running_mean, float* running_var,
@@ -726,13 +724,12 @@ extern "C" int mt4_bn_apply_sums_t(const void* x, int32_t x_dtype, const double*
     const dim3 grid(cdiv(C, 64), bn_row_slabs(M, C));
     hipStream_t s = (hipStream_t)stream;
     if (x_dtype == MT4_BF16)
-        hipLaunchKernelGGL((bn_apply_t_kernel<u16, true>), grid, dim3(256), 0, s, (const u16*)x, mean, invstd, gamma, beta, (const u16*)residual_bf16, (u16*)y_bf16,
-                           (long long)M, C, relu, stat_sums, running_mean, running_var, momentum, eps);
-    else if (x_dtype == MT4_F32)
-        hipLaunchKernelGGL((bn_apply_t_kernel<float, true>), grid, dim3(256), 0, s, (const float*)x, mean, invstd, gamma, beta, (const u16*)residual_bf16,
-                           (u16*)y_bf16, (long long)M, C, relu, stat_sums, running_mean, running_var, momentum, eps);
-    else return MT4_EUNSUPPORTED;
-    return mt4_check_launch();
+        return mt4_launch<bn_apply_t_kernel<u16, true>>(grid, dim3(256), 0, s, (const u16*)x, mean, invstd, gamma, beta, (const u16*)residual_bf16, (u16*)y_bf16,
+                                                        (long long)M, C, relu, stat_sums, running_mean, running_var, momentum, eps);
+    if (x_dtype == MT4_F32)
+        return mt4_launch<bn_apply_t_kernel<float, true>>(grid, dim3(256), 0, s, (const float*)x, mean, invstd, gamma, beta, (const u16*)residual_bf16, (u16*)y_bf16,
+                                                          (long long)M, C, relu, stat_sums, running_mean, running_var, momentum, eps);
+    return MT4_EUNSUPPORTED;
 }
 
 static int bn_backward_t(const void* dy_bf16, const void* y_post_bf16, const void* x, int32_t x_dtype, const float* mean, const float* invstd,
@@ -744,31 +741,25 @@ static int bn_backward_t(const void* dy_bf16, const void* y_post_bf16, const voi
     if (C % 4 || (det && ((uintptr_t)ws & 15))) return MT4_EALIGN;
     if (x_dtype != MT4_BF16 && x_dtype != MT4_F32) return MT4_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    const int slabs = bn_reduce_slabs(M, C);
-    if (det && ws_bytes < (long long)slabs * 2 * C * (long long)sizeof(double)) return MT4_EINVAL;
-    const dim3 g1(cdiv(C, 64), slabs), g2(cdiv(C, 64), bn_row_slabs(M, C));
+    const DetParts p = bn_parts(M, C);
+    if (det && ws_bytes < p.bytes()) return MT4_EINVAL;
+    const dim3 g1(cdiv(C, 64), p.nparts), g2(cdiv(C, 64), bn_row_slabs(M, C));
     const u16 *dy = (const u16*)dy_bf16, *yp = (const u16*)y_post_bf16;
-    if (det) {
-        if (x_dtype == MT4_BF16)
-            hipLaunchKernelGGL((bn_bwd_reduce_t_kernel<u16, true>), g1, dim3(1024), 0, s, dy, yp, (const u16*)x, mean, invstd, gamma, beta, ws, (long long)M, C, relu);
-        else
-            hipLaunchKernelGGL((bn_bwd_reduce_t_kernel<float, true>), g1, dim3(1024), 0, s, dy, yp, (const float*)x, mean, invstd, gamma, beta, ws, (long long)M, C, relu);
-        const int lc = mt4_check_launch();
-        if (lc != MT4_OK) return lc;
-        const int fc = mt4_fold_parts_chunked_f64(ws, slabs, 2LL * C, 2LL * C, sums, 0, stream);
-        if (fc != MT4_OK) return fc;
-    } else if (x_dtype == MT4_BF16) {
-        hipLaunchKernelGGL((bn_bwd_reduce_t_kernel<u16, false>), g1, dim3(1024), 0, s, dy, yp, (const u16*)x, mean, invstd, gamma, beta, sums, (long long)M, C, relu);
-    } else {
-        hipLaunchKernelGGL((bn_bwd_reduce_t_kernel<float, false>), g1, dim3(1024), 0, s, dy, yp, (const float*)x, mean, invstd, gamma, beta, sums, (long long)M, C, relu);
-    }
+    double* dst = det ? ws : sums;
+    int rc;
     if (x_dtype == MT4_BF16)
-        hipLaunchKernelGGL(bn_bwd_apply_t_kernel<u16>, g2, dim3(256), 0, s, dy, yp, (const u16*)x, mean, invstd, gamma, beta, sums, (u16*)dx, (u16*)dres_bf16, dgamma,
-                           dbeta, (long long)M, C, relu);
+        rc = det ? mt4_launch<bn_bwd_reduce_t_kernel<u16, true>>(g1, dim3(1024), 0, s, dy, yp, (const u16*)x, mean, invstd, gamma, beta, dst, (long long)M, C, relu)
+                 : mt4_launch<bn_bwd_reduce_t_kernel<u16, false>>(g1, dim3(1024), 0, s, dy, yp, (const u16*)x, mean, invstd, gamma, beta, dst, (long long)M, C, relu);
     else
-        hipLaunchKernelGGL(bn_bwd_apply_t_kernel<float>, g2, dim3(256), 0, s, dy, yp, (const float*)x, mean, invstd, gamma, beta, sums, (float*)dx, (u16*)dres_bf16,
-                           dgamma, dbeta, (long long)M, C, relu);
-    return mt4_check_launch();
+        rc = det ? mt4_launch<bn_bwd_reduce_t_kernel<float, true>>(g1, dim3(1024), 0, s, dy, yp, (const float*)x, mean, invstd, gamma, beta, dst, (long long)M, C, relu)
+                 : mt4_launch<bn_bwd_reduce_t_kernel<float, false>>(g1, dim3(1024), 0, s, dy, yp, (const float*)x, mean, invstd, gamma, beta, dst, (long long)M, C, relu);
+    if (rc == MT4_OK && det) rc = mt4_fold_parts_chunked_f64(ws, p.nparts, p.part_elems, p.part_elems, sums, 0, stream);
+    if (rc != MT4_OK) return rc;
+    if (x_dtype == MT4_BF16)
+        return mt4_launch<bn_bwd_apply_t_kernel<u16>>(g2, dim3(256), 0, s, dy, yp, (const u16*)x, mean, invstd, gamma, beta, sums, (u16*)dx, (u16*)dres_bf16, dgamma,
+                                                      dbeta, (long long)M, C, relu);
+    return mt4_launch<bn_bwd_apply_t_kernel<float>>(g2, dim3(256), 0, s, dy, yp, (const float*)x, mean, invstd, gamma, beta, sums, (float*)dx, (u16*)dres_bf16, dgamma,
+                                                    dbeta, (long long)M, C, relu);
 }
 
 extern "C" int mt4_bn_backward_t(const void* dy_bf16, const void* y_post_bf16, const void* x, int32_t x_dtype, const float* mean, const float* invstd,
@@ -811,20 +802,21 @@ static int wgrad_bf16_dispatch(WgK a, int K, int stride, hipStream_t s, bool lau
     }
 }
 
-extern "C" int mt4_wgrad_conv2d_bf16(const void* dy, const void* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo,
-                                     int32_t Cout, int32_t K, int32_t stride, void* stream) {
-    mt4_clear_error();
-    if (!dy || !x || !dw_packed || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) return MT4_EINVAL;
-    if ((K != 1 && K != 3) || (stride != 1 && stride != 2)) return MT4_EUNSUPPORTED;
-    if ((Cin % 8) || (Cout % 8)) return MT4_EALIGN;
-    if (Ho != (H + 2 * (K / 2) - K) / stride + 1 || Wo != (W + 2 * (K / 2) - K) / stride + 1) return MT4_EINVAL;
-    if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dw_packed) & 15) return MT4_EALIGN;
+static WgK wgrad_bf16_args(const void* dy, const void* x, float* dw, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo, int32_t Cout, int32_t K) {
     WgK a;
-    a.dy = (const u16*)dy; a.x = (const u16*)x; a.dw = dw_packed;
+    a.dy = (const u16*)dy; a.x = (const u16*)x; a.dw = dw;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
     a.kpad = (int)mt4_conv_packed_k(Cin, K, K, MT4_F32);
     a.tapw = (Cin + 3) / 4 * 4;
-    return wgrad_bf16_dispatch<false>(a, K, stride, (hipStream_t)stream, true, nullptr, nullptr);
+    return a;
+}
+
+// the parts of a shape: the dispatch's own form and split, nothing launched; a part is an image of the packed dW
+static int wgrad_bf16_parts(const WgK& a, int K, int stride, DetParts* p) {
+    int f = 0, ns = 0;
+    const int rc = wgrad_bf16_dispatch<true>(a, K, stride, nullptr, false, &f, &ns);
+    *p = {f, ns, (long long)a.Cout * a.kpad, (int32_t)sizeof(float)};
+    return rc;
 }
 
 extern "C" int mt4_wgrad_conv2d_bf16_det_plan(int32_t B, int32_t Ho, int32_t Wo, int32_t Cout, int32_t Cin, int32_t K, int32_t stride, int32_t* form,
@@ -832,44 +824,40 @@ extern "C" int mt4_wgrad_conv2d_bf16_det_plan(int32_t B, int32_t Ho, int32_t Wo,
     if (B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0) return MT4_EINVAL;
     if ((K != 1 && K != 3) || (stride != 1 && stride != 2)) return MT4_EUNSUPPORTED;
     if ((Cin % 8) || (Cout % 8)) return MT4_EALIGN;
-    WgK a;
-    a.dy = nullptr; a.x = nullptr; a.dw = nullptr;
-    a.B = B; a.H = 0; a.W = 0; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;         // (the form and the split depend on the output pixels and the channels alone)
-    a.kpad = (int)mt4_conv_packed_k(Cin, K, K, MT4_F32);
-    a.tapw = (Cin + 3) / 4 * 4;
-    int f = 0, ns = 0;
-    const int rc = wgrad_bf16_dispatch<true>(a, K, stride, nullptr, false, &f, &ns);
-    if (rc != MT4_OK) return rc;
-    if (form) *form = f;
-    if (nparts) *nparts = ns;
-    if (part_elems) *part_elems = (long long)Cout * a.kpad;
-    if (ws_bytes) *ws_bytes = (long long)ns * Cout * a.kpad * (long long)sizeof(float);
-    return MT4_OK;
+    DetParts p;       // (the form and the split depend on the output pixels and the channels alone)
+    const int rc = wgrad_bf16_parts(wgrad_bf16_args(nullptr, nullptr, nullptr, B, 0, 0, Cin, Ho, Wo, Cout, K), K, stride, &p);
+    return rc != MT4_OK ? rc : det_plan_out(p, form, nparts, part_elems, ws_bytes);
 }
 
 // fold order (the contract): parts z = 0 .. nparts-1 (split z holds the spatial tiles t of TH x 16 output pixels with t % nparts == z, added in ascending t)
 // front to back; the sum is then ADDED to dw_packed (accumulate != 0) or stored
-extern "C" int mt4_wgrad_conv2d_det_bf16(const void* dy, const void* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo,
-                                         int32_t Cout, int32_t K, int32_t stride, int32_t accumulate, float* ws, int64_t ws_bytes, void* stream) {
+static int wgrad_conv2d_bf16_impl(const void* dy, const void* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo,
+                                  int32_t Cout, int32_t K, int32_t stride, int32_t accumulate, float* ws, int64_t ws_bytes, bool det, void* stream) {
     mt4_clear_error();
-    if (!dy || !x || !dw_packed || !ws || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) return MT4_EINVAL;
+    if (!dy || !x || !dw_packed || (det && !ws) || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) return MT4_EINVAL;
     if ((K != 1 && K != 3) || (stride != 1 && stride != 2)) return MT4_EUNSUPPORTED;
     if ((Cin % 8) || (Cout % 8)) return MT4_EALIGN;
     if (Ho != (H + 2 * (K / 2) - K) / stride + 1 || Wo != (W + 2 * (K / 2) - K) / stride + 1) return MT4_EINVAL;
-    if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dw_packed | (uintptr_t)ws) & 15) return MT4_EALIGN;
-    WgK a;
-    a.dy = (const u16*)dy; a.x = (const u16*)x; a.dw = ws;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
-    a.kpad = (int)mt4_conv_packed_k(Cin, K, K, MT4_F32);
-    a.tapw = (Cin + 3) / 4 * 4;
-    int ns = 0;
-    int rc = wgrad_bf16_dispatch<true>(a, K, stride, nullptr, false, nullptr, &ns);
+    if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dw_packed | (det ? (uintptr_t)ws : 0)) & 15) return MT4_EALIGN;
+    const WgK a = wgrad_bf16_args(dy, x, det ? ws : dw_packed, B, H, W, Cin, Ho, Wo, Cout, K);
+    if (!det) return wgrad_bf16_dispatch<false>(a, K, stride, (hipStream_t)stream, true, nullptr, nullptr);
+    DetParts p;
+    int rc = wgrad_bf16_parts(a, K, stride, &p);
     if (rc != MT4_OK) return rc;
-    const long long pe = (long long)Cout * a.kpad;
-    if (ws_bytes < ns * pe * (long long)sizeof(float)) return MT4_EINVAL;
+    if (ws_bytes < p.bytes()) return MT4_EINVAL;
     rc = wgrad_bf16_dispatch<true>(a, K, stride, (hipStream_t)stream, true, nullptr, nullptr);
     if (rc != MT4_OK) return rc;
-    return mt4_fold_parts_f32(ws, ns, pe, pe, dw_packed, accumulate, stream);
+    return mt4_fold_parts_f32(ws, p.nparts, p.part_elems, p.part_elems, dw_packed, accumulate, stream);
+}
+
+extern "C" int mt4_wgrad_conv2d_bf16(const void* dy, const void* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo,
+                                     int32_t Cout, int32_t K, int32_t stride, void* stream) {
+    return wgrad_conv2d_bf16_impl(dy, x, dw_packed, B, H, W, Cin, Ho, Wo, Cout, K, stride, 1, nullptr, 0, false, stream);
+}
+
+extern "C" int mt4_wgrad_conv2d_det_bf16(const void* dy, const void* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo,
+                                         int32_t Cout, int32_t K, int32_t stride, int32_t accumulate, float* ws, int64_t ws_bytes, void* stream) {
+    return wgrad_conv2d_bf16_impl(dy, x, dw_packed, B, H, W, Cin, Ho, Wo, Cout, K, stride, accumulate, ws, ws_bytes, true, stream);
 }
 
 extern "C" int mt4_maxpool3x3s2_bwd_bf16(const void* x, const void* dy, void* dx, int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
@@ -878,30 +866,26 @@ extern "C" int mt4_maxpool3x3s2_bwd_bf16(const void* x, const void* dy, void* dx
     if ((C & 7) || (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15)) return MT4_EALIGN;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     if (!(C & 63) && (long long)B * (C >> 6) <= 65535) {
-        hipLaunchKernelGGL(maxpool3x3s2_bwd_bf16_tile_kernel, dim3(cdiv(W, 16), cdiv(H, 16), B * (C >> 6)), dim3(256), 0, (hipStream_t)stream, (const u16*)x,
-                           (const u16*)dy, (u16*)dx, H, W, C, Ho, Wo);
-        return mt4_check_launch();
+        return mt4_launch<maxpool3x3s2_bwd_bf16_tile_kernel>(dim3(cdiv(W, 16), cdiv(H, 16), B * (C >> 6)), dim3(256), 0, (hipStream_t)stream, (const u16*)x,
+                                                             (const u16*)dy, (u16*)dx, H, W, C, Ho, Wo);
     }
     const long long n = (long long)B * H * W * (C / 8);
-    hipLaunchKernelGGL(maxpool3x3s2_bwd_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const u16*)x, (const u16*)dy,
-                       (u16*)dx, B, H, W, C, Ho, Wo);
-    return mt4_check_launch();
+    return mt4_launch<maxpool3x3s2_bwd_bf16_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const u16*)x, (const u16*)dy, (u16*)dx,
+                                                    B, H, W, C, Ho, Wo);
 }
 
 extern "C" int mt4_avgpool_bwd_bf16(const float* dfeat, void* dx, int32_t B, int32_t HW, int32_t C, void* stream) {
     mt4_clear_error();
     if (!dfeat || !dx || B <= 0 || HW <= 0 || C <= 0 || (C & 3)) return MT4_EINVAL;
     const long long n4 = (long long)B * HW * C / 4;
-    hipLaunchKernelGGL(avgpool_bwd_bf16_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dfeat, (u16*)dx, HW, C, n4);
-    return mt4_check_launch();
+    return mt4_launch<avgpool_bwd_bf16_kernel>(dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dfeat, (u16*)dx, HW, C, n4);
 }
 
 extern "C" int mt4_cast_f32_bf16(const float* x, void* y_bf16, int64_t n, void* stream) {
     mt4_clear_error();
     if (!x || !y_bf16 || n <= 0 || (n & 7)) return MT4_EINVAL;
     if (((uintptr_t)x | (uintptr_t)y_bf16) & 15) return MT4_EALIGN;
-    hipLaunchKernelGGL(cast_bf16_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, (u16*)y_bf16, (long long)(n / 8));
-    return mt4_check_launch();
+    return mt4_launch<cast_bf16_kernel>(dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, (u16*)y_bf16, (long long)(n / 8));
 }
 
 extern "C" int mt4_repack_weight_bf16(const float* w_f32_packed, void* w_bf16_packed, int32_t Cout, int32_t Cin, int32_t KH, int32_t KW, void* stream) {
@@ -909,7 +893,6 @@ extern "C" int mt4_repack_weight_bf16(const float* w_f32_packed, void* w_bf16_pa
     if (!w_f32_packed || !w_bf16_packed || Cout <= 0 || Cin <= 0 || KH <= 0 || KW <= 0) return MT4_EINVAL;
     const long long k32 = mt4_conv_packed_k(Cin, KH, KW, MT4_F32), k16 = mt4_conv_packed_k(Cin, KH, KW, MT4_BF16);
     const long long total = (long long)Cout * k16;
-    hipLaunchKernelGGL(repack_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_f32_packed, (u16*)w_bf16_packed, KH * KW,
-                       (Cin + 3) / 4 * 4, k32, (Cin + 7) / 8 * 8, k16, total);
-    return mt4_check_launch();
+    return mt4_launch<repack_bf16_kernel>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_f32_packed, (u16*)w_bf16_packed, KH * KW,
+                                          (Cin + 3) / 4 * 4, k32, (Cin + 7) / 8 * 8, k16, total);
 }

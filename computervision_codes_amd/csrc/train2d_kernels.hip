@@ -3,6 +3,7 @@
 // fp32, channels-last.  Data gradients of the convolutions reuse mt4_conv_nhwc (transposed weights; strided convs as
 // 4 sub-pixel phases scattered through the output row map).
 #include "mt4_common.h"
+#include "det_parts.h"
 
 // ------------------------------------------------------------------------------------------------ BatchNorm2d (training)
 // pass 1: sums[0][c] += sum_m x[m][c], sums[1][c] += sum_m x^2   (sums zeroed by the caller; atomics over row slabs).
@@ -49,49 +50,40 @@ __global__ void bn_finalize_kernel(const double* __restrict__ sums, float* __res
     }
 }
 
-extern "C" int mt4_bn_stats_f32(const float* x, double* sums_zeroed, float* mean, float* invstd, float* running_mean, float* running_var,
-                                int64_t M, int32_t C, float momentum, float eps, void* stream) {
-    mt4_clear_error();
-    if (!x || !sums_zeroed || !mean || !invstd || M <= 0 || C <= 0) return MT4_EINVAL;
-    if (C % 4) return MT4_EALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_stats_kernel<false>, dim3(cdiv(C, 64), bn_reduce_slabs(M, C)), dim3(1024), 0, s, x, sums_zeroed, (long long)M, C);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, sums_zeroed, mean, invstd, running_mean, running_var,
-                       (long long)M, C, momentum, eps);
-    return mt4_check_launch();
-}
-
 // ---- deterministic BatchNorm reductions (both tensor types; the bf16-tensor entry points are in train2d_bf16.hip)
-// parts [slabs][2][C] float64, one per row slab of the 1024-thread reduction; fold order: the fixed chunks of mt4_fold_parts_chunked_f64 over the slabs (up
+// parts [slabs][2][C] float64, one per row slab of the 1024-thread reduction (bn_parts); fold order: the fixed chunks of mt4_fold_parts_chunked_f64 over the slabs (up
 // to 512 of them, a few thousand elements each: the sequential fold was 15 us a launch, 106 launches a ResNet-50 step), INTO `sums` (stored: `sums` needs no
 // zeroing), which the unchanged finalize / apply kernels then read
 extern "C" int mt4_bn_det_plan(int64_t M, int32_t C, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
     if (M <= 0 || C <= 0) return MT4_EINVAL;
     if (C % 4) return MT4_EALIGN;
-    const int slabs = bn_reduce_slabs(M, C);
-    if (form) *form = 0;
-    if (nparts) *nparts = slabs;
-    if (part_elems) *part_elems = 2LL * C;
-    if (ws_bytes) *ws_bytes = (long long)slabs * 2 * C * (long long)sizeof(double);
-    return MT4_OK;
+    return det_plan_out(bn_parts(M, C), form, nparts, part_elems, ws_bytes);
+}
+
+static int bn_stats_impl(const float* x, double* sums, float* mean, float* invstd, float* running_mean, float* running_var, int64_t M, int32_t C,
+                         float momentum, float eps, double* ws, int64_t ws_bytes, bool det, void* stream) {
+    mt4_clear_error();
+    if (!x || !sums || !mean || !invstd || (det && !ws) || M <= 0 || C <= 0) return MT4_EINVAL;
+    if (C % 4 || (det && ((uintptr_t)ws & 15))) return MT4_EALIGN;
+    const DetParts p = bn_parts(M, C);
+    if (det && ws_bytes < p.bytes()) return MT4_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(cdiv(C, 64), p.nparts);
+    int rc = det ? mt4_launch<bn_stats_kernel<true>>(grid, dim3(1024), 0, s, x, ws, (long long)M, C)
+                 : mt4_launch<bn_stats_kernel<false>>(grid, dim3(1024), 0, s, x, sums, (long long)M, C);
+    if (rc == MT4_OK && det) rc = mt4_fold_parts_chunked_f64(ws, p.nparts, p.part_elems, p.part_elems, sums, 0, stream);
+    if (rc != MT4_OK) return rc;
+    return mt4_launch<bn_finalize_kernel>(dim3(cdiv(C, 256)), dim3(256), 0, s, sums, mean, invstd, running_mean, running_var, (long long)M, C, momentum, eps);
+}
+
+extern "C" int mt4_bn_stats_f32(const float* x, double* sums_zeroed, float* mean, float* invstd, float* running_mean, float* running_var,
+                                int64_t M, int32_t C, float momentum, float eps, void* stream) {
+    return bn_stats_impl(x, sums_zeroed, mean, invstd, running_mean, running_var, M, C, momentum, eps, nullptr, 0, false, stream);
 }
 
 extern "C" int mt4_bn_stats_det_f32(const float* x, double* sums, float* mean, float* invstd, float* running_mean, float* running_var, int64_t M,
                                     int32_t C, float momentum, float eps, double* ws, int64_t ws_bytes, void* stream) {
-    mt4_clear_error();
-    if (!x || !sums || !mean || !invstd || !ws || M <= 0 || C <= 0) return MT4_EINVAL;
-    if (C % 4 || ((uintptr_t)ws & 15)) return MT4_EALIGN;
-    const int slabs = bn_reduce_slabs(M, C);
-    if (ws_bytes < (long long)slabs * 2 * C * (long long)sizeof(double)) return MT4_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_stats_kernel<true>, dim3(cdiv(C, 64), slabs), dim3(1024), 0, s, x, ws, (long long)M, C);
-    const int lc = mt4_check_launch();
-    if (lc != MT4_OK) return lc;
-    const int fc = mt4_fold_parts_chunked_f64(ws, slabs, 2LL * C, 2LL * C, sums, 0, stream);
-    if (fc != MT4_OK) return fc;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, sums, mean, invstd, running_mean, running_var, (long long)M, C, momentum,
-                       eps);
-    return mt4_check_launch();
+    return bn_stats_impl(x, sums, mean, invstd, running_mean, running_var, M, C, momentum, eps, ws, ws_bytes, true, stream);
 }
 
 // y = act( (x - mean) * invstd * gamma + beta [+ residual] ): column slabs, the 4 channels' parameters in registers (one element group per
@@ -166,9 +158,8 @@ extern "C" int mt4_bn_apply_f32(const float* x, const float* mean, const float* 
     mt4_clear_error();
     if (!x || !mean || !invstd || !gamma || !beta || !y || M <= 0 || C <= 0) return MT4_EINVAL;
     if (C % 4) return MT4_EALIGN;
-    hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(cdiv(C, 64), bn_row_slabs(M, C)), dim3(256), 0, (hipStream_t)stream, x, (float*)mean, (float*)invstd,
-                       gamma, beta, residual, y, (long long)M, C, relu, (const double*)nullptr, (float*)nullptr, (float*)nullptr, 0.f, 0.f);
-    return mt4_check_launch();
+    return mt4_launch<bn_apply_kernel<false>>(dim3(cdiv(C, 64), bn_row_slabs(M, C)), dim3(256), 0, (hipStream_t)stream, x, (float*)mean, (float*)invstd, gamma,
+                                              beta, residual, y, (long long)M, C, relu, (const double*)nullptr, (float*)nullptr, (float*)nullptr, 0.f, 0.f);
 }
 
 extern "C" int mt4_bn_apply_sums_f32(const float* x, const double* stat_sums, float* mean, float* invstd, float* running_mean, float* running_var,
@@ -177,9 +168,8 @@ extern "C" int mt4_bn_apply_sums_f32(const float* x, const double* stat_sums, fl
     mt4_clear_error();
     if (!x || !stat_sums || !mean || !invstd || !gamma || !beta || !y || M <= 0 || C <= 0) return MT4_EINVAL;
     if (C % 4) return MT4_EALIGN;
-    hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(cdiv(C, 64), bn_row_slabs(M, C)), dim3(256), 0, (hipStream_t)stream, x, mean, invstd, gamma, beta, residual,
-                       y, (long long)M, C, relu, stat_sums, running_mean, running_var, momentum, eps);
-    return mt4_check_launch();
+    return mt4_launch<bn_apply_kernel<true>>(dim3(cdiv(C, 64), bn_row_slabs(M, C)), dim3(256), 0, (hipStream_t)stream, x, mean, invstd, gamma, beta, residual, y,
+                                             (long long)M, C, relu, stat_sums, running_mean, running_var, momentum, eps);
 }
 
 // backward pass 1: with dy' = relu ? (y > 0 ? dy : 0) : dy :  sums[0][c] += sum dy',  sums[1][c] += sum dy' * xhat
@@ -289,40 +279,34 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     }
 }
 
+static int bn_backward_impl(const float* dy, const float* y_post, const float* x, const float* mean, const float* invstd, const float* gamma,
+                            const float* beta, double* sums, float* dx, float* dres, float* dgamma, float* dbeta, int64_t M, int32_t C, int32_t relu,
+                            double* ws, int64_t ws_bytes, bool det, void* stream) {
+    mt4_clear_error();
+    if (!dy || !x || !mean || !invstd || !gamma || !sums || !dx || !dgamma || !dbeta || (det && !ws) || M <= 0 || C <= 0) return MT4_EINVAL;
+    if (relu < 0 || relu > 2 || (relu == 1 && !y_post) || (relu == 2 && !beta)) return MT4_EINVAL;
+    if (C % 4 || (det && ((uintptr_t)ws & 15))) return MT4_EALIGN;
+    const DetParts p = bn_parts(M, C);
+    if (det && ws_bytes < p.bytes()) return MT4_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 g1(cdiv(C, 64), p.nparts), g2(cdiv(C, 64), bn_row_slabs(M, C));
+    int rc = det ? mt4_launch<bn_bwd_reduce_kernel<true>>(g1, dim3(1024), 0, s, dy, y_post, x, mean, invstd, gamma, beta, ws, (long long)M, C, relu)
+                 : mt4_launch<bn_bwd_reduce_kernel<false>>(g1, dim3(1024), 0, s, dy, y_post, x, mean, invstd, gamma, beta, sums, (long long)M, C, relu);
+    if (rc == MT4_OK && det) rc = mt4_fold_parts_chunked_f64(ws, p.nparts, p.part_elems, p.part_elems, sums, 0, stream);
+    if (rc != MT4_OK) return rc;
+    return mt4_launch<bn_bwd_apply_kernel>(g2, dim3(256), 0, s, dy, y_post, x, mean, invstd, gamma, beta, sums, dx, dres, dgamma, dbeta, (long long)M, C, relu);
+}
+
 extern "C" int mt4_bn_backward_f32(const float* dy, const float* y_post, const float* x, const float* mean, const float* invstd,
                                    const float* gamma, const float* beta, double* sums_zeroed, float* dx, float* dres, float* dgamma, float* dbeta,
                                    int64_t M, int32_t C, int32_t relu, void* stream) {
-    mt4_clear_error();
-    if (!dy || !x || !mean || !invstd || !gamma || !sums_zeroed || !dx || !dgamma || !dbeta || M <= 0 || C <= 0) return MT4_EINVAL;
-    if (relu < 0 || relu > 2 || (relu == 1 && !y_post) || (relu == 2 && !beta)) return MT4_EINVAL;
-    if (C % 4) return MT4_EALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(cdiv(C, 64), bn_reduce_slabs(M, C)), dim3(1024), 0, s, dy, y_post, x, mean, invstd, gamma, beta, sums_zeroed,
-                       (long long)M, C, relu);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(cdiv(C, 64), bn_row_slabs(M, C)), dim3(256), 0, s, dy, y_post, x, mean, invstd, gamma, beta, sums_zeroed, dx,
-                       dres, dgamma, dbeta, (long long)M, C, relu);
-    return mt4_check_launch();
+    return bn_backward_impl(dy, y_post, x, mean, invstd, gamma, beta, sums_zeroed, dx, dres, dgamma, dbeta, M, C, relu, nullptr, 0, false, stream);
 }
 
 extern "C" int mt4_bn_backward_det_f32(const float* dy, const float* y_post, const float* x, const float* mean, const float* invstd, const float* gamma,
                                        const float* beta, double* sums, float* dx, float* dres, float* dgamma, float* dbeta, int64_t M, int32_t C,
                                        int32_t relu, double* ws, int64_t ws_bytes, void* stream) {
-    mt4_clear_error();
-    if (!dy || !x || !mean || !invstd || !gamma || !sums || !dx || !dgamma || !dbeta || !ws || M <= 0 || C <= 0) return MT4_EINVAL;
-    if (relu < 0 || relu > 2 || (relu == 1 && !y_post) || (relu == 2 && !beta)) return MT4_EINVAL;
-    if (C % 4 || ((uintptr_t)ws & 15)) return MT4_EALIGN;
-    const int slabs = bn_reduce_slabs(M, C);
-    if (ws_bytes < (long long)slabs * 2 * C * (long long)sizeof(double)) return MT4_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(cdiv(C, 64), slabs), dim3(1024), 0, s, dy, y_post, x, mean, invstd, gamma, beta, ws, (long long)M, C,
-                       relu);
-    const int lc = mt4_check_launch();
-    if (lc != MT4_OK) return lc;
-    const int fc = mt4_fold_parts_chunked_f64(ws, slabs, 2LL * C, 2LL * C, sums, 0, stream);
-    if (fc != MT4_OK) return fc;
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(cdiv(C, 64), bn_row_slabs(M, C)), dim3(256), 0, s, dy, y_post, x, mean, invstd, gamma, beta, sums, dx, dres,
-                       dgamma, dbeta, (long long)M, C, relu);
-    return mt4_check_launch();
+    return bn_backward_impl(dy, y_post, x, mean, invstd, gamma, beta, sums, dx, dres, dgamma, dbeta, M, C, relu, ws, ws_bytes, true, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ Conv2d weight gradient
@@ -524,11 +508,12 @@ __global__ __launch_bounds__(256) void wgrad_conv2d_f32_wide_kernel(const float*
         }
 }
 
-// The launch form of a shape and its pixel split -- shared by the launch, the deterministic launch and its host-only plan query.
+// The launch form of a shape and its pixel split = its parts (a part: an image of the packed dW) -- read by both launches and the host-only plan
+// query; a.rows_per_split is set here.
 // form 0: 64 x 64 tiles; 1 / 2 / 3: the wide kernel <2,2> / <1,2> / <2,1>.  Wider tiles where the channel counts allow AND the launch still has >= 2
 // workgroups per CU (each pixel split covers >= 256 pixels: a small batch has few of them -- ResNet-50 at batch 8: 9.6 ms with the 64 x 64 kernel
 // everywhere, 10.2 with the wide tiles); the 64 x 64 kernel: the narrowest layers, small batches
-static int wgrad32_form(Wg2& a, int Cout, long long* splits_out) {
+static DetParts wgrad32_parts(Wg2& a, int Cout) {
     const long long max_splits = (a.M + 255) / 256;             // at least 256 rows per split
     auto fills = [&](int bm, int bn) { return (long long)cdiv(a.Kpad, bn) * cdiv(Cout, bm) * max_splits >= 512; };
     int form = 0, bm = 64, bn = 64;
@@ -540,21 +525,17 @@ static int wgrad32_form(Wg2& a, int Cout, long long* splits_out) {
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     a.rows_per_split = ((a.M + splits - 1) / splits + 31) / 32 * 32;
-    *splits_out = (a.M + a.rows_per_split - 1) / a.rows_per_split;
-    return form;
+    return {form, (int32_t)((a.M + a.rows_per_split - 1) / a.rows_per_split), (long long)Cout * a.Kpad, (int32_t)sizeof(float)};
 }
 
 template <bool DET>
-static int launch_wgrad32(const float* dy, const float* x, float* dw, Wg2 a, int Cout, hipStream_t s) {
-    long long splits;
-    const int form = wgrad32_form(a, Cout, &splits);
-    const int bm = (form == 1 || form == 3) ? 128 : 64, bn = (form == 1 || form == 2) ? 128 : 64;
-    const dim3 grid(cdiv(a.Kpad, bn), cdiv(Cout, bm), (unsigned)splits);
-    if (form == 1) hipLaunchKernelGGL((wgrad_conv2d_f32_wide_kernel<2, 2, DET>), grid, dim3(256), 0, s, dy, x, dw, a);
-    else if (form == 2) hipLaunchKernelGGL((wgrad_conv2d_f32_wide_kernel<1, 2, DET>), grid, dim3(256), 0, s, dy, x, dw, a);
-    else if (form == 3) hipLaunchKernelGGL((wgrad_conv2d_f32_wide_kernel<2, 1, DET>), grid, dim3(256), 0, s, dy, x, dw, a);
-    else hipLaunchKernelGGL(wgrad_conv2d_f32_kernel<DET>, grid, dim3(256), 0, s, dy, x, dw, a);
-    return mt4_check_launch();
+static int launch_wgrad32(const float* dy, const float* x, float* dw, const Wg2& a, const DetParts& p, int Cout, hipStream_t s) {
+    const int form = p.form, bm = (form == 1 || form == 3) ? 128 : 64, bn = (form == 1 || form == 2) ? 128 : 64;
+    const dim3 grid(cdiv(a.Kpad, bn), cdiv(Cout, bm), (unsigned)p.nparts);
+    if (form == 1) return mt4_launch<wgrad_conv2d_f32_wide_kernel<2, 2, DET>>(grid, dim3(256), 0, s, dy, x, dw, a);
+    if (form == 2) return mt4_launch<wgrad_conv2d_f32_wide_kernel<1, 2, DET>>(grid, dim3(256), 0, s, dy, x, dw, a);
+    if (form == 3) return mt4_launch<wgrad_conv2d_f32_wide_kernel<2, 1, DET>>(grid, dim3(256), 0, s, dy, x, dw, a);
+    return mt4_launch<wgrad_conv2d_f32_kernel<DET>>(grid, dim3(256), 0, s, dy, x, dw, a);
 }
 
 static void wgrad32_args(Wg2& a, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo, int32_t Cout, int32_t KH, int32_t KW, int32_t stride_h,
@@ -567,52 +548,46 @@ static void wgrad32_args(Wg2& a, int32_t B, int32_t H, int32_t W, int32_t Cin, i
     a.rows_per_split = 0;
 }
 
-extern "C" int mt4_wgrad_conv2d_f32(const float* dy, const float* x, float* dw_packed_zeroed, int32_t B, int32_t H, int32_t W, int32_t Cin,
-                                    int32_t Ho, int32_t Wo, int32_t Cout, int32_t KH, int32_t KW, int32_t stride_h, int32_t stride_w,
-                                    int32_t pad_h, int32_t pad_w, int32_t dil_h, int32_t dil_w, void* stream) {
-    mt4_clear_error();
-    if (!dy || !x || !dw_packed_zeroed || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || KH <= 0 || KW <= 0)
-        return MT4_EINVAL;
-    if (Cin % 4 || Cout % 4 || (((uintptr_t)dy | (uintptr_t)x) & 15)) return MT4_EALIGN;
-    Wg2 a;
-    wgrad32_args(a, B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
-    return launch_wgrad32<false>(dy, x, dw_packed_zeroed, a, Cout, (hipStream_t)stream);
-}
-
 extern "C" int mt4_wgrad_conv2d_det_plan(int32_t B, int32_t Ho, int32_t Wo, int32_t Cout, int32_t Cin, int32_t KH, int32_t KW, int32_t* form, int32_t* nparts,
                                          int64_t* part_elems, int64_t* ws_bytes) {
     if (B <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || Cin <= 0 || KH <= 0 || KW <= 0) return MT4_EINVAL;
     if (Cin % 4 || Cout % 4) return MT4_EALIGN;
     Wg2 a;
     wgrad32_args(a, B, 1, 1, Cin, Ho, Wo, Cout, KH, KW, 1, 1, 0, 0, 1, 1);      // (the form and the split depend on the output pixels and the channels alone)
-    long long splits;
-    const int f = wgrad32_form(a, Cout, &splits);
-    if (form) *form = f;
-    if (nparts) *nparts = (int32_t)splits;
-    if (part_elems) *part_elems = (long long)Cout * a.Kpad;
-    if (ws_bytes) *ws_bytes = splits * Cout * a.Kpad * (long long)sizeof(float);
-    return MT4_OK;
+    return det_plan_out(wgrad32_parts(a, Cout), form, nparts, part_elems, ws_bytes);
 }
 
 // fold order (the contract): parts z = 0 .. nparts-1 (ascending ranges of the B*Ho*Wo output pixels, rows_per_split each) front to back; the sum is then
 // ADDED to dw_packed (accumulate != 0) or stored
+static int wgrad_conv2d_impl(const float* dy, const float* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho, int32_t Wo,
+                             int32_t Cout, int32_t KH, int32_t KW, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w, int32_t dil_h,
+                             int32_t dil_w, int32_t accumulate, float* ws, int64_t ws_bytes, bool det, void* stream) {
+    mt4_clear_error();
+    if (!dy || !x || !dw_packed || (det && !ws) || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || KH <= 0 || KW <= 0)
+        return MT4_EINVAL;
+    if (Cin % 4 || Cout % 4 || (((uintptr_t)dy | (uintptr_t)x | (det ? (uintptr_t)ws : 0)) & 15)) return MT4_EALIGN;
+    Wg2 a;
+    wgrad32_args(a, B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
+    const DetParts p = wgrad32_parts(a, Cout);
+    if (!det) return launch_wgrad32<false>(dy, x, dw_packed, a, p, Cout, (hipStream_t)stream);
+    if (ws_bytes < p.bytes()) return MT4_EINVAL;
+    const int lc = launch_wgrad32<true>(dy, x, ws, a, p, Cout, (hipStream_t)stream);
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_f32(ws, p.nparts, p.part_elems, p.part_elems, dw_packed, accumulate, stream);
+}
+
+extern "C" int mt4_wgrad_conv2d_f32(const float* dy, const float* x, float* dw_packed_zeroed, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                                    int32_t Ho, int32_t Wo, int32_t Cout, int32_t KH, int32_t KW, int32_t stride_h, int32_t stride_w,
+                                    int32_t pad_h, int32_t pad_w, int32_t dil_h, int32_t dil_w, void* stream) {
+    return wgrad_conv2d_impl(dy, x, dw_packed_zeroed, B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, 0, nullptr, 0, false,
+                             stream);
+}
+
 extern "C" int mt4_wgrad_conv2d_det_f32(const float* dy, const float* x, float* dw_packed, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Ho,
                                         int32_t Wo, int32_t Cout, int32_t KH, int32_t KW, int32_t stride_h, int32_t stride_w, int32_t pad_h,
                                         int32_t pad_w, int32_t dil_h, int32_t dil_w, int32_t accumulate, float* ws, int64_t ws_bytes, void* stream) {
-    mt4_clear_error();
-    if (!dy || !x || !dw_packed || !ws || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || KH <= 0 || KW <= 0)
-        return MT4_EINVAL;
-    if (Cin % 4 || Cout % 4 || (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)ws) & 15)) return MT4_EALIGN;
-    Wg2 a;
-    wgrad32_args(a, B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w);
-    long long splits;
-    Wg2 probe = a;
-    (void)wgrad32_form(probe, Cout, &splits);
-    const long long pe = (long long)Cout * a.Kpad;
-    if (ws_bytes < splits * pe * (long long)sizeof(float)) return MT4_EINVAL;
-    const int lc = launch_wgrad32<true>(dy, x, ws, a, Cout, (hipStream_t)stream);
-    if (lc != MT4_OK) return lc;
-    return mt4_fold_parts_f32(ws, (int32_t)splits, pe, pe, dw_packed, accumulate, stream);
+    return wgrad_conv2d_impl(dy, x, dw_packed, B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, accumulate, ws, ws_bytes, true,
+                             stream);
 }
 
 // ------------------------------------------------------------------------------------------------ pooling backward
@@ -648,9 +623,7 @@ extern "C" int mt4_maxpool3x3s2_bwd_f32(const float* x, const float* dy, float* 
     if (!x || !dy || !dx_zeroed || B <= 0 || H <= 0 || W <= 0 || C <= 0) return MT4_EINVAL;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const long long n = (long long)B * Ho * Wo * C;
-    hipLaunchKernelGGL(maxpool3x3s2_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx_zeroed, B, H, W, C, Ho,
-                       Wo);
-    return mt4_check_launch();
+    return mt4_launch<maxpool3x3s2_bwd_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx_zeroed, B, H, W, C, Ho, Wo);
 }
 
 // The same gradient in gather form, no atomics and no zeroing (modelled on maxpool3x3s2_bwd_bf16_kernel): a thread owns 4 channels of one INPUT pixel
@@ -702,8 +675,7 @@ extern "C" int mt4_maxpool3x3s2_bwd_gather_f32(const float* x, const float* dy, 
     if (C % 4 || (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15)) return MT4_EALIGN;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const long long n = (long long)B * H * W * (C >> 2);
-    hipLaunchKernelGGL(maxpool3x3s2_bwd_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, B, H, W, C, Ho, Wo);
-    return mt4_check_launch();
+    return mt4_launch<maxpool3x3s2_bwd_gather_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, B, H, W, C, Ho, Wo);
 }
 
 // AdaptiveAvgPool2d(1) backward: dx[b][p][c] = dfeat[b][c] / HW
@@ -719,8 +691,7 @@ extern "C" int mt4_avgpool_bwd_f32(const float* dfeat, float* dx, int32_t B, int
     mt4_clear_error();
     if (!dfeat || !dx || B <= 0 || HW <= 0 || C <= 0) return MT4_EINVAL;
     const long long n = (long long)B * HW * C;
-    hipLaunchKernelGGL(avgpool_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dfeat, dx, HW, C, n);
-    return mt4_check_launch();
+    return mt4_launch<avgpool_bwd_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dfeat, dx, HW, C, n);
 }
 
 // ------------------------------------------------------------------------------------------------ losses
@@ -756,39 +727,39 @@ __global__ __launch_bounds__(256) void bce_pw_kernel(const float* __restrict__ y
     }
 }
 
-extern "C" int mt4_bce_logits_pw_f32(const float* y, const float* z, const float* pos_weight, const float* col_scale, float* dy, float* col_loss,
-                                     int32_t M, int32_t N, int32_t ld_y, int32_t ld_dy, void* stream) {
-    mt4_clear_error();
-    if (!y || !z || !col_scale || !dy || !col_loss || M <= 0 || N <= 0 || ld_y < N || ld_dy < N) return MT4_EINVAL;
-    if (cdiv(M, 64) > 65535) return MT4_EUNSUPPORTED;
-    hipLaunchKernelGGL(bce_pw_kernel<false>, dim3(cdiv(N, 64), cdiv(M, 64)), dim3(256), 0, (hipStream_t)stream, y, z, pos_weight, col_scale, dy, col_loss, M, N,
-                       ld_y, ld_dy);
-    return mt4_check_launch();
-}
+static DetParts bce_pw_parts(int M, int N) { return {0, cdiv(M, 64), N, (int32_t)sizeof(float)}; }      // a part: the N sums of one 64-row slab
 
 extern "C" int mt4_bce_logits_pw_det_plan(int32_t M, int32_t N, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
     if (M <= 0 || N <= 0) return MT4_EINVAL;
     if (cdiv(M, 64) > 65535) return MT4_EUNSUPPORTED;
-    if (form) *form = 0;
-    if (nparts) *nparts = cdiv(M, 64);
-    if (part_elems) *part_elems = N;
-    if (ws_bytes) *ws_bytes = (long long)cdiv(M, 64) * N * (long long)sizeof(float);
-    return MT4_OK;
+    return det_plan_out(bce_pw_parts(M, N), form, nparts, part_elems, ws_bytes);
 }
 
 // fold order (the contract): 64-row slabs y = 0 .. nparts-1 front to back (a slab's sum: four row groups r = m % 4 of ascending rows, (g0 + g1) + (g2 + g3)),
 // then ADDED to col_loss
+static int bce_pw_impl(const float* y, const float* z, const float* pos_weight, const float* col_scale, float* dy, float* col_loss, int32_t M, int32_t N,
+                       int32_t ld_y, int32_t ld_dy, float* ws, int64_t ws_bytes, bool det, void* stream) {
+    mt4_clear_error();
+    if (!y || !z || !col_scale || !dy || !col_loss || (det && !ws) || M <= 0 || N <= 0 || ld_y < N || ld_dy < N) return MT4_EINVAL;
+    if (cdiv(M, 64) > 65535) return MT4_EUNSUPPORTED;
+    const DetParts p = bce_pw_parts(M, N);
+    if (det && ws_bytes < p.bytes()) return MT4_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(cdiv(N, 64), p.nparts);
+    if (!det) return mt4_launch<bce_pw_kernel<false>>(grid, dim3(256), 0, s, y, z, pos_weight, col_scale, dy, col_loss, M, N, ld_y, ld_dy);
+    const int lc = mt4_launch<bce_pw_kernel<true>>(grid, dim3(256), 0, s, y, z, pos_weight, col_scale, dy, ws, M, N, ld_y, ld_dy);
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_f32(ws, p.nparts, N, N, col_loss, 1, stream);
+}
+
+extern "C" int mt4_bce_logits_pw_f32(const float* y, const float* z, const float* pos_weight, const float* col_scale, float* dy, float* col_loss,
+                                     int32_t M, int32_t N, int32_t ld_y, int32_t ld_dy, void* stream) {
+    return bce_pw_impl(y, z, pos_weight, col_scale, dy, col_loss, M, N, ld_y, ld_dy, nullptr, 0, false, stream);
+}
+
 extern "C" int mt4_bce_logits_pw_det_f32(const float* y, const float* z, const float* pos_weight, const float* col_scale, float* dy, float* col_loss,
                                          int32_t M, int32_t N, int32_t ld_y, int32_t ld_dy, float* ws, int64_t ws_bytes, void* stream) {
-    mt4_clear_error();
-    if (!y || !z || !col_scale || !dy || !col_loss || !ws || M <= 0 || N <= 0 || ld_y < N || ld_dy < N) return MT4_EINVAL;
-    if (cdiv(M, 64) > 65535) return MT4_EUNSUPPORTED;
-    if (ws_bytes < (long long)cdiv(M, 64) * N * (long long)sizeof(float)) return MT4_EINVAL;
-    hipLaunchKernelGGL(bce_pw_kernel<true>, dim3(cdiv(N, 64), cdiv(M, 64)), dim3(256), 0, (hipStream_t)stream, y, z, pos_weight, col_scale, dy, ws, M, N, ld_y,
-                       ld_dy);
-    const int lc = mt4_check_launch();
-    if (lc != MT4_OK) return lc;
-    return mt4_fold_parts_f32(ws, cdiv(M, 64), N, N, col_loss, 1, stream);
+    return bce_pw_impl(y, z, pos_weight, col_scale, dy, col_loss, M, N, ld_y, ld_dy, ws, ws_bytes, true, stream);
 }
 
 // DistillKL (run.py:284-295): loss += T^2/B * sum_k p_t (log p_t - log_softmax(y_s/T)),  p_t = softmax(sigmoid(t_pred)/T);
@@ -835,36 +806,36 @@ __global__ void distill_kl_kernel(const float* __restrict__ ys, const float* __r
     }
 }
 
-extern "C" int mt4_distill_kl_f32(const float* y_s, const float* t_pred, float* dy_s, float* loss, int32_t B, int32_t K, int32_t ld_y, int32_t ld_dy,
-                                  float temp, float grad_scale, int32_t accumulate, void* stream) {
-    mt4_clear_error();
-    if (!y_s || !t_pred || !dy_s || !loss || B <= 0 || K <= 0 || K > 128 || ld_y < K || ld_dy < K) return MT4_EINVAL;
-    hipLaunchKernelGGL(distill_kl_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, y_s, t_pred, dy_s, loss, B, K, ld_y, ld_dy, temp, grad_scale,
-                       accumulate);
-    return mt4_check_launch();
-}
-
 // the two scalar losses: one part element per workgroup (DistillKL: per batch row; MSE: per 256 elements), folded in the fixed chunks of mt4_fold_parts_chunked_f32 and ADDED
 // to *loss.  Tiny either way: a batch of 64 rows, 3 x 384 workgroups of the feature MSE.
+static DetParts distill_kl_parts(int B) { return {0, B, 1, (int32_t)sizeof(float)}; }
+
 extern "C" int mt4_distill_kl_det_plan(int32_t B, int32_t K, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
     if (B <= 0 || K <= 0 || K > 128) return MT4_EINVAL;
-    if (form) *form = 0;
-    if (nparts) *nparts = B;
-    if (part_elems) *part_elems = 1;
-    if (ws_bytes) *ws_bytes = (long long)B * (long long)sizeof(float);
-    return MT4_OK;
+    return det_plan_out(distill_kl_parts(B), form, nparts, part_elems, ws_bytes);
+}
+
+static int distill_kl_impl(const float* y_s, const float* t_pred, float* dy_s, float* loss, int32_t B, int32_t K, int32_t ld_y, int32_t ld_dy, float temp,
+                           float grad_scale, int32_t accumulate, float* ws, int64_t ws_bytes, bool det, void* stream) {
+    mt4_clear_error();
+    if (!y_s || !t_pred || !dy_s || !loss || (det && !ws) || B <= 0 || K <= 0 || K > 128 || ld_y < K || ld_dy < K) return MT4_EINVAL;
+    const DetParts p = distill_kl_parts(B);
+    if (det && ws_bytes < p.bytes()) return MT4_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (!det) return mt4_launch<distill_kl_kernel<false>>(dim3(p.nparts), dim3(64), 0, s, y_s, t_pred, dy_s, loss, B, K, ld_y, ld_dy, temp, grad_scale, accumulate);
+    const int lc = mt4_launch<distill_kl_kernel<true>>(dim3(p.nparts), dim3(64), 0, s, y_s, t_pred, dy_s, ws, B, K, ld_y, ld_dy, temp, grad_scale, accumulate);
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_chunked_f32(ws, p.nparts, 1, 1, loss, 1, stream);
+}
+
+extern "C" int mt4_distill_kl_f32(const float* y_s, const float* t_pred, float* dy_s, float* loss, int32_t B, int32_t K, int32_t ld_y, int32_t ld_dy,
+                                  float temp, float grad_scale, int32_t accumulate, void* stream) {
+    return distill_kl_impl(y_s, t_pred, dy_s, loss, B, K, ld_y, ld_dy, temp, grad_scale, accumulate, nullptr, 0, false, stream);
 }
 
 extern "C" int mt4_distill_kl_det_f32(const float* y_s, const float* t_pred, float* dy_s, float* loss, int32_t B, int32_t K, int32_t ld_y, int32_t ld_dy,
                                       float temp, float grad_scale, int32_t accumulate, float* ws, int64_t ws_bytes, void* stream) {
-    mt4_clear_error();
-    if (!y_s || !t_pred || !dy_s || !loss || !ws || B <= 0 || K <= 0 || K > 128 || ld_y < K || ld_dy < K) return MT4_EINVAL;
-    if (ws_bytes < (long long)B * (long long)sizeof(float)) return MT4_EINVAL;
-    hipLaunchKernelGGL(distill_kl_kernel<true>, dim3(B), dim3(64), 0, (hipStream_t)stream, y_s, t_pred, dy_s, ws, B, K, ld_y, ld_dy, temp, grad_scale,
-                       accumulate);
-    const int lc = mt4_check_launch();
-    if (lc != MT4_OK) return lc;
-    return mt4_fold_parts_chunked_f32(ws, B, 1, 1, loss, 1, stream);
+    return distill_kl_impl(y_s, t_pred, dy_s, loss, B, K, ld_y, ld_dy, temp, grad_scale, accumulate, ws, ws_bytes, true, stream);
 }
 
 // MSELoss (mean): loss += sum (a-b)^2 / n ; da = scale * 2 (a-b) / n
@@ -890,32 +861,32 @@ __global__ void mse_kernel(const float* __restrict__ a, const float* __restrict_
     }
 }
 
-extern "C" int mt4_mse_f32(const float* a, const float* b, float* da, float* loss, int64_t n, float grad_scale, void* stream) {
-    mt4_clear_error();
-    if (!a || !b || !da || !loss || n <= 0) return MT4_EINVAL;
-    hipLaunchKernelGGL(mse_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, da, loss, (long long)n, grad_scale);
-    return mt4_check_launch();
-}
+static DetParts mse_parts(long long n) { return {0, (int32_t)((n + 255) / 256), 1, (int32_t)sizeof(float)}; }      // (the deterministic form bounds n first)
 
 extern "C" int mt4_mse_det_plan(int64_t n, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
     if (n <= 0 || (n + 255) / 256 > 0x7fffffff) return MT4_EINVAL;
-    if (form) *form = 0;
-    if (nparts) *nparts = (int32_t)((n + 255) / 256);
-    if (part_elems) *part_elems = 1;
-    if (ws_bytes) *ws_bytes = (n + 255) / 256 * (long long)sizeof(float);
-    return MT4_OK;
+    return det_plan_out(mse_parts(n), form, nparts, part_elems, ws_bytes);
+}
+
+static int mse_impl(const float* a, const float* b, float* da, float* loss, int64_t n, float grad_scale, float* ws, int64_t ws_bytes, bool det, void* stream) {
+    mt4_clear_error();
+    if (!a || !b || !da || !loss || (det && !ws) || n <= 0 || (det && (n + 255) / 256 > 0x7fffffff)) return MT4_EINVAL;
+    const DetParts p = mse_parts(n);
+    if (det && ws_bytes < p.bytes()) return MT4_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (!det) return mt4_launch<mse_kernel<false>>(dim3((unsigned)p.nparts), dim3(256), 0, s, a, b, da, loss, (long long)n, grad_scale);
+    const int lc = mt4_launch<mse_kernel<true>>(dim3((unsigned)p.nparts), dim3(256), 0, s, a, b, da, ws, (long long)n, grad_scale);
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_chunked_f32(ws, p.nparts, 1, 1, loss, 1, stream);
+}
+
+extern "C" int mt4_mse_f32(const float* a, const float* b, float* da, float* loss, int64_t n, float grad_scale, void* stream) {
+    return mse_impl(a, b, da, loss, n, grad_scale, nullptr, 0, false, stream);
 }
 
 extern "C" int mt4_mse_det_f32(const float* a, const float* b, float* da, float* loss, int64_t n, float grad_scale, float* ws, int64_t ws_bytes,
                                void* stream) {
-    mt4_clear_error();
-    if (!a || !b || !da || !loss || !ws || n <= 0 || (n + 255) / 256 > 0x7fffffff) return MT4_EINVAL;
-    const long long wgs = (n + 255) / 256;
-    if (ws_bytes < wgs * (long long)sizeof(float)) return MT4_EINVAL;
-    hipLaunchKernelGGL(mse_kernel<true>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, a, b, da, ws, (long long)n, grad_scale);
-    const int lc = mt4_check_launch();
-    if (lc != MT4_OK) return lc;
-    return mt4_fold_parts_chunked_f32(ws, (int32_t)wgs, 1, 1, loss, 1, stream);
+    return mse_impl(a, b, da, loss, n, grad_scale, ws, ws_bytes, true, stream);
 }
 
 // KD mixing backward (forward: mt4_kd_mix).  u_n = s a_n, a = softmax_n(l), l_n = s tau_n / sqrt(C), tau_n = sum_d tea_n[b][d].
@@ -961,6 +932,5 @@ extern "C" int mt4_kd_mix_bwd_f32(const float* s, const float* tea_i, const floa
                                   const float* g_t, float* ds, float* dtau, int32_t B, int32_t C, void* stream) {
     mt4_clear_error();
     if (!s || !tea_i || !tea_v || !tea_t || !g_i || !g_v || !g_t || !ds || !dtau || B <= 0 || C <= 0) return MT4_EINVAL;
-    hipLaunchKernelGGL(kd_mix_bwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, s, tea_i, tea_v, tea_t, g_i, g_v, g_t, ds, dtau, C);
-    return mt4_check_launch();
+    return mt4_launch<kd_mix_bwd_kernel>(dim3(B), dim3(256), 0, (hipStream_t)stream, s, tea_i, tea_v, tea_t, g_i, g_v, g_t, ds, dtau, C);
 }

@@ -2,6 +2,7 @@
 // bias gradient, BCE-with-logits loss + gradient, SGD update, and the small element-wise pieces.  fp32 throughout
 // (the reference trains in fp32); the data gradients reuse the forward implicit-GEMM kernel with transposed weights.
 #include "mt4_common.h"
+#include "det_parts.h"
 
 // ------------------------------------------------------------------------------------------------ conv1d weight gradient
 // dW[co][tap*Cin + ci] (+)= sum_{b,t} dY[b,t][co] * X[b, t + tap*dil - pad][ci]        (zero outside [0,T))
@@ -124,77 +125,71 @@ __global__ void zero_f32_kernel(float* __restrict__ p, long long n) {
     const long long t0 = head + nv * 4;
     if (i < 4 && t0 + i < n) p[t0 + i] = 0.f;
 }
-static inline void zero_f32(float* p, long long n, hipStream_t s) {
-    hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, s, p, n);
+static inline int zero_f32(float* p, long long n, hipStream_t s) {
+    return mt4_launch<zero_f32_kernel>(dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, s, p, n);
 }
 
-// the time split of a conv1d weight gradient: `splits` workgroups per dW tile, each over `rps` rows (a multiple of the 32-row chunk)
-static void wgrad_conv1d_split(long long M, int Kpad, int Cout, long long* splits_out, long long* rps_out) {
+// the parts of a conv1d weight gradient = its time split: `nparts` workgroups per 64 x 64 dW tile (one launch form), each over `rps` rows (a
+// multiple of the 32-row chunk); a part is an image of the packed dW, with the bias gradient's Cout sums behind it where there is one
+static DetParts wgrad_conv1d_parts(long long M, int Cout, int Cin, int taps, bool with_bias, int* Kpad_out, long long* rps_out) {
+    const int Kpad = (int)mt4_conv_packed_k(Cin, 1, taps, MT4_F32);
     const long long max_splits = (M + 255) / 256;              // at least 256 rows per split
     const int tiles = cdiv(Kpad, 64) * cdiv(Cout, 64);
     long long splits = (1024 + tiles - 1) / tiles;            // ~4 workgroups per CU in total
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     const long long rps = ((M + splits - 1) / splits + 31) / 32 * 32;
-    *splits_out = (M + rps - 1) / rps;
+    *Kpad_out = Kpad;
     *rps_out = rps;
-}
-
-extern "C" int mt4_wgrad_conv1d_f32(const float* dy, const float* x, float* dw_packed, int32_t B, int32_t T, int32_t Cout, int32_t Cin,
-                                    int32_t taps, int32_t dil, int32_t pad, int32_t accumulate, float* bias_grad, void* stream) {
-    mt4_clear_error();
-    if (!dy || !x || !dw_packed || B <= 0 || T <= 0 || Cout <= 0 || Cin <= 0 || taps <= 0 || dil <= 0 || pad < 0) return MT4_EINVAL;
-    if (Cin % 4 || Cout % 4 || (((uintptr_t)dy | (uintptr_t)x) & 15)) return MT4_EALIGN;
-    const int Kpad = (int)mt4_conv_packed_k(Cin, 1, taps, MT4_F32);
-    hipStream_t s = (hipStream_t)stream;
-    long long splits, rps;
-    wgrad_conv1d_split((long long)B * T, Kpad, Cout, &splits, &rps);
-    if (splits > 1 && !accumulate) zero_f32(dw_packed, (long long)Cout * Kpad, s);
-    const dim3 grid(cdiv(Kpad, 64), cdiv(Cout, 64), (unsigned)splits);
-    hipLaunchKernelGGL(wgrad_conv1d_f32_kernel<false>, grid, dim3(256), 0, s, dy, x, dw_packed, B, T, Cout, Cin, taps, dil, pad, Kpad, accumulate, rps, bias_grad);
-    return mt4_check_launch();
+    return {0, (int32_t)((M + rps - 1) / rps), (long long)Cout * Kpad + (with_bias ? Cout : 0), (int32_t)sizeof(float)};
 }
 
 extern "C" int mt4_wgrad_conv1d_det_plan(int32_t B, int32_t T, int32_t Cout, int32_t Cin, int32_t taps, int32_t with_bias, int32_t* form, int32_t* nparts,
                                          int64_t* part_elems, int64_t* ws_bytes) {
     if (B <= 0 || T <= 0 || Cout <= 0 || Cin <= 0 || taps <= 0) return MT4_EINVAL;
     if (Cin % 4 || Cout % 4) return MT4_EALIGN;
-    const int Kpad = (int)mt4_conv_packed_k(Cin, 1, taps, MT4_F32);
-    long long splits, rps;
-    wgrad_conv1d_split((long long)B * T, Kpad, Cout, &splits, &rps);
-    const long long pe = (long long)Cout * Kpad + (with_bias ? Cout : 0);
-    if (form) *form = 0;                                     // one launch form: 64 x 64 tiles of dW, the rows split over gridDim.z
-    if (nparts) *nparts = (int32_t)splits;
-    if (part_elems) *part_elems = pe;
-    if (ws_bytes) *ws_bytes = splits * pe * (long long)sizeof(float);
-    return MT4_OK;
+    int Kpad;
+    long long rps;
+    return det_plan_out(wgrad_conv1d_parts((long long)B * T, Cout, Cin, taps, with_bias != 0, &Kpad, &rps), form, nparts, part_elems, ws_bytes);
+}
+
+static int wgrad_conv1d_impl(const float* dy, const float* x, float* dw_packed, int32_t B, int32_t T, int32_t Cout, int32_t Cin, int32_t taps, int32_t dil,
+                             int32_t pad, int32_t accumulate, float* bias_grad, float* ws, int64_t ws_bytes, bool det, void* stream) {
+    mt4_clear_error();
+    if (!dy || !x || !dw_packed || (det && !ws) || B <= 0 || T <= 0 || Cout <= 0 || Cin <= 0 || taps <= 0 || dil <= 0 || pad < 0) return MT4_EINVAL;
+    if (Cin % 4 || Cout % 4 || (((uintptr_t)dy | (uintptr_t)x | (det ? (uintptr_t)ws : 0)) & 15)) return MT4_EALIGN;
+    int Kpad;
+    long long rps;
+    const DetParts p = wgrad_conv1d_parts((long long)B * T, Cout, Cin, taps, bias_grad != nullptr, &Kpad, &rps);
+    if (det && ws_bytes < p.bytes()) return MT4_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(cdiv(Kpad, 64), cdiv(Cout, 64), (unsigned)p.nparts);
+    const long long nw = (long long)Cout * Kpad, pe = p.part_elems;
+    if (!det) {
+        if (p.nparts > 1 && !accumulate) {
+            const int zc = zero_f32(dw_packed, nw, s);
+            if (zc != MT4_OK) return zc;
+        }
+        return mt4_launch<wgrad_conv1d_f32_kernel<false>>(grid, dim3(256), 0, s, dy, x, dw_packed, B, T, Cout, Cin, taps, dil, pad, Kpad, accumulate, rps, bias_grad);
+    }
+    const int lc = mt4_launch<wgrad_conv1d_f32_kernel<true>>(grid, dim3(256), 0, s, dy, x, ws, B, T, Cout, Cin, taps, dil, pad, Kpad, 0, rps, bias_grad);
+    if (lc != MT4_OK) return lc;
+    // fold order (the contract): parts z = 0 .. nparts-1 (ascending row ranges) summed front to back, then added to dW (accumulate) / stored, and
+    // ADDED to bias_grad -- one launch where the bias gradient lies right behind dW and both accumulate (the trainers' flat gradient buffer)
+    if (bias_grad && accumulate && bias_grad == dw_packed + nw) return mt4_fold_parts_f32(ws, p.nparts, pe, pe, dw_packed, 1, stream);
+    const int fc = mt4_fold_parts_f32(ws, p.nparts, nw, pe, dw_packed, accumulate, stream);
+    if (fc != MT4_OK || !bias_grad) return fc;
+    return mt4_fold_parts_f32(ws + nw, p.nparts, Cout, pe, bias_grad, 1, stream);
+}
+
+extern "C" int mt4_wgrad_conv1d_f32(const float* dy, const float* x, float* dw_packed, int32_t B, int32_t T, int32_t Cout, int32_t Cin,
+                                    int32_t taps, int32_t dil, int32_t pad, int32_t accumulate, float* bias_grad, void* stream) {
+    return wgrad_conv1d_impl(dy, x, dw_packed, B, T, Cout, Cin, taps, dil, pad, accumulate, bias_grad, nullptr, 0, false, stream);
 }
 
 extern "C" int mt4_wgrad_conv1d_det_f32(const float* dy, const float* x, float* dw_packed, int32_t B, int32_t T, int32_t Cout, int32_t Cin, int32_t taps,
                                         int32_t dil, int32_t pad, int32_t accumulate, float* bias_grad, float* ws, int64_t ws_bytes, void* stream) {
-    mt4_clear_error();
-    if (!dy || !x || !dw_packed || !ws || B <= 0 || T <= 0 || Cout <= 0 || Cin <= 0 || taps <= 0 || dil <= 0 || pad < 0) return MT4_EINVAL;
-    if (Cin % 4 || Cout % 4 || (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)ws) & 15)) return MT4_EALIGN;
-    int32_t nparts;
-    int64_t pe, need;
-    const int rc = mt4_wgrad_conv1d_det_plan(B, T, Cout, Cin, taps, bias_grad != nullptr, nullptr, &nparts, &pe, &need);
-    if (rc != MT4_OK) return rc;
-    if (ws_bytes < need) return MT4_EINVAL;
-    const int Kpad = (int)mt4_conv_packed_k(Cin, 1, taps, MT4_F32);
-    hipStream_t s = (hipStream_t)stream;
-    long long splits, rps;
-    wgrad_conv1d_split((long long)B * T, Kpad, Cout, &splits, &rps);
-    const dim3 grid(cdiv(Kpad, 64), cdiv(Cout, 64), (unsigned)splits);
-    hipLaunchKernelGGL(wgrad_conv1d_f32_kernel<true>, grid, dim3(256), 0, s, dy, x, ws, B, T, Cout, Cin, taps, dil, pad, Kpad, 0, rps, bias_grad);
-    const int lc = mt4_check_launch();
-    if (lc != MT4_OK) return lc;
-    // fold order (the contract): parts z = 0 .. nparts-1 (ascending row ranges) summed front to back, then added to dW (accumulate) / stored, and
-    // ADDED to bias_grad -- one launch where the bias gradient lies right behind dW and both accumulate (the trainers' flat gradient buffer)
-    const long long nw = (long long)Cout * Kpad;
-    if (bias_grad && accumulate && bias_grad == dw_packed + nw) return mt4_fold_parts_f32(ws, nparts, pe, pe, dw_packed, 1, stream);
-    const int fc = mt4_fold_parts_f32(ws, nparts, nw, pe, dw_packed, accumulate, stream);
-    if (fc != MT4_OK || !bias_grad) return fc;
-    return mt4_fold_parts_f32(ws + nw, nparts, Cout, pe, bias_grad, 1, stream);
+    return wgrad_conv1d_impl(dy, x, dw_packed, B, T, Cout, Cin, taps, dil, pad, accumulate, bias_grad, ws, ws_bytes, true, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ column sums (bias gradient)
@@ -218,44 +213,45 @@ __global__ __launch_bounds__(256) void colsum_f32_kernel(const float* __restrict
     }
 }
 
-static long long colsum_slabs(long long M, int C) {
+static DetParts colsum_parts(long long M, int C) {            // a part: the C sums of one row slab
     long long slabs = (M + 63) / 64;                     // >= 16 rows per wave and slab
     const long long cap = (1024 + cdiv(C, 64) - 1) / cdiv(C, 64);
     if (slabs > cap) slabs = cap;
-    return slabs < 1 ? 1 : slabs;
-}
-
-extern "C" int mt4_colsum_f32(const float* x, float* out, int64_t M, int32_t C, int32_t ld, int32_t accumulate, void* stream) {
-    mt4_clear_error();
-    if (!x || !out || M <= 0 || C <= 0 || ld < C) return MT4_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    if (!accumulate) zero_f32(out, C, s);      // (any float-aligned `out`: bias slices of a flat gradient buffer)
-    const long long slabs = colsum_slabs(M, C);
-    hipLaunchKernelGGL(colsum_f32_kernel<false>, dim3(cdiv(C, 64), (unsigned)slabs), dim3(256), 0, s, x, out, (long long)M, C, ld);
-    return mt4_check_launch();
+    return {0, (int32_t)(slabs < 1 ? 1 : slabs), C, (int32_t)sizeof(float)};
 }
 
 extern "C" int mt4_colsum_det_plan(int64_t M, int32_t C, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
     if (M <= 0 || C <= 0) return MT4_EINVAL;
-    const long long slabs = colsum_slabs(M, C);
-    if (form) *form = 0;
-    if (nparts) *nparts = (int32_t)slabs;
-    if (part_elems) *part_elems = C;
-    if (ws_bytes) *ws_bytes = slabs * C * (long long)sizeof(float);
-    return MT4_OK;
+    return det_plan_out(colsum_parts(M, C), form, nparts, part_elems, ws_bytes);
 }
 
 // fold order (the contract): row slabs y = 0 .. nparts-1 (slab y holds the rows m with (m / 4) % nparts == y) front to back, then added to / stored in `out`
+static int colsum_impl(const float* x, float* out, int64_t M, int32_t C, int32_t ld, int32_t accumulate, float* ws, int64_t ws_bytes, bool det, void* stream) {
+    mt4_clear_error();
+    if (!x || !out || (det && !ws) || M <= 0 || C <= 0 || ld < C) return MT4_EINVAL;
+    const DetParts p = colsum_parts(M, C);
+    if (det && ws_bytes < p.bytes()) return MT4_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(cdiv(C, 64), (unsigned)p.nparts);
+    if (!det) {
+        if (!accumulate) {                      // (any float-aligned `out`: bias slices of a flat gradient buffer)
+            const int zc = zero_f32(out, C, s);
+            if (zc != MT4_OK) return zc;
+        }
+        return mt4_launch<colsum_f32_kernel<false>>(grid, dim3(256), 0, s, x, out, (long long)M, C, ld);
+    }
+    const int lc = mt4_launch<colsum_f32_kernel<true>>(grid, dim3(256), 0, s, x, ws, (long long)M, C, ld);
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_f32(ws, p.nparts, C, C, out, accumulate, stream);
+}
+
+extern "C" int mt4_colsum_f32(const float* x, float* out, int64_t M, int32_t C, int32_t ld, int32_t accumulate, void* stream) {
+    return colsum_impl(x, out, M, C, ld, accumulate, nullptr, 0, false, stream);
+}
+
 extern "C" int mt4_colsum_det_f32(const float* x, float* out, int64_t M, int32_t C, int32_t ld, int32_t accumulate, float* ws, int64_t ws_bytes,
                                   void* stream) {
-    mt4_clear_error();
-    if (!x || !out || !ws || M <= 0 || C <= 0 || ld < C) return MT4_EINVAL;
-    const long long slabs = colsum_slabs(M, C);
-    if (ws_bytes < slabs * C * (long long)sizeof(float)) return MT4_EINVAL;
-    hipLaunchKernelGGL(colsum_f32_kernel<true>, dim3(cdiv(C, 64), (unsigned)slabs), dim3(256), 0, (hipStream_t)stream, x, ws, (long long)M, C, ld);
-    const int lc = mt4_check_launch();
-    if (lc != MT4_OK) return lc;
-    return mt4_fold_parts_f32(ws, (int32_t)slabs, C, C, out, accumulate, stream);
+    return colsum_impl(x, out, M, C, ld, accumulate, ws, ws_bytes, true, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ BCE with logits: loss + gradient
@@ -287,43 +283,39 @@ __global__ __launch_bounds__(256) void bce_logits_kernel(const float* __restrict
     }
 }
 
-static int bce_logits_slabs(long long M) {
+static DetParts bce_logits_parts(long long M, int N) {        // a part: the N sums of one row slab
     const long long gy = (M + 63) / 64;
-    return gy > 64 ? 64 : (int)gy;
-}
-
-extern "C" int mt4_bce_logits_f32(const float* y, const float* z, const float* col_scale, float* dy, float* col_loss, int64_t M, int32_t N,
-                                  int32_t ld_y, int32_t ld_dy, void* stream) {
-    mt4_clear_error();
-    if (!y || !z || !col_scale || !dy || !col_loss || M <= 0 || N <= 0 || ld_y < N || ld_dy < N) return MT4_EINVAL;
-    const int gy = bce_logits_slabs(M);
-    hipLaunchKernelGGL(bce_logits_kernel<false>, dim3(cdiv(N, 64), gy), dim3(256), 0, (hipStream_t)stream, y, z, col_scale, dy, col_loss,
-                       (long long)M, N, ld_y, ld_dy);
-    return mt4_check_launch();
+    return {0, gy > 64 ? 64 : (int32_t)gy, N, (int32_t)sizeof(float)};
 }
 
 extern "C" int mt4_bce_logits_det_plan(int64_t M, int32_t N, int32_t* form, int32_t* nparts, int64_t* part_elems, int64_t* ws_bytes) {
     if (M <= 0 || N <= 0) return MT4_EINVAL;
-    const int gy = bce_logits_slabs(M);
-    if (form) *form = 0;
-    if (nparts) *nparts = gy;
-    if (part_elems) *part_elems = N;
-    if (ws_bytes) *ws_bytes = (long long)gy * N * (long long)sizeof(float);
-    return MT4_OK;
+    return det_plan_out(bce_logits_parts(M, N), form, nparts, part_elems, ws_bytes);
 }
 
 // fold order (the contract): row slabs y = 0 .. nparts-1 (slab y holds the rows m with (m / 4) % nparts == y) front to back, then ADDED to col_loss
+static int bce_logits_impl(const float* y, const float* z, const float* col_scale, float* dy, float* col_loss, int64_t M, int32_t N, int32_t ld_y,
+                           int32_t ld_dy, float* ws, int64_t ws_bytes, bool det, void* stream) {
+    mt4_clear_error();
+    if (!y || !z || !col_scale || !dy || !col_loss || (det && !ws) || M <= 0 || N <= 0 || ld_y < N || ld_dy < N) return MT4_EINVAL;
+    const DetParts p = bce_logits_parts(M, N);
+    if (det && ws_bytes < p.bytes()) return MT4_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(cdiv(N, 64), p.nparts);
+    if (!det) return mt4_launch<bce_logits_kernel<false>>(grid, dim3(256), 0, s, y, z, col_scale, dy, col_loss, (long long)M, N, ld_y, ld_dy);
+    const int lc = mt4_launch<bce_logits_kernel<true>>(grid, dim3(256), 0, s, y, z, col_scale, dy, ws, (long long)M, N, ld_y, ld_dy);
+    if (lc != MT4_OK) return lc;
+    return mt4_fold_parts_f32(ws, p.nparts, N, N, col_loss, 1, stream);
+}
+
+extern "C" int mt4_bce_logits_f32(const float* y, const float* z, const float* col_scale, float* dy, float* col_loss, int64_t M, int32_t N,
+                                  int32_t ld_y, int32_t ld_dy, void* stream) {
+    return bce_logits_impl(y, z, col_scale, dy, col_loss, M, N, ld_y, ld_dy, nullptr, 0, false, stream);
+}
+
 extern "C" int mt4_bce_logits_det_f32(const float* y, const float* z, const float* col_scale, float* dy, float* col_loss, int64_t M, int32_t N,
                                       int32_t ld_y, int32_t ld_dy, float* ws, int64_t ws_bytes, void* stream) {
-    mt4_clear_error();
-    if (!y || !z || !col_scale || !dy || !col_loss || !ws || M <= 0 || N <= 0 || ld_y < N || ld_dy < N) return MT4_EINVAL;
-    const int gy = bce_logits_slabs(M);
-    if (ws_bytes < (long long)gy * N * (long long)sizeof(float)) return MT4_EINVAL;
-    hipLaunchKernelGGL(bce_logits_kernel<true>, dim3(cdiv(N, 64), gy), dim3(256), 0, (hipStream_t)stream, y, z, col_scale, dy, ws, (long long)M, N,
-                       ld_y, ld_dy);
-    const int lc = mt4_check_launch();
-    if (lc != MT4_OK) return lc;
-    return mt4_fold_parts_f32(ws, gy, N, N, col_loss, 1, stream);
+    return bce_logits_impl(y, z, col_scale, dy, col_loss, M, N, ld_y, ld_dy, ws, ws_bytes, true, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ SGD (no momentum) and element-wise pieces
@@ -346,9 +338,7 @@ extern "C" int mt4_sgd_step_f32(float* p, const float* g, int64_t n, float lr, f
     if (!p || !g || n <= 0) return MT4_EINVAL;
     if (((uintptr_t)p | (uintptr_t)g) & 15) return MT4_EALIGN;
     const long long threads = (n + 3) / 4;
-    hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, (long long)n, lr, weight_decay,
-                       grad_scale);
-    return mt4_check_launch();
+    return mt4_launch<sgd_kernel>(dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, (long long)n, lr, weight_decay, grad_scale);
 }
 
 // y = a * b (+ c)   element-wise fp32: dropout masks forward (z + o*m) and backward (df*m)
@@ -361,8 +351,7 @@ __global__ void mul_add_kernel(const float* __restrict__ a, const float* __restr
 extern "C" int mt4_mul_add_f32(const float* a, const float* b, const float* c, float* y, int64_t n, void* stream) {
     mt4_clear_error();
     if (!a || !b || !y || n <= 0) return MT4_EINVAL;
-    hipLaunchKernelGGL(mul_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, c, y, (long long)n);
-    return mt4_check_launch();
+    return mt4_launch<mul_add_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, c, y, (long long)n);
 }
 
 // packed conv1d weight [Cout][Kpad] (row = taps x CPT chunks) -> the data-gradient operator's packed weight
@@ -385,7 +374,6 @@ extern "C" int mt4_transpose_pack_conv1d_f32(const float* w_packed, float* wt_pa
     const int Kpad = (int)mt4_conv_packed_k(Cin, 1, taps, MT4_F32), KpadT = (int)mt4_conv_packed_k(Cout, 1, taps, MT4_F32);
     const int tapw_src = ((Cin * 4 + 15) / 16) * 4, tapw_dst = ((Cout * 4 + 15) / 16) * 4;   // elements per tap incl. chunk padding
     const long long total = (long long)Cin * KpadT;
-    hipLaunchKernelGGL(transpose_pack_conv1d_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_packed, wt_packed,
-                       Cout, Cin, taps, Kpad, KpadT, tapw_src, tapw_dst);
-    return mt4_check_launch();
+    return mt4_launch<transpose_pack_conv1d_kernel>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_packed, wt_packed, Cout, Cin,
+                                                    taps, Kpad, KpadT, tapw_src, tapw_dst);
 }

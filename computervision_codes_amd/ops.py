@@ -931,6 +931,17 @@ def check_workspace(ws: torch.Tensor, plan: DetPlan, what: str):
     return ws.data_ptr(), nbytes
 
 
+def _launch_form(atomic: str, det: str, args: tuple, workspace: Optional[torch.Tensor], plan, what: str, det_args: tuple = ()) -> None:
+    """one launch of a training reduction in either form, from ONE argument list: the symbol `atomic` without a workspace; with one, `det` -- after
+    `check_workspace` against the op's plan (`plan()`, host-only) -- with `det_args` and the workspace's (pointer, bytes) behind the shared arguments.
+    The stream goes last; a failure is reported under the name of the symbol called.  (`lib` is the module global, read at call time.)"""
+    if workspace is None:
+        name = atomic
+    else:
+        name, args = det, args + det_args + check_workspace(workspace, plan(), what)
+    check(getattr(lib, name)(*args, _stream()), name)
+
+
 FOLD_CHUNKS = 16      # MT4_FOLD_CHUNKS
 
 
@@ -971,14 +982,10 @@ def wgrad_conv1d(dy: torch.Tensor, x: torch.Tensor, dw_packed: torch.Tensor, *, 
     cout, cin = dy.shape[-1], x.shape[-1]
     assert dw_packed.shape == (cout, packed_k(cin, 1, taps, torch.float32)) and dy.numel() == batch * t * cout
     assert bias_grad is None or (bias_grad.dtype == torch.float32 and bias_grad.numel() >= cout)
-    gb = bias_grad.data_ptr() if bias_grad is not None else None
-    if workspace is not None:
-        ws, nbytes = check_workspace(workspace, wgrad_conv1d_plan(batch, t, cout, cin, taps, bias_grad is not None), "wgrad_conv1d")
-        check(lib.mt4_wgrad_conv1d_det_f32(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), batch, t, cout, cin, taps, dil, pad,
-                                           1 if accumulate else 0, gb, ws, nbytes, _stream()), "mt4_wgrad_conv1d_det_f32")
-        return
-    check(lib.mt4_wgrad_conv1d_f32(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), batch, t, cout, cin, taps, dil, pad,
-                                   1 if accumulate else 0, gb, _stream()), "mt4_wgrad_conv1d_f32")
+    args = (dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), batch, t, cout, cin, taps, dil, pad, 1 if accumulate else 0,
+            bias_grad.data_ptr() if bias_grad is not None else None)
+    _launch_form("mt4_wgrad_conv1d_f32", "mt4_wgrad_conv1d_det_f32", args, workspace,
+                 lambda: wgrad_conv1d_plan(batch, t, cout, cin, taps, bias_grad is not None), "wgrad_conv1d")
 
 
 def colsum(x2d: torch.Tensor, out: torch.Tensor, accumulate: bool = False, workspace: Optional[torch.Tensor] = None) -> None:
@@ -986,12 +993,8 @@ def colsum(x2d: torch.Tensor, out: torch.Tensor, accumulate: bool = False, works
     _need_cuda(x2d, out)
     assert x2d.dtype == out.dtype == torch.float32 and x2d.stride(-1) == 1
     m, c = x2d.shape
-    if workspace is not None:
-        ws, nbytes = check_workspace(workspace, colsum_plan(m, out.numel()), "colsum")
-        check(lib.mt4_colsum_det_f32(x2d.data_ptr(), out.data_ptr(), m, out.numel(), x2d.stride(0), 1 if accumulate else 0, ws, nbytes, _stream()),
-              "mt4_colsum_det_f32")
-        return
-    check(lib.mt4_colsum_f32(x2d.data_ptr(), out.data_ptr(), m, out.numel(), x2d.stride(0), 1 if accumulate else 0, _stream()), "mt4_colsum_f32")
+    _launch_form("mt4_colsum_f32", "mt4_colsum_det_f32", (x2d.data_ptr(), out.data_ptr(), m, out.numel(), x2d.stride(0), 1 if accumulate else 0), workspace,
+                 lambda: colsum_plan(m, out.numel()), "colsum")
 
 
 def bce_logits(y: torch.Tensor, z: torch.Tensor, col_scale: torch.Tensor, dy: torch.Tensor, col_loss: torch.Tensor,
@@ -1001,13 +1004,8 @@ def bce_logits(y: torch.Tensor, z: torch.Tensor, col_scale: torch.Tensor, dy: to
     _need_cuda(y, z, col_scale, dy, col_loss)
     m, n = z.shape
     assert z.is_contiguous() and y.stride(-1) == 1 and dy.stride(-1) == 1
-    if workspace is not None:
-        ws, nbytes = check_workspace(workspace, bce_logits_plan(m, n), "bce_logits")
-        check(lib.mt4_bce_logits_det_f32(y.data_ptr(), z.data_ptr(), col_scale.data_ptr(), dy.data_ptr(), col_loss.data_ptr(), m, n, y.stride(0),
-                                         dy.stride(0), ws, nbytes, _stream()), "mt4_bce_logits_det_f32")
-        return
-    check(lib.mt4_bce_logits_f32(y.data_ptr(), z.data_ptr(), col_scale.data_ptr(), dy.data_ptr(), col_loss.data_ptr(), m, n, y.stride(0),
-                                 dy.stride(0), _stream()), "mt4_bce_logits_f32")
+    args = (y.data_ptr(), z.data_ptr(), col_scale.data_ptr(), dy.data_ptr(), col_loss.data_ptr(), m, n, y.stride(0), dy.stride(0))
+    _launch_form("mt4_bce_logits_f32", "mt4_bce_logits_det_f32", args, workspace, lambda: bce_logits_plan(m, n), "bce_logits")
 
 
 def sgd_step(p: torch.Tensor, g: torch.Tensor, lr: float, weight_decay: float, grad_scale: float = 1.0) -> None:
@@ -1283,13 +1281,9 @@ def bn_stats(x2d, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, s
     assert sums.dtype == torch.float64 and sums.numel() == 2 * c
     mean, invstd = torch.empty(c, device=x2d.device), torch.empty(c, device=x2d.device)
     rm, rv = (running_mean.data_ptr() if running_mean is not None else None), (running_var.data_ptr() if running_var is not None else None)
-    if workspace is not None:      # the deterministic form (`bn_plan(m, c).bytes`): slab sums stored and folded in slab order into `sums`
-        ws, nbytes = check_workspace(workspace, bn_plan(m, c), "bn_stats")
-        check(lib.mt4_bn_stats_det_f32(x2d.data_ptr(), sums.data_ptr(), mean.data_ptr(), invstd.data_ptr(), rm, rv, m, c, momentum, eps, ws, nbytes,
-                                       _stream()), "mt4_bn_stats_det_f32")
-        return mean, invstd
-    check(lib.mt4_bn_stats_f32(x2d.data_ptr(), sums.data_ptr(), mean.data_ptr(), invstd.data_ptr(), rm, rv, m, c, momentum, eps, _stream()),
-          "mt4_bn_stats_f32")
+    # workspace: the deterministic form (`bn_plan(m, c).bytes`): slab sums stored and folded in slab order into `sums`
+    _launch_form("mt4_bn_stats_f32", "mt4_bn_stats_det_f32", (x2d.data_ptr(), sums.data_ptr(), mean.data_ptr(), invstd.data_ptr(), rm, rv, m, c, momentum, eps),
+                 workspace, lambda: bn_plan(m, c), "bn_stats")
     return mean, invstd
 
 
@@ -1315,11 +1309,7 @@ def bn_backward(dy, y_post, x2d, mean, invstd, gamma, dgamma, dbeta, relu=True, 
     args = (dy.data_ptr(), y_post.data_ptr() if (y_post is not None and code == 1) else None, x2d.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
             gamma.data_ptr(), beta.data_ptr() if beta is not None else None, sums.data_ptr(), dx.data_ptr(), dres.data_ptr() if want_dres else None,
             dgamma.data_ptr(), dbeta.data_ptr(), m, c, code)
-    if workspace is not None:      # the deterministic form (`bn_plan(m, c).bytes`)
-        ws, nbytes = check_workspace(workspace, bn_plan(m, c), "bn_backward")
-        check(lib.mt4_bn_backward_det_f32(*args, ws, nbytes, _stream()), "mt4_bn_backward_det_f32")
-        return dx, dres
-    check(lib.mt4_bn_backward_f32(*args, _stream()), "mt4_bn_backward_f32")
+    _launch_form("mt4_bn_backward_f32", "mt4_bn_backward_det_f32", args, workspace, lambda: bn_plan(m, c), "bn_backward")      # (workspace: `bn_plan(m, c).bytes`)
     return dx, dres
 
 
@@ -1331,15 +1321,11 @@ def wgrad_conv2d(dy, x, dw_packed, kh, kw, stride, pad, dil=(1, 1), zero=True, w
     b, ho, wo, cout = dy.shape
     _, h, w, cin = x.shape
     assert dw_packed.shape == (cout, packed_k(cin, kh, kw, torch.float32)) and dy.is_contiguous() and x.is_contiguous()
-    if workspace is not None:
-        ws, nbytes = check_workspace(workspace, wgrad_conv2d_plan(b, ho, wo, cout, cin, kh, kw), "wgrad_conv2d")
-        check(lib.mt4_wgrad_conv2d_det_f32(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), b, h, w, cin, ho, wo, cout, kh, kw, stride[0], stride[1],
-                                           pad[0], pad[1], dil[0], dil[1], 0 if zero else 1, ws, nbytes, _stream()), "mt4_wgrad_conv2d_det_f32")
-        return
-    if zero:
+    if zero and workspace is None:
         dw_packed.zero_()
-    check(lib.mt4_wgrad_conv2d_f32(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), b, h, w, cin, ho, wo, cout, kh, kw, stride[0], stride[1],
-                                   pad[0], pad[1], dil[0], dil[1], _stream()), "mt4_wgrad_conv2d_f32")
+    args = (dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), b, h, w, cin, ho, wo, cout, kh, kw, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1])
+    _launch_form("mt4_wgrad_conv2d_f32", "mt4_wgrad_conv2d_det_f32", args, workspace, lambda: wgrad_conv2d_plan(b, ho, wo, cout, cin, kh, kw), "wgrad_conv2d",
+                 det_args=(0 if zero else 1,))
 
 
 def maxpool3x3s2_bwd(x, dy, gather=False):
@@ -1364,35 +1350,22 @@ def avgpool_bwd(dfeat, b, hw, c):
 
 def bce_logits_pw(y, z, pos_weight, col_scale, dy, col_loss, workspace=None):
     m, n = z.shape
-    if workspace is not None:      # the deterministic form (`bce_logits_pw_plan(m, n).bytes`)
-        ws, nbytes = check_workspace(workspace, bce_logits_pw_plan(m, n), "bce_logits_pw")
-        check(lib.mt4_bce_logits_pw_det_f32(y.data_ptr(), z.data_ptr(), pos_weight.data_ptr() if pos_weight is not None else None, col_scale.data_ptr(),
-                                            dy.data_ptr(), col_loss.data_ptr(), m, n, y.stride(0), dy.stride(0), ws, nbytes, _stream()),
-              "mt4_bce_logits_pw_det_f32")
-        return
-    check(lib.mt4_bce_logits_pw_f32(y.data_ptr(), z.data_ptr(), pos_weight.data_ptr() if pos_weight is not None else None, col_scale.data_ptr(),
-                                    dy.data_ptr(), col_loss.data_ptr(), m, n, y.stride(0), dy.stride(0), _stream()), "mt4_bce_logits_pw_f32")
+    args = (y.data_ptr(), z.data_ptr(), pos_weight.data_ptr() if pos_weight is not None else None, col_scale.data_ptr(), dy.data_ptr(), col_loss.data_ptr(),
+            m, n, y.stride(0), dy.stride(0))
+    _launch_form("mt4_bce_logits_pw_f32", "mt4_bce_logits_pw_det_f32", args, workspace, lambda: bce_logits_pw_plan(m, n), "bce_logits_pw")      # (workspace: the plan's bytes)
 
 
 def distill_kl(y_s, t_pred, dy_s, loss, temp, grad_scale, accumulate=True, workspace=None):
     b, k = t_pred.shape
     assert t_pred.is_contiguous() and t_pred.shape == y_s.shape      # the kernel reads t_pred with pitch K; y_s / dy_s carry their own pitches
-    if workspace is not None:      # the deterministic form (`distill_kl_plan(b, k).bytes`)
-        ws, nbytes = check_workspace(workspace, distill_kl_plan(b, k), "distill_kl")
-        check(lib.mt4_distill_kl_det_f32(y_s.data_ptr(), t_pred.data_ptr(), dy_s.data_ptr(), loss.data_ptr(), b, k, y_s.stride(0), dy_s.stride(0), temp,
-                                         grad_scale, 1 if accumulate else 0, ws, nbytes, _stream()), "mt4_distill_kl_det_f32")
-        return
-    check(lib.mt4_distill_kl_f32(y_s.data_ptr(), t_pred.data_ptr(), dy_s.data_ptr(), loss.data_ptr(), b, k, y_s.stride(0), dy_s.stride(0), temp,
-                                 grad_scale, 1 if accumulate else 0, _stream()), "mt4_distill_kl_f32")
+    args = (y_s.data_ptr(), t_pred.data_ptr(), dy_s.data_ptr(), loss.data_ptr(), b, k, y_s.stride(0), dy_s.stride(0), temp, grad_scale, 1 if accumulate else 0)
+    _launch_form("mt4_distill_kl_f32", "mt4_distill_kl_det_f32", args, workspace, lambda: distill_kl_plan(b, k), "distill_kl")      # (workspace: the plan's bytes)
 
 
 def mse(a, b, loss, grad_scale, workspace=None):
     da = torch.empty_like(a)
-    if workspace is not None:      # the deterministic form (`mse_plan(n).bytes`)
-        ws, nbytes = check_workspace(workspace, mse_plan(a.numel()), "mse")
-        check(lib.mt4_mse_det_f32(a.data_ptr(), b.data_ptr(), da.data_ptr(), loss.data_ptr(), a.numel(), grad_scale, ws, nbytes, _stream()), "mt4_mse_det_f32")
-        return da
-    check(lib.mt4_mse_f32(a.data_ptr(), b.data_ptr(), da.data_ptr(), loss.data_ptr(), a.numel(), grad_scale, _stream()), "mt4_mse_f32")
+    _launch_form("mt4_mse_f32", "mt4_mse_det_f32", (a.data_ptr(), b.data_ptr(), da.data_ptr(), loss.data_ptr(), a.numel(), grad_scale), workspace,
+                 lambda: mse_plan(a.numel()), "mse")      # (workspace: `mse_plan(n).bytes`)
     return da
 
 
@@ -1472,11 +1445,7 @@ def bn_stats_t(x2d, running_mean=None, running_var=None, momentum=0.1, eps=1e-5,
     mean, invstd = torch.empty(c, device=x2d.device), torch.empty(c, device=x2d.device)
     args = (x2d.data_ptr(), dt_code(x2d.dtype), sums.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
             running_mean.data_ptr() if running_mean is not None else None, running_var.data_ptr() if running_var is not None else None, m, c, momentum, eps)
-    if workspace is not None:      # the deterministic form (`bn_plan(m, c).bytes`)
-        ws, nbytes = check_workspace(workspace, bn_plan(m, c), "bn_stats_t")
-        check(lib.mt4_bn_stats_det_t(*args, ws, nbytes, _stream()), "mt4_bn_stats_det_t")
-        return mean, invstd
-    check(lib.mt4_bn_stats_t(*args, _stream()), "mt4_bn_stats_t")
+    _launch_form("mt4_bn_stats_t", "mt4_bn_stats_det_t", args, workspace, lambda: bn_plan(m, c), "bn_stats_t")      # (workspace: `bn_plan(m, c).bytes`)
     return mean, invstd
 
 
@@ -1536,11 +1505,7 @@ def bn_backward_t(dy, y_post, x2d, mean, invstd, gamma, dgamma, dbeta, relu=True
     args = (dy.data_ptr(), y_post.data_ptr() if (y_post is not None and code == 1) else None, x2d.data_ptr(), dt_code(x2d.dtype), mean.data_ptr(),
             invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr() if beta is not None else None, sums.data_ptr(), dx.data_ptr(),
             dres.data_ptr() if want_dres else None, dgamma.data_ptr(), dbeta.data_ptr(), m, c, code)
-    if workspace is not None:      # the deterministic form (`bn_plan(m, c).bytes`)
-        ws, nbytes = check_workspace(workspace, bn_plan(m, c), "bn_backward_t")
-        check(lib.mt4_bn_backward_det_t(*args, ws, nbytes, _stream()), "mt4_bn_backward_det_t")
-        return dx, dres
-    check(lib.mt4_bn_backward_t(*args, _stream()), "mt4_bn_backward_t")
+    _launch_form("mt4_bn_backward_t", "mt4_bn_backward_det_t", args, workspace, lambda: bn_plan(m, c), "bn_backward_t")      # (workspace: `bn_plan(m, c).bytes`)
     return dx, dres
 
 
@@ -1553,14 +1518,9 @@ def wgrad_conv2d_bf16(dy, x, dw_packed, k, stride, workspace=None, accumulate=Tr
     _, h, w, cin = x.shape
     assert dy.dtype == x.dtype == BF16 and dy.is_contiguous() and x.is_contiguous() and dw_packed.dtype == torch.float32
     assert dw_packed.shape == (cout, packed_k(cin, k, k, torch.float32))
-    if workspace is not None:
-        ws, nbytes = check_workspace(workspace, wgrad_conv2d_bf16_plan(b, ho, wo, cout, cin, k, stride), "wgrad_conv2d_bf16")
-        check(lib.mt4_wgrad_conv2d_det_bf16(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), b, h, w, cin, ho, wo, cout, k, stride,
-                                            1 if accumulate else 0, ws, nbytes, _stream()), "mt4_wgrad_conv2d_det_bf16")
-        return
-    assert accumulate, "the atomic form always adds"
-    check(lib.mt4_wgrad_conv2d_bf16(dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), b, h, w, cin, ho, wo, cout, k, stride, _stream()),
-          "mt4_wgrad_conv2d_bf16")
+    assert accumulate or workspace is not None, "the atomic form always adds"
+    _launch_form("mt4_wgrad_conv2d_bf16", "mt4_wgrad_conv2d_det_bf16", (dy.data_ptr(), x.data_ptr(), dw_packed.data_ptr(), b, h, w, cin, ho, wo, cout, k, stride),
+                 workspace, lambda: wgrad_conv2d_bf16_plan(b, ho, wo, cout, cin, k, stride), "wgrad_conv2d_bf16", det_args=(1 if accumulate else 0,))
 
 
 def maxpool3x3s2_bwd_bf16(x, dy):

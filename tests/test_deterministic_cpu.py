@@ -16,7 +16,7 @@ def _cdiv(a, b):
 
 # ------------------------------------------------------------------------------------------------ the launch rules, replicated
 def wgrad1d_parts(b, t, cout, cin, taps):
-    """parts of `mt4_wgrad_conv1d_det_f32` = the row splits of `mt4_wgrad_conv1d_f32` (csrc/train_kernels.hip, `wgrad_conv1d_split`): about 1024
+    """parts of `mt4_wgrad_conv1d_det_f32` = the row splits of `mt4_wgrad_conv1d_f32` (csrc/train_kernels.hip, `wgrad_conv1d_parts`): about 1024
     workgroups in all, at least 256 rows per split, rows per split rounded up to the 32-row chunk"""
     kpad = _cdiv(taps * _cdiv(cin * 4, 16), 8) * 8 * 4                  # mt4_conv_packed_k(cin, 1, taps, MT4_F32)
     m, tiles = b * t, _cdiv(kpad, 64) * _cdiv(cout, 64)
@@ -26,12 +26,12 @@ def wgrad1d_parts(b, t, cout, cin, taps):
 
 
 def colsum_parts(m, c):
-    """row slabs of `mt4_colsum_f32` (`colsum_slabs`): 64 rows per slab, at most ceil(1024 / column blocks) slabs"""
+    """row slabs of `mt4_colsum_f32` (`colsum_parts`): 64 rows per slab, at most ceil(1024 / column blocks) slabs"""
     return max(1, min(_cdiv(m, 64), _cdiv(1024, _cdiv(c, 64))))
 
 
 def bce_parts(m):
-    return min(_cdiv(m, 64), 64)                                         # `bce_logits_slabs`
+    return min(_cdiv(m, 64), 64)                                         # `bce_logits_parts`
 
 
 WGRAD1D_SHAPES = [(1, 1000, 64, 64, 3), (1, 200, 64, 64, 3), (1, 600, 64, 64, 3), (1, 600, 64, 32, 1), (1, 2000, 512, 512, 3), (1, 2000, 132, 512, 1),
@@ -115,6 +115,38 @@ def test_entry_points_refuse_null_and_short_workspaces_without_a_device():
     assert lib.mt4_bce_logits_det_f32(p, p, p, p, p, 600, 100, 100, 100, p, ops.bce_logits_plan(600, 100).bytes - 4, None) == -1
 
 
+def test_spatial_entry_points_refuse_null_and_short_workspaces_without_a_device():
+    """the deterministic entries of the spatial stage, at shapes whose plans have several parts: a NULL workspace, one a part element short of the
+    plan's bytes and an empty one are all MT4_EINVAL before any launch -- the bytes the plan query names are the bytes the launch asks for"""
+    lib, buf = _lib.lib, ctypes.create_string_buffer(64)
+    p = (ctypes.addressof(buf) + 15) // 16 * 16
+    F32, BF16 = _lib.MT4_F32, _lib.MT4_BF16
+    bn, m, c = ops.bn_plan(200, 64), 200, 64
+    (wb, wh, ww, wcin, wcout, wk), (_, wparts) = WGRAD2D_TABLE[0]                                 # 2, 24 x 24, 64 -> 64, 3 x 3 (pad 1): 5 parts
+    w32 = ops.wgrad_conv2d_plan(wb, wh, ww, wcout, wcin, wk, wk)
+    w16 = ops.wgrad_conv2d_bf16_plan(2, 16, 32, 64, 64, 3, 1)                                     # the 3 x 3 base shape of the GPU tests: 16 parts
+    assert (bn.nparts, w32.nparts, w16.nparts) == (4, wparts, 16)
+    cases = [("mt4_bn_stats_det_f32", bn, (p, p, p, p, None, None, m, c, 0.1, 1e-5)),
+             ("mt4_bn_stats_det_t", bn, (p, BF16, p, p, p, None, None, m, c, 0.1, 1e-5)),
+             ("mt4_bn_stats_det_t", bn, (p, F32, p, p, p, None, None, m, c, 0.1, 1e-5)),
+             ("mt4_bn_backward_det_f32", bn, (p, p, p, p, p, p, p, p, p, None, p, p, m, c, 1)),
+             ("mt4_bn_backward_det_t", bn, (p, p, p, BF16, p, p, p, p, p, p, None, p, p, m, c, 1)),
+             ("mt4_bn_backward_det_t", bn, (p, p, p, F32, p, p, p, p, p, p, None, p, p, m, c, 2)),
+             ("mt4_wgrad_conv2d_det_f32", w32, (p, p, p, wb, wh, ww, wcin, wh, ww, wcout, wk, wk, 1, 1, 1, 1, 1, 1, 0)),
+             ("mt4_wgrad_conv2d_det_bf16", w16, (p, p, p, 2, 16, 32, 64, 16, 32, 64, 3, 1, 1)),
+             ("mt4_bce_logits_pw_det_f32", ops.bce_logits_pw_plan(130, 100), (p, p, None, p, p, p, 130, 100, 100, 100)),
+             ("mt4_distill_kl_det_f32", ops.distill_kl_plan(5, 10), (p, p, p, p, 5, 10, 10, 10, 4.0, 1.0, 1)),
+             ("mt4_mse_det_f32", ops.mse_plan(1000), (p, p, p, p, 1000, 1.0))]
+    for name, plan, args in cases:
+        assert plan.nparts > 1, name                                                              # several parts: the formula matters
+        esize = plan.bytes // (plan.nparts * plan.part_elems)
+        assert esize == (8 if "_bn_" in name else 4) and plan.bytes == plan.nparts * plan.part_elems * esize
+        fn = getattr(lib, name)
+        assert fn(*args, None, 1 << 30, None) == -1, name                                         # NULL workspace
+        assert fn(*args, p, plan.bytes - esize, None) == -1, name                                 # one element short
+        assert fn(*args, p, 0, None) == -1, name                                                  # empty
+
+
 # ------------------------------------------------------------------------------------------------ the flag
 @pytest.mark.parametrize("stage", ["spatial_cnn", "spatial_transformer", "mstct", "tenco"])
 def test_deterministic_flag_is_declared_off_by_default_and_refused_where_not_covered(stage, capsys):
@@ -168,7 +200,7 @@ def test_fold_parts_host_is_sequential_in_the_element_type():
 
 
 # ------------------------------------------------------------------------------------------------ the spatial stage's plans
-# (b, ho, wo, cin, cout, k) -> (form, parts): worked out by hand from the dispatch of `mt4_wgrad_conv2d_f32` (csrc/train2d_kernels.hip, `wgrad32_form`):
+# (b, ho, wo, cin, cout, k) -> (form, parts): worked out by hand from the dispatch of `mt4_wgrad_conv2d_f32` (csrc/train2d_kernels.hip, `wgrad32_parts`):
 # max_splits = ceil(M / 256), M = b ho wo; a wide form needs tiles x max_splits >= 512; splits = min(ceil(768 | 1024 / tiles), max_splits); rows per
 # split rounded up to 32.  Kpad in floats.
 #   2, 24 x 24,   64 ->  64, 3 x 3 (Kpad  576): M   1152, max 5; <1,2>: 5 x 1 x 5 = 25 < 512           -> 64 x 64, 9 tiles, min(114, 5)    -> 5 parts

@@ -4,9 +4,11 @@
 layers, 512 maps), at --lengths frames; `resnet50_bf16`, `resnet50_fp32`, `resnet18_bf16` = the student step on 64 uint8 frames of 256 x 448 (one
 "length": the batch).
 
-  python3 tools/deterministic_bench.py [--workload tenco] [--parent DIR] [--reps 7] [--steps 40] [--lengths 256,2000]
+  python3 tools/deterministic_bench.py [--workload tenco] [--parent DIR] [--parent-det] [--eager] [--reps 7] [--steps 40] [--lengths 256,2000]
         every repetition starts one fresh child process per variant, alternating: the default step of the checkout at DIR (a built parent
-        checkout carried in the tree, when given), the default step of this tree, the deterministic step of this tree.  A child times its steps
+        checkout carried in the tree, when given; --parent-det: its deterministic step too), the default step of this tree, the deterministic
+        step of this tree.  --eager: every child launches its kernels one by one (the host's time in the entry points is on the timed path only
+        there).  A child times its steps
         with device events after a warm-up that includes the graph capture and reports the median step; the table gives, per variant and
         length, the median of the repetitions' medians and their spread (min .. max).  Each child runs under a time limit of its own and the
         run stops at the first child that does not exit with status 0.
@@ -93,19 +95,21 @@ def main():
     p.add_argument("--steps", type=int, default=40)
     p.add_argument("--warmup", type=int, default=8)
     p.add_argument("--lengths", default="256,2000")
-    p.add_argument("--eager", action="store_true", help="(--child) launch the step's kernels one by one instead of replaying a graph: for a kernel trace")
+    p.add_argument("--parent-det", action="store_true", help="with --parent: the parent's deterministic step as a fourth variant")
+    p.add_argument("--eager", action="store_true", help="launch the step's kernels one by one instead of replaying a graph: a kernel trace, the host's share")
     a = p.parse_args()
     lengths = [int(t) for t in a.lengths.split(",")] if a.workload == "tenco" else [64]
     if a.child:
         if a.workload != "tenco":
             return student_child(a.workload, a.child, os.path.abspath(a.root), a.steps, a.warmup, not a.eager)
         return child(a.child, os.path.abspath(a.root), lengths, a.steps, a.warmup, not a.eager)
-    variants = ([("parent default", "default", os.path.abspath(a.parent))] if a.parent else []) + [("default", "default", HERE), ("deterministic", "det", HERE)]
+    variants = ([("parent default", "default", os.path.abspath(a.parent))] if a.parent else []) + [("default", "default", HERE)]
+    variants += ([("parent det", "det", os.path.abspath(a.parent))] if a.parent and a.parent_det else []) + [("deterministic", "det", HERE)]
     res = {name: {T: [] for T in lengths} for name, _, _ in variants}
     for rep in range(a.reps):
         for name, mode, root in variants:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode, "--workload", a.workload, "--root", root, "--steps", str(a.steps),
-                                "--warmup", str(a.warmup), "--lengths", a.lengths], capture_output=True, text=True, timeout=240)
+                                "--warmup", str(a.warmup), "--lengths", a.lengths] + (["--eager"] if a.eager else []), capture_output=True, text=True, timeout=240)
             if r.returncode != 0:
                 sys.exit(f"{name}: exit status {r.returncode}\n{r.stdout[-1000:]}{r.stderr[-2000:]}")
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -113,7 +117,7 @@ def main():
             for T, v in json.loads(line)["ms"].items():
                 res[name][int(T)].append(v)
     what = "temporal step (device draws), T frames" if a.workload == "tenco" else f"{a.workload} student step, batch of 256 x 448 frames"
-    print(f"\n{what}; hipGraph replay, ms: median of {a.reps} process medians (min .. max)")
+    print(f"\n{what}; {'eager launches' if a.eager else 'hipGraph replay'}, ms: median of {a.reps} process medians (min .. max)")
     for T in lengths:
         for name, _, _ in variants:
             v = res[name][T]
