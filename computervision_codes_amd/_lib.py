@@ -151,6 +151,8 @@ SIGNATURES = {
     "mt4_optim_advance": (C.c_int, [_vp, C.c_double, C.c_double, _vp, _vp]),
     "mt4_sgd_momentum_step_f32": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _i32, _vp, _vp]),
     "mt4_adamw_step_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_double, C.c_double, C.c_float, _vp, _vp, _vp]),
+    "mt4_ema_advance": (C.c_int, [_vp, C.c_double, _i32, _vp, _vp]),
+    "mt4_ema_step_f32": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
     "mt4_mul_add_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "mt4_transpose_pack_conv1d_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mt4_bn_stats_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i32, C.c_float, C.c_float, _vp]),

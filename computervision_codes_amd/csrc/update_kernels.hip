@@ -350,3 +350,75 @@ extern "C" int mt4_adamw_step_f32(float* p, const float* g, float* m, float* v, 
                        weight_decay, grad_scale, beta1, beta2, eps, optim_state, guard_state);
     return mt4_check_launch();
 }
+
+// ------------------------------------------------------------------------------------------------ weight average (--ema_decay)
+// E <- decay E + (1 - decay) P behind the parameter update, the decay of the step kept in a device record for the reason mt4_optim_state is: under
+// --skip_nonfinite the host never learns whether a step counted.  `ops.ema_advance_host` / `ops.ema_step_host` restate both and give the same bits.
+
+// one thread: unless the guard says skip, t += 1 and the step's decay d = warmup ? min(decay, (1 + t) / (10 + t)) : decay in IEEE double (the
+// num_updates form of TensorFlow's ExponentialMovingAverage); decay = (float)d, comp = (float)(1.0 - d), each rounded once
+__global__ void ema_advance_kernel(mt4_ema_state* __restrict__ es, double decay, int warmup, const mt4_guard_state* __restrict__ guard) {
+    if (guard && guard->skip) return;
+    const long long t = es->t + 1;
+    double d = decay;
+    if (warmup) {
+        const double w = (1.0 + (double)t) / (10.0 + (double)t);
+        if (w < d) d = w;
+    }
+    es->t = t;
+    es->decay = (float)d;
+    es->comp = (float)(1.0 - d);
+}
+
+extern "C" int mt4_ema_advance(mt4_ema_state* ema_state, double decay, int32_t warmup, const mt4_guard_state* guard_state, void* stream) {
+    mt4_clear_error();
+    if (!ema_state || !(decay >= 0. && decay < 1.)) return MT4_EINVAL;
+    if (((uintptr_t)ema_state | (uintptr_t)guard_state) & 7) return MT4_EALIGN;
+    hipLaunchKernelGGL(ema_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, ema_state, decay, warmup ? 1 : 0, guard_state);
+    return mt4_check_launch();
+}
+
+#define EMA_THREADS 256
+#define EMA_MAX_BLOCKS 2048LL     // 8 workgroups per CU: a longer buffer is walked with the grid's stride
+
+// two multiplies and one add, each ONE round-to-nearest operation in this order.  HIP's __fmul_rn / __fadd_rn are the plain operators, which hipcc's
+// default -ffp-contract=fast fuses into an FMA: the pragma (here and in the kernel body, as in sgdm_elem) is what keeps the three roundings
+__device__ __forceinline__ float ema_elem(float e, float p, float d, float c) {
+#pragma clang fp contract(off)
+    const float de = d * e;
+    const float cp = c * p;
+    return de + cp;
+}
+
+// a pure stream of 12 bytes per element (e read and written, p read): 16-byte accesses, the n % 4 tail element by element in the thread whose
+// float4 it would be
+__global__ __launch_bounds__(EMA_THREADS) void ema_step_kernel(float* __restrict__ e, const float* __restrict__ p, long long n,
+                                                               const mt4_ema_state* __restrict__ es, const mt4_guard_state* __restrict__ guard) {
+#pragma clang fp contract(off)
+    if (guard && guard->skip) return;
+    const float d = es->decay, c = es->comp;
+    const long long stride = (long long)gridDim.x * EMA_THREADS * 4;
+    for (long long i = ((long long)blockIdx.x * EMA_THREADS + threadIdx.x) * 4; i < n; i += stride) {
+        if (i + 3 < n) {
+            float4 ev = *(float4*)(e + i);
+            const float4 pv = *(const float4*)(p + i);
+            ev.x = ema_elem(ev.x, pv.x, d, c); ev.y = ema_elem(ev.y, pv.y, d, c);
+            ev.z = ema_elem(ev.z, pv.z, d, c); ev.w = ema_elem(ev.w, pv.w, d, c);
+            *(float4*)(e + i) = ev;
+        } else {
+            for (long long j = i; j < n; ++j) e[j] = ema_elem(e[j], p[j], d, c);
+        }
+    }
+}
+
+extern "C" int mt4_ema_step_f32(float* e, const float* p, int64_t n, const mt4_ema_state* ema_state, const mt4_guard_state* guard_state,
+                                void* stream) {
+    mt4_clear_error();
+    if (!e || !p || !ema_state || n <= 0) return MT4_EINVAL;
+    if ((((uintptr_t)e | (uintptr_t)p) & 15) || (((uintptr_t)ema_state | (uintptr_t)guard_state) & 7)) return MT4_EALIGN;
+    const long long threads = (n + 3) / 4;
+    const long long blocks = min((threads + EMA_THREADS - 1) / EMA_THREADS, EMA_MAX_BLOCKS);
+    hipLaunchKernelGGL(ema_step_kernel, dim3((unsigned)blocks), dim3(EMA_THREADS), 0, (hipStream_t)stream, e, p, (long long)n, ema_state,
+                       guard_state);
+    return mt4_check_launch();
+}

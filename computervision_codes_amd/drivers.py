@@ -104,6 +104,22 @@ _OPTIM = [
     _flag("--adam_betas", type=float, nargs=2, default=[0.9, 0.999], metavar=("B1", "B2"), help="AdamW's betas, each in [0, 1)"),
     _flag("--adam_eps", type=float, default=1e-8, help="AdamW's epsilon (> 0)"),
 ]
+# --ema_decay / --ema_warmup / --ema_eval (the reference ships `ModelEma`, Spatial_transformer/utils/misc.py:433-458, and no driver calls it): every
+# trainer, `FlatTrainer._ema_update` (`flatparams.Ema`) and `trainloop.run_epochs`
+_EMA = [
+    _flag("--ema_decay", type=float, default=0.0,
+          help="D in (0, 1): keep an exponential moving average of the weights on the device, E <- D E + (1 - D) P behind every applied update "
+               "(mt4_ema_advance + mt4_ema_step_f32; the student's BatchNorm running statistics are averaged with it), validate IT and save IT "
+               "as the best `.pth` -- a plain state dict, so extraction, test.py and predict.py need no flag; `_latest.pth` stays the raw weights "
+               "and --resume keeps the average beside it (`<latest>.ema.e<epoch>`).  A step --skip_nonfinite skips does not enter the average; "
+               "without --skip_nonfinite a non-finite parameter stays in it for good, as in the optimizer state.  0: off"),
+    _flag("--ema_warmup", action="store_true",
+          help="the decay of the t-th averaged step is min(D, (1 + t) / (10 + t)) (TensorFlow's ExponentialMovingAverage with num_updates): the "
+               "average follows the weights closely at first (needs --ema_decay > 0)"),
+    _flag("--ema_eval", type=str, default="ema", choices=["ema", "both"],
+          help="both: validation also scores the raw weights and the `video-wise |` line shows it as `| raw => ...`; the best `.pth` is still "
+               "chosen by, and holds, the averaged weights (needs --ema_decay > 0)"),
+]
 _DETERMINISTIC_STAGES = ("spatial_cnn", "tenco")
 _NOT_DETERMINISTIC = {
     "spatial_transformer": "the sequence trainers' reductions are not covered yet (csrc/seq_train_kernels.hip: LayerNorm dgamma/dbeta, the "
@@ -132,7 +148,7 @@ _FRAME_TRAIN = [
     _OPERAND_DTYPE,
     _DETERMINISTIC,
     _RESUME,
-] + _GUARD + _OPTIM
+] + _GUARD + _OPTIM + _EMA
 # stage -> (the flags every entry point of the stage parses, the flags of its trainer alone), on top of `_common` and -- the trainer --
 # `add_schedule_flags`.  --teacher_dim: the student mixes in the 1536-wide Swin-L feature (`Spatial_cnn/run.py`), the transformer stage's
 # `loss_type all` variant the 512-wide ResNet-18 one (`Spatial_transformer/run.py:82`, `test.py:82`)
@@ -152,7 +168,7 @@ _FLAGS = {
     "mstct": ([_flag("--input_dim", type=int, default=1536),
                _flag("--final_embedding_dim", type=int, default=512)],
               [_flag("--num_clips", type=int, default=256, help="window length (the reference hard-codes 256, dataloader.py:237)"), _OPERAND_DTYPE,
-               _DETERMINISTIC, _RESUME] + _GUARD + _OPTIM),
+               _DETERMINISTIC, _RESUME] + _GUARD + _OPTIM + _EMA),
     # --mask_draw / --subclip (not in the reference) device: the step's random pieces are drawn by HIP kernels from (seed, step) and whole-video
     # steps replay as hipGraphs; host: drawn with torch's generator and uploaded.  reference: `Temporal_tenco/dataloader.py:219-222` sub-clip sampling
     "tenco": ([_flag("--num_layers_PG", default=11, type=int),
@@ -168,7 +184,7 @@ _FLAGS = {
                _flag("--input_dim", type=int, default=512)],
               [_flag("--mask_draw", choices=("host", "device"), default="host"),
                _flag("--subclip", choices=("off", "reference"), default="off"),
-               _DETERMINISTIC, _RESUME] + _GUARD + _OPTIM),
+               _DETERMINISTIC, _RESUME] + _GUARD + _OPTIM + _EMA),
 }
 _LATEST = {"spatial_cnn": "_latest.pth", "spatial_transformer": "_latest.pth", "tenco": "_latest.pth",
            "mstct": "latest.pth"}                            # <stem> + this = the trainer's newest checkpoint; MS-TCT: no underscore (`Temporal_mstct/run.py:268`)
@@ -248,17 +264,38 @@ def _optim(F) -> dict:
     return {"optim": o if o.stateful else None}
 
 
-def _resume(F, latest: str, optim=None):
+def _ema(F) -> dict:
+    """--ema_decay / --ema_warmup / --ema_eval of a trainer, read before any model is built: a decay outside [0, 1) and --ema_warmup or
+    --ema_eval both without a decay are refused, an average is said once at start; -> the trainer's keyword argument"""
+    from .flatparams import Ema
+    decay, warmup = float(getattr(F, "ema_decay", 0.0)), bool(getattr(F, "ema_warmup", False))
+    if not 0 <= decay < 1:
+        raise ValueError(f"--ema_decay {decay:g}: in [0, 1) (0: off)")
+    if warmup and decay == 0:
+        raise ValueError("--ema_warmup needs --ema_decay > 0")
+    if getattr(F, "ema_eval", "ema") == "both" and decay == 0:
+        raise ValueError("--ema_eval both needs --ema_decay > 0: without an average there is nothing beside the raw weights to validate")
+    e = Ema(decay, warmup).check()
+    if e.active:
+        print(f"weight average: decay {decay:g}" + (" warmup" if warmup else ""), flush=True)
+    return {"ema": e if e.active else None}
+
+
+def _resume(F, latest: str, optim=None, ema=None):
     """--resume of a trainer, read before any model is built: what `trainloop.load_resume` finds beside `latest` for this rank (a fresh run,
-    the state to continue from, or its ValueError -- also when the recorded optimizer state does not belong to the flags `optim` was made from);
-    None without the flag"""
-    return load_resume(latest, *_dist(), optim=optim.config() if optim is not None else None) if getattr(F, "resume", False) else None
+    the state to continue from, or its ValueError -- also when the recorded optimizer state or weight average does not belong to the flags
+    `optim` / `ema` were made from); None without the flag"""
+    if not getattr(F, "resume", False):
+        return None
+    return load_resume(latest, *_dist(), optim=optim.config() if optim is not None else None, ema=ema.config() if ema is not None else None)
 
 
 def _load_optim(tr, resume):
-    """the optimizer state `load_resume` read beside the checkpoint goes into the trainer (after its `load_state_dict`)"""
+    """the optimizer state and the weight average `load_resume` read beside the checkpoint go into the trainer (after its `load_state_dict`)"""
     if resume is not None and resume.optim_state is not None:
         tr.load_optimizer_state_dict(resume.optim_state())
+    if resume is not None and resume.ema_state is not None:
+        tr.load_ema_export(resume.ema_state())
 
 
 def _latest_state(latest: str, resume):
@@ -648,12 +685,12 @@ def spatial_cnn_train(argv=None) -> Dict[str, float]:
     if F.loss_type not in ("all", "i", "v", "t"):
         raise ValueError("--loss_type all | i | v | t (`Spatial_cnn/run.py:165-192`)")
     single = F.loss_type != "all"
-    guard = dict(_guard(F), **_optim(F))
+    guard = dict(_guard(F), **_optim(F), **_ema(F))
     rank, world = _dist()
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold)
     latest = stem + _LATEST["spatial_cnn"]
-    resume = _resume(F, latest, guard["optim"])
+    resume = _resume(F, latest, guard["optim"], guard["ema"])
     sd = student_start(F, latest, resume, say=print if rank == 0 else None)
     tr = SpatialCnnTrainer(F.network, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay, rates=F.rates, temp=float(F.temp),
                            teacher_dim=F.teacher_dim, loss_type=F.loss_type,
@@ -763,9 +800,9 @@ def _tenco_train(F):
         # `loss_v`, `loss_t` stay the int 0 they start as (`run.py:190`) and `loss_i.item()` raises AttributeError at `run.py:214` in the first step
         raise NotImplementedError("Temporal_tenco training needs --fpn (Scripts/train_fold1.sh:28): without it the reference's train loop itself fails "
                                   "in its first step (run.py:190,214: .item() on the int 0 that loss_i stays when the model returns no per-component logits)")
-    guard = dict(_guard(F), **_optim(F))
+    guard = dict(_guard(F), **_optim(F), **_ema(F))
     init = stem + _LATEST["tenco"]
-    resume = _resume(F, init, guard["optim"])
+    resume = _resume(F, init, guard["optim"], guard["ema"])
     tr = TencoTrainer(F.num_layers_PG, F.num_layers_R, F.num_R, 512, F.input_dim, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                       hier=bool(getattr(F, "hier", False)),      # --hier True: pooled refinement levels (`network.py:147,154-155`, `run.py:159-179`)
                       causal=bool(getattr(F, "causal", False)),
@@ -995,14 +1032,14 @@ def _mstct_train(F):
     from .mstct_train import NCLS, MstctTrainer, draw_windows
     from . import shapes, synth
     _deterministic("mstct", F)
-    guard = dict(_guard(F), **_optim(F))
+    guard = dict(_guard(F), **_optim(F), **_ema(F))
     rank, world = _dist()
     lt = F.loss_type
     if lt not in NCLS:
         raise ValueError("Temporal_mstct trains one task at a time: --loss_type i | v | t | ivt (Scripts/train_fold1.sh:16)")
     stem = _stem(F, task_dir=True)
     latest = stem + _LATEST["mstct"]
-    resume = _resume(F, latest, guard["optim"])
+    resume = _resume(F, latest, guard["optim"], guard["ema"])
     tr = MstctTrainer(*_MSTCT_ARCH, F.input_dim, F.final_embedding_dim, lt, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                       operand_dtype=_dtype(F.operand_dtype), **guard)
     state = _latest_state(latest, resume)
@@ -1069,7 +1106,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     from . import shapes, synth
     F = _parser("spatial_transformer", True).parse_known_args(argv)[0]
     _deterministic("spatial_transformer", F)
-    guard = dict(_guard(F), **_optim(F))
+    guard = dict(_guard(F), **_optim(F), **_ema(F))
     if F.loss_type not in ("i", "v", "t", "all"):
         raise ValueError("--loss_type i | v | t | all (`Spatial_transformer/run.py:168-197`)")
     single = F.loss_type != "all"
@@ -1078,7 +1115,7 @@ def spatial_transformer_train(argv=None) -> Dict[str, float]:
     kfold = F.kfold if "crossval" in F.dataset_variant else 0
     stem = _stem(F, kfold, task_dir=True)
     logfile, latest = stem + ".log", stem + _LATEST["spatial_transformer"]
-    resume = _resume(F, latest, guard["optim"])
+    resume = _resume(F, latest, guard["optim"], guard["ema"])
     tr = Q2LTrainer(F.backbone, F.img_size, F.hidden_dim, F.loss_type, lr=F.initial_learning_rates[2], weight_decay=F.weight_decay,
                     drop_path_rate=F.drop_path_rate, operand_dtype=_dtype(F.operand_dtype),
                     teacher_dim=F.teacher_dim, rates=F.rates, temp=float(F.temp), **guard)

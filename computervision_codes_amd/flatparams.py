@@ -3,7 +3,8 @@ GEMM layouts, every slot padded to 4 floats), the weight copies derived from the
 -- per-bucket all-reduces behind the backward or one flat all-reduce after it -- ahead of one `mt4_sgd_step_f32`, or, with a gradient-norm clip or
 the non-finite guard on, of the guarded update (norm and decisions taken on the device: `mt4_grad_norm_parts_f32`, `mt4_grad_guard_finalize`,
 `mt4_sgd_step_guarded_f32`), or, with momentum or AdamW (`Optim`), of the update that also carries flat state buffers of P's layout
-(`mt4_sgd_momentum_step_f32`, `mt4_optim_advance` + `mt4_adamw_step_f32`).
+(`mt4_sgd_momentum_step_f32`, `mt4_optim_advance` + `mt4_adamw_step_f32`).  With a weight average (`Ema`) the update is followed by
+`mt4_ema_advance` + `mt4_ema_step_f32` on one more flat buffer of P's layout.
 
 * `FlatParams` lays the slots out in the order they are declared, loads them from the reference state dict and exports P or G back in the
   reference's key names and shapes;
@@ -65,6 +66,28 @@ class Optim(NamedTuple):
                 raise ValueError(f"momentum {self.momentum}: in [0, 1)")
             if self.nesterov and self.momentum == 0:
                 raise ValueError("nesterov needs a momentum > 0")
+        return self
+
+
+class Ema(NamedTuple):
+    """the weight average of a `FlatTrainer` (--ema_decay, --ema_warmup): E <- d E + (1 - d) P behind every applied update, d = `decay`, or with
+    `warmup` min(decay, (1 + t) / (10 + t)) at the t-th averaged step.  The default is off: no buffer, no record, no launch"""
+    decay: float = 0.0
+    warmup: bool = False
+
+    @property
+    def active(self) -> bool:
+        return self.decay > 0
+
+    def config(self) -> dict:
+        """what is written beside a checkpoint and compared on --resume"""
+        return {"decay": float(self.decay), "warmup": bool(self.warmup)}
+
+    def check(self) -> "Ema":
+        if not 0 <= self.decay < 1:                          # (a NaN fails both comparisons)
+            raise ValueError(f"ema decay {self.decay}: in [0, 1)")
+        if self.warmup and not self.decay > 0:
+            raise ValueError("ema warmup needs a decay > 0")
         return self
 
 
@@ -223,16 +246,23 @@ class FlatTrainer:
     all-reduces the whole of G once."""
 
     def __init__(self, lr: float, weight_decay: float, device, process_group, overlap: bool = False, clip_grad_norm: float = 0.0,
-                 skip_nonfinite: bool = False, optim: Optional[Optim] = None):
+                 skip_nonfinite: bool = False, optim: Optional[Optim] = None, ema: Optional[Ema] = None):
         """clip_grad_norm > 0: the exchanged gradient is scaled to that global L2 norm when it is longer; skip_nonfinite: a step whose exchanged
         gradient holds a NaN or an Inf changes nothing (`apply_update`, the guarded update).  Both off: the plain `mt4_sgd_step_f32`.
         optim: the update rule (`Optim`); None or the default: plain SGD, today's launches, no state buffer.  With momentum or AdamW the state
-        lives in flat buffers of P's layout (`fp.S`), allocated by `load_state_dict`; see `apply_update`."""
+        lives in flat buffers of P's layout (`fp.S`), allocated by `load_state_dict`; see `apply_update`.
+        ema: the weight average (`Ema`); None or the default: none kept, every launch and byte as without it.  Active: `fp.S["ema"]` starts as a
+        copy of the loaded P and follows every applied update (`_ema_update`); `ema_state_dict()` exports it.  A skipped step (--skip_nonfinite)
+        does not enter the average: the count t, E and the averaged running statistics stay as they were.  Without --skip_nonfinite a non-finite
+        parameter poisons the average for good, as it does the optimizer state."""
         if not clip_grad_norm >= 0:
             raise ValueError(f"clip_grad_norm {clip_grad_norm}: 0 (off) or a positive norm")
         optim = Optim(*optim).check() if optim is not None else None
         self.optim = optim if optim is not None and optim.stateful else None
         self._ostate = None                         # AdamW: the device step record (mt4_optim_state)
+        ema = Ema(*ema).check() if ema is not None else None
+        self.ema = ema if ema is not None and ema.active else None
+        self._estate = None                         # the average's device record (mt4_ema_state)
         self._omap = None                           # reference key -> flat indices (`load_optimizer_state_dict`)
         self.lr, self.wd = lr, weight_decay
         self.clip_grad_norm, self.skip_nonfinite = float(clip_grad_norm), bool(skip_nonfinite)
@@ -326,6 +356,7 @@ class FlatTrainer:
             return
         if not self.guarded:
             ops.sgd_step(self.P, self.G, self.lr, self.wd, scale)
+            self._ema_update(None)
             self._refresh()
             return
         # the guarded update: norm and decisions from the fully exchanged G -- the same on every rank (NaN and Inf survive a sum), so all ranks clip
@@ -334,6 +365,7 @@ class FlatTrainer:
         ops.grad_guard(self.G, scale, self.clip_grad_norm, self.skip_nonfinite, ws, state, stats)
         ops.sgd_step_guarded(self.P, self.G, self.lr, self.wd, scale, state)
         self._restore_skipped(state)
+        self._ema_update(state)
         self._refresh()
 
     @property
@@ -366,18 +398,99 @@ class FlatTrainer:
             ops.sgd_momentum_step(self.P, self.G, S["momentum_buffer"], self.lr, self.wd, scale, o.momentum, o.nesterov, state)
         if state is not None:
             self._restore_skipped(state)
+        self._ema_update(state)
         self._refresh()
 
     def _optim_buffers(self):
         """`load_state_dict`, once `fp` is built and before any graph capture: the zero-filled state buffers of the update rule (padding columns
-        and reserved slots stay exact zeros, as in G: their gradient and parameter are zero) and a fresh step record.  Nothing for plain SGD."""
+        and reserved slots stay exact zeros, as in G: their gradient and parameter are zero) and a fresh step record.  Nothing for plain SGD.  The
+        weight average's buffer and record are allocated at the same point (`_ema_buffers`)."""
         self._omap = None
+        self._ema_buffers()
         if self.optim is None:
             return
         for name in self.optim.buffers:
             self.fp.S[name] = torch.zeros_like(self.fp.P)
         if self.optim.kind == "adamw":
             self._ostate = ops.optim_state_buffer(self.dev)
+
+    # ------------------------------------------------------------------ weight average
+    def _ema_update(self, state: Optional[torch.Tensor]):
+        """behind the parameter update and `_restore_skipped` of every `apply_update` branch: `mt4_ema_advance`, then `mt4_ema_step_f32` on P and on
+        the trainer's other averaged buffers (`_ema_step_extra`), all reading the step's guard record `state` on the device where there is one --
+        a skipped step leaves t, E and those buffers as they were.  Outside the replayed hipGraphs, so eager and replayed steps give the same
+        bits; every rank averages the same P, so E is the same on every rank and is never exchanged.  Nothing without an average."""
+        if self.ema is None:
+            return
+        ops.ema_advance(self._estate, self.ema.decay, self.ema.warmup, state)
+        ops.ema_step(self.fp.S["ema"], self.P, self._estate, state)
+        self._ema_step_extra(state)
+
+    def _ema_step_extra(self, state: Optional[torch.Tensor]):
+        """buffers besides P that are averaged with the same record (the student's BatchNorm running statistics)"""
+
+    def _ema_buffers(self):
+        """`load_state_dict`, once the weights are loaded (`_optim_buffers` calls it): E starts as a COPY of P -- padding columns and reserved slots
+        stay exact zeros under d 0 + c 0 -- beside a fresh record.  Nothing without an average."""
+        self._estate = None
+        self.fp.S.pop("ema", None)
+        if self.ema is None:
+            return
+        self.fp.S["ema"] = self.fp.P.clone()
+        self._estate = ops.ema_state_buffer(self.dev)
+
+    def ema_config(self) -> Optional[dict]:
+        """the average's config as --resume records it; None without one"""
+        return self.ema.config() if self.ema is not None else None
+
+    def ema_record(self) -> dict:
+        """the average's record on the host: t, decay, comp (one device-to-host copy); {} without an average"""
+        return ops.read_ema_state(self._estate) if self._estate is not None else {}
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """the trainer's own `state_dict()` with E in place of P (the student: the averaged running statistics in place of the running ones,
+        `num_batches_tracked` the trainer's own integer); parameters the trainer keeps verbatim are unchanged.  Same keys, shapes, dtypes and
+        order: what `validate` scores and the best `.pth` holds when the average is on"""
+        if self.ema is None:
+            raise ValueError("this trainer keeps no weight average (ema=None)")
+        return self.state_dict("ema")
+
+    def ema_export(self) -> dict:
+        """{"ema": the config, "t": the averaged steps, "state": `ema_state_dict()`} on the CPU: what --resume keeps beside a checkpoint"""
+        return {"ema": self.ema_config(), "t": int(self.ema_record()["t"]), "state": self.ema_state_dict()}
+
+    def load_ema_export(self, exp: dict):
+        """the inverse of `ema_export`: the tensors go back to their flat places through the map `load_optimizer_state_dict` uses, the record is
+        rebuilt by `t` host advances"""
+        if self.ema is None:
+            raise ValueError("this trainer keeps no weight average (ema=None)")
+        if exp.get("ema") != self.ema.config():
+            raise ValueError(f"weight average of {exp.get('ema')} does not belong to this trainer's {self.ema.config()}")
+        state, omap = exp["state"], self._flat_map()
+        if set(state) != set(self.state_dict()):
+            raise ValueError("weight average holds other tensors than this trainer's state dict")
+        flat = torch.zeros(self.fp.P.numel(), dtype=F32)
+        for k, idx in omap.items():
+            if tuple(state[k].shape) != tuple(idx.shape):
+                raise ValueError(f"weight average {k}: shape {tuple(state[k].shape)}, expected {tuple(idx.shape)}")
+            flat[idx.reshape(-1).long()] = state[k].reshape(-1).to(F32)
+        self.fp.S["ema"].copy_(flat.to(self.dev))
+        self._load_ema_extra(state)
+        rec = {"t": 0, "decay": 0.0, "comp": 1.0}
+        for _ in range(int(exp["t"])):
+            rec = ops.ema_advance_host(rec, self.ema.decay, self.ema.warmup)
+        ops.write_ema_state(self._estate, rec["t"], rec["decay"], rec["comp"])
+
+    def _load_ema_extra(self, state: Dict[str, torch.Tensor]):
+        """the averaged buffers besides E out of a loaded `ema_state_dict()`"""
+
+    def _flat_map(self) -> Dict[str, torch.Tensor]:
+        """reference key -> the flat indices of its elements (found by exporting a buffer of flat indices, so every packing and head fusion of the
+        export is inverted by construction)"""
+        if self._omap is None:
+            n = self.fp.P.numel()
+            self._omap = self._export_any(torch.arange(n, dtype=torch.int32 if n < 2 ** 31 else torch.int64, device=self.dev))
+        return self._omap
 
     def _export_any(self, which) -> Dict[str, torch.Tensor]:
         """`fp.export` through the trainer's own `_export` where it has one (fused heads cut back into the reference's tensors)"""
@@ -409,14 +522,12 @@ class FlatTrainer:
             raise ValueError("this trainer keeps no optimizer state (plain SGD)")
         if osd.get("optim") != self.optim.config():
             raise ValueError(f"optimizer state of {osd.get('optim')} does not belong to this trainer's {self.optim.config()}")
-        if self._omap is None:
-            n = self.fp.P.numel()
-            self._omap = self._export_any(torch.arange(n, dtype=torch.int32 if n < 2 ** 31 else torch.int64, device=self.dev))
-        if set(osd["state"]) != set(self._omap):
+        omap = self._flat_map()
+        if set(osd["state"]) != set(omap):
             raise ValueError("optimizer state holds other parameters than this trainer's")
         for name in self.optim.buffers:
             flat = torch.zeros(self.fp.P.numel(), dtype=F32)
-            for k, idx in self._omap.items():
+            for k, idx in omap.items():
                 t = osd["state"][k][name]
                 if tuple(t.shape) != tuple(idx.shape):
                     raise ValueError(f"optimizer state {k}.{name}: shape {tuple(t.shape)}, expected {tuple(idx.shape)}")

@@ -41,9 +41,9 @@ class MstctTrainer(GemmTrainer):
     def __init__(self, inter_channels: Sequence[int] = (256, 384, 576, 864), num_block: int = 2, head: int = 8, mlp_ratio: int = 8,
                  in_feat_dim: int = 1536, final_embedding_dim: int = 512, loss_type: str = "i", lr: float = 0.1, weight_decay: float = 1e-5,
                  device: str = "cuda", process_group=None, operand_dtype: torch.dtype = torch.float32, clip_grad_norm: float = 0.0,
-                 skip_nonfinite: bool = False, optim=None):
+                 skip_nonfinite: bool = False, optim=None, ema=None):
         assert loss_type in NCLS
-        super().__init__(lr, weight_decay, device, process_group, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, optim=optim)
+        super().__init__(lr, weight_decay, device, process_group, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, optim=optim, ema=ema)
         assert operand_dtype in (torch.float32, torch.bfloat16)
         # bfloat16: the nn.Linear GEMMs (forward, data and weight gradients) read bf16 copies of their operands -- activations are cast on the
         # way in (`mt4_cast_f32_bf16`), weights re-derived from the fp32 masters after every step -- and accumulate / store in fp32; everything
@@ -114,9 +114,9 @@ class MstctTrainer(GemmTrainer):
                 ops.axpby_(l.b, self._bsum[j], 1.0, 0.0 if n == 0 else 1.0)
             ops.transpose_pack_conv1d(self._wsum[j], self.E, self.E, 1, out=self._wsum_t[j])
 
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        """reference layout and key names (`Temporal_mstct/network.py`), on the CPU"""
-        out = self.fp.export("p")
+    def state_dict(self, which: str = "p") -> Dict[str, torch.Tensor]:
+        """reference layout and key names (`Temporal_mstct/network.py`), on the CPU; which "ema": the weight average in place of P"""
+        out = self.fp.export(which)
         return {k: out[k] for k, _ in self._table}
 
     def grads(self) -> Dict[str, torch.Tensor]:

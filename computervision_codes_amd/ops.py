@@ -1254,6 +1254,74 @@ def optim_step_host(kind: str, p, g, m, v=None, *, lr: float, weight_decay: floa
     return out
 
 
+# ----------------------------------------------------------------------------------------- weight average (--ema_decay)
+EMA_STATE_BYTES = 16          # mt4_ema_state: int64 t, float decay, float comp
+
+
+def ema_state_buffer(device) -> torch.Tensor:
+    """a fresh mt4_ema_state on the device: t = 0, decay 0, comp 1 (a float64 tensor of two 8-byte words, like the guard records)"""
+    buf = torch.zeros(EMA_STATE_BYTES // 8, dtype=torch.float64, device=device)
+    write_ema_state(buf, 0, 0.0, 1.0)
+    return buf
+
+
+def read_ema_state(ema_state: torch.Tensor) -> dict:
+    """mt4_ema_state on the host (one device-to-host copy): t, decay, comp -- the two floats as Python floats holding float32 values"""
+    import struct
+    t, d, c = struct.unpack("<qff", ema_state.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()[:EMA_STATE_BYTES])
+    return {"t": t, "decay": d, "comp": c}
+
+
+def write_ema_state(ema_state: torch.Tensor, t: int, decay: float, comp: float) -> None:
+    """set the record (a fresh one; loading a saved average)"""
+    import struct
+    import numpy as np
+    words = np.frombuffer(struct.pack("<qff", int(t), float(decay), float(comp)), dtype=np.float64).copy()
+    ema_state[:2].copy_(torch.from_numpy(words).to(ema_state.device))
+
+
+def ema_advance(ema_state: torch.Tensor, decay: float, warmup: bool = False, guard_state: Optional[torch.Tensor] = None) -> None:
+    """one step counted into the average: t += 1 and the step's decay written, unless the guard state says skip (`mt4_ema_advance`)"""
+    check(lib.mt4_ema_advance(_guard_record(ema_state, EMA_STATE_BYTES, "ema_advance ema_state"), float(decay), 1 if warmup else 0,
+                              _guard_or_null(guard_state, "ema_advance guard state"), _stream()), "mt4_ema_advance")
+
+
+def ema_step(e: torch.Tensor, p: torch.Tensor, ema_state: torch.Tensor, guard_state: Optional[torch.Tensor] = None) -> None:
+    """e <- decay e + comp p with the record's two floats -- `ema_advance` first; nothing written when the guard state says skip
+    (`mt4_ema_step_f32`)"""
+    _flat_f32(e, p)
+    check(lib.mt4_ema_step_f32(e.data_ptr(), p.data_ptr(), e.numel(), _guard_record(ema_state, EMA_STATE_BYTES, "ema_step ema_state"),
+                               _guard_or_null(guard_state, "ema_step guard state"), _stream()), "mt4_ema_step_f32")
+
+
+def ema_advance_host(record: dict, decay: float, warmup: bool = False, skip: bool = False) -> dict:
+    """`mt4_ema_advance` on the host: Python floats are IEEE doubles and the division and the subtraction are single operations, so the record
+    follows the device's exactly.  d = min(decay, (1 + t) / (10 + t)) with warmup; decay, comp = float32(d), float32(1.0 - d)"""
+    import numpy as np
+    if skip:
+        return dict(record)
+    t = record["t"] + 1
+    d = float(decay)
+    if warmup:
+        d = min(d, (1.0 + t) / (10.0 + t))
+    return {"t": t, "decay": float(np.float32(d)), "comp": float(np.float32(1.0 - d))}
+
+
+def ema_step_host(e, p, record: dict, skip: bool = False) -> torch.Tensor:
+    """`mt4_ema_step_f32` restated in numpy float32: (decay * e) + (comp * p), the two products and the sum one round-to-nearest operation each, in
+    that order, so the kernel equals it bit for bit.  record: AFTER `ema_advance_host`.  -> float32 on the CPU (e's own values when skipped)"""
+    import numpy as np
+    f32 = np.float32
+    arr = lambda x: (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)).astype(f32, copy=True)
+    en, pn = arr(e), arr(p)
+    if not skip:
+        with np.errstate(all="ignore"):
+            de = f32(record["decay"]) * en
+            cp = f32(record["comp"]) * pn
+            en = de + cp
+    return torch.from_numpy(np.ascontiguousarray(en, dtype=f32))
+
+
 def mul_add(a: torch.Tensor, b: torch.Tensor, c: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _need_cuda(a, b, c)
     assert a.is_contiguous() and b.is_contiguous() and a.dtype == torch.float32 and a.numel() == b.numel()

@@ -44,7 +44,7 @@ class Q2LTrainer(GemmTrainer):
     def __init__(self, backbone: str = "swin_L_384_22k", img_size: int = 384, hidden_dim: int = 1536, loss_type: str = "i", lr: float = 0.01,
                  weight_decay: float = 1e-5, drop_path_rate: float = 0.1, device: str = "cuda", process_group=None,
                  operand_dtype: torch.dtype = torch.float32, teacher_dim: int = 512, rates=(1.0, 0.0, 0.1), temp: float = 4.0,
-                 clip_grad_norm: float = 0.0, skip_nonfinite: bool = False, optim=None):
+                 clip_grad_norm: float = 0.0, skip_nonfinite: bool = False, optim=None, ema=None):
         if loss_type not in ("i", "v", "t", "all"):
             raise ValueError("loss_type: i | v | t | all (Spatial_transformer/run.py:168-197)")
         self.backbone, self.S, self.d, self.loss_type = backbone, int(img_size), int(hidden_dim), loss_type
@@ -53,7 +53,7 @@ class Q2LTrainer(GemmTrainer):
         self.teacher_dim, self.rates, self.temp = int(teacher_dim), tuple(float(r) for r in rates), float(temp)   # `run.py:66,70` (--rates default 1 0 0.1)
         self.cfg = SWIN_CFG[backbone]
         assert self.d == self.cfg["embed_dim"] * 8, "hidden_dim is the backbone's final width (backbone.py:188-201)"
-        super().__init__(lr, weight_decay, device, process_group, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, optim=optim)
+        super().__init__(lr, weight_decay, device, process_group, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, optim=optim, ema=ema)
         assert operand_dtype in (torch.float32, torch.bfloat16)
         # bfloat16: the nn.Linear / patch-embedding GEMMs (forward, data and weight gradients) read bf16 copies of their operands; activations,
         # accumulation, everything between the GEMMs and the master weights stay fp32 (as in `MstctTrainer`)
@@ -130,10 +130,10 @@ class Q2LTrainer(GemmTrainer):
         self.pos_w = {t: torch.tensor(POS_W[t], dtype=F32, device=self.dev) for t in self.tasks if t in POS_W}     # ivt: plain BCE (`run.py:342`)
         return self
 
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        """the reference's parameter names and shapes; loss_type all: followed by the shared transformer's three alias entries per tensor
+    def state_dict(self, which: str = "p") -> Dict[str, torch.Tensor]:
+        """(which "ema": the weight average in place of P) the reference's parameter names and shapes; loss_type all: followed by the shared transformer's three alias entries per tensor
         (decoder_v / _t / _ivt.transformer.*), as the reference module's own `state_dict()` lists them (`run.py:266-277` saves that)"""
-        out = self.fp.export("p")
+        out = self.fp.export(which)
         sd = {k: out[k] for k, _ in self._table}
         if self.loss_type == "all":
             from .shapes import q2l_state_dict_aliases

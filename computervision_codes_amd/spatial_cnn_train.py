@@ -46,7 +46,7 @@ class SpatialCnnTrainer(FlatTrainer):
     def __init__(self, network: str = "resnet50", lr: float = 0.01, weight_decay: float = 1e-5, rates: Sequence[float] = (1.0, 1.0, 1.0),
                  temp: float = 4.0, device: str = "cuda", process_group=None, overlap: bool = True, teacher_dim: int = 1536,
                  loss_type: str = "all", operand_dtype: torch.dtype = torch.float32, epilogue_stats: bool = True, deterministic: bool = False,
-                 clip_grad_norm: float = 0.0, skip_nonfinite: bool = False, optim=None):
+                 clip_grad_norm: float = 0.0, skip_nonfinite: bool = False, optim=None, ema=None):
         """loss_type 'all': the distillation recipe (four heads, KD branch, hard + soft + feature losses: `run.py:180-192`);
         'i' | 'v' | 't': a single-task student -- only that classifier exists (`network.py:34-41`) and the loss is its BCE alone
         (`run.py:165-179`)"""
@@ -71,7 +71,7 @@ class SpatialCnnTrainer(FlatTrainer):
         self.NH = sum(k for _, k in self.heads)
         self.NHP = (self.NH + 3) // 4 * 4
         # overlap: each gradient bucket is all-reduced as soon as the backward has written it (DDP, `FlatTrainer`)
-        super().__init__(lr, weight_decay, device, process_group, overlap, clip_grad_norm, skip_nonfinite, optim)
+        super().__init__(lr, weight_decay, device, process_group, overlap, clip_grad_norm, skip_nonfinite, optim, ema)
         self.network, self.rates, self.temp = network, tuple(rates), float(temp)
         self.C = resnet_feat_dim(network)
         self.TD = int(teacher_dim)          # `--teacher_dim` (`Spatial_cnn/run.py:82`): width of the teachers' frame features
@@ -142,6 +142,8 @@ class SpatialCnnTrainer(FlatTrainer):
             u.w16, u.wt16, u.phase_w16 = None, None, None
             self.units[conv] = u
             trained |= {bn + ".running_mean", bn + ".running_var", bn + ".num_batches_tracked"}
+        # the weight average (`FlatTrainer._ema_update`) also averages the running statistics: a copy of the loaded buffer, stepped with E's record
+        self._rstats_ema = self._rstats.clone() if self.ema is not None else None
         # float64 scratch of every BatchNorm reduction of a step (forward 2C -- or its STAT_REPLICAS copies when the convolution's epilogue
         # fills them -- and backward 2C), zeroed once per step
         rep = ops.STAT_REPLICAS if self.epilogue_stats else 1
@@ -203,6 +205,18 @@ class SpatialCnnTrainer(FlatTrainer):
         if self.skip_nonfinite and self._rstats_keep is not None:
             ops.restore_if_skipped(self._rstats, self._rstats_keep, state)
 
+    def _ema_step_extra(self, state):
+        """the averaged running statistics follow E: the same record, the same skip rule (the statistics of a skipped step were restored above)"""
+        ops.ema_step(self._rstats_ema, self._rstats, self._estate, state)
+
+    def _load_ema_extra(self, state: Dict[str, torch.Tensor]):
+        ro = 0
+        for u in self.units.values():
+            co = u.cout
+            self._rstats_ema[ro:ro + co].copy_(state[u.bn + ".running_mean"].float())
+            self._rstats_ema[ro + _r4(co):ro + _r4(co) + co].copy_(state[u.bn + ".running_var"].float())
+            ro += 2 * _r4(co)
+
     # ------------------------------------------------------------------ deterministic mode: the workspace
     def workspace_bytes(self, b: int, h: int, w: int) -> int:
         """the largest workspace over the launches of a step on b frames of h x w, from the plan queries (host only: needs no device, no weights)"""
@@ -238,11 +252,17 @@ class SpatialCnnTrainer(FlatTrainer):
             self._ws = torch.empty((n + 15) // 16 * 4, dtype=F32, device=self.dev)
             self._ws64 = self._ws.view(torch.float64)
 
-    def running_stats(self) -> Dict[str, torch.Tensor]:
-        """the BatchNorm buffers only (what a train-mode forward changes)"""
-        out = {}
+    def running_stats(self, ema: bool = False) -> Dict[str, torch.Tensor]:
+        """the BatchNorm buffers only (what a train-mode forward changes); ema: the averaged statistics in place of the running ones"""
+        out, ro = {}, 0
         for u in self.units.values():
-            out[u.bn + ".running_mean"], out[u.bn + ".running_var"] = u.rmean.clone().cpu(), u.rvar.clone().cpu()
+            co = u.cout
+            if ema:
+                mean, var = self._rstats_ema[ro:ro + co], self._rstats_ema[ro + _r4(co):ro + _r4(co) + co]
+            else:
+                mean, var = u.rmean, u.rvar
+            ro += 2 * _r4(co)
+            out[u.bn + ".running_mean"], out[u.bn + ".running_var"] = mean.clone().cpu(), var.clone().cpu()
             out[u.bn + ".num_batches_tracked"] = torch.tensor(self.nbt[u.bn], dtype=torch.int64)
         return out
 
@@ -257,8 +277,9 @@ class SpatialCnnTrainer(FlatTrainer):
             o += k
         return out
 
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        out = dict(self._extra, **self._export("p"), **self.running_stats())
+    def state_dict(self, which: str = "p") -> Dict[str, torch.Tensor]:
+        """which "ema": the weight average in place of P and the averaged running statistics in place of the running ones"""
+        out = dict(self._extra, **self._export(which), **self.running_stats(which == "ema"))
         return {k: out[k] for k, _ in self._table}
 
     def grads(self) -> Dict[str, torch.Tensor]:

@@ -35,9 +35,9 @@ NHP = 132  # padded to a multiple of 4 (16-byte rows for the gradient GEMMs)
 class TencoTrainer(FlatTrainer):
     def __init__(self, num_layers_PG=11, num_layers_R=10, num_R=3, num_f_maps=512, dim=512, num_classes=100, lr=0.1, weight_decay=1e-5,
                  device: str = "cuda", process_group=None, overlap: bool = True, hier: bool = False, max_graphs: int = 64,
-                 deterministic: bool = False, clip_grad_norm: float = 0.0, skip_nonfinite: bool = False, optim=None, causal: bool = False):
+                 deterministic: bool = False, clip_grad_norm: float = 0.0, skip_nonfinite: bool = False, optim=None, causal: bool = False, ema=None):
         # overlap: a stage's gradients are all-reduced as soon as its backward has written them (DDP, `FlatTrainer`)
-        super().__init__(lr, weight_decay, device, process_group, overlap, clip_grad_norm, skip_nonfinite, optim)
+        super().__init__(lr, weight_decay, device, process_group, overlap, clip_grad_norm, skip_nonfinite, optim, ema)
         # hier = `args.hier` (`network.py:147,154-155`): AvgPool1d(7, 3) behind every refinement stage, so level l has its own length T_l, the FPN
         # resamples (`:96`) and `fusion` scores every level against the labels resized to it (`run.py:159-179,196-212`)
         self.hier = bool(hier)
@@ -111,9 +111,9 @@ class TencoTrainer(FlatTrainer):
             o += k
         return out
 
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        """reference layout and key names (`Temporal_tenco/network.py`), on the CPU"""
-        out = dict(self._extra, **self._export("p"))
+    def state_dict(self, which: str = "p") -> Dict[str, torch.Tensor]:
+        """reference layout and key names (`Temporal_tenco/network.py`), on the CPU; which "ema": the weight average in place of P"""
+        out = dict(self._extra, **self._export(which))
         return {k: out[k] for k, _ in self._table}
 
     def grads(self) -> Dict[str, torch.Tensor]:

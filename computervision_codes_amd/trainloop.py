@@ -106,8 +106,13 @@ def save_atomic(state: Dict[str, torch.Tensor], path: str):
 #                            "optim": {"file": its base name, "digest": "sha256:<hex of its bytes>", "config": the rule's config}
 # Both records' files are kept; older ones are removed once the pair is written, so a kill at any point leaves every named file in place.  Every
 # rank reads the file on resume (the state is the same on every rank).  Without optimizer state nothing of this is written.
+# A trainer with a weight average (--ema_decay) adds, with exactly that life cycle,
+#   <latest>.ema.e<epoch>    rank 0: torch.save of `tr.ema_export()` behind that epoch, named in the record as
+#                            "ema": {"file": its base name, "digest": "sha256:<hex of its bytes>", "config": the average's config}
+# Without the average nothing of this is written.
 RESUME_SUFFIX = ".resume"
 OPTIM_SUFFIX = ".optim.e"
+EMA_SUFFIX = ".ema.e"
 _RESUME_FORMAT = 1
 
 
@@ -175,8 +180,10 @@ class Resume:
     `state_dict()` = the tensors of exactly the `<latest>` bytes the digest was checked on (None for a fresh run)"""
 
     def __init__(self, epoch: int = -1, top: float = 0.0, generators: dict = None, data: bytes = None, record: dict = None,
-                 optim_data: bytes = None):
+                 optim_data: bytes = None, ema_data: bytes = None):
         self.epoch, self.top, self.generators, self._data, self.record = epoch, top, generators or {}, data, record
+        # `ema_state()` = the `ema_export()` of exactly the bytes the record's digest was checked on; None where the record names none
+        self.ema_state = None if ema_data is None else (lambda: torch.load(io.BytesIO(ema_data), map_location="cpu"))
         # `optim_state()` = the optimizer state of exactly the bytes the record's digest was checked on; None where the record names none
         self.optim_state = None if optim_data is None else (lambda: torch.load(io.BytesIO(optim_data), map_location="cpu"))
 
@@ -216,12 +223,45 @@ def _load_optim_bytes(latest: str, side: str, rec: dict, optim) -> bytes:
     return data
 
 
-def load_resume(latest: str, rank: int = 0, world: int = 1, optim: dict = None) -> Resume:
+def ema_file(latest: str, epoch: int) -> str:
+    """the file the weight average behind `epoch` is kept in, beside the checkpoint `latest`"""
+    return latest + EMA_SUFFIX + str(epoch)
+
+
+def _load_ema_bytes(latest: str, side: str, rec: dict, ema) -> bytes:
+    """the weight-average file a record names, checked against the record and against this run's flags (`ema` = their config, None: no average)"""
+    named = rec.get("ema")
+    if named is None:
+        if ema is not None:
+            raise ValueError(f"--resume: {side} (epoch {rec.get('epoch')}) holds no weight average and this run asks for {ema}: the run that wrote it "
+                             "kept none.  Drop --ema_decay / --ema_warmup to continue it as it was, or drop --resume to start again at epoch 0 "
+                             "from the weights with a fresh average")
+        return None
+    path = os.path.join(os.path.dirname(latest), named["file"])
+    if ema is None:
+        raise ValueError(f"--resume: {side} (epoch {rec.get('epoch')}) was written with a weight average ({named['config']}, {path}) and this run has "
+                         "no --ema_decay: give the flags of the run that wrote it, or drop --resume to start again at epoch 0 from the weights")
+    if named["config"] != ema:
+        raise ValueError(f"--resume: the weight average {path} belongs to {named['config']} and this run asks for {ema}; changing the average "
+                         "across a resume is not supported.  Give the recorded flags, or drop --resume to start again at epoch 0 from the weights")
+    if not os.path.exists(path):
+        raise ValueError(f"--resume: the weight average {path} that {side} names is missing.  Put it back, or drop --resume to start again at epoch 0 "
+                         "from the weights (the average starts from them)")
+    with open(path, "rb") as f:
+        data = f.read()
+    if _digest(data) != named["digest"]:
+        raise ValueError(f"--resume: {path} ({_digest(data)[:19]}...) is not the weight average {side} was written for ({named['digest'][:19]}...): it "
+                         "was replaced or its write was torn.  Put the matching file back, or drop --resume to start again at epoch 0 from the weights")
+    return data
+
+
+def load_resume(latest: str, rank: int = 0, world: int = 1, optim: dict = None, ema: dict = None) -> Resume:
     """--resume at the start of a run, before any model is built and without touching a file: a fresh `Resume` when there is no `latest`, the
     state to continue from when its sidecar names the bytes of `latest`, ValueError otherwise (no sidecar: the checkpoint was written without
     --resume; another `world`; no record with the digest of `latest`; rank > 0: no record of that epoch in its own file).  optim: the config of
     this run's update rule (`flatparams.Optim.config()`), None for plain SGD: the record's optimizer file must be there with the recorded
-    digest and config, a record without one takes no optimizer flags and one with it needs them (ValueError otherwise)"""
+    digest and config, a record without one takes no optimizer flags and one with it needs them (ValueError otherwise).  ema: the config of
+    this run's weight average (`flatparams.Ema.config()`), None without one: the same rules for the record's weight-average file"""
     if not os.path.exists(latest):
         return Resume()                                            # (a sidecar alone: the run died before its first checkpoint; it is overwritten)
     side = resume_file(latest)
@@ -241,6 +281,7 @@ def load_resume(latest: str, rank: int = 0, world: int = 1, optim: dict = None) 
                          f"{[r.get('epoch') for r in obj['records']]}): it was replaced or its write was torn.  Put the matching file back, or move "
                          "both away to start a fresh run, or drop --resume to start again at epoch 0 from these weights")
     optim_data = _load_optim_bytes(latest, side, rec, optim)
+    ema_data = _load_ema_bytes(latest, side, rec, ema)
     gens = rec["generators"]
     if rank:
         mine = resume_file(latest, rank)
@@ -252,15 +293,38 @@ def load_resume(latest: str, rank: int = 0, world: int = 1, optim: dict = None) 
             raise ValueError(f"--resume: {mine} (world {own.get('world')}, epochs {[r.get('epoch') for r in own['records']]}) does not belong to "
                              f"epoch {rec['epoch']} of {side} (world {world}); restore the matching file or start a fresh run")
         gens = own_rec["generators"]
-    return Resume(int(rec["epoch"]), float(rec["top"]), gens, data, rec, optim_data)
+    return Resume(int(rec["epoch"]), float(rec["top"]), gens, data, rec, optim_data, ema_data)
 
 
-def _save_pair(state, latest: str, record: dict, older: list, world: int, optim_state: dict = None):
+def _save_named(obj, path: str) -> str:
+    """torch.save through a temporary file and os.replace; -> the digest of the bytes"""
+    tmp = path + ".tmp"
+    try:
+        torch.save(obj, tmp)
+        digest = _file_digest(tmp)
+        os.replace(tmp, path)
+        return digest
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def _remove_unnamed(latest: str, suffix: str, key: str, records: list):
+    """the `<latest><suffix><epoch>` files none of `records` names under `key` are removed"""
+    keep = {r[key]["file"] for r in records if r.get(key)}
+    head, where = os.path.basename(latest) + suffix, os.path.dirname(latest) or "."
+    for name in os.listdir(where):
+        if name.startswith(head) and name[len(head):].isdigit() and name not in keep:
+            os.remove(os.path.join(where, name))
+
+
+def _save_pair(state, latest: str, record: dict, older: list, world: int, optim_state: dict = None, ema_state: dict = None):
     """`latest` and its sidecar: the checkpoint is written to its temporary file and digested there, the sidecar (the new record in front of
     the one before) is replaced, then `latest` is.  Killed before the first replace: the old pair; between the two: the new sidecar, whose
     older record names the old `latest`; after: the new pair.  optim_state (a trainer with optimizer state): written to `optim_file` of the
     record's epoch (temporary file, then replace) BEFORE the sidecar that names it; the optimizer files neither kept record names are removed
-    behind the pair -- a kill at any point leaves a pair whose optimizer file exists"""
+    behind the pair -- a kill at any point leaves a pair whose optimizer file exists.  ema_state (a trainer with a weight average,
+    `tr.ema_export()`): `ema_file` of the record's epoch, in exactly the same way"""
     os.makedirs(os.path.dirname(latest) or ".", exist_ok=True)
     tmp = latest + ".tmp"
     try:
@@ -268,22 +332,16 @@ def _save_pair(state, latest: str, record: dict, older: list, world: int, optim_
         record["digest"] = _file_digest(tmp)
         if optim_state is not None:
             opath = optim_file(latest, record["epoch"])
-            otmp = opath + ".tmp"
-            try:
-                torch.save(optim_state, otmp)
-                record["optim"] = {"file": os.path.basename(opath), "digest": _file_digest(otmp), "config": optim_state["optim"]}
-                os.replace(otmp, opath)
-            finally:
-                if os.path.exists(otmp):
-                    os.remove(otmp)
+            record["optim"] = {"file": os.path.basename(opath), "digest": _save_named(optim_state, opath), "config": optim_state["optim"]}
+        if ema_state is not None:
+            epath = ema_file(latest, record["epoch"])
+            record["ema"] = {"file": os.path.basename(epath), "digest": _save_named(ema_state, epath), "config": ema_state["ema"]}
         _write_json_atomic({"format": _RESUME_FORMAT, "world": world, "records": [record] + older[:1]}, resume_file(latest))
         os.replace(tmp, latest)
         if optim_state is not None:
-            keep = {r["optim"]["file"] for r in [record] + older[:1] if r.get("optim")}
-            head = os.path.basename(latest) + OPTIM_SUFFIX
-            for name in os.listdir(os.path.dirname(latest) or "."):
-                if name.startswith(head) and name[len(head):].isdigit() and name not in keep:
-                    os.remove(os.path.join(os.path.dirname(latest) or ".", name))
+            _remove_unnamed(latest, OPTIM_SUFFIX, "optim", [record] + older[:1])
+        if ema_state is not None:
+            _remove_unnamed(latest, EMA_SUFFIX, "ema", [record] + older[:1])
     finally:
         if os.path.exists(tmp):
             os.remove(tmp)
@@ -312,16 +370,25 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
 
     Optimizer state (`tr.optimizer_state_dict()` not None: --momentum, --optimizer adamw) under --resume: rank 0 writes it beside every `latest`
     (`optim_file`, named and digested in the record; `_save_pair`), the driver has loaded `resume.optim_state()` into `tr`.  Without --resume no
-    optimizer file is written; without optimizer state the sidecar is byte for byte what it was."""
+    optimizer file is written; without optimizer state the sidecar is byte for byte what it was.
+
+    Weight average (`tr.ema_config()` not None: --ema_decay; off: every byte and line as above): `validate` is given `tr.ema_state_dict()`, its
+    score decides the best `.pth` and the best `.pth` HOLDS the averaged weights, so everything that loads a best `.pth` gets them; `latest`
+    stays the raw weights (a continued run needs them).  --ema_eval both also validates the raw weights and appends `| raw => ...` to the
+    `video-wise |` line; that score decides nothing.  The `Traning |` line gets `| ema t N decay D` from the device record (one read per epoch on
+    rank 0).  Under --resume rank 0 writes `tr.ema_export()` beside every `latest` (`ema_file`, named and digested in the record), the driver
+    has loaded `resume.ema_state()` into `tr`."""
     val_interval = max(1, F.epochs - 1 if F.val_interval == -1 else F.val_interval)
     top, last, first = 0.0, {}, 0
     resuming = bool(getattr(F, "resume", False))
     clip, skip_nonfinite = guard_flags(F)
     guarded = clip > 0 or skip_nonfinite
+    ema_config = getattr(tr, "ema_config", lambda: None)()
+    averaged, ema_both = ema_config is not None, getattr(F, "ema_eval", "ema") == "both"
     if resuming:
         world = _dist()[1] if world is None else world
         generators = generators or {}
-        resume = load_resume(latest, rank, world, getattr(tr, "optim_config", lambda: None)()) if resume is None else resume
+        resume = load_resume(latest, rank, world, getattr(tr, "optim_config", lambda: None)(), ema_config) if resume is None else resume
         older = [resume.record] if resume.record else []           # rank 0: the record on disk that names the `latest` on disk
         own_older = [{"epoch": resume.epoch, "generators": resume.generators}] if resume.epoch >= 0 else []
         if resume.epoch >= 0:
@@ -350,7 +417,11 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
                 tot, steps = float("nan"), 1
         last = {"loss": tot / steps, "lr": tr.lr}
         val = epoch % val_interval == 0
+        ema_state = None
         if rank == 0:
+            if averaged:
+                er = tr.ema_record()
+                note += f" | ema t {er['t']} decay {er['decay']:.6g}"
             _log(logfile, f"Traning | lr: {tr.lr:.6f} | epoch {epoch} | loss {tot / steps:.4f} | {time.time() - t0:.2f} secs" + note)
             if val or latest_every_epoch:
                 state = tr.state_dict()
@@ -358,14 +429,18 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
                     save_atomic(state, latest)
                 else:                                              # (None: the trainer keeps no optimizer state)
                     optim_state = getattr(tr, "optimizer_state_dict", lambda: None)()
+                    ema_state = tr.ema_export() if averaged else None
             if val:
                 t1 = time.time()
-                score, shown = validate(state)
+                scored = state if not averaged else ema_state["state"] if ema_state is not None else tr.ema_state_dict()
+                score, shown = validate(scored)
                 last[score_key] = score
                 if score > top or not os.path.exists(best):
                     top = max(top, score)
-                    save_atomic(state, best)
+                    save_atomic(scored, best)
                     _log(logfile, f">>> Saving checkpoint for epoch {epoch + 1} at {best}, time {time.ctime()} ")
+                if averaged and ema_both:                          # (the raw weights' score is shown and decides nothing)
+                    shown += f" | raw => {validate(state)[1]}"
                 _log(logfile, f"\t\t\t\t\t\t\t video-wise | eta {time.time() - t1:.2f} secs | mAP => {shown} ")
         if resuming and (val or latest_every_epoch):
             gens = {name: _generator_state(g) for name, g in generators.items()}
@@ -376,7 +451,7 @@ def run_epochs(F, tr, rank: int, train_epoch: Callable[[int], Tuple[float, int]]
             _barrier()                                             # every other rank's record of this epoch is on disk before rank 0's names it
             if rank == 0:
                 rec = {"epoch": epoch, "top": top, "generators": gens}
-                _save_pair(state, latest, rec, older, world, optim_state)
+                _save_pair(state, latest, rec, older, world, optim_state, ema_state)
                 older = [rec]
         _barrier()
     _barrier()                                                     # the last checkpoint is on disk before any rank goes on to -e

@@ -578,6 +578,27 @@ int mt4_sgd_momentum_step_f32(float* p, const float* g, float* m, int64_t n, flo
  *   q = p - lw * p;  h = g * s;  m <- b1 * m + c1 * h;  v <- b2 * v + c2 * (h * h);  p <- q - step * (m / (sqrt(v) / r2 + eps)) */
 int mt4_adamw_step_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float weight_decay, float grad_scale, double beta1,
                        double beta2, float eps, const mt4_optim_state* optim_state, const mt4_guard_state* guard_state, void* stream);
+/*
+ * Weight average (--ema_decay; the reference ships the class, `ModelEma` in Spatial_transformer/utils/misc.py:433-458, and no driver calls it): an
+ * exponential moving average e of the parameters p, stepped behind the parameter update.  The step's decay lives in a device record because the skip
+ * decision does (as mt4_optim_state).  `ops.ema_advance_host` / `ops.ema_step_host` restate both entry points and give the same bits.
+ * Refusals, before any launch: MT4_EINVAL for a NULL e / p / ema_state, n <= 0, a decay outside [0, 1) or NaN; MT4_EALIGN for e or p off the 16-byte
+ * grid or a record off the 8-byte grid.
+ *
+ * mt4_ema_state (16 bytes, 8-byte aligned).  Its owner initialises it to {0, 0, 1}.
+ */
+typedef struct mt4_ema_state {
+    int64_t t;    /* steps that entered the average */
+    float decay;  /* (float)d of step t */
+    float comp;   /* (float)(1.0 - d), the subtraction in double */
+} mt4_ema_state;
+/* One thread: unless guard_state says skip, t += 1, then in IEEE double d = warmup ? min(decay, (1.0 + t) / (10.0 + t)) : decay (the num_updates form
+ * of TensorFlow's ExponentialMovingAverage), decay = (float)d, comp = (float)(1.0 - d).  A skipped step leaves the record as it was. */
+int mt4_ema_advance(mt4_ema_state* ema_state, double decay, int32_t warmup, const mt4_guard_state* guard_state, void* stream);
+/* Behind the parameter update and mt4_ema_advance; per element, all float: e <- (decay * e) + (comp * p) -- two multiplies and one add, each one
+ * round-to-nearest operation in that order, no FMA contraction.  Nothing at all is written when guard_state says skip; NULL: unguarded.  16-byte
+ * accesses, the n % 4 tail element by element, no atomics; any fp32 buffer that is averaged with the same record is one more call. */
+int mt4_ema_step_f32(float* e, const float* p, int64_t n, const mt4_ema_state* ema_state, const mt4_guard_state* guard_state, void* stream);
 /* y = a * b (+ c): dropout masks (network.py:194-196) forward and backward */
 int mt4_mul_add_f32(const float* a, const float* b, const float* c, float* y, int64_t n, void* stream);
 /* packed Conv1d weight [Cout][Kpad(Cin,taps)] -> packed weight of its data-gradient conv [Cin][Kpad(Cout,taps)] */
